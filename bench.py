@@ -18,9 +18,15 @@ Ranks.  `--gpus N` with N > 1 needs N processes, one per GPU:
     exits non-zero if any child fails.
 A rank whose world size differs from --gpus exits non-zero: a number is never scaled by a
 GPU count that did not run.  The line carries "ranks_seen" and every rank's device.
-For N > 1 a second timed region puts the one real exchange step -- the gather of the
-pre-zlib streams to rank 0 over RCCL (dctzhip_comm_gather) -- INSIDE the step
+For N > 1, `--full` adds a second timed region that puts the one real exchange step -- the
+gather of the pre-zlib streams to rank 0 over RCCL (dctzhip_comm_gather) -- INSIDE the step
 ("with_gather").
+
+A plain run sets up, runs --warmup untimed steps and --steps timed steps, and prints the
+line: `value` / `ms_per_step` are that window.  `--full` measures everything else after it
+(the settled window, the scaled-copy variant, per-kernel HIP-event durations and the roofline,
+the device entropy stage, the CPU baseline, a list's one-call-per-array form, the gather).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 
 `--plumbing-only`: the launcher, the rendezvous and the gather alone (gloo, synthetic byte
 streams, no kernels, no GPU, no `value`): what the CPU test of the N > 1 path runs.
@@ -28,7 +34,7 @@ streams, no kernels, no GPU, no `value`): what the CPU test of the N > 1 path ru
 `--config c1|c2|c3|c4|c5` selects one of BASELINE.json's five configurations at its own size (default c4 = the headline:
 the line's shape is the same for all of them).  c5 is a LIST of arrays (the six list-msst19 lengths in fp64 and the five
 CESM-sized fp32 fields, error bounds 1e-3 .. 1e-6 each): its step is one dctzhip_compress_batch + one
-dctzhip_decompress_batch over the whole list, and the line also carries the same list done one call per array ("looped").
+dctzhip_decompress_batch over the whole list, and a --full line also carries the same list done one call per array ("looped").
 
 Prints ONE JSON line on rank 0.
 """
@@ -45,6 +51,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_BUDGET = 60 << 20      # --dump-outputs: bytes of array data in all (the .npy headers stay well inside 64 MiB)
 
 
 def kernel_source_hash(root=ROOT):
@@ -78,6 +85,55 @@ def lookup_traffic(record_path, kernel, key, source_hash):
     return ent["hbm_bytes_per_launch"], name + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on these sources, gfx950 correction applied)"
 
 
+def step_outputs(out, info, rec, n, mode_qt, prefix=""):
+    """What a caller of one compress + decompress step receives, by name: the three streams (AC_exact up to cnt), the
+    scalars of the info structure, the reconstruction, and the QT table."""
+    import numpy as np
+    res = [(prefix + "bin_index", out["bin_index"][:n]), (prefix + "dc", out["dc"][:(n + 63) // 64]),
+           (prefix + "ac_exact", out["ac_exact"][:int(info.cnt)]),
+           (prefix + "info", np.array([info.sf, info.mean, info.max_abs, info.min_abs, info.cnt, info.nblk], dtype=np.float64)),
+           (prefix + "reconstruction", rec)]
+    if mode_qt:
+        res.append((prefix + "qtable", np.array(info.qtable[:], dtype=np.float64)))
+    return res
+
+
+def dump_outputs(d, named, budget=DUMP_BUDGET):
+    """Writes every (name, array) of `named` -- torch tensors (any device) or numpy arrays, 1-D -- as d/<name>.npy:
+    float64 arrays stay float64, everything else becomes float32 (exact for the uint8 bin ids).  The budget is shared
+    out smallest array first; an array larger than its share is replaced by the values at a fixed sample of positions
+    (seeded by its name and length, sorted), so two runs with the same arguments write the same positions."""
+    import zlib
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def width(a):
+        return 8 if str(a.dtype) in ("float64", "torch.float64") else 4
+
+    def count(a):
+        return int(a.numel()) if callable(getattr(a, "numel", None)) else int(a.size)
+    items = sorted(named, key=lambda kv: count(kv[1]) * width(kv[1]))
+    left = budget
+    written = 0
+    for i, (name, a) in enumerate(items):
+        size, w = count(a), width(a)
+        share = left // (len(items) - i)
+        m = min(size, share // w)
+        if m < size:
+            idx = np.unique(np.random.default_rng(zlib.crc32(f"{name}:{size}".encode())).integers(0, size, m))
+            if hasattr(a, "device"):
+                import torch
+                a = a[torch.from_numpy(idx).to(a.device)]
+            else:
+                a = a[idx]
+        v = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+        v = np.ascontiguousarray(v, dtype=np.float64 if w == 8 else np.float32)
+        np.save(os.path.join(d, name + ".npy"), v)
+        left -= v.nbytes
+        written += v.nbytes
+    return written
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -103,7 +159,16 @@ def parse(argv=None):
     ap.add_argument("--no-speculation", action="store_true", help="always run the separate statistics pass first")
     ap.add_argument("--cpu-sample", type=int, default=1 << 27, help="elements of the shard the CPU oracle is timed on")
     ap.add_argument("--cpu-repeats", type=int, default=4, help="passes of the CPU oracle over the sample (about 10 s in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the settled window, the scaled-copy and one-call-per-array variants, "
+                         "per-kernel durations and the roofline, the device entropy stage, the CPU baseline and (N > 1) the gather "
+                         "step.  Off: the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (streams, info, reconstruction) as "
+                         "DIR/<name>.npy, float32 / float64, %d MiB at most (a fixed seeded sample of larger arrays)" % (DUMP_BUDGET >> 20))
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.mode is None:
         a.mode = "qt" if a.config == "c3" else "ec"
     if a.eb is None:
@@ -367,277 +432,293 @@ def run_rank(a, rank, local_rank, world):
     for _ in range(a.steps):
         infos = step()
     barrier()
-    unsettled_ms = shard.max_over_ranks(time.perf_counter() - u0, red_dev) * 1e3 / a.steps
-    # Settling, in front of a second set of W warm-up steps: the part's power management answers sustained load with a dip
-    # -- steps 4 to 12 of a fresh process run 12 % slower than steps 1 to 3 and than everything from step 15 on
-    # (tools/warm_probe.py: 0.51 / 0.60 / 0.52 ms; host time follows the GPU's, it is not the library).  The 20-step window
-    # behind 5 warm-up steps above measures that dip; the window below measures the steady state.  --settle-ms 0: off.
-    settle_steps = 0
-    if a.settle_ms > 0:
-        torch.cuda.synchronize()
-        s0 = time.perf_counter()
-        while (time.perf_counter() - s0) * 1e3 < a.settle_ms or settle_steps < 2:
-            infos = step()
-            torch.cuda.synchronize()
-            settle_steps += 1
-    for _ in range(a.warmup):
-        infos = step()
-    if infos is None:
-        infos = step()
-
-    # ---- timed region: exactly K steps, profiling off (no event overhead) ------
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        infos = step()
-    barrier()
-    local_elapsed = time.perf_counter() - t0
-    elapsed = shard.max_over_ranks(local_elapsed, red_dev)
-    settled_ms = elapsed * 1e3 / a.steps
-    # The line's `value` / `ms_per_step` is the form EXACTLY AS ASKED (W warm-up steps of a fresh process, K timed steps:
-    # ADVICE r4); the figure behind the settling is the secondary one (`settled_ms_per_step` / `settled_value`).
+    u_local = time.perf_counter() - u0
+    unsettled_ms = shard.max_over_ranks(u_local, red_dev) * 1e3 / a.steps
     ms_per_step = unsettled_ms
     info = infos[0]
+    if a.dump_outputs:
+        # what the last timed step handed its caller (the buffers are overwritten every step, so read them now); an N-rank
+        # run writes every rank's outputs under an r<rank>_ prefix within the same budget
+        named = []
+        for j in range(len(xs)):
+            pre = (f"r{rank}_" if world > 1 else "") + (f"a{j:02d}_" if many else "")
+            named += step_outputs(outs[j], infos[j], recs[j], ns[j], qt, prefix=pre)
+        dump_outputs(a.dump_outputs, named, DUMP_BUDGET // world)
+    if a.full:
+        # Settling, in front of a second set of W warm-up steps: the part's power management answers sustained load with a dip
+        # -- steps 4 to 12 of a fresh process run 12 % slower than steps 1 to 3 and than everything from step 15 on
+        # (tools/warm_probe.py: 0.51 / 0.60 / 0.52 ms; host time follows the GPU's, it is not the library).  The 20-step window
+        # behind 5 warm-up steps above measures that dip; the window below measures the steady state.  --settle-ms 0: off.
+        settle_steps = 0
+        if a.settle_ms > 0:
+            torch.cuda.synchronize()
+            s0 = time.perf_counter()
+            while (time.perf_counter() - s0) * 1e3 < a.settle_ms or settle_steps < 2:
+                infos = step()
+                torch.cuda.synchronize()
+                settle_steps += 1
+        for _ in range(a.warmup):
+            infos = step()
+        if infos is None:
+            infos = step()
 
-    # ---- the step with the reference's in-place scaling made visible: dctz_compress divides the CALLER's array by sf
-    # (dctz-comp-lib.c:193-216); the device entry point does that on request into d_scaled -- written by the compress kernel
-    # itself (the SC variant of k_compress / k_compress_one: the scaled tile goes registers -> LDS image -> rows while it is
-    # in registers anyway).  `value` is quoted without it ("add s"); this is the same K steps with it ----
-    with_scaled = None
-    if not many:
-        sc = torch.empty_like(x)
-        def step_scaled():
-            _, inf = ctx.compress(x, ebs[0], mode, out=out, scaled=sc)
-            ctx.decompress(out, inf.cnt, n, tdt[0], ebs[0], inf.sf, mode, qtable=inf.qtable if qt else None, dst=rec)
-        for _ in range(3):
-            step_scaled()
+        # ---- timed region: exactly K steps, profiling off (no event overhead) ------
         barrier()
-        w0 = time.perf_counter()
+        t0 = time.perf_counter()
         for _ in range(a.steps):
-            step_scaled()
+            infos = step()
         barrier()
-        w_ms = shard.max_over_ranks(time.perf_counter() - w0, red_dev) * 1e3 / a.steps
-        with_scaled = {"ms_per_step": w_ms, "value": in_bytes * world / (w_ms * 1e-3) / 1e9,
-                       "note": "compress writes x / sf into a second buffer as well (the reference's in-place scaling of the caller's array), by the SC variant of the compress kernel"}
-        del sc
+        local_elapsed = time.perf_counter() - t0
+        elapsed = shard.max_over_ranks(local_elapsed, red_dev)
+        settled_ms = elapsed * 1e3 / a.steps
+        # The line's `value` / `ms_per_step` is the form EXACTLY AS ASKED (W warm-up steps of a fresh process, K timed steps:
+        # ADVICE r4); the figure behind the settling is the secondary one (`settled_ms_per_step` / `settled_value`).
 
-    # ---- a list of arrays: the same list with one call per array (what the batch entry points replace) ----
-    looped = None
-    if many:
-        def loop_step():
-            for j in range(len(xs)):
-                _, ij = ctx.compress(xs[j], ebs[j], mode, out=outs[j])
-                ctx.decompress(outs[j], ij.cnt, ns[j], tdt[j], ebs[j], ij.sf, mode, qtable=ij.qtable if qt else None, dst=recs[j])
-        loop_step()
-        k_loop = max(3, min(a.steps, 20))
-        barrier()
-        l0 = time.perf_counter()
-        for _ in range(k_loop):
-            loop_step()
-        barrier()
-        l_ms = shard.max_over_ranks(time.perf_counter() - l0, red_dev) * 1e3 / k_loop
-        looped = {"ms_per_step": l_ms, "value": in_bytes * world / (l_ms * 1e-3) / 1e9, "steps": k_loop, "speedup_of_the_batch": l_ms / ms_per_step,
-                  "note": "the same arrays, one dctzhip_compress + one dctzhip_decompress call per array"}
+        # ---- the step with the reference's in-place scaling made visible: dctz_compress divides the CALLER's array by sf
+        # (dctz-comp-lib.c:193-216); the device entry point does that on request into d_scaled -- written by the compress kernel
+        # itself (the SC variant of k_compress / k_compress_one: the scaled tile goes registers -> LDS image -> rows while it is
+        # in registers anyway).  `value` is quoted without it ("add s"); this is the same K steps with it ----
+        with_scaled = None
+        if not many:
+            sc = torch.empty_like(x)
+            def step_scaled():
+                _, inf = ctx.compress(x, ebs[0], mode, out=out, scaled=sc)
+                ctx.decompress(out, inf.cnt, n, tdt[0], ebs[0], inf.sf, mode, qtable=inf.qtable if qt else None, dst=rec)
+            for _ in range(3):
+                step_scaled()
+            barrier()
+            w0 = time.perf_counter()
+            for _ in range(a.steps):
+                step_scaled()
+            barrier()
+            w_ms = shard.max_over_ranks(time.perf_counter() - w0, red_dev) * 1e3 / a.steps
+            with_scaled = {"ms_per_step": w_ms, "value": in_bytes * world / (w_ms * 1e-3) / 1e9,
+                           "note": "compress writes x / sf into a second buffer as well (the reference's in-place scaling of the caller's array), by the SC variant of the compress kernel"}
+            del sc
 
-        # the launch-bound part of the list by itself: the 24 small fp64 arrays, and those + ONE fp32 field at C2's bound
-        # (the list a single `tests/test-dctz.sh` + one CESM run amounts to), batch against one call per array
-        def sub(sel):
-            sx, se, so, sr = [xs[j] for j in sel], [ebs[j] for j in sel], [outs[j] for j in sel], [recs[j] for j in sel]
-            sn, sd = [ns[j] for j in sel], [tdt[j] for j in sel]
-            _, si, cp = ctx.compress_batch(sx, se, mode, outs=so)
-            _, _, dp = ctx.decompress_batch(so, [i.cnt for i in si], sn, sd, se, [i.sf for i in si], mode,
-                                            qtables=[np.array(i.qtable[:]) for i in si] if qt else None, dsts=sr)
-            def b_step():
-                ctx.compress_batch(None, None, mode, prepared=cp)
-                ctx.decompress_batch(None, None, None, None, None, None, mode, prepared=dp)
-            def l_step():
-                for j in sel:
+        # ---- a list of arrays: the same list with one call per array (what the batch entry points replace) ----
+        looped = None
+        if many:
+            def loop_step():
+                for j in range(len(xs)):
                     _, ij = ctx.compress(xs[j], ebs[j], mode, out=outs[j])
                     ctx.decompress(outs[j], ij.cnt, ns[j], tdt[j], ebs[j], ij.sf, mode, qtable=ij.qtable if qt else None, dst=recs[j])
-            res = {}
-            for nm, fn, reps in (("batch", b_step, max(20, a.steps)), ("looped", l_step, max(5, min(a.steps, 20)))):
-                for _ in range(3):
-                    fn()
-                torch.cuda.synchronize()
-                q0 = time.perf_counter()
-                for _ in range(reps):
-                    fn()
-                torch.cuda.synchronize()
-                res[nm + "_ms"] = (time.perf_counter() - q0) * 1e3 / reps
-            sb = sum(ns[j] * xs_host[j].itemsize for j in sel)
-            res.update({"arrays": len(sel), "bytes": int(sb), "speedup_of_the_batch": res["looped_ms"] / res["batch_ms"],
-                        "batch_GBps": sb / (res["batch_ms"] * 1e-3) / 1e9, "looped_GBps": sb / (res["looped_ms"] * 1e-3) / 1e9})
-            return res
-        small = [j for j in range(len(xs)) if xs_host[j].itemsize == 8]
-        c2_like = [j for j in range(len(xs)) if xs_host[j].itemsize == 4 and ebs[j] == 1e-4][:1]
-        looped["subsets"] = {"msst19_24_small_fp64": sub(small), "msst19_24_plus_one_fp32_field_at_1e-4": sub(small + c2_like)}
+            loop_step()
+            k_loop = max(3, min(a.steps, 20))
+            barrier()
+            l0 = time.perf_counter()
+            for _ in range(k_loop):
+                loop_step()
+            barrier()
+            l_ms = shard.max_over_ranks(time.perf_counter() - l0, red_dev) * 1e3 / k_loop
+            looped = {"ms_per_step": l_ms, "value": in_bytes * world / (l_ms * 1e-3) / 1e9, "steps": k_loop, "speedup_of_the_batch": l_ms / ms_per_step,
+                      "note": "the same arrays, one dctzhip_compress + one dctzhip_decompress call per array"}
 
-    # ---- per-kernel durations (HIP events on the launch stream), same K steps --
-    ctx.set_profiling(True)
-    acc = {"c_stats": 0.0, "c_main": 0.0, "c_tail": 0.0, "d_pre": 0.0, "d_main": 0.0, "d_tail": 0.0}
-    seqs = {"f64": dict(acc), "f32": dict(acc)}                # a list: per element-type launch sequence
-    t_c = t_d = 0.0
-    for _ in range(a.steps):
-        torch.cuda.synchronize()
-        s0 = time.perf_counter()
-        if many:
-            _, infos, _ = ctx.compress_batch(None, None, mode, prepared=state["cp"])
-        else:
-            _, info = ctx.compress(x, ebs[0], mode, out=out)
-        s1 = time.perf_counter()
-        if many:
-            bt = ctx.batch_timings()
-            for nm in seqs:
-                seqs[nm]["c_stats"] += bt[nm]["stats_ms"]; seqs[nm]["c_main"] += bt[nm]["main_ms"]; seqs[nm]["c_tail"] += bt[nm]["tail_ms"]
-        else:
-            tm = ctx.timings()
-            acc["c_stats"] += tm["stats_ms"]; acc["c_main"] += tm["main_ms"]; acc["c_tail"] += tm["tail_ms"]
-        s2 = time.perf_counter()
-        if many:
-            ctx.decompress_batch(None, None, None, None, None, None, mode, prepared=state["dp"])
-        else:
-            ctx.decompress(out, info.cnt, n, tdt[0], ebs[0], info.sf, mode, qtable=info.qtable if qt else None, dst=rec)
-        s3 = time.perf_counter()
-        if many:
-            bt = ctx.batch_timings()
-            for nm in seqs:
-                seqs[nm]["d_pre"] += bt[nm]["stats_ms"]; seqs[nm]["d_main"] += bt[nm]["main_ms"]; seqs[nm]["d_tail"] += bt[nm]["tail_ms"]
-        else:
-            tm = ctx.timings()
-            acc["d_pre"] += tm["stats_ms"]; acc["d_main"] += tm["main_ms"]; acc["d_tail"] += tm["tail_ms"]
-        t_c += s1 - s0; t_d += s3 - s2
-    ctx.set_profiling(False)
-    info = infos[0] if many else info
+            # the launch-bound part of the list by itself: the 24 small fp64 arrays, and those + ONE fp32 field at C2's bound
+            # (the list a single `tests/test-dctz.sh` + one CESM run amounts to), batch against one call per array
+            def sub(sel):
+                sx, se, so, sr = [xs[j] for j in sel], [ebs[j] for j in sel], [outs[j] for j in sel], [recs[j] for j in sel]
+                sn, sd = [ns[j] for j in sel], [tdt[j] for j in sel]
+                _, si, cp = ctx.compress_batch(sx, se, mode, outs=so)
+                _, _, dp = ctx.decompress_batch(so, [i.cnt for i in si], sn, sd, se, [i.sf for i in si], mode,
+                                                qtables=[np.array(i.qtable[:]) for i in si] if qt else None, dsts=sr)
+                def b_step():
+                    ctx.compress_batch(None, None, mode, prepared=cp)
+                    ctx.decompress_batch(None, None, None, None, None, None, mode, prepared=dp)
+                def l_step():
+                    for j in sel:
+                        _, ij = ctx.compress(xs[j], ebs[j], mode, out=outs[j])
+                        ctx.decompress(outs[j], ij.cnt, ns[j], tdt[j], ebs[j], ij.sf, mode, qtable=ij.qtable if qt else None, dst=recs[j])
+                res = {}
+                for nm, fn, reps in (("batch", b_step, max(20, a.steps)), ("looped", l_step, max(5, min(a.steps, 20)))):
+                    for _ in range(3):
+                        fn()
+                    torch.cuda.synchronize()
+                    q0 = time.perf_counter()
+                    for _ in range(reps):
+                        fn()
+                    torch.cuda.synchronize()
+                    res[nm + "_ms"] = (time.perf_counter() - q0) * 1e3 / reps
+                sb = sum(ns[j] * xs_host[j].itemsize for j in sel)
+                res.update({"arrays": len(sel), "bytes": int(sb), "speedup_of_the_batch": res["looped_ms"] / res["batch_ms"],
+                            "batch_GBps": sb / (res["batch_ms"] * 1e-3) / 1e9, "looped_GBps": sb / (res["looped_ms"] * 1e-3) / 1e9})
+                return res
+            small = [j for j in range(len(xs)) if xs_host[j].itemsize == 8]
+            c2_like = [j for j in range(len(xs)) if xs_host[j].itemsize == 4 and ebs[j] == 1e-4][:1]
+            looped["subsets"] = {"msst19_24_small_fp64": sub(small), "msst19_24_plus_one_fp32_field_at_1e-4": sub(small + c2_like)}
 
-    # algorithmic bytes per element: transform pass of compress reads s, writes 1 (bin) + 4/64 (DC) + 4p
-    # (AC_exact); decompress reads 1 + 4/64 + 4p, writes s.  A list: the arrays of the element type that carries most
-    # of the list's bytes (its launch sequence holds the dominant kernel)
-    def alg_bytes(js):
-        return sum(ns[j] * (xs_host[j].itemsize + 1.0 + 4.0 / 64.0 + 4.0 * infos_all[j].cnt / ns[j]) for j in js)
-    infos_all = infos if many else [info]
-    kern_name = {"c": "k_compress", "d": "k_decompress"}
-    one_launch = bool(infos_all[0].flags & dctz_amd.hip.INFO_ONE_LAUNCH)   # the whole call was ONE kernel (dctz_kernels_one.hip)
-    if one_launch and not many:
-        tn = "double" if es == 8 else "float"
-        kern_name = {"c": f"k_compress_one<{tn}>", "d": f"k_decompress_one<{tn}>"}
-    if many:
-        by = {"f64": [j for j in range(len(xs)) if xs_host[j].itemsize == 8], "f32": [j for j in range(len(xs)) if xs_host[j].itemsize == 4]}
-        dom_seq = max(by, key=lambda nm: sum(ns[j] * xs_host[j].itemsize for j in by[nm]))
-        for nm in seqs:
-            for k in seqs[nm]:
-                seqs[nm][k] /= a.steps
-        acc = dict(seqs[dom_seq])
-        bytes_main = alg_bytes(by[dom_seq])
-        bytes_stats = sum(ns[j] * xs_host[j].itemsize for j in by[dom_seq])
-        kern_name = {"c": f"k_compress_batch<{'double' if dom_seq == 'f64' else 'float'}>", "d": f"k_decompress_batch<{'double' if dom_seq == 'f64' else 'float'}>"}
-        other = "f32" if dom_seq == "f64" else "f64"
-        kern_all = sum(seqs[nm][k] for nm in seqs for k in seqs[nm])
-    else:
-        for k in acc:
-            acc[k] /= a.steps
-        bytes_main = alg_bytes([0])
-        bytes_stats = n * es
-        kern_all = sum(acc.values())
-    t_c = t_c * 1e3 / a.steps
-    t_d = t_d * 1e3 / a.steps
-
-    fused = bool(info.flags & dctz_amd.hip.INFO_STATS_FUSED)     # statistics computed inside k_compress (guess verified)
-    p = sum(i.cnt for i in infos_all) / float(sum(ns))          # exception fraction (of the whole list)
-    ach_c = bytes_main / (acc["c_main"] * 1e-3) / 1e9
-    ach_d = bytes_main / (acc["d_main"] * 1e-3) / 1e9
-    ach_s = bytes_stats / (acc["c_stats"] * 1e-3) / 1e9
-    dominant = "c" if acc["c_main"] >= acc["d_main"] else "d"
-
-    # HBM traffic of the dominant kernel: NOT measured in this run (PMC counters need rocprofv3 passes of their own);
-    # the committed record of the same command on the same build is quoted with its source, or null
-    src_hash = kernel_source_hash()
-    tkey = f"{a.config}_{a.dtype}_{a.n}_{a.mode}_{a.eb:g}"
-    # (the record is keyed by the kernel's full name -- every template argument: variants of one kernel differ in traffic)
-    kern_exact = {"c": ctx.last_kernel(0) or kern_name["c"], "d": ctx.last_kernel(1) or kern_name["d"]}
-    if many:
-        kern_exact = {"c": ctx.last_kernel(2 if dom_seq == "f64" else 3) or kern_name["c"], "d": ctx.last_kernel(4 if dom_seq == "f64" else 5) or kern_name["d"]}
-    traffic, traffic_source = lookup_traffic(os.path.join(ROOT, "profiles", "pmc_traffic.json"), kern_exact[dominant], tkey, src_hash)
-
-    # ---- the entropy stage on the device, rank 0, outside the timed region: what
-    # it costs to turn the streams of the last compress call into the container's three zlib sections in HBM ----
-    entropy = None
-    if rank == 0 and not a.no_entropy_stage and not many:
-        try:
-            cnt = int(info.cnt)
-            secs = [out["bin_index"], out["dc"], out["ac_exact"][:cnt]]
-            raw = [t.numel() * t.element_size() for t in secs]
-            zs = ctx.deflate(secs, literals=[False, True, True])
+        # ---- per-kernel durations (HIP events on the launch stream), same K steps --
+        ctx.set_profiling(True)
+        acc = {"c_stats": 0.0, "c_main": 0.0, "c_tail": 0.0, "d_pre": 0.0, "d_main": 0.0, "d_tail": 0.0}
+        seqs = {"f64": dict(acc), "f32": dict(acc)}                # a list: per element-type launch sequence
+        t_c = t_d = 0.0
+        for _ in range(a.steps):
             torch.cuda.synchronize()
-            tt = []
-            for _ in range(10):
-                e0 = time.perf_counter()
-                zs = ctx.deflate(secs, literals=[False, True, True])   # returns after the stream has drained (it hands the lengths back)
-                tt.append(time.perf_counter() - e0)
-            med = sorted(tt)[len(tt) // 2]
-            entropy = {"what": "dctzhip_deflate of bin_index / DC / AC_exact where k_compress left them: three standard zlib streams in HBM",
-                       "ms": med * 1e3, "raw_bytes": sum(raw), "stream_bytes": int(sum(z.numel() for z in zs)),
-                       "GBps_of_streams": sum(raw) / med / 1e9, "container_ratio": n * es / float(sum(z.numel() for z in zs) + 56),
-                       "note": "not part of `value`; reference: three host threads of zlib, 6.6 s per GiB shard (profiles/r02_e2e_dropin.json)"}
-        except Exception as ex:                            # the stage is reported, never required, by the benchmark
-            entropy = {"error": str(ex)}
+            s0 = time.perf_counter()
+            if many:
+                _, infos, _ = ctx.compress_batch(None, None, mode, prepared=state["cp"])
+            else:
+                _, info = ctx.compress(x, ebs[0], mode, out=out)
+            s1 = time.perf_counter()
+            if many:
+                bt = ctx.batch_timings()
+                for nm in seqs:
+                    seqs[nm]["c_stats"] += bt[nm]["stats_ms"]; seqs[nm]["c_main"] += bt[nm]["main_ms"]; seqs[nm]["c_tail"] += bt[nm]["tail_ms"]
+            else:
+                tm = ctx.timings()
+                acc["c_stats"] += tm["stats_ms"]; acc["c_main"] += tm["main_ms"]; acc["c_tail"] += tm["tail_ms"]
+            s2 = time.perf_counter()
+            if many:
+                ctx.decompress_batch(None, None, None, None, None, None, mode, prepared=state["dp"])
+            else:
+                ctx.decompress(out, info.cnt, n, tdt[0], ebs[0], info.sf, mode, qtable=info.qtable if qt else None, dst=rec)
+            s3 = time.perf_counter()
+            if many:
+                bt = ctx.batch_timings()
+                for nm in seqs:
+                    seqs[nm]["d_pre"] += bt[nm]["stats_ms"]; seqs[nm]["d_main"] += bt[nm]["main_ms"]; seqs[nm]["d_tail"] += bt[nm]["tail_ms"]
+            else:
+                tm = ctx.timings()
+                acc["d_pre"] += tm["stats_ms"]; acc["d_main"] += tm["main_ms"]; acc["d_tail"] += tm["tail_ms"]
+            t_c += s1 - s0; t_d += s3 - s2
+        ctx.set_profiling(False)
+        info = infos[0] if many else info
 
-    # ---- CPU baseline: the oracle (a port), bounded sample, rank 0 only ---
-    cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        from oracle import oracle as O
-        omode = O.QT if a.mode == "qt" else O.EC
-        # the sample: the rank-0 arrays themselves (each bounded by --cpu-sample elements), passed over until about
-        # ten seconds of CPU work are on the clock (a 1 GiB shard: --cpu-repeats passes)
-        samp = [xh[:min(xh.size, a.cpu_sample)] for xh in xs_host]
-        s_bytes = sum(v.size * v.itemsize for v in samp)
-        tc = td = 0.0
-        reps = 0
-        while True:
-            for v, eb in zip(samp, ebs):
-                c0 = time.perf_counter()
-                c = O.compress(v, eb, omode, O.FAST)
-                c1 = time.perf_counter()
-                O.decompress(c, O.FAST)
-                c2 = time.perf_counter()
-                tc += c1 - c0
-                td += c2 - c1
-            reps += 1
-            if (reps >= max(1, a.cpu_repeats) and tc + td >= 3.0) or tc + td >= 20.0 or reps >= 4000:
-                break
-        # the same port on ALL host cores at once ("all cores via one process per shard", core count stated):
-        # contiguous block-aligned slices of the sample, one thread each (the C oracle runs outside the GIL); a list of
-        # arrays: whole arrays dealt round to the threads
-        from concurrent.futures import ThreadPoolExecutor
-        nthr = max(1, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+        # algorithmic bytes per element: transform pass of compress reads s, writes 1 (bin) + 4/64 (DC) + 4p
+        # (AC_exact); decompress reads 1 + 4/64 + 4p, writes s.  A list: the arrays of the element type that carries most
+        # of the list's bytes (its launch sequence holds the dominant kernel)
+        def alg_bytes(js):
+            return sum(ns[j] * (xs_host[j].itemsize + 1.0 + 4.0 / 64.0 + 4.0 * infos_all[j].cnt / ns[j]) for j in js)
+        infos_all = infos if many else [info]
+        kern_name = {"c": "k_compress", "d": "k_decompress"}
+        one_launch = bool(infos_all[0].flags & dctz_amd.hip.INFO_ONE_LAUNCH)   # the whole call was ONE kernel (dctz_kernels_one.hip)
+        if one_launch and not many:
+            tn = "double" if es == 8 else "float"
+            kern_name = {"c": f"k_compress_one<{tn}>", "d": f"k_decompress_one<{tn}>"}
         if many:
-            jobs = [(v, eb) for v, eb in zip(samp, ebs)]
+            by = {"f64": [j for j in range(len(xs)) if xs_host[j].itemsize == 8], "f32": [j for j in range(len(xs)) if xs_host[j].itemsize == 4]}
+            dom_seq = max(by, key=lambda nm: sum(ns[j] * xs_host[j].itemsize for j in by[nm]))
+            for nm in seqs:
+                for k in seqs[nm]:
+                    seqs[nm][k] /= a.steps
+            acc = dict(seqs[dom_seq])
+            bytes_main = alg_bytes(by[dom_seq])
+            bytes_stats = sum(ns[j] * xs_host[j].itemsize for j in by[dom_seq])
+            kern_name = {"c": f"k_compress_batch<{'double' if dom_seq == 'f64' else 'float'}>", "d": f"k_decompress_batch<{'double' if dom_seq == 'f64' else 'float'}>"}
+            other = "f32" if dom_seq == "f64" else "f64"
+            kern_all = sum(seqs[nm][k] for nm in seqs for k in seqs[nm])
         else:
-            m = samp[0].size
-            cuts = [(m * i // nthr) // 64 * 64 for i in range(nthr)] + [m]
-            jobs = [(samp[0][cuts[i]:cuts[i + 1]], ebs[0]) for i in range(nthr)]
+            for k in acc:
+                acc[k] /= a.steps
+            bytes_main = alg_bytes([0])
+            bytes_stats = n * es
+            kern_all = sum(acc.values())
+        t_c = t_c * 1e3 / a.steps
+        t_d = t_d * 1e3 / a.steps
 
-        def one(job):
-            if job[0].size:
-                O.decompress(O.compress(job[0], job[1], omode, O.FAST), O.FAST)
+        fused = bool(info.flags & dctz_amd.hip.INFO_STATS_FUSED)     # statistics computed inside k_compress (guess verified)
+        p = sum(i.cnt for i in infos_all) / float(sum(ns))          # exception fraction (of the whole list)
+        ach_c = bytes_main / (acc["c_main"] * 1e-3) / 1e9
+        ach_d = bytes_main / (acc["d_main"] * 1e-3) / 1e9
+        ach_s = bytes_stats / (acc["c_stats"] * 1e-3) / 1e9
+        dominant = "c" if acc["c_main"] >= acc["d_main"] else "d"
 
-        with ThreadPoolExecutor(nthr) as ex:
-            list(ex.map(one, jobs))                         # warm the threads / page in
-            m0 = time.perf_counter()
-            list(ex.map(one, jobs))
-            tm_all = time.perf_counter() - m0
-        cpu = {"value": reps * s_bytes / (tc + td) / 1e9, "unit": "GB/s (input bytes, compress+decompress)",
-               "cores": 1, "kind": "port",
-               "sample": f"the rank-0 workload ({len(samp)} array(s), {s_bytes / 2**20:.1f} MiB) x {reps} passes, oracle FAST "
-                         f"flow, compress {tc:.2f} s + decompress {td:.2f} s in all; zlib excluded on both sides",
-               "compress_GBps": reps * s_bytes / tc / 1e9, "decompress_GBps": reps * s_bytes / td / 1e9,
-               "all_cores": {"cores": nthr, "host_cpu_count": os.cpu_count(), "value": s_bytes / tm_all / 1e9,
-                             "note": "same port, one pass: " + ("whole arrays dealt to the threads" if many else
-                                     "the sample cut into one slice per available core (each slice its own sf)")}}
+        # HBM traffic of the dominant kernel: NOT measured in this run (PMC counters need rocprofv3 passes of their own);
+        # the committed record of the same command on the same build is quoted with its source, or null
+        src_hash = kernel_source_hash()
+        tkey = f"{a.config}_{a.dtype}_{a.n}_{a.mode}_{a.eb:g}"
+        # (the record is keyed by the kernel's full name -- every template argument: variants of one kernel differ in traffic)
+        kern_exact = {"c": ctx.last_kernel(0) or kern_name["c"], "d": ctx.last_kernel(1) or kern_name["d"]}
+        if many:
+            kern_exact = {"c": ctx.last_kernel(2 if dom_seq == "f64" else 3) or kern_name["c"], "d": ctx.last_kernel(4 if dom_seq == "f64" else 5) or kern_name["d"]}
+        traffic, traffic_source = lookup_traffic(os.path.join(ROOT, "profiles", "pmc_traffic.json"), kern_exact[dominant], tkey, src_hash)
+
+        # ---- the entropy stage on the device, rank 0, outside the timed region: what
+        # it costs to turn the streams of the last compress call into the container's three zlib sections in HBM ----
+        entropy = None
+        if rank == 0 and not a.no_entropy_stage and not many:
+            try:
+                cnt = int(info.cnt)
+                secs = [out["bin_index"], out["dc"], out["ac_exact"][:cnt]]
+                raw = [t.numel() * t.element_size() for t in secs]
+                zs = ctx.deflate(secs, literals=[False, True, True])
+                torch.cuda.synchronize()
+                tt = []
+                for _ in range(10):
+                    e0 = time.perf_counter()
+                    zs = ctx.deflate(secs, literals=[False, True, True])   # returns after the stream has drained (it hands the lengths back)
+                    tt.append(time.perf_counter() - e0)
+                med = sorted(tt)[len(tt) // 2]
+                entropy = {"what": "dctzhip_deflate of bin_index / DC / AC_exact where k_compress left them: three standard zlib streams in HBM",
+                           "ms": med * 1e3, "raw_bytes": sum(raw), "stream_bytes": int(sum(z.numel() for z in zs)),
+                           "GBps_of_streams": sum(raw) / med / 1e9, "container_ratio": n * es / float(sum(z.numel() for z in zs) + 56),
+                           "note": "not part of `value`; reference: three host threads of zlib, 6.6 s per GiB shard (profiles/r02_e2e_dropin.json)"}
+            except Exception as ex:                            # the stage is reported, never required, by the benchmark
+                entropy = {"error": str(ex)}
+
+        # ---- CPU baseline: the oracle (a port), bounded sample, rank 0 only ---
+        cpu = None
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            from oracle import oracle as O
+            omode = O.QT if a.mode == "qt" else O.EC
+            # the sample: the rank-0 arrays themselves (each bounded by --cpu-sample elements), passed over until about
+            # ten seconds of CPU work are on the clock (a 1 GiB shard: --cpu-repeats passes)
+            samp = [xh[:min(xh.size, a.cpu_sample)] for xh in xs_host]
+            s_bytes = sum(v.size * v.itemsize for v in samp)
+            tc = td = 0.0
+            reps = 0
+            while True:
+                for v, eb in zip(samp, ebs):
+                    c0 = time.perf_counter()
+                    c = O.compress(v, eb, omode, O.FAST)
+                    c1 = time.perf_counter()
+                    O.decompress(c, O.FAST)
+                    c2 = time.perf_counter()
+                    tc += c1 - c0
+                    td += c2 - c1
+                reps += 1
+                if (reps >= max(1, a.cpu_repeats) and tc + td >= 3.0) or tc + td >= 20.0 or reps >= 4000:
+                    break
+            # the same port on ALL host cores at once ("all cores via one process per shard", core count stated):
+            # contiguous block-aligned slices of the sample, one thread each (the C oracle runs outside the GIL); a list of
+            # arrays: whole arrays dealt round to the threads
+            from concurrent.futures import ThreadPoolExecutor
+            nthr = max(1, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+            if many:
+                jobs = [(v, eb) for v, eb in zip(samp, ebs)]
+            else:
+                m = samp[0].size
+                cuts = [(m * i // nthr) // 64 * 64 for i in range(nthr)] + [m]
+                jobs = [(samp[0][cuts[i]:cuts[i + 1]], ebs[0]) for i in range(nthr)]
+
+            def one(job):
+                if job[0].size:
+                    O.decompress(O.compress(job[0], job[1], omode, O.FAST), O.FAST)
+
+            with ThreadPoolExecutor(nthr) as ex:
+                list(ex.map(one, jobs))                         # warm the threads / page in
+                m0 = time.perf_counter()
+                list(ex.map(one, jobs))
+                tm_all = time.perf_counter() - m0
+            cpu = {"value": reps * s_bytes / (tc + td) / 1e9, "unit": "GB/s (input bytes, compress+decompress)",
+                   "cores": 1, "kind": "port",
+                   "sample": f"the rank-0 workload ({len(samp)} array(s), {s_bytes / 2**20:.1f} MiB) x {reps} passes, oracle FAST "
+                             f"flow, compress {tc:.2f} s + decompress {td:.2f} s in all; zlib excluded on both sides",
+                   "compress_GBps": reps * s_bytes / tc / 1e9, "decompress_GBps": reps * s_bytes / td / 1e9,
+                   "all_cores": {"cores": nthr, "host_cpu_count": os.cpu_count(), "value": s_bytes / tm_all / 1e9,
+                                 "note": "same port, one pass: " + ("whole arrays dealt to the threads" if many else
+                                         "the sample cut into one slice per available core (each slice its own sf)")}}
 
     # every rank's own figures (an N-GPU run: the curve's points come with the spread behind them)
-    mine_rank = {"rank": rank, "device": f"cuda:{dev}", "ms_per_step_local": local_elapsed * 1e3 / a.steps,
-                 "k_compress_ms": acc["c_main"], "k_decompress_ms": acc["d_main"], "compress_tail_ms": acc["c_tail"],
-                 "decompress_count_ms": acc["d_pre"], "exception_fraction": p}
+    if not a.full:
+        p = sum(i.cnt for i in infos) / float(sum(ns))          # exception fraction (of the whole list)
+        fused = bool(info.flags & dctz_amd.hip.INFO_STATS_FUSED)
+        one_launch = bool(info.flags & dctz_amd.hip.INFO_ONE_LAUNCH)
+    mine_rank = {"rank": rank, "device": f"cuda:{dev}", "ms_per_step_local": (local_elapsed if a.full else u_local) * 1e3 / a.steps}
+    if a.full:
+        mine_rank.update({"k_compress_ms": acc["c_main"], "k_decompress_ms": acc["d_main"], "compress_tail_ms": acc["c_tail"],
+                          "decompress_count_ms": acc["d_pre"]})
+    mine_rank["exception_fraction"] = p
     per_rank = [None] * world
     if dist is not None:
         dist.all_gather_object(per_rank, mine_rank)
@@ -645,8 +726,6 @@ def run_rank(a, rank, local_rank, world):
         per_rank = [mine_rank]
     if rank == 0:
         value = in_bytes * world / (ms_per_step * 1e-3) / 1e9
-        kern_sum = kern_all
-        dom = {"c": (acc["c_main"], ach_c), "d": (acc["d_main"], ach_d)}[dominant]
         headline = a.config == "c4" and a.dtype == "f64" and a.mode == "ec" and a.eb == 1e-3
         line = {
             "metric": "compress+decompress GB/s (input bytes), fp64 1e-3 EC" if headline
@@ -655,52 +734,58 @@ def run_rank(a, rank, local_rank, world):
             "value": value, "unit": "GB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             # value / ms_per_step: the K steps behind nothing but the W warm-up steps of a fresh process, what a caller who makes
-            # W + K calls sees.  settled_*: the same K steps timed a second time in this run, behind `settle` (untimed steps) and
-            # another W warm-up steps -- the steady state; both are of this build and this box.
-            "settled_ms_per_step": settled_ms, "settled_value": in_bytes * world / (settled_ms * 1e-3) / 1e9,
-            "settle": {"ms": a.settle_ms, "steps": settle_steps, "note": "untimed steps between the as-asked window and the settled one: the "
-                       "power management's dip under fresh load (steps 4-12 of a process run 12 % slow, tools/warm_probe.py)"},
+            # W + K calls sees.  --full adds settled_*: the same K steps timed a second time in this run, behind `settle`
+            # (untimed steps) and another W warm-up steps -- the steady state; both are of this build and this box.
             "unsettled_ms_per_step": unsettled_ms, "unsettled_value": in_bytes * world / (unsettled_ms * 1e-3) / 1e9,
-            "kernel_source_hash": src_hash,
+            "full": a.full,
+            "kernel_source_hash": kernel_source_hash(),
             "dtype": a.dtype if not many else "f64+f32", "data": "synthetic",
             "config": {"workload": wl_name + ("; step = dctzhip_compress + dctzhip_decompress" if not many else "") + ", inputs resident in HBM",
                        "config": a.config, "arrays_per_gpu": len(xs), "elements_per_gpu": int(sum(ns)), "bytes_per_gpu": int(in_bytes),
                        "exception_fraction": p, "parallelism": f"shard-per-gpu x{world}"},
             "ranks_seen": len({d["rank"] for d in devices}), "devices": devices, "per_rank": per_rank,
             "pct_hbm_peak_input": 100.0 * (in_bytes / (ms_per_step * 1e-3) / 1e9) / HBM_PEAK_GBPS,
-            # kernel: the name rocprofv3 lists the timed kernel under (what the context says it launched last); which: how it was chosen
-            "roofline": {"bound": "hbm", "kernel": kern_exact[dominant],
-                         "which": "the longer of the two big kernels in THIS run" + (f", launch sequence of the {dom_seq} arrays: they carry most of the list's bytes" if many else ""),
-                         "achieved": dom[1], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": dom[1] / HBM_PEAK_GBPS,
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": bytes_main, "avg_launch_ms": dom[0],
-                         "k_compress_frac": ach_c / HBM_PEAK_GBPS, "k_decompress_frac": ach_d / HBM_PEAK_GBPS},
             "statistics": ("inside the one kernel of the call: every workgroup posts the decade of its maximum, the scaling factor follows "
                            "from a sweep of those (dctz_kernels_one.hip)") if one_launch else
                           ("fused into k_compress behind a sampled guess of sf, verified every step "
                            "(k_stats below = the 1/64 sample + final reduction)") if fused else "separate k_stats pass",
             "one_launch_per_call": one_launch,
-            "kernels": {"k_stats": ({"ms": acc["c_stats"], "sampled_fraction": 1.0 / 64.0} if fused else
-                                    {"ms": acc["c_stats"], "GBps": ach_s, "frac": ach_s / HBM_PEAK_GBPS}),
-                        "k_compress": {"ms": acc["c_main"], "GBps": ach_c, "frac": ach_c / HBM_PEAK_GBPS},
-                        "k_decompress": {"ms": acc["d_main"], "GBps": ach_d, "frac": ach_d / HBM_PEAK_GBPS},
-                        "compress_tail_ms": acc["c_tail"], "decompress_count_scan_ms": acc["d_pre"], "decompress_tail_ms": acc["d_tail"],
-                        "sum_ms": kern_sum},
-            # step time minus the event spans.  The spans come from a SEPARATE, profiled run of the same K steps and carry the
-            # event markers' own cost (about 4 us per span); since the host returns from a call while its last kernel is still
-            # running (early hand-off) the unprofiled step can be SHORTER than their sum -- the difference is then negative
-            "host_gap_ms": ms_per_step - kern_sum,
-            "host_call_ms": {"compress": t_c, "decompress": t_d},
-            "compress_GBps_input": in_bytes / (t_c * 1e-3) / 1e9,
-            "decompress_GBps_input": in_bytes / (t_d * 1e-3) / 1e9,
-            "cpu_baseline": cpu,
-            "entropy_stage": entropy,
         }
-        if many:
-            line["kernels"]["other_sequence"] = {"element_type": other, **seqs[other]}
-            line["looped"] = looped
-        if with_scaled is not None:
-            line["with_scaled_copy"] = with_scaled
+        if a.full:
+            kern_sum = kern_all
+            dom = {"c": (acc["c_main"], ach_c), "d": (acc["d_main"], ach_d)}[dominant]
+            line.update({
+                "settled_ms_per_step": settled_ms, "settled_value": in_bytes * world / (settled_ms * 1e-3) / 1e9,
+                "settle": {"ms": a.settle_ms, "steps": settle_steps, "note": "untimed steps between the as-asked window and the settled one: the "
+                           "power management's dip under fresh load (steps 4-12 of a process run 12 % slow, tools/warm_probe.py)"},
+                # kernel: the name rocprofv3 lists the timed kernel under (what the context says it launched last); which: how it was chosen
+                "roofline": {"bound": "hbm", "kernel": kern_exact[dominant],
+                             "which": "the longer of the two big kernels in THIS run" + (f", launch sequence of the {dom_seq} arrays: they carry most of the list's bytes" if many else ""),
+                             "achieved": dom[1], "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": dom[1] / HBM_PEAK_GBPS,
+                             "traffic": traffic, "traffic_source": traffic_source,
+                             "algorithmic_bytes_per_launch": bytes_main, "avg_launch_ms": dom[0],
+                             "k_compress_frac": ach_c / HBM_PEAK_GBPS, "k_decompress_frac": ach_d / HBM_PEAK_GBPS},
+                "kernels": {"k_stats": ({"ms": acc["c_stats"], "sampled_fraction": 1.0 / 64.0} if fused else
+                                        {"ms": acc["c_stats"], "GBps": ach_s, "frac": ach_s / HBM_PEAK_GBPS}),
+                            "k_compress": {"ms": acc["c_main"], "GBps": ach_c, "frac": ach_c / HBM_PEAK_GBPS},
+                            "k_decompress": {"ms": acc["d_main"], "GBps": ach_d, "frac": ach_d / HBM_PEAK_GBPS},
+                            "compress_tail_ms": acc["c_tail"], "decompress_count_scan_ms": acc["d_pre"], "decompress_tail_ms": acc["d_tail"],
+                            "sum_ms": kern_sum},
+                # step time minus the event spans.  The spans come from a SEPARATE, profiled run of the same K steps and carry the
+                # event markers' own cost (about 4 us per span); since the host returns from a call while its last kernel is still
+                # running (early hand-off) the unprofiled step can be SHORTER than their sum -- the difference is then negative
+                "host_gap_ms": ms_per_step - kern_sum,
+                "host_call_ms": {"compress": t_c, "decompress": t_d},
+                "compress_GBps_input": in_bytes / (t_c * 1e-3) / 1e9,
+                "decompress_GBps_input": in_bytes / (t_d * 1e-3) / 1e9,
+                "cpu_baseline": cpu,
+                "entropy_stage": entropy,
+            })
+            if many:
+                line["kernels"]["other_sequence"] = {"element_type": other, **seqs[other]}
+                line["looped"] = looped
+            if with_scaled is not None:
+                line["with_scaled_copy"] = with_scaled
         if a.rehearse_one_gpu:
             line["rehearsal"] = (f"{world} ranks SHARE one GPU (gloo barriers; the gather runs through the RCCL test double of "
                                  "tests/c/rccl_double.cpp): the N > 1 code path end to end, NOT a scaling measurement")
@@ -712,7 +797,8 @@ def run_rank(a, rank, local_rank, world):
     # reports has been measured by now.  This is the one phase that talks to a second collective library instance (RCCL
     # through the C ABI's own dlopen) and that no box of this project could ever run on N GPUs: if it fails on any rank, or
     # does not finish in --gather-timeout seconds, the line goes out without it (with the reason) instead of not at all.
-    if dist is not None and not many:
+    # (--full only: a plain run's line has no with_gather)
+    if dist is not None and not many and a.full:
         import threading
         barrier()                                             # (rank 0 comes from its CPU baseline: the timers below start together)
 

@@ -53,7 +53,7 @@ def test_dropin_exports_reference_api(so):
     C.CDLL(os.path.join(LIB, so))                     # loads, resolves libdctzhip via $ORIGIN
 
 
-def test_header_layout_matches_reference_abi():
+def test_header_layout_matches_reference_abi(tmp_path):
     """struct header is 56 bytes with the offsets recorded in SURVEY 8b; t_var is 32."""
     code = r'''
 #include <stddef.h>
@@ -64,7 +64,7 @@ int main(void){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(struc
  offsetof(struct header,DC_sz_compressed), offsetof(struct header,AC_exact_sz_compressed), sizeof(t_var)); return 0; }
 '''
     for flags, extra in (([], None), (["-DUSE_QTABLE"], 52)):
-        exe = "/tmp/dctz_hdr_probe"
+        exe = str(tmp_path / "dctz_hdr_probe")
         subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe] + flags,
                        input=code, text=True, check=True)
         vals = [int(v) for v in subprocess.check_output([exe], text=True).split()]

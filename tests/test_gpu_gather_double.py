@@ -78,7 +78,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--n", "256", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-entropy-stage"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-entropy-stage"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and [d["rank"] for d in line["devices"]] == [0, 1]
@@ -93,7 +93,7 @@ def test_bench_line_survives_a_gather_that_cannot_start():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["DCTZ_BENCH_RCCL_OVERRIDE"] = "/nonexistent/librccl.so"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--n", "256", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-entropy-stage"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-entropy-stage"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["value"] > 0

@@ -8,8 +8,8 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 for rep in 1 2 3; do
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-entropy-stage "$@" > $O/a$rep.json 2> $O/a$rep.err || exit 1
-  DCTZHIP_LIBRARY=$R/$LIBB timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-entropy-stage "$@" > $O/b$rep.json 2> $O/b$rep.err || exit 1
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-entropy-stage "$@" > $O/a$rep.json 2> $O/a$rep.err || exit 1
+  DCTZHIP_LIBRARY=$R/$LIBB timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-entropy-stage "$@" > $O/b$rep.json 2> $O/b$rep.err || exit 1
 done
 python3 - $O <<'PY'
 import json, sys, glob

@@ -7,7 +7,7 @@ mkdir -p $OUT
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
     name=${v%%=*}; path=${v#*=}
-    DCTZHIP_LIBRARY=$PWD/$path python3 bench.py --no-cpu-baseline --steps 40 ${BENCH_ARGS:-} > $OUT/${name}_$r.json 2> $OUT/${name}_$r.err || echo "run $name $r failed"
+    DCTZHIP_LIBRARY=$PWD/$path python3 bench.py --full --no-cpu-baseline --steps 40 ${BENCH_ARGS:-} > $OUT/${name}_$r.json 2> $OUT/${name}_$r.err || echo "run $name $r failed"
   done
 done
 python3 - "$OUT" <<'PY'

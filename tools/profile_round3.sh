@@ -15,7 +15,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-B="python3 bench.py"
+B="python3 bench.py --full"
 timeout -k 10 300 $B --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err
 timeout -k 10 300 $B --steps 20 --warmup 5 --settle-ms 0 --no-cpu-baseline --no-entropy-stage > $O/bench_driver_form_unsettled.json 2> $O/bench_driver_form_unsettled.err
 python3 tools/warm_probe.py 80 > $O/warm_probe.json 2> $O/warm_probe.err

@@ -18,7 +18,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-B="python3 bench.py"
+B="python3 bench.py --full"
 if [[ $PART == *A* ]]; then
 timeout -k 10 300 $B --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err
 echo "driver form done"

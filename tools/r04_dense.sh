@@ -4,9 +4,9 @@ set -o pipefail
 D=gpurun_out/${1:-r04f}
 mkdir -p $D
 for eb in 1e-3 1e-4 1e-5; do
-  python3 bench.py --no-cpu-baseline --no-entropy-stage --eb $eb --steps 50 --warmup 10 > $D/bench_f64_ec_$eb.json 2> $D/bench_f64_ec_$eb.err
+  python3 bench.py --full --no-cpu-baseline --no-entropy-stage --eb $eb --steps 50 --warmup 10 > $D/bench_f64_ec_$eb.json 2> $D/bench_f64_ec_$eb.err
 done
-python3 bench.py --config c3 --no-cpu-baseline --no-entropy-stage --steps 50 --warmup 10 > $D/bench_c3.json 2> $D/bench_c3.err
+python3 bench.py --full --config c3 --no-cpu-baseline --no-entropy-stage --steps 50 --warmup 10 > $D/bench_c3.json 2> $D/bench_c3.err
 python3 - <<PY
 import json
 for nm in ("f64_ec_1e-3", "f64_ec_1e-4", "f64_ec_1e-5", "c3"):

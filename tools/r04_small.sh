@@ -4,8 +4,8 @@ set -o pipefail
 D=gpurun_out/${1:-r04a}
 mkdir -p $D
 for c in c1 c2; do
-  python3 bench.py --config $c --no-cpu-baseline --no-entropy-stage > $D/bench_$c.json 2> $D/bench_$c.err
-  DCTZHIP_ONE=0 python3 bench.py --config $c --no-cpu-baseline --no-entropy-stage > $D/bench_${c}_chain.json 2> $D/bench_${c}_chain.err
+  python3 bench.py --full --config $c --no-cpu-baseline --no-entropy-stage > $D/bench_$c.json 2> $D/bench_$c.err
+  DCTZHIP_ONE=0 python3 bench.py --full --config $c --no-cpu-baseline --no-entropy-stage > $D/bench_${c}_chain.json 2> $D/bench_${c}_chain.err
 done
 python3 - <<PY
 import json

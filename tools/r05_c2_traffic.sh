@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-B="python3 bench.py --config c2 --no-cpu-baseline --no-entropy-stage --steps 20 --warmup 5"
+B="python3 bench.py --full --config c2 --no-cpu-baseline --no-entropy-stage --steps 20 --warmup 5"
 timeout -k 10 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -d $O/t1 -o t1 -- $B > /dev/null 2> $O/t1.err
 timeout -k 10 300 rocprofv3 --pmc TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum -d $O/t2 -o t2 -- $B > /dev/null 2> $O/t2.err
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/t3 -o t3 -- $B > /dev/null 2> $O/t3.err

@@ -9,8 +9,8 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 for rep in 1 2 3; do
-  DCTZHIP_EO=0 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-entropy-stage "$@" > $O/a$rep.json 2> $O/a$rep.err || exit 1
-  DCTZHIP_EO=1 timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-entropy-stage "$@" > $O/b$rep.json 2> $O/b$rep.err || exit 1
+  DCTZHIP_EO=0 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-entropy-stage "$@" > $O/a$rep.json 2> $O/a$rep.err || exit 1
+  DCTZHIP_EO=1 timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-entropy-stage "$@" > $O/b$rep.json 2> $O/b$rep.err || exit 1
 done
 python3 - $O <<'PY'
 import json, sys, glob
@@ -21,6 +21,6 @@ for f in sorted(glob.glob(o + "/[ab][0-9].json")):
     print(f[-7:], "ms/step %.4f unsettled %.4f" % (d["ms_per_step"], d.get("unsettled_ms_per_step", 0)), {a: round(b, 4) for a, b in k.items()})
 PY
 export DCTZHIP_EO=1
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python3 bench.py --no-cpu-baseline --no-entropy-stage "$@" > $O/kt_bench.json 2> $O/kt.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python3 bench.py --full --no-cpu-baseline --no-entropy-stage "$@" > $O/kt_bench.json 2> $O/kt.err
 python3 tools/pmc_summary.py $O/kt > $O/kernel_stats_eo.csv 2>&1
 head -12 $O/kernel_stats_eo.csv

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-B="python3 bench.py --no-cpu-baseline --no-entropy-stage --steps 5 --warmup 2"
+B="python3 bench.py --full --no-cpu-baseline --no-entropy-stage --steps 5 --warmup 2"
 for eo in 0 1; do
   export DCTZHIP_EO=$eo
   timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $O/p1_$eo -o p1 -- $B "$@" > /dev/null 2> $O/p1_$eo.err

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-B="python3 bench.py --no-cpu-baseline --no-entropy-stage --steps 5 --warmup 2"
+B="python3 bench.py --full --no-cpu-baseline --no-entropy-stage --steps 5 --warmup 2"
 for eo in 0 1; do
   export DCTZHIP_EO=$eo
   timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_BRANCH -d $O/q1_$eo -o q1 -- $B "$@" > /dev/null 2> $O/q1_$eo.err

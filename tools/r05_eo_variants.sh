@@ -23,7 +23,7 @@ O=$R/gpurun_out/$TAG; mkdir -p $O
 for rep in 1 2 3; do
   for name in "$@"; do
     if [ $name = old ]; then E=0; L=$R/dctz_amd/lib/libdctzhip.so; elif [ $name = base ]; then E=1; L=$R/dctz_amd/lib/libdctzhip.so; else E=1; L=$R/dctz_amd/lib_$name/libdctzhip.so; fi
-    DCTZHIP_EO=$E DCTZHIP_LIBRARY=$L timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-entropy-stage --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/${name}_$rep.json 2> $O/${name}_$rep.err || echo "run $name $rep failed"
+    DCTZHIP_EO=$E DCTZHIP_LIBRARY=$L timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-entropy-stage --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/${name}_$rep.json 2> $O/${name}_$rep.err || echo "run $name $rep failed"
   done
 done
 python3 - $O "$@" <<'PY'

@@ -7,7 +7,7 @@ O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 for rep in $(seq 1 ${REPS:-3}); do for v in "$@"; do
   name=${v%%=*}; dir=${v#*=}
-  DCTZHIP_LIBRARY=$R/dctz_amd/$dir/libdctzhip.so timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-entropy-stage --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/${name}_$rep.json 2> $O/${name}_$rep.err || echo "run $name $rep failed"
+  DCTZHIP_LIBRARY=$R/dctz_amd/$dir/libdctzhip.so timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-entropy-stage --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/${name}_$rep.json 2> $O/${name}_$rep.err || echo "run $name $rep failed"
 done; done
 python3 - $O "$@" <<'PY'
 import json, sys, glob, statistics
