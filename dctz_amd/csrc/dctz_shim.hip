@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <algorithm>
 #include <atomic>
 #include <thread>
 #include <vector>
@@ -909,6 +910,62 @@ static int check_common(dctzhip_ctx* c, size_t n, int dtype, int mode) {
 }
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ---- the buffers of one call against each other (include/dctz_hip.h, "Buffers of one call") ----
+// Every buffer of a call is a byte range: READ (an input), IN_PLACE (an input that its own item divides by sf at the end:
+// d_scaled == d_in) or OUT (bin_index, DC, the capacity of AC_exact, a separate scaled copy, the coefficient tap, a decode's
+// output).  Any number of READ ranges may overlap each other and IN_PLACE ranges; everything else that overlaps is refused.
+namespace {
+enum { SPAN_READ = 0, SPAN_IN_PLACE = 1, SPAN_OUT = 2 };
+struct Span { uintptr_t lo, hi; int kind, item; };
+}
+static void add_span(Span* v, size_t* m, const void* p, size_t bytes, int kind, int item) {
+  if (p && bytes) v[(*m)++] = Span{(uintptr_t)p, (uintptr_t)p + bytes, kind, item};
+}
+// Sorted by start, a range overlaps an earlier one iff that one ends beyond its start: O(m log m).  shared (or null): set for
+// every item whose IN_PLACE range another item reads -- its division has to wait for every read of the call.  In-place
+// ranges are disjoint once the check passes, so the last one met is the only one that can cover a later start.
+static int check_spans(dctzhip_ctx* c, Span* v, size_t m, const char* what, char* shared) {
+  std::sort(v, v + m, [](const Span& a, const Span& b) { return a.lo < b.lo; });
+  uintptr_t end_any = 0, end_written = 0, end_out = 0, end_read = 0, ip_hi = 0;
+  int ip_item = -1;
+  for (size_t i = 0; i < m; i++) {
+    const Span& s = v[i];
+    const uintptr_t end = s.kind == SPAN_OUT ? end_any : s.kind == SPAN_IN_PLACE ? end_written : end_out;
+    if (end > s.lo)
+      return fail(c, DCTZHIP_E_ARG, "%s: a buffer of array %d overlaps %s of the call", what, s.item,
+                  s.kind == SPAN_READ ? "an output" : s.kind == SPAN_IN_PLACE ? "an output or another in-place range" : "another buffer");
+    if (shared) {
+      if (s.kind == SPAN_READ && ip_hi > s.lo && ip_item != s.item) shared[ip_item] = 1;
+      if (s.kind == SPAN_IN_PLACE && end_read > s.lo) shared[s.item] = 1;
+    }
+    end_any = std::max(end_any, s.hi);
+    if (s.kind != SPAN_READ) end_written = std::max(end_written, s.hi);
+    if (s.kind == SPAN_OUT) end_out = std::max(end_out, s.hi);
+    if (s.kind == SPAN_READ) end_read = std::max(end_read, s.hi);
+    if (s.kind == SPAN_IN_PLACE) { ip_hi = s.hi; ip_item = s.item; }
+  }
+  return DCTZHIP_OK;
+}
+// the ranges of one compress item; d_coef (single calls only) is n elements of the data type
+static void compress_spans(Span* v, size_t* m, int item, const void* d_in, size_t n, int dtype, const void* d_bin, const void* d_dc,
+                           const void* d_ac, const void* d_scaled, const void* d_coef) {
+  const size_t es = dtype == DCTZHIP_F64 ? 8 : 4;
+  const bool in_place = d_scaled && d_scaled == d_in;
+  add_span(v, m, d_in, n * es, in_place ? SPAN_IN_PLACE : SPAN_READ, item);
+  add_span(v, m, d_bin, n, SPAN_OUT, item);
+  add_span(v, m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_OUT, item);
+  add_span(v, m, d_ac, n * sizeof(float), SPAN_OUT, item);
+  if (!in_place) add_span(v, m, d_scaled, n * es, SPAN_OUT, item);
+  add_span(v, m, d_coef, n * es, SPAN_OUT, item);
+}
+static void decompress_spans(Span* v, size_t* m, int item, const void* d_bin, const void* d_dc, const void* d_ac, uint32_t ac_count,
+                             size_t n, int dtype, const void* d_out) {
+  add_span(v, m, d_bin, n, SPAN_READ, item);
+  add_span(v, m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, item);
+  add_span(v, m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, item);
+  add_span(v, m, d_out, n * (dtype == DCTZHIP_F64 ? 8 : 4), SPAN_OUT, item);
+}
+
 // remainder-block tables -> device (cached per (l, dtype))
 template <typename T>
 static int upload_rtab(dctzhip_ctx* c, int l) {
@@ -1604,6 +1661,13 @@ extern "C" int dctzhip_compress(dctzhip_ctx* c, const void* d_in, size_t n, int 
       (d_scaled && !aligned16(d_scaled)) || (d_coef && !aligned16(d_coef)))
     return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
   if (eb < 1E-6) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
+  {
+    Span sp[6];
+    size_t m = 0;
+    compress_spans(sp, &m, 0, d_in, n, dtype, d_bin, d_dc, d_ac, d_scaled, d_coef);
+    rc = check_spans(c, sp, m, "dctzhip_compress", nullptr);
+    if (rc) return rc;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   rc = ensure_scratch(c, n, dtype, mode);
   if (rc) return rc;
@@ -1779,6 +1843,13 @@ extern "C" int dctzhip_decompress(dctzhip_ctx* c, const void* d_bin, const float
   if (!d_bin || !d_dc || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   if (!aligned16(d_bin) || !aligned16(d_out)) return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
   if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    Span sp[4];
+    size_t m = 0;
+    decompress_spans(sp, &m, 0, d_bin, d_dc, d_ac, ac_count, n, dtype, d_out);
+    rc = check_spans(c, sp, m, "dctzhip_decompress", nullptr);
+    if (rc) return rc;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   rc = ensure_scratch(c, n, dtype, DCTZHIP_EC, false);
   if (rc) return rc;
@@ -2605,7 +2676,8 @@ static int batch_one_decompress(dctzhip_ctx* c, int k, const dctzhip_batch_ditem
   return DCTZHIP_OK;
 }
 
-extern "C" int dctzhip_compress_batch(dctzhip_ctx* c, int k, const dctzhip_batch_citem* items, int mode, dctzhip_cinfo* infos) {
+extern "C" int dctzhip_compress_batch(dctzhip_ctx* c, int k, const dctzhip_batch_citem* items_in, int mode, dctzhip_cinfo* infos) {
+  const dctzhip_batch_citem* items = items_in;
   if (!c) return DCTZHIP_E_ARG;
   if (k < 0 || (k && !items)) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_batch: bad arguments");
   if (k == 0) return DCTZHIP_OK;
@@ -2617,6 +2689,30 @@ extern "C" int dctzhip_compress_batch(dctzhip_ctx* c, int k, const dctzhip_batch
     if (!aligned16(it.d_in) || !aligned16(it.d_bin_index) || !aligned16(it.d_dc) || !aligned16(it.d_ac_exact) || (it.d_scaled && !aligned16(it.d_scaled)))
       return fail(c, DCTZHIP_E_ARG, "array %d: device buffers must be 16-byte aligned", i);
     if (it.error_bound < 1E-6) return fail(c, DCTZHIP_E_BOUND, "array %d: ERROR BOUND is not acceptable", i);   // dctz-comp-lib.c:135-138
+  }
+  // Every item compresses its input as it was when the call was made.  An item that scales its input in place while another
+  // item reads those bytes -- in another sequence, on the other chain, on the single-array path or in a redo -- is planned
+  // as a reader (no scaled copy) and its division runs at the very end, behind every read of the call.
+  std::vector<char> deferred((size_t)k, 0);
+  bool any_deferred = false;
+  {
+    std::vector<Span> sp(5 * (size_t)k);
+    size_t m = 0;
+    for (int i = 0; i < k; i++) {
+      const dctzhip_batch_citem& it = items[i];
+      compress_spans(sp.data(), &m, i, it.d_in, it.n, it.dtype, it.d_bin_index, it.d_dc, it.d_ac_exact, it.d_scaled, nullptr);
+    }
+    int rc = check_spans(c, sp.data(), m, "dctzhip_compress_batch", deferred.data());
+    if (rc) return rc;
+    for (int i = 0; i < k; i++) any_deferred = any_deferred || deferred[i];
+  }
+  std::vector<dctzhip_batch_citem> planned;
+  std::vector<dctzhip_cinfo> own_infos;
+  if (any_deferred) {
+    planned.assign(items_in, items_in + k);
+    for (int i = 0; i < k; i++) if (deferred[i]) planned[i].d_scaled = nullptr;
+    items = planned.data();
+    if (!infos) { own_infos.resize((size_t)k); infos = own_infos.data(); }     // (the deferred divisions need the sf)
   }
   HIPCHK(c, hipSetDevice(c->device));
   const bool box = c->handoff != 0 && c->dev_sf && c->sf_nk[0] > 0 && c->sf_nk[1] > 0;
@@ -2742,6 +2838,16 @@ extern "C" int dctzhip_compress_batch(dctzhip_ctx* c, int k, const dctzhip_batch
                               infos ? &infos[i] : nullptr);
     if (rc) return rc;
   }
+  // the deferred in-place divisions, on the context's stream behind both chains and every single-array call (k_scale: the
+  // division of k_scale_batch, dctz-comp-lib.c:193-216)
+  for (int i = 0; i < k && any_deferred; i++) {
+    if (!deferred[i]) continue;
+    const dctzhip_batch_citem& it = items_in[i];
+    const double sf = infos[i].sf;
+    if (it.dtype == DCTZHIP_F64) { if (sf != 1.0) launch_scale<double>((const double*)it.d_in, (double*)it.d_scaled, it.n, sf, c->num_cu * 8, c->stream); }
+    else if ((float)sf != 1.0f) launch_scale<float>((const float*)it.d_in, (float*)it.d_scaled, it.n, (float)sf, c->num_cu * 8, c->stream);
+  }
+  if (any_deferred) HIPCHK(c, hipGetLastError());
   if (c->blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
   return DCTZHIP_OK;
 }
@@ -2844,6 +2950,14 @@ extern "C" int dctzhip_decompress_batch(dctzhip_ctx* c, int k, const dctzhip_bat
     if (!aligned16(it.d_bin_index) || !aligned16(it.d_out)) return fail(c, DCTZHIP_E_ARG, "array %d: device buffers must be 16-byte aligned", i);
     if (mode == DCTZHIP_QT && !it.qtable_host) return fail(c, DCTZHIP_E_ARG, "array %d: QT mode needs the 64-entry table", i);
     if (status) status[i] = DCTZHIP_OK;
+  }
+  {
+    std::vector<Span> sp(4 * (size_t)k);
+    size_t m = 0;
+    for (int i = 0; i < k; i++)
+      decompress_spans(sp.data(), &m, i, items[i].d_bin_index, items[i].d_dc, items[i].d_ac_exact, items[i].ac_count, items[i].n, items[i].dtype, items[i].d_out);
+    int rc = check_spans(c, sp.data(), m, "dctzhip_decompress_batch", nullptr);
+    if (rc) return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
   const bool box = c->handoff != 0;

@@ -1226,8 +1226,40 @@ static void batch_buffers(dctzhip_ctx *c, size_t host_bytes, size_t dev_bytes) {
   grow(&g_batch.dev, &g_batch.dev_cap, dev_bytes);
 }
 
+/* Caller arrays that share bytes (one t_var twice, two t_vars over one buffer): the second call of the loop reads what the
+ * first one's in-place scaling left there, which the pool -- sums and divisions of all arrays at once -- cannot reproduce.
+ * Such a list is run as that loop; the sort makes the check O(k log k). */
+typedef struct { uintptr_t lo, hi; } brange;
+static int brange_cmp(const void *a, const void *b) {
+  const uintptr_t x = ((const brange *)a)->lo, y = ((const brange *)b)->lo;
+  return x < y ? -1 : x > y;
+}
+static int batch_inputs_overlap(int k, t_var *const *vars, const int *N) {
+  brange *r = (brange *)malloc((size_t)k * sizeof(*r));
+  if (!r) { fprintf(stderr, "Out of memory: batch\n"); exit(1); }
+  for (int i = 0; i < k; i++) {
+    const int is_d = vars[i]->datatype == DOUBLE;
+    r[i].lo = (uintptr_t)(is_d ? (void *)vars[i]->buf.d : (void *)vars[i]->buf.f);
+    r[i].hi = r[i].lo + (size_t)(N[i] > 0 ? N[i] : 0) * (is_d ? 8 : 4);
+  }
+  qsort(r, (size_t)k, sizeof(*r), brange_cmp);
+  int hit = 0;
+  uintptr_t end = 0;
+  for (int i = 0; i < k && !hit; i++) {
+    if (r[i].hi == r[i].lo) continue;
+    hit = i > 0 && end > r[i].lo;
+    if (r[i].hi > end) end = r[i].hi;
+  }
+  free(r);
+  return hit;
+}
+
 int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSizes, t_var *const *vars_z, const double *error_bounds) {
   if (k <= 0) return 1;
+  if (batch_inputs_overlap(k, vars, N)) {
+    for (int i = 0; i < k; i++) if (dctz_compress(vars[i], N[i], &outSizes[i], vars_z[i], error_bounds[i]) != 1) return 0;
+    return 1;
+  }
   dctzhip_ctx *c = ctx();
   /* layout of the staging area (host, pinned) and of its device twin: inputs | bin_index | DC | AC_exact, array after array */
   size_t *off_in = (size_t *)malloc(4 * (size_t)k * sizeof(size_t));

@@ -129,7 +129,10 @@ void dctz_dct_blocks_f(float *a, float *b, size_t n, int inverse);
  * single-shot deflate per section, dctz-comp-lib.c:620-732 -- for all 3 k sections on a pool of host threads.  Arguments
  * as dctz_compress()'s, per array: vars[i] (N[i] elements, scaled in place by its sf on return), vars_z[i] (>= N[i] *
  * type_size bytes), outSizes[i], error_bounds[i].  Container i is byte for byte what dctz_compress(vars[i], ...) writes
- * with the default tail.  Flat blocks only.  dctz_decompress_batch() is the mirror image (any flat containers). */
+ * with the default tail.  Flat blocks only.  dctz_decompress_batch() is the mirror image (any flat containers).
+ * Arrays may share bytes (one t_var twice, two t_vars over one buffer): the result -- containers, outSizes and the final
+ * contents of every array -- is then that of the loop of dctz_compress(vars[i], ...) in index order, where a later call
+ * reads what an earlier one's in-place scaling left; such a list is run as that loop. */
 int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSizes, t_var *const *vars_z, const double *error_bounds);
 int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every

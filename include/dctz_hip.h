@@ -201,7 +201,11 @@ int dctzhip_host_unregister(dctzhip_ctx *ctx, void *ptr);
  *               (= dct_result.bin under -DDCT_FILE_DEBUG, :422-428); may be NULL
  * On return *info is filled (the host has waited for it); the last kernels of the
  * call may still be running: the output buffers are complete in STREAM order --
- * for any later call or copy on the context's stream, or after dctzhip_sync(). */
+ * for any later call or copy on the context's stream, or after dctzhip_sync().
+ * Buffers of one call: no output (d_bin_index n bytes, d_dc nblk floats, d_ac_exact
+ * its capacity of n floats, d_scaled unless it is d_in, d_coef) may overlap d_in or
+ * another output; d_scaled either is d_in exactly or lies clear of it.  Anything else
+ * returns DCTZHIP_E_ARG before a launch. */
 int dctzhip_compress(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype,
                      double error_bound, int mode, void *d_bin_index, float *d_dc,
                      float *d_ac_exact, void *d_scaled, void *d_coef,
@@ -245,7 +249,9 @@ int dctzhip_scale_inplace(dctzhip_ctx *ctx, void *d_x, size_t n, int dtype, doub
  *   qtable_host  QT: the 64 table values in the data type, HOST memory (as read
  *                from the stream tail, dctz-decomp-lib.c:193-199); EC: NULL
  *   sf           header scaling factor (scaling_factor.d, or .f widened)
- *   d_out        n elements out
+ *   d_out        n elements out; must not overlap d_bin_index (n bytes), d_dc (nblk
+ *                floats) or the ac_count floats of d_ac_exact (else DCTZHIP_E_ARG
+ *                before a launch)
  * Returns once the stream is known to be consistent with ac_count (the only thing the
  * host has to learn); the reconstruction itself is complete in STREAM order -- for
  * any later call or copy on the context's stream, or after dctzhip_sync(). */
@@ -263,16 +269,27 @@ int dctzhip_decompress(dctzhip_ctx *ctx, const void *d_bin_index, const float *d
  * sequence per element type with ONE hand-off.  Every array's outputs (streams, scaled copy, *info) are bit for bit
  * those of its own dctzhip_compress() / dctzhip_decompress() call.  Arrays of 2^24 elements or more are handed to the
  * single-array path inside the call (their kernels dwarf the launch cost, and that path saves the statistics pass).
- * Fields have the meaning of the same-named arguments of dctzhip_compress / dctzhip_decompress. */
+ * Fields have the meaning of the same-named arguments of dctzhip_compress / dctzhip_decompress.
+ *
+ * Buffers shared between items of a compress batch:
+ *   - every item compresses its d_in as it was when the call was made;
+ *   - any number of items may read the same or overlapping input ranges, with any dtype (a bound sweep over one array
+ *     reads it once for all of them);
+ *   - an item scales in place only with d_scaled == d_in exactly; its buffer ends as that item's x / sf, written after
+ *     every read of the call (an input another item reads is divided at the very end of the call);
+ *   - DCTZHIP_E_ARG, before anything is launched: two in-place items whose ranges overlap; a d_scaled that is not its
+ *     item's d_in and overlaps any input; any output (d_bin_index n bytes, d_dc nblk floats, d_ac_exact its capacity of
+ *     n floats, d_scaled) that overlaps another output or any input.
+ * Items of a decode batch may share their inputs; d_out must not overlap any item's inputs or another d_out (E_ARG). */
 typedef struct {
-  const void *d_in;          /* n elements of dtype, device, 16-byte aligned; not modified unless d_scaled aliases it */
+  const void *d_in;          /* n elements of dtype, device, 16-byte aligned; not modified unless d_scaled is d_in */
   size_t n;
   int dtype;                 /* DCTZHIP_F32 | DCTZHIP_F64, per array */
   double error_bound;        /* per array */
   void *d_bin_index;         /* n bytes out */
   float *d_dc;               /* ceil(n / 64) floats out */
   float *d_ac_exact;         /* capacity n floats out */
-  void *d_scaled;            /* optional: x / sf (dctz-comp-lib.c:193-216); may be NULL, may alias d_in */
+  void *d_scaled;            /* optional: x / sf (dctz-comp-lib.c:193-216); may be NULL, may be d_in exactly */
 } dctzhip_batch_citem;
 typedef struct {
   const void *d_bin_index;
