@@ -462,6 +462,26 @@ template <typename T> void launch_dct_blocks(const T* x, T* out, const T* gtab, 
                                              bool inverse, int grid, hipStream_t s);
 template <typename T> void launch_psnr(const T* x, const T* r, size_t n, double* part, int nparts, double* out, hipStream_t s);
 
+// Rate-distortion probe (dctz_kernels_rd.hip: k_rd_probe, k_rd_probe_rem, k_rd_final)
+constexpr int RD_MAXK = 16;                  // error bounds per call
+constexpr int RD_WG = 256;                   // threads per workgroup of k_rd_probe
+constexpr int RD_SLOT = 2 + 2 * RD_MAXK;     // doubles per slab row: min x, max x, then per bound sum err^2 and the count (u64 bits)
+template <typename T>
+struct RdParams {
+  const T* x;                      // the array (not modified)
+  unsigned nfull;                  // whole blocks
+  int k;                           // bounds
+  T sf;                            // scaling factor (util.c:29), as k_compress gets it
+  unsigned fast_sf;                // FastDiv may run on sf (the host's divisor window)
+  unsigned fast_bw;                // bit i: FastDiv may run on bound i's bin width
+  const T* bounds;                 // device: per bound range_min, range_max, bin_width (dctz-comp-lib.c:271-281)
+  const T* tab;                    // forward transform constants
+  const T* rtab;                   // remainder-block tables (length n % 64)
+  double* slab;                    // (grid + 1) rows of RD_SLOT
+  double* out;                     // 2 + 2 k doubles: min x, max x, {sum err^2, count} per bound
+};
+template <typename T> void launch_rd_probe(const RdParams<T>& p, int grid, int rem, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

@@ -181,6 +181,13 @@ struct dctzhip_ctx {
   hipEvent_t b_ev[2][5] = {};       // profiling: per element-type sequence of the last batch call
   dctzhip_timings b_last[2] = {};
   int b_have_timings = 0;
+  // rate-distortion probe and target-PSNR compression (dctzhip_rd_probe / dctzhip_compress_psnr)
+  double* rd_slab = nullptr;        // k_rd_probe's workgroup rows, then 64 doubles of bound constants and 64 of results
+  size_t rd_slab_cap = 0;           // doubles
+  void* rd_rec = nullptr;           // dctzhip_compress_psnr: the decoded array it measures (n elements)
+  size_t rd_rec_cap = 0;            // bytes
+  int rd_sse_div = 1;               // (tests: dctzhip_debug_knob 3) every predicted SSE is divided by this
+  unsigned long long rd_stepdowns = 0;   // dctzhip_compress_psnr: measured misses that stepped to the next smaller bound
   char err[512] = {0};
 };
 
@@ -212,7 +219,7 @@ static int fail(dctzhip_ctx* c, int code, const char* fmt, ...) {
       return fail((c), DCTZHIP_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" const char* dctzhip_version(void) { return "0.1.0"; }
+extern "C" const char* dctzhip_version(void) { return "0.2.0"; }
 
 extern "C" const char* dctzhip_last_error(const dctzhip_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
 
@@ -310,7 +317,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess};
+  void* bufs[] = {c->tile_pre, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -390,6 +397,7 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 7: *value = c->spec_misses; break;
     case 8: *value = c->b_spec_items; break;         // batch items that took their scaling factor from a sample
     case 9: *value = c->b_spec_misses; break;        // ... whose guess the true statistics refused (done again on their own)
+    case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
   return DCTZHIP_OK;
@@ -400,6 +408,7 @@ extern "C" int dctzhip_debug_knob(dctzhip_ctx* c, int key, int value) {
     case 0: c->one_withhold = value != 0; break;     // workgroup 0 of the one-launch kernels withholds its granule: a launch that gives up
     case 1: c->eo_lb_fail = value != 0; break;       // one tile's look-back of k_compress_eo reports that it gave up
     case 2: c->one_cooldown = value; break;
+    case 3: c->rd_sse_div = value > 1 ? value : 1; break;   // every predicted SSE of dctzhip_rd_probe divided by value (step-down path)
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_knob: no knob %d", key);
   }
   return DCTZHIP_OK;
@@ -2040,6 +2049,176 @@ extern "C" int dctzhip_psnr_terms(dctzhip_ctx* c, const void* d_x, const void* d
   HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int i = 0; i < 4; i++) out[i] = hs[i];
   return DCTZHIP_OK;
+}
+
+// ---- rate-distortion probe and target-PSNR compression (include/dctz_hip.h; dctz_kernels_rd.hip) ----------------------
+// calc_psnr (util.c:54-104): 20 log10(range / rmse), rmse = sqrt(sse / N)
+static double psnr_of(double lo, double hi, double sse, size_t n) { return 20.0 * log10((hi - lo) / sqrt(sse / (double)(int)n)); }
+
+template <typename T>
+static int rd_probe_impl(dctzhip_ctx* c, const T* d_in, size_t n, int k, const double* ebs, dctzhip_rd_point* pts, double range[2]) {
+  const int dtype = sizeof(T) == 8 ? DCTZHIP_F64 : DCTZHIP_F32;
+  hipStream_t s = c->stream;
+  double mx, mn, sum;
+  int rc = stats_impl<T>(c, d_in, n, &mx, &mn, &sum);          // calc_data_stat: only sf is needed (util.c:29)
+  if (rc) return rc;
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  const unsigned ntiles = (nfull + TILE_BLKS - 1) / TILE_BLKS;
+  constexpr unsigned NW = RD_WG / 64;
+  // one workgroup per CU (fp64: one wave per SIMD, the kernel's register budget) / two (fp32); fewer for small arrays
+  unsigned grid = (unsigned)c->num_cu * (sizeof(T) == 8 ? 1u : 2u);
+  if (grid > (ntiles + NW - 1) / NW) grid = (ntiles + NW - 1) / NW;
+  const size_t need = ((size_t)grid + 1) * RD_SLOT + 128;           // rows, then 64 doubles of bound constants, 64 of results
+  {
+    rc = regrow(c, &c->rd_slab, &c->rd_slab_cap, need, sizeof(double));
+    if (rc) return rc;
+  }
+  if (rem) { rc = upload_rtab<T>(c, rem); if (rc) return rc; }   // (synchronous: the staging area is free again)
+  RdParams<T> p;
+  memset(&p, 0, sizeof(p));
+  p.x = d_in; p.nfull = nfull; p.k = k;
+  const double sf = scaling_factor(dtype, mx);
+  p.sf = (T)sf;
+  // the launch constants of k_compress (compress_pass): FastDiv where the host's windows allow it
+  p.fast_sf = c->fastdiv ? divisor_in_window(dtype, (double)p.sf) : 0u;
+  if (p.fast_sf && c->fastdiv >= 2 && value_in_window(dtype, mn) && value_in_window(dtype, mx)) p.fast_sf = 2;
+  T* hb = reinterpret_cast<T*>(c->h_pin + PIN_TAB);
+  const int half = DCTZHIP_NBINS / 2;
+  for (int i = 0; i < k; i++) {                                   // dctz-comp-lib.c:271-281 (computed in double, stored in T)
+    const double eb = ebs[i];
+    hb[3 * i] = (T)(-(half * 2 + 1) * (eb * 1.0));
+    hb[3 * i + 1] = (T)((half * 2 + 1) * (eb * 1.0));
+    hb[3 * i + 2] = (T)(eb * 2.0 * 1.0);
+    if (c->fastdiv && divisor_in_window(dtype, (double)hb[3 * i + 2])) p.fast_bw |= 1u << i;
+  }
+  double* d_bounds = c->rd_slab + ((size_t)grid + 1) * RD_SLOT;
+  p.bounds = reinterpret_cast<const T*>(d_bounds);
+  p.tab = tab_of<T>(c); p.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.slab = c->rd_slab;
+  p.out = d_bounds + 64;
+  HIPCHK(c, hipMemcpyAsync(d_bounds, hb, sizeof(T) * 3 * (size_t)k, hipMemcpyHostToDevice, s));
+  launch_rd_probe<T>(p, (int)grid, rem, s);
+  HIPCHK(c, hipGetLastError());
+  double* ho = reinterpret_cast<double*>(c->h_pin + PIN_TAB + 1024);
+  HIPCHK(c, hipMemcpyAsync(ho, p.out, sizeof(double) * (2 + 2 * (size_t)k), hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  const double sf2 = (double)p.sf * (double)p.sf;
+  const size_t nblk = (n + 63) / 64;
+  for (int i = 0; i < k; i++) {
+    uint64_t cnt;
+    memcpy(&cnt, &ho[3 + 2 * i], sizeof(cnt));
+    dctzhip_rd_point& r = pts[i];
+    r.error_bound = ebs[i];
+    r.cnt = cnt;
+    r.sse = sf2 * ho[2 + 2 * i] / (double)c->rd_sse_div;
+    r.psnr = psnr_of(ho[0], ho[1], r.sse, n);
+    r.raw_bytes = (uint64_t)n + 4 * (uint64_t)nblk + 4 * cnt + DCTZHIP_RD_HEADER_BYTES;
+  }
+  if (range) { range[0] = ho[0]; range[1] = ho[1]; }
+  return DCTZHIP_OK;
+}
+
+static int rd_probe_checked(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, int k, const double* ebs, dctzhip_rd_point* pts,
+                            double range[2]) {
+  return dtype == DCTZHIP_F64 ? rd_probe_impl<double>(c, (const double*)d_in, n, k, ebs, pts, range)
+                              : rd_probe_impl<float>(c, (const float*)d_in, n, k, ebs, pts, range);
+}
+
+extern "C" int dctzhip_rd_probe(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, int k, const double* error_bounds,
+                                dctzhip_rd_point* pts, double range[2]) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (!d_in || !error_bounds || !pts) return fail(c, DCTZHIP_E_ARG, "dctzhip_rd_probe: null pointer");
+  if (!aligned16(d_in)) return fail(c, DCTZHIP_E_ARG, "dctzhip_rd_probe: d_in must be 16-byte aligned");
+  if (k < 1 || k > DCTZHIP_RD_MAXK) return fail(c, DCTZHIP_E_ARG, "dctzhip_rd_probe: k = %d, must be 1 .. %d", k, DCTZHIP_RD_MAXK);
+  for (int i = 0; i < k; i++)
+    if (!(error_bounds[i] >= 1E-6)) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
+  HIPCHK(c, hipSetDevice(c->device));
+  return rd_probe_checked(c, d_in, n, dtype, k, error_bounds, pts, range);
+}
+
+// The candidate grid of dctzhip_compress_psnr, ascending: the doubles nearest to m * 10^e, e = -6 .. -1, then 1.
+static constexpr int RD_GRID_N = 61;
+static const char* const RD_MANT[10] = {"1", "1.25", "1.5", "2", "2.5", "3", "4", "5", "6", "8"};
+static void rd_grid(double g[RD_GRID_N]) {
+  int i = 0;
+  for (int e = -6; e <= -1; e++)
+    for (int m = 0; m < 10; m++) {
+      char buf[32];
+      snprintf(buf, sizeof(buf), "%se%d", RD_MANT[m], e);
+      g[i++] = strtod(buf, nullptr);
+    }
+  g[i] = 1.0;
+}
+
+extern "C" int dctzhip_compress_psnr(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, double target_psnr, void* d_bin,
+                                     float* d_dc, float* d_ac, dctzhip_cinfo* info, double* error_bound_used, double* psnr_measured) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (!d_in || !d_bin || !d_dc || !d_ac || !info || !error_bound_used || !psnr_measured)
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: null pointer");
+  if (!aligned16(d_in) || !aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac))
+    return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
+  if (!std::isfinite(target_psnr)) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: the target must be finite");
+  {
+    Span sp[6];
+    size_t m = 0;
+    compress_spans(sp, &m, 0, d_in, n, dtype, d_bin, d_dc, d_ac, nullptr, nullptr);
+    rc = check_spans(c, sp, m, "dctzhip_compress_psnr", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  double g[RD_GRID_N];
+  rd_grid(g);
+  // call 1: the decade points 1e-6 .. 1 (grid indices 0, 10, ..., 60); the largest whose prediction reaches the target
+  double ebs[DCTZHIP_RD_MAXK];
+  dctzhip_rd_point pts[DCTZHIP_RD_MAXK];
+  double range[2];
+  for (int d = 0; d < 7; d++) ebs[d] = g[10 * d];
+  rc = rd_probe_checked(c, d_in, n, dtype, 7, ebs, pts, range);
+  if (rc) return rc;
+  if (!std::isfinite(range[0]) || !std::isfinite(range[1]))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: the array's range is not finite (PSNR undefined)");
+  if (range[0] == range[1]) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: constant array (PSNR undefined)");
+  for (int d = 0; d < 7; d++)
+    if (std::isnan(pts[d].sse)) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: the array holds a NaN (PSNR undefined)");
+  int at = -1;
+  for (int d = 6; d >= 0 && at < 0; d--)
+    if (pts[d].psnr >= target_psnr) at = 10 * d;
+  if (at < 0) return fail(c, DCTZHIP_E_BOUND, "dctzhip_compress_psnr: no error bound >= 1e-6 reaches %.3f dB", target_psnr);
+  // call 2: the nine interior points above that decade point; the largest whose prediction reaches the target
+  if (at < RD_GRID_N - 1) {
+    for (int i = 0; i < 9; i++) ebs[i] = g[at + 1 + i];
+    rc = rd_probe_checked(c, d_in, n, dtype, 9, ebs, pts, nullptr);
+    if (rc) return rc;
+    for (int i = 8; i >= 0; i--)
+      if (pts[i].psnr >= target_psnr) { at = at + 1 + i; break; }
+  }
+  // compress at the chosen point, decode into the context's scratch and measure; a miss steps down the grid
+  const size_t es = elem_size(dtype);
+  {
+    char* r = (char*)c->rd_rec;
+    rc = regrow(c, &r, &c->rd_rec_cap, n * es, 1);
+    c->rd_rec = r;
+    if (rc) return rc;
+  }
+  for (;; at--) {
+    const double eb = g[at];
+    rc = dctzhip_compress(c, d_in, n, dtype, eb, DCTZHIP_EC, d_bin, d_dc, d_ac, nullptr, nullptr, info);
+    if (rc) return rc;
+    rc = dctzhip_decompress(c, d_bin, d_dc, d_ac, info->cnt, nullptr, n, dtype, eb, info->sf, DCTZHIP_EC, c->rd_rec);
+    if (rc) return rc;
+    double t[4];
+    rc = dctzhip_psnr_terms(c, d_in, c->rd_rec, n, dtype, t);
+    if (rc) return rc;
+    const double psnr = psnr_of(t[0], t[1], t[3], n);
+    *error_bound_used = eb;
+    *psnr_measured = psnr;
+    if (psnr >= target_psnr) return DCTZHIP_OK;
+    if (at == 0) return fail(c, DCTZHIP_E_BOUND, "dctzhip_compress_psnr: measured %.3f dB at 1e-6, under the target %.3f dB", psnr, target_psnr);
+    c->rd_stepdowns++;
+  }
 }
 
 // ---- batches of arrays (include/dctz_hip.h: dctzhip_compress_batch / dctzhip_decompress_batch) ---------------------

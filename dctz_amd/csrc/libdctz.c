@@ -1212,6 +1212,39 @@ static void bpool_run(bjob *jobs, size_t njobs) {
   bpool_worker(&p);
   for (int t = 0; t < started; t++) pthread_join(th[t], NULL);
 }
+/* --------------------------------------------------- compress to a target PSNR (ADDITION, dctz.h) --- */
+/* The array goes to the device, dctzhip_compress_psnr chooses the bound (include/dctz_hip.h: probe, compress, measure,
+ * step down), and the container is then simply dctz_compress(var, N, outSize, var_z, bound) -- byte for byte that call's
+ * output, the in-place x /= sf of the caller's buffer included.  (The second H2D copy inside dctz_compress is the price of
+ * that identity.)  EC only: the QT build refuses without touching anything. */
+int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double target_psnr, double *error_bound_used) {
+#ifdef USE_QTABLE
+  (void)var; (void)N; (void)outSize; (void)var_z; (void)target_psnr; (void)error_bound_used;
+  return DCTZHIP_E_ARG;                          /* QT bin widths come from a whole-array table: no probe for them */
+#else
+  if (!var || !var_z || !outSize || !error_bound_used || N <= 0) return DCTZHIP_E_ARG;
+  if (g_nd || (getenv("DCTZ_BLOCK_DIMS") && *getenv("DCTZ_BLOCK_DIMS"))) return DCTZHIP_E_ARG;   /* flat blocks only */
+  const int is_d = (var->datatype == DOUBLE);
+  if (!is_d && var->datatype != FLOAT) return DCTZHIP_E_ARG;
+  const void *host_in = is_d ? (const void *)var->buf.d : (const void *)var->buf.f;
+  if (!host_in) return DCTZHIP_E_ARG;
+  const size_t n = (size_t)N, ts = is_d ? sizeof(double) : sizeof(float);
+  dctzhip_ctx *c = ctx();
+  grow(&g_dev.in, &g_dev.in_cap, n * ts);
+  grow(&g_dev.bin, &g_dev.bin_cap, n);
+  grow(&g_dev.dc, &g_dev.dc_cap, CEIL(n, BLK_SZ) * sizeof(float));
+  grow(&g_dev.ac, &g_dev.ac_cap, n * sizeof(float));
+  if (dctzhip_memcpy_h2d(c, g_dev.in, host_in, n * ts) != DCTZHIP_OK) die("H2D");
+  dctzhip_cinfo info;
+  double eb = 0.0, psnr = 0.0;
+  const int rc = dctzhip_compress_psnr(c, g_dev.in, n, is_d ? DCTZHIP_F64 : DCTZHIP_F32, target_psnr, g_dev.bin, (float *)g_dev.dc,
+                                       (float *)g_dev.ac, &info, &eb, &psnr);
+  if (rc != DCTZHIP_OK) return rc;
+  *error_bound_used = eb;
+  return dctz_compress(var, N, outSize, var_z, eb);
+#endif
+}
+
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 static struct { void *pin; size_t pin_cap; void *dev; size_t dev_cap; } g_batch;
 static void batch_buffers(dctzhip_ctx *c, size_t host_bytes, size_t dev_bytes) {

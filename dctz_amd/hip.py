@@ -53,6 +53,19 @@ class BatchDItem(C.Structure):       # dctzhip_batch_ditem
                 ("sf", C.c_double), ("d_out", C.c_void_p)]
 
 
+class RdPoint(C.Structure):          # dctzhip_rd_point
+    _fields_ = [("error_bound", C.c_double), ("cnt", C.c_uint64), ("sse", C.c_double), ("psnr", C.c_double),
+                ("raw_bytes", C.c_uint64)]
+
+
+RD_MAXK = 16                         # DCTZHIP_RD_MAXK: bounds per dctzhip_rd_probe call
+
+
+def psnr_grid():
+    """The candidate bounds of dctzhip_compress_psnr, ascending (include/dctz_hip.h): m * 10^e for e = -6 .. -1, then 1."""
+    return [float(f"{m}e{e}") for e in range(-6, 0) for m in ("1", "1.25", "1.5", "2", "2.5", "3", "4", "5", "6", "8")] + [1.0]
+
+
 _lib = None
 
 _PROTOS = {
@@ -102,6 +115,10 @@ _PROTOS = {
     "dctzhip_debug_divide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p,
                                        C.c_void_p]),
     "dctzhip_psnr_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
+    "dctzhip_rd_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                   C.POINTER(RdPoint), C.POINTER(C.c_double)]),
+    "dctzhip_compress_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(CompressInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dctzhip_deflate_bound": (C.c_size_t, [C.c_size_t]),
     "dctzhip_deflate_chunk_bytes": (C.c_size_t, []),
     "dctzhip_deflate_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
@@ -436,6 +453,33 @@ class Context:
         rc = self.lib.dctzhip_psnr_terms(self.h, x.data_ptr(), r.data_ptr(), x.numel(), _dt(x.dtype), out)
         self._check(rc, "dctzhip_psnr_terms")
         return tuple(out)
+
+    def rd_probe(self, x, ebs):
+        """Rate-distortion probe (dctzhip_rd_probe): one read of x, up to RD_MAXK error bounds.  Returns (points, (min x, max x)),
+        points[i] a dict {error_bound, cnt, sse, psnr, raw_bytes} for ebs[i]: exact count, predicted SSE / PSNR."""
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 1
+        self._bind_stream()
+        k = len(ebs)
+        e = (C.c_double * max(k, 1))(*[float(v) for v in ebs])
+        pts = (RdPoint * max(k, 1))()
+        rng = (C.c_double * 2)()
+        rc = self.lib.dctzhip_rd_probe(self.h, x.data_ptr(), x.numel(), _dt(x.dtype), k, e, pts, rng)
+        self._check(rc, "dctzhip_rd_probe")
+        return [{f: getattr(pts[i], f) for f, _ in RdPoint._fields_} for i in range(k)], (rng[0], rng[1])
+
+    def compress_psnr(self, x, target, out=None):
+        """EC compression at the largest bound of psnr_grid() whose measured PSNR reaches `target` dB
+        (dctzhip_compress_psnr).  Returns (out, info, eb, psnr): the streams are those of compress(x, eb)."""
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 1
+        self._bind_stream()
+        n = x.numel()
+        if out is None:
+            out = self.alloc_outputs(n, x.dtype)
+        info, eb, ps = CompressInfo(), C.c_double(0.0), C.c_double(0.0)
+        rc = self.lib.dctzhip_compress_psnr(self.h, x.data_ptr(), n, _dt(x.dtype), float(target), out["bin_index"].data_ptr(),
+                                            out["dc"].data_ptr(), out["ac_exact"].data_ptr(), C.byref(info), C.byref(eb), C.byref(ps))
+        self._check(rc, "dctzhip_compress_psnr")
+        return out, info, eb.value, ps.value
 
     def deflate(self, sections, want_index=False, literals=None):
         """zlib streams of byte sections, made on the GPU (dctzhip_deflate).  sections: device tensors (any dtype,

@@ -135,6 +135,14 @@ void dctz_dct_blocks_f(float *a, float *b, size_t n, int inverse);
  * reads what an earlier one's in-place scaling left; such a list is run as that loop. */
 int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSizes, t_var *const *vars_z, const double *error_bounds);
 int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r);
+/* Compression to a target PSNR (ADDITION, EC).  The error bound is chosen on the device -- rate-distortion probe, then
+ * compress, decode and measure, stepping down a fixed grid of bounds on a miss (include/dctz_hip.h: dctzhip_compress_psnr) --
+ * and the container is then dctz_compress(var, N, outSize, var_z, *error_bound_used): byte for byte that call's output,
+ * the in-place x /= sf of var->buf included.  Its calc_psnr against the original is >= target_psnr.  Returns what
+ * dctz_compress returns (1), or without writing anything: DCTZHIP_E_BOUND (-2) when no bound >= 1e-6 reaches the
+ * target, DCTZHIP_E_ARG (-1) for bad arguments, a constant array or a NaN (PSNR undefined), pending multi-dimensional
+ * blocks (flat blocks only), and always in the QT library (its bin widths come from a whole-array table). */
+int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double target_psnr, double *error_bound_used);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

@@ -131,9 +131,10 @@ int dctzhip_set_split(dctzhip_ctx *ctx, int on);
 /* (tests and tools)  Counters of the context -- which: 0 one-launch calls, 1 one-launch launches that gave up (run again
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
- * items of batches / those whose guess was refused -- and knobs that
+ * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
- * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2. */
+ * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
+ * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
 int dctzhip_debug_counter(dctzhip_ctx *ctx, int which, unsigned long long *value);
 int dctzhip_debug_knob(dctzhip_ctx *ctx, int key, int value);
 /* (tools) the name rocprofv3 lists the big kernel of the last call under, every template argument: which = 0 compress,
@@ -375,6 +376,53 @@ int dctzhip_comm_gather(dctzhip_ctx *ctx, int root, const void *d_bin, const flo
  * (util.c:67-73 / :83-89).  The sum is a tree reduction: its last digits differ from
  * the reference's serial loop (relative 1e-15), min / max / maxdiff are exact. */
 int dctzhip_psnr_terms(dctzhip_ctx *ctx, const void *d_x, const void *d_r, size_t n, int dtype, double out[4]);
+
+/* ---- rate-distortion probe and target-PSNR compression (EC mode) --------------------------------------------------- */
+/* Which error bound does an array need?  The reference's answer is a sweep: the whole compressor, a decode and calc_psnr
+ * once per bound (tests/test-dctz.sh, zc-patches/zc-ratedistortion.sh over errBounds.cfg).  The probe reads the array ONCE,
+ * scales and transforms every block as dctzhip_compress does, and bins the coefficients against up to DCTZHIP_RD_MAXK
+ * bounds in registers.  Per bound it gives the exact count of coefficients stored exactly and the squared error of the
+ * reconstruction predicted from the coefficients' own errors (the transform is orthonormal; the decoder's value of every
+ * coefficient -- bin centre, float-truncated exact value, float-truncated DC -- is known when it is binned).  The
+ * prediction misses the measured sum only by the rounding of the inverse transform and of the de-scaling.
+ *   error_bounds  k bounds, 1 <= k <= DCTZHIP_RD_MAXK, any order, repeats allowed; each >= 1e-6 (else DCTZHIP_E_BOUND)
+ *   pts           k results, pts[i] for error_bounds[i]; a bound's result does not depend on the other bounds of the call
+ *   range         (or NULL) min x and max x, calc_psnr's range (util.c:61-66; = dctzhip_psnr_terms' out[0], out[1])
+ * d_in (16-byte aligned) is not modified.  Host-synchronous on return.  Sums are bitwise reproducible from run to run. */
+#define DCTZHIP_RD_MAXK 16
+#define DCTZHIP_RD_HEADER_BYTES 56   /* struct header of the EC container (dctz.h:96-119) */
+typedef struct {
+  double error_bound;
+  uint64_t cnt;        /* tot_AC_exact_count dctzhip_compress would report at this bound (exact) */
+  double sse;          /* predicted sum (x - x')^2 of the reconstruction, data units (sf^2 * sum err^2) */
+  double psnr;         /* predicted calc_psnr: 20 log10((max - min) / sqrt(sse / n)) */
+  uint64_t raw_bytes;  /* pre-zlib bytes: n + 4 nblk + 4 cnt + DCTZHIP_RD_HEADER_BYTES (exact; zlib's output is not predicted) */
+} dctzhip_rd_point;
+int dctzhip_rd_probe(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, int k, const double *error_bounds,
+                     dctzhip_rd_point *pts, double range[2]);
+/* Compression to a target PSNR.  Deterministic contract:
+ *   grid      candidate bounds G = {m * 10^e : m in {1, 1.25, 1.5, 2, 2.5, 3, 4, 5, 6, 8}, e = -6 .. -1} u {1}: 61 points, each
+ *             the double nearest to the decimal value (strtod of "1.25e-3", ...)
+ *   probes    call 1 probes the decade points 1e-6, 1e-5, ..., 1 and takes the largest whose predicted PSNR >= target; call 2
+ *             probes the 9 points of G above that decade point and takes the largest whose prediction >= target (else the
+ *             decade point)
+ *   compress  the chosen bound goes through the ordinary dctzhip_compress: the streams and *info are bit for bit those of
+ *             dctzhip_compress(d_in, ..., *error_bound_used, DCTZHIP_EC, ..., d_scaled = NULL, d_coef = NULL)
+ *   measure   the streams are decoded into scratch of the context (n elements of the data type: a device buffer kept for
+ *             later calls) and the PSNR is measured with dctzhip_psnr_terms' reductions -> *psnr_measured
+ *   step down a measured PSNR under the target moves to the next smaller point of G and repeats (debug counter 10 counts
+ *             these); so a rounding-level miss of the prediction costs time, never the target
+ *   guarantee on DCTZHIP_OK the returned streams decode to a measured PSNR >= target_psnr
+ *   refusals  before anything is written: no point of G is predicted to reach the target -> DCTZHIP_E_BOUND; a constant
+ *             array (max == min), a non-finite min / max or a NaN in the array (PSNR undefined), a non-finite target ->
+ *             DCTZHIP_E_ARG.  (Should even 1e-6 measure under the target after the prediction reached it, the call returns
+ *             DCTZHIP_E_BOUND with the streams of 1e-6 written.)
+ *   buffers   as dctzhip_compress's (no scaled copy, no coefficient tap): overlaps are refused with DCTZHIP_E_ARG.
+ * Host-synchronous on return.  (tests) dctzhip_debug_knob(ctx, 3, f) divides every predicted SSE by f (the step-down path
+ * on purpose); f <= 1 switches it off. */
+int dctzhip_compress_psnr(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, double target_psnr,
+                          void *d_bin_index, float *d_dc, float *d_ac_exact, dctzhip_cinfo *info,
+                          double *error_bound_used, double *psnr_measured);
 
 /* ---- entropy stage on the GPU -------------------------- */
 /* Replaces the reference's zlib tail on the compress side -- deflateInit / deflate of bin_index, DC and AC_exact on
