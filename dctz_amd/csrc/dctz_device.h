@@ -482,6 +482,28 @@ struct RdParams {
 };
 template <typename T> void launch_rd_probe(const RdParams<T>& p, int grid, int rem, hipStream_t s);
 
+// Random access on decode (dctz_kernels_ra.hip: k_ac_index, k_ac_index_scan, k_ac_index_add, k_decompress_range,
+// k_decompress_range_rem).  The streams and the index describe the whole array; [lo, hi) is the range, [t0, t1) its tiles.
+constexpr int IX_TPW = 64;                   // tiles per workgroup of k_ac_index (one wave scans their counts)
+template <typename T>
+struct RangeParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[t0 .. t1] are read
+  T* out;                          // hi - lo elements
+  const T* tab;
+  const T* rtab;                   // remainder-block tables (length n % 64)
+  const T* qtab;                   // QT: the table (device)
+  Ctl* ctl;                        // error = 2: the index disagrees with the tiles' flags or overruns ac_count
+  unsigned n, nfull, lo, hi, t0, t1, ac_count;
+  T sf, bin_width, range_min, range_max;
+  double eb;
+};
+void launch_ac_index(const uint8_t* bin, unsigned n, unsigned* idx, unsigned* wg_sum, hipStream_t s);
+template <typename T> int range_occupancy(int mode);
+template <typename T> void launch_decompress_range(const RangeParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

@@ -1,0 +1,359 @@
+// dctz_kernels_ra.hip -- random access on decode (include/dctz_hip.h: dctzhip_ac_index, dctzhip_decompress_range).
+//
+// The blocks of a DCTZ stream are independent except for ONE running value: the position `pos` in AC_exact at which a
+// block's exact coefficients start (dctz-decomp-lib.c:370, :402-412), the number of "stored exactly" flags in front of
+// it.  The exception index gives that number every 4096 elements (a tile of 64 blocks):
+//   idx[i] = flags (bin id 255 at an in-block position j with 1 <= j < block length) in elements [0, min(n, 4096 i)),
+//   i = 0 .. m, m = ceil(n / 4096);  idx[m] = tot_AC_exact_count.
+// k_ac_index counts the flags of 64 tiles per workgroup and scans them in one wave; k_ac_index_scan scans the workgroup
+// sums in one workgroup; k_ac_index_add adds the workgroups' offsets back.
+//
+// k_decompress_range rebuilds elements [lo, hi) of the array from the tiles [t0, t1) that hold them: one wave per tile,
+// lane b block b (the decomposition of k_decompress), the tile's exact coefficients AC_exact[idx[t], idx[t + 1]) staged
+// in LDS, in-tile placement a wave scan of the blocks' flag counts.  Bin centres, QT de-quantisation, the inverse block
+// transform and the de-scaling are the whole-array decoders' own functions in the same order, so every element is bit
+// for bit what dctzhip_decompress writes.  The reconstructed tile goes through an LDS image (a block per row, one
+// 16-byte pad per row: conflict-free both ways) and leaves in output order: 16-byte stores for the chunks of d_out the
+// tile owns wholly, element stores at the range's and the tile's edges.  The short last block is
+// k_decompress_range_rem's (the length-l transform of k_decompress_rem).
+#include "dctz_kernel_common.h"
+
+namespace dctz {
+
+// bit 7 of byte i set <=> byte i of w is 255 (a "stored exactly" flag)
+__device__ __forceinline__ unsigned ra_flags(unsigned w) {
+  const unsigned v = ~w;                                           // a zero byte of v <=> bin id 255
+  const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;        // bit 7 of a byte set <=> that byte of v is non-zero
+  return ~z & 0x80808080u;
+}
+
+// ================================================================== the index ==
+// Workgroup g takes tiles [64 g, 64 g + 64): wave w the tiles w, w + 4, ..., IX_TF of them in flight, 16-byte loads as
+// k_count_tiles reads them.  The one 16-byte group that holds the array's last byte (n % 16 != 0) is read byte by byte:
+// bytes beyond n count as 0 (no flag), and the short block's positions j >= l lie beyond n.
+constexpr int IX_TF = 4;
+__global__ __launch_bounds__(SWG) void k_ac_index(const uint8_t* __restrict__ bin, unsigned n, unsigned m, unsigned* __restrict__ idx,
+                                                  unsigned* __restrict__ wg_sum) {
+  __shared__ unsigned tcs[IX_TPW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  constexpr unsigned NW = SWG / 64;
+  const unsigned first = blockIdx.x * (unsigned)IX_TPW;
+  for (unsigned r0 = (unsigned)wave; r0 < (unsigned)IX_TPW; r0 += IX_TF * NW) {
+    uint4 wv[IX_TF][4];
+#pragma unroll
+    for (int h = 0; h < IX_TF; h++) {
+      const unsigned tile = first + r0 + (unsigned)h * NW;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const size_t o = (size_t)tile * TILE_ELEMS + (size_t)i * 1024 + (size_t)lane * 16;
+        wv[h][i] = make_uint4(0u, 0u, 0u, 0u);
+        if (tile < m && o + 16 <= (size_t)n) wv[h][i] = *reinterpret_cast<const uint4*>(bin + o);
+        else if (tile < m && o < (size_t)n) {
+          unsigned w[4] = {0u, 0u, 0u, 0u};
+          for (unsigned b = 0; b < 16u && o + b < (size_t)n; b++) w[b >> 2] |= (unsigned)bin[o + b] << (8 * (b & 3));
+          wv[h][i] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < IX_TF; h++) {
+      unsigned c = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const unsigned w[4] = {wv[h][i].x, wv[h][i].y, wv[h][i].z, wv[h][i].w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          unsigned f = ra_flags(w[k]);
+          if (k == 0 && (lane & 3) == 0) f &= ~0x80u;                    // byte 0 of every 64: j = 0, the DC slot
+          c += (unsigned)__popc(f);
+        }
+      }
+      const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(c), 63);
+      if (lane == 0) tcs[r0 + (unsigned)h * NW] = tot;                 // (0 for tiles beyond m: nothing was loaded)
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const unsigned v = tcs[lane];
+    const unsigned incl = wave_incl_scan(v);
+    const unsigned tile = first + (unsigned)lane;
+    if (tile < m) idx[tile] = incl - v;                                // exclusive prefix inside the workgroup's tiles
+    if (lane == 63) wg_sum[blockIdx.x] = incl;
+  }
+}
+
+// One workgroup: exclusive prefix of the g workgroup sums, in place; idx[m] = their total
+constexpr int IX_SWG = 1024;
+__global__ __launch_bounds__(IX_SWG) void k_ac_index_scan(unsigned* __restrict__ wg_sum, unsigned g, unsigned* __restrict__ idx, unsigned m) {
+  __shared__ unsigned wtot[IX_SWG / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned run = 0;
+  for (unsigned i0 = 0; i0 < g; i0 += IX_SWG) {
+    const unsigned i = i0 + threadIdx.x;
+    const unsigned v = i < g ? wg_sum[i] : 0u;
+    const unsigned incl = wave_incl_scan(v);
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < IX_SWG / 64; w++) {
+      const unsigned t = wtot[w];
+      before += w < wave ? t : 0u;
+      all += t;
+    }
+    if (i < g) wg_sum[i] = run + before + incl - v;
+    run += all;
+    __syncthreads();                                                   // wtot is rewritten by the next round
+  }
+  if (threadIdx.x == 0) idx[m] = run;
+}
+
+__global__ __launch_bounds__(SWG) void k_ac_index_add(unsigned* __restrict__ idx, unsigned m, const unsigned* __restrict__ wg_pre) {
+  const unsigned t = blockIdx.x * (unsigned)SWG + threadIdx.x;
+  if (t < m) idx[t] += wg_pre[t / (unsigned)IX_TPW];
+}
+
+void launch_ac_index(const uint8_t* bin, unsigned n, unsigned* idx, unsigned* wg_sum, hipStream_t s) {
+  const unsigned m = (n + TILE_ELEMS - 1) / TILE_ELEMS;
+  const unsigned g = (m + IX_TPW - 1) / IX_TPW;
+  hipLaunchKernelGGL(k_ac_index, dim3(g), dim3(SWG), 0, s, bin, n, m, idx, wg_sum);
+  hipLaunchKernelGGL(k_ac_index_scan, dim3(1), dim3(IX_SWG), 0, s, wg_sum, g, idx, m);
+  if (g > 1) hipLaunchKernelGGL(k_ac_index_add, dim3((m + SWG - 1) / SWG), dim3(SWG), 0, s, idx, m, (const unsigned*)wg_sum);
+}
+
+// ============================================================== range decode ==
+// LDS image of a reconstructed tile: block b at elements [b * STRIDE, b * STRIDE + 64), one 16-byte pad behind every
+// block, so that the lanes' 16-byte writes of their own blocks (rows STRIDE elements apart) and the reads in output order
+// (consecutive elements across the lanes) both spread over the banks.  The tile's exact coefficients (up to 63 * 64
+// floats) are staged in the same array before the image is written.
+template <typename T> struct RaGeo {
+  static constexpr int EPV = Traits<T>::EPV;
+  static constexpr int STRIDE = 64 + EPV;
+  static constexpr int BYTES = TILE_BLKS * STRIDE * (int)sizeof(T);
+  static_assert(BYTES >= 63 * 64 * 4, "a dense tile's exact coefficients fit the image");
+};
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(64) void k_decompress_range(RangeParams<T> p) {
+  using G = RaGeo<T>;
+  using Vec = typename Traits<T>::Vec;
+  constexpr int EPV = G::EPV;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[G::BYTES];
+  float* const stage = reinterpret_cast<float*>(lds);
+  T* const img = reinterpret_cast<T*>(lds);
+  const int lane = threadIdx.x;
+  const CTab<T> tab = as_ctab<T>(p.tab);
+  QtLanes<T> qtl{};
+  if (MODE == DCTZHIP_QT) qtl.load(p.qtab, lane);
+  const bool scale = (p.sf != T(1));                                   // dctz-decomp-lib.c:496 / :505
+  const unsigned rem = p.n - p.nfull * 64u;
+  const unsigned full_end = p.nfull * 64u;
+  bool bad = false;
+  for (unsigned t = p.t0 + blockIdx.x; t < p.t1; t += gridDim.x) {
+    // (a compiler barrier per trip: keeps the transform's scalar constant loads inside the loop, as in k_rd_probe)
+    asm volatile("" ::: "memory");
+    const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)lane;
+    const bool full = blk < p.nfull;
+    unsigned w[16];
+    float dcv = 0.f;
+    unsigned cnt = 0;
+    if (full) {
+      const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const u32x4 v = src[i];
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+      }
+      dcv = p.dc[blk];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; i++) w[i] = 0u;
+      // the short block's flags count for the tile (its elements are k_decompress_range_rem's: this lane stores nothing)
+      if (blk == p.nfull && rem)
+        for (unsigned j = 1; j < rem; j++) cnt += p.bin[(size_t)full_end + j] == 255u ? 1u : 0u;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      unsigned f = ra_flags(w[i]);
+      if (i == 0) f &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
+      cnt += (unsigned)__popc(f);
+    }
+    const unsigned incl = wave_incl_scan(cnt);
+    const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+    const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
+    // the index must agree with the tile's own flags and stay inside the caller's AC_exact (else: refused, nothing read)
+    if (s1 < s0 || s1 - s0 != tot || s1 > p.ac_count) { bad = true; continue; }
+    for (unsigned i = (unsigned)lane; i < tot; i += 64u) stage[i] = p.ac[s0 + i];
+    __syncthreads();
+    unsigned ptr = incl - cnt;                                         // this block's first exact coefficient in the tile
+    T x[64];
+    x[0] = (T)dcv;                                                     // :392 / :438
+#pragma unroll
+    for (int j = 1; j < 64; j++) {
+      const unsigned wj = w[j >> 2];
+      const unsigned b = (wj >> (8 * (j & 3))) & 255u;
+      T v = bin_centre<T>(((wj >> 1) & 0x7F7F7F7Fu) + (wj & 0x01010101u), ~wj, j & 3, p.bin_width);   // :416 / :462
+      if (b == 255u) {                                                 // :400 / :446
+        v = (T)stage[min(ptr, (unsigned)(63 * 64 - 1))];
+        ptr++;
+        if (MODE == DCTZHIP_QT) v = qt_restore(v, qtl.at(j), p.eb, T(10), p.range_min, p.range_max);
+      }
+      x[j] = v;
+    }
+    __syncthreads();                                                   // the staged coefficients are consumed
+    block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
+    if (scale) {
+#pragma unroll
+      for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                 // dctz-decomp-lib.c:494-511
+    }
+#pragma unroll
+    for (int ch = 0; ch < 64 / EPV; ch++)
+      *reinterpret_cast<Vec*>(img + lane * G::STRIDE + ch * EPV) = Traits<T>::pack(&x[ch * EPV]);
+    __syncthreads();
+    // the tile's whole-block elements inside [lo, hi) -> d_out, in output order
+    const unsigned ts = t * (unsigned)TILE_ELEMS;
+    const unsigned A = max(p.lo, ts), B = min(p.hi, min(ts + (unsigned)TILE_ELEMS, full_end));
+    if (A < B) {
+      const unsigned oa = A - p.lo, ob = B - p.lo;                     // output positions [oa, ob)
+      const unsigned qf = oa / EPV, ql = (ob + EPV - 1) / EPV;         // 16-byte chunks of d_out they touch
+      const unsigned base = qf * EPV;
+      // (a descriptor per tile, based at the tile's first chunk -- never in front of d_out -- and ending at its last element)
+      const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(p.out + base, 0, (int)((ob - base) * sizeof(T)), 0x00020000);
+      for (unsigned q0 = qf; q0 < ql; q0 += 64u) {
+        const unsigned q = q0 + (unsigned)lane;
+        if (q < ql) {
+          T v[EPV];
+          bool in[EPV];
+#pragma unroll
+          for (int k = 0; k < EPV; k++) {
+            const unsigned o = q * EPV + (unsigned)k;
+            in[k] = o >= oa && o < ob;
+            const unsigned e = in[k] ? o + p.lo - ts : 0u;             // element of the tile
+            v[k] = img[e + (e >> 6) * EPV];
+          }
+          const int at = (int)((q - qf) * 16u);
+          bool whole = true;
+#pragma unroll
+          for (int k = 0; k < EPV; k++) whole = whole && in[k];
+          if (whole) {
+            const Vec pv = Traits<T>::pack(v);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pv), r_out, at, 0, 0);
+          } else {
+#pragma unroll
+            for (int k = 0; k < EPV; k++) {
+              if (!in[k]) continue;
+              if constexpr (sizeof(T) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v[k]), r_out, at + 8 * k, 0, 0);
+              else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[k]), r_out, at + 4 * k, 0, 0);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();                                                   // the image is read out before the next tile's staging
+  }
+  if (bad && lane == 0) atomicExch(&p.ctl->error, 2u);
+}
+
+// The short last block (length l = n % 64) when the range reaches into it: k_decompress_rem's length-l inverse transform
+// (dctz-decomp-lib.c:423-428, dct.c:144-199), its first exact coefficient = idx[t] + the flags of the tile's whole blocks.
+template <typename T, int MODE>
+__global__ __launch_bounds__(64) void k_decompress_range_rem(RangeParams<T> p) {
+  __shared__ T a[64];
+  __shared__ T cr[128];
+  __shared__ T ci[128];
+  const int k = threadIdx.x;
+  const unsigned l = p.n - p.nfull * 64u;
+  const size_t base = (size_t)p.nfull * 64;
+  const unsigned t = p.nfull / (unsigned)TILE_BLKS;                    // the tile that holds the short block
+  const T* rt = p.rtab;
+  const int N = (l & 1) ? 2 * (int)l : (int)l;
+  // flags of the tile's whole blocks in front of the short block
+  unsigned c = 0;
+  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)k;
+  if (blk < p.nfull) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u32x4 v = src[i];
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        unsigned f = ra_flags(w[q]);
+        if (i == 0 && q == 0) f &= ~0x80u;
+        c += (unsigned)__popc(f);
+      }
+    }
+  }
+  const unsigned start = p.idx[t] + (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(c), 63);
+  const unsigned lim = min(p.ac_count, p.idx[t + 1]);
+  unsigned b = 0;
+  if ((unsigned)k < l) b = p.bin[base + k];
+  const bool exc = ((unsigned)k < l) && (k != 0) && (b == 255u);
+  const unsigned long long msk = __ballot(exc);
+  const unsigned rank = (unsigned)__popcll(msk & ((1ull << k) - 1ull));
+  cr[k] = T(0); ci[k] = T(0); cr[k + 64] = T(0); ci[k + 64] = T(0);
+  if ((unsigned)k < l) {
+    T val;
+    if (k == 0) val = (T)p.dc[p.nfull];
+    else if (exc) {
+      T v = T(0);
+      if (start + rank < lim) v = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u);
+      if (MODE == DCTZHIP_QT) v = qt_restore(v, p.qtab[k], p.eb, T(10), p.range_min, p.range_max);
+      val = v;
+    } else {
+      const int ti = (b & 1u) ? (int)(b >> 1) + 1 : -(int)(b >> 1);
+      val = (T)ti * p.bin_width;
+    }
+    a[k] = val;
+  }
+  __syncthreads();
+  if ((unsigned)k < l) {
+    cr[k] = rt[RTAB_IAS + k] * a[k];                                   // dct.c:146-151 / :166-172
+    ci[k] = rt[RTAB_IAX + k] * a[k];
+    if ((l & 1) && k >= 1) {                                           // dct.c:152-153
+      cr[l + k] = rt[RTAB_IAX + k] * a[l - k];
+      ci[l + k] = -(rt[RTAB_IAS + k] * a[l - k]);
+    }
+  }
+  __syncthreads();
+  if ((unsigned)k < l) {
+    const int L = (int)l;
+    const int s = (l & 1) ? k : ((k & 1) ? L - 1 - (k >> 1) : (k >> 1));   // dct.c:189-199
+    T acc = T(0);
+    for (int j = 0; j < N; j++) {
+      const int tt = (s * j) % N;
+      acc = acc + (cr[j] * rt[RTAB_WR + tt] - ci[j] * rt[RTAB_WI + tt]);
+    }
+    T val = (l & 1) ? (acc / (T)L) / T(2) : acc / (T)L;                // dct.c:163 / :185
+    if (p.sf != T(1)) val = val * p.sf;
+    const size_t e = base + (size_t)k;
+    if (e >= p.lo && e < p.hi) p.out[e - p.lo] = val;
+  }
+}
+
+template <typename T>
+int range_occupancy(int mode) {
+  int n = 0;
+  const hipError_t e = mode == DCTZHIP_EC
+      ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress_range<T, DCTZHIP_EC>, 64, 0)
+      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress_range<T, DCTZHIP_QT>, 64, 0);
+  return e == hipSuccess ? n : 0;
+}
+
+template <typename T>
+void launch_decompress_range(const RangeParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s) {
+  if (grid > 0) {
+    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_range<T, DCTZHIP_EC>), dim3(grid), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((k_decompress_range<T, DCTZHIP_QT>), dim3(grid), dim3(64), 0, s, p);
+  }
+  if (with_rem) {
+    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_range_rem<T, DCTZHIP_EC>), dim3(1), dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((k_decompress_range_rem<T, DCTZHIP_QT>), dim3(1), dim3(64), 0, s, p);
+  }
+}
+template int range_occupancy<double>(int);
+template int range_occupancy<float>(int);
+template void launch_decompress_range<double>(const RangeParams<double>&, int, int, bool, hipStream_t);
+template void launch_decompress_range<float>(const RangeParams<float>&, int, int, bool, hipStream_t);
+
+}  // namespace dctz

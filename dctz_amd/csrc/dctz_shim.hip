@@ -70,6 +70,9 @@ struct dctzhip_ctx {
   unsigned* qcnt = nullptr;         // k_compress -> k_compact_ac: per block, the counts of its tile's sub-lists (dctz_device.h: Sub)
   unsigned* ttot = nullptr;         // ... per tile, its "stored exactly" coefficients
   unsigned* tile_pre = nullptr;     // decode, tile-interleaved k_decompress: per tile, the counts of its range's tiles in front of it
+  unsigned* ix_part = nullptr;      // dctzhip_ac_index: flag counts per workgroup of k_ac_index, then their exclusive prefix
+  size_t ix_part_cap = 0;           // entries
+  int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
   int dec_il = 1;                   // 0: k_decompress with a contiguous tile range per workgroup; 1: interleaved for fp64 EC; 2: for all (DCTZHIP_DEC_IL)
   size_t qcnt_cap = 0;              // tiles the two hold
   void* qt_item = nullptr;
@@ -219,7 +222,7 @@ static int fail(dctzhip_ctx* c, int code, const char* fmt, ...) {
       return fail((c), DCTZHIP_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" const char* dctzhip_version(void) { return "0.2.0"; }
+extern "C" const char* dctzhip_version(void) { return "0.3.0"; }
 
 extern "C" const char* dctzhip_last_error(const dctzhip_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
 
@@ -317,7 +320,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -1867,6 +1870,115 @@ extern "C" int dctzhip_decompress(dctzhip_ctx* c, const void* d_bin, const float
            : decompress_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, n, eb, sf, mode, (float*)d_out);
   if (rc == DCTZHIP_OK && c->blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
   return rc;
+}
+
+// ---- random access on decode (include/dctz_hip.h; dctz_kernels_ra.hip) ------------------------------------------
+extern "C" size_t dctzhip_ac_index_len(size_t n) { return (n + DCTZHIP_INDEX_STRIDE - 1) / DCTZHIP_INDEX_STRIDE + 1; }
+
+extern "C" int dctzhip_ac_index(dctzhip_ctx* c, const void* d_bin, size_t n, uint32_t* d_index, uint32_t* total) {
+  if (!c) return DCTZHIP_E_ARG;
+  if (n == 0 || n > (size_t)INT_MAX) return fail(c, DCTZHIP_E_ARG, "dctzhip_ac_index: n must be in [1, INT_MAX]");
+  if (!d_bin || !d_index) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || ((uintptr_t)d_index & 3u)) return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, the index 4-byte aligned");
+  const size_t m = dctzhip_ac_index_len(n) - 1;
+  {
+    Span sp[2];
+    size_t k = 0;
+    add_span(sp, &k, d_bin, n, SPAN_READ, 0);
+    add_span(sp, &k, d_index, (m + 1) * sizeof(uint32_t), SPAN_OUT, 0);
+    int rc = check_spans(c, sp, k, "dctzhip_ac_index", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = regrow(c, &c->ix_part, &c->ix_part_cap, (m + IX_TPW - 1) / IX_TPW, sizeof(unsigned));
+  if (rc) return rc;
+  launch_ac_index((const uint8_t*)d_bin, (unsigned)n, d_index, c->ix_part, c->stream);
+  HIPCHK(c, hipGetLastError());
+  uint32_t* h = reinterpret_cast<uint32_t*>(c->h_pin + PIN_STATS);
+  HIPCHK(c, hipMemcpyAsync(h, d_index + m, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (total) *total = *h;
+  return DCTZHIP_OK;
+}
+
+template <typename T>
+static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                 const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
+                                 size_t lo, size_t hi, T* d_out) {
+  hipStream_t s = c->stream;
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  const unsigned t0 = (unsigned)(lo / TILE_ELEMS), t1 = (unsigned)((hi + TILE_ELEMS - 1) / TILE_ELEMS);
+  const bool with_rem = rem && hi > (size_t)nfull * 64;
+  if (c->ctl_dirty) HIPCHK(c, hipMemsetAsync(c->ctl, 0, sizeof(Ctl), s));
+  c->ctl_dirty = 1;                                 // until this call's error word has been read back clean
+  if (mode == DCTZHIP_QT) {
+    // staged through pinned memory that the next call may rewrite: this call ends with a stream synchronisation
+    T* hq = reinterpret_cast<T*>(c->h_pin + PIN_TAB + sizeof(double) * RTAB_SIZE);
+    memcpy(hq, qtable_host, sizeof(T) * 64);
+    HIPCHK(c, hipMemcpyAsync(c->qtab, hq, sizeof(T) * 64, hipMemcpyHostToDevice, s));
+  }
+  if (with_rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+  RangeParams<T> p;
+  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index; p.out = d_out;
+  p.tab = tab_of<T>(c); p.rtab = reinterpret_cast<const T*>(c->rtab); p.qtab = reinterpret_cast<const T*>(c->qtab);
+  p.ctl = c->ctl;
+  p.n = (unsigned)n; p.nfull = nfull; p.lo = (unsigned)lo; p.hi = (unsigned)hi; p.t0 = t0; p.t1 = t1; p.ac_count = ac_count;
+  p.sf = (T)sf;
+  p.bin_width = (T)((T)eb * 2 * 1.0);               // as decompress_impl (binning.c:17 / :37)
+  p.range_max = (T)(eb * DCTZHIP_NBINS);
+  p.range_min = (T)(-eb * DCTZHIP_NBINS);
+  p.eb = eb;
+  // one single-wave workgroup per tile of the range, persistent only beyond what is resident at once
+  int& occ = c->ra_occ[sizeof(T) == 8][mode == DCTZHIP_QT];    // (per context: the context's device)
+  if (occ == 0) occ = std::max(range_occupancy<T>(mode), 1);
+  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+  const unsigned tiles = t1 - t0;
+  const int grid = (int)(tiles < resident ? tiles : resident);
+  // (no stage timings: dctzhip_last_timings keeps reporting the last compress / decompress call)
+  launch_decompress_range<T>(p, mode, grid, with_rem, s);
+  SET_LAST(c, 1, "k_decompress_range<%s, %d>", tname<T>(), mode);
+  HIPCHK(c, hipGetLastError());
+  Ctl* hc = reinterpret_cast<Ctl*>(c->h_pin + PIN_CTL);
+  HIPCHK(c, hipMemcpyAsync(hc, c->ctl, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (!hc->error) c->ctl_dirty = 0;
+  if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
+  if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_decompress_range(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                        const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf,
+                                        int mode, size_t lo, size_t hi, void* d_out) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  if (lo >= hi || hi > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_range: the range [%zu, %zu) is not inside [0, %zu)", lo, hi, n);
+  if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    // what the call reads: the bin ids and DC of the range's tiles, their index entries, AC_exact (all of it: where the
+    // range's part starts is only known on the device)
+    const size_t t0 = lo / TILE_ELEMS, t1 = (hi + TILE_ELEMS - 1) / TILE_ELEMS;
+    const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n, t1 * (size_t)TILE_ELEMS);
+    Span sp[5];
+    size_t m = 0;
+    add_span(sp, &m, (const uint8_t*)d_bin + b0, b1 - b0, SPAN_READ, 0);
+    add_span(sp, &m, d_dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_out, (hi - lo) * elem_size(dtype), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_decompress_range", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? decompress_range_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, lo, hi,
+                                             (double*)d_out)
+             : decompress_range_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, lo, hi,
+                                            (float*)d_out);
 }
 
 // ---- multi-dimensional blocks (include/dctz_hip.h) -------------------------------------------------

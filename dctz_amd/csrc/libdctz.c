@@ -52,8 +52,8 @@
 /* ------------------------------------------------------------------ state -- */
 static dctzhip_ctx *g_ctx = NULL;
 static struct {
-  void *in, *bin, *dc, *ac, *out, *z[3];
-  size_t in_cap, bin_cap, dc_cap, ac_cap, out_cap, z_cap[3];
+  void *in, *bin, *dc, *ac, *out, *z[3], *idx;
+  size_t in_cap, bin_cap, dc_cap, ac_cap, out_cap, z_cap[3], idx_cap;
 } g_dev;
 /* Host copies of the raw streams (what the zlib tails read / the inflates write), kept between calls like the device
  * buffers above: a fresh 170 MB allocation per call costs its page faults on the way in and an munmap on the way out
@@ -384,7 +384,10 @@ static void *ix_worker(void *arg) {
       zs.next_in = (Bytef *)c->src; zs.avail_in = c->zlen;
       zs.next_out = c->dst; zs.avail_out = c->len;
       const int rc = inflate(&zs, Z_SYNC_FLUSH);
-      if ((rc != Z_OK && rc != Z_BUF_ERROR) || zs.avail_in != 0 || zs.avail_out != 0) c->err = 1;
+      if ((rc != Z_OK && rc != Z_BUF_ERROR) || zs.avail_in != 0 || zs.avail_out != 0) {
+        c->err = 1;
+        memset(zs.next_out, 0, zs.avail_out);   /* what a damaged chunk did not write: zeros, not what the buffer held before */
+      }
       inflateEnd(&zs);
       c->adler = adler32(adler32(0L, Z_NULL, 0), c->dst, c->len);
     }
@@ -417,6 +420,23 @@ static int read_index(const unsigned char *const sec[3], const unsigned int zlen
   return 1;
 }
 
+/* Inflates a list of independent chunks side by side on DCTZ_ZLIB_THREADS host threads (default: the cores, at most 32). */
+static void ix_run(ix_chunk *chunks, size_t total) {
+  int threads = zlib_threads();
+  if (threads <= 0) { long nc = sysconf(_SC_NPROCESSORS_ONLN); threads = nc > 32 ? 32 : (nc < 1 ? 1 : (int)nc); }
+  if ((size_t)threads > total) threads = total ? (int)total : 1;
+  ix_queue q;
+  q.chunks = chunks; q.nchunks = total; q.next = 0;
+  pthread_mutex_init(&q.mu, NULL);
+  pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)threads);
+  int started = 0;
+  if (th) for (int t = 0; t < threads - 1; t++) { if (pthread_create(&th[started], NULL, ix_worker, &q)) break; started++; }
+  ix_worker(&q);
+  for (int t = 0; t < started; t++) pthread_join(th[t], NULL);
+  free(th);
+  pthread_mutex_destroy(&q.mu);
+}
+
 /* The three sections of an indexed container inflated chunk by chunk on host threads (sizes / chunk from read_index).
  * Returns 1, or 0 when a chunk does not inflate or the content's adler32 is not the stream's: the caller then hands the
  * sections to the ordinary inflate, which treats damage the way the reference's reader does (dctz-decomp-lib.c:244-322
@@ -437,19 +457,7 @@ static int inflate_indexed(const unsigned char *const sec[3], const unsigned int
       off += sizes[i][j];
     }
   }
-  int threads = zlib_threads();
-  if (threads <= 0) { long nc = sysconf(_SC_NPROCESSORS_ONLN); threads = nc > 32 ? 32 : (nc < 1 ? 1 : (int)nc); }
-  if ((size_t)threads > total) threads = total ? (int)total : 1;
-  ix_queue q;
-  q.chunks = chunks; q.nchunks = total; q.next = 0;
-  pthread_mutex_init(&q.mu, NULL);
-  pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)threads);
-  int started = 0;
-  if (th) for (int t = 0; t < threads - 1; t++) { if (pthread_create(&th[started], NULL, ix_worker, &q)) break; started++; }
-  ix_worker(&q);
-  for (int t = 0; t < started; t++) pthread_join(th[t], NULL);
-  free(th);
-  pthread_mutex_destroy(&q.mu);
+  ix_run(chunks, total);
   int ok = 1;
   k = 0;
   for (int i = 0; i < 3 && ok; i++) {                   /* what inflate() checks at the end of a stream: the adler32 of the content */
@@ -1867,6 +1875,131 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   if (on_device) { g_times.zlib_s -= t_h2d_z; g_times.h2d_s += t_h2d_z; }      /* the compressed sections' way to the device is a copy, not inflate */
   g_times.total_s = now_s() - t_begin;
   return 1;
+}
+
+/* ---------------------------------------------------- dctz_decompress_range -- */
+/* The first `want` bytes of one section into dst.  Indexed (sizes != NULL): only the chunks that hold them, side by side
+ * on host threads (dst has room for whole chunks: min(raw, chunks * chunk) bytes); a chunk that does not inflate sends the
+ * section to the streaming inflate.  Otherwise one inflate that stops once `want` bytes are out.  Returns the bytes made. */
+static size_t inflate_prefix(const unsigned char *sec, unsigned int zlen, size_t raw, size_t want, unsigned char *dst, size_t chunk,
+                             const uint32_t *sizes) {
+  if (want == 0) return 0;
+  if (sizes) {
+    const size_t nch = (want + chunk - 1) / chunk;
+    ix_chunk *chunks = (ix_chunk *)calloc(nch, sizeof(ix_chunk));
+    if (!chunks) { fprintf(stderr, "Out of memory: chunk list\n"); exit(1); }
+    size_t off = 2;
+    for (size_t j = 0; j < nch; j++) {
+      chunks[j].src = sec + off; chunks[j].zlen = sizes[j];
+      chunks[j].dst = dst + j * chunk;
+      chunks[j].len = (unsigned int)(raw - j * chunk < chunk ? raw - j * chunk : chunk);
+      off += sizes[j];
+    }
+    ix_run(chunks, nch);
+    int ok = 1;
+    for (size_t j = 0; j < nch; j++) if (chunks[j].err) ok = 0;
+    free(chunks);
+    if (ok) return want;
+  }
+  z_stream zs;
+  memset(&zs, 0, sizeof(zs));
+  if (inflateInit(&zs) != Z_OK) return 0;
+  zs.next_in = (Bytef *)sec;
+  zs.avail_in = zlen;
+  size_t done = 0;
+  while (done < want) {
+    const size_t left = want - done;
+    const uInt step = left > ((size_t)1 << 30) ? (uInt)1 << 30 : (uInt)left;
+    zs.next_out = (Bytef *)dst + done;
+    zs.avail_out = step;
+    const int rc = inflate(&zs, Z_NO_FLUSH);
+    done += step - zs.avail_out;
+    if (rc != Z_OK) break;                                   /* end of stream, damage, or no progress */
+  }
+  inflateEnd(&zs);
+  return done;
+}
+
+int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
+  const double t_begin = now_s();
+  const int is_d = (var_z->datatype == DOUBLE);
+  const size_t ts = is_d ? sizeof(double) : sizeof(float);
+  const int dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const unsigned char *cur = is_d ? (const unsigned char *)var_z->buf.d : (const unsigned char *)var_z->buf.f;
+  struct header h;
+  memcpy(&h, cur, sizeof(h)); /* dctz-decomp-lib.c:84-94 */
+  cur += sizeof(h);
+  const size_t n = h.num_elements;
+  const unsigned int cnt = h.tot_AC_exact_count;
+  if (DCTZ_GEOM_OF(h.datatype) != 0 || n == 0 || lo >= hi || hi > n) return -1;   /* DZND: element order is not block order */
+  const size_t S = DCTZHIP_INDEX_STRIDE, nblk = (n + BLK_SZ - 1) / BLK_SZ;
+  const size_t t1 = (hi + S - 1) / S;                        /* the range's tiles end here */
+  const size_t need[3] = {MIN(n, S * t1),                    /* bin ids: the flags in front give AC_exact's position */
+                          (hi + BLK_SZ - 1) / BLK_SZ * sizeof(float),   /* DC up to the range's last block */
+                          0};                                /* AC_exact up to idx[t1]: known once the index is built */
+  const size_t dc_dev = MIN(nblk, t1 * (S / BLK_SZ));        /* DC words the range's tiles cover on the device */
+
+  dctzhip_ctx *c = ctx();
+  const unsigned int zl[3] = {h.bindex_sz_compressed, h.DC_sz_compressed, h.AC_exact_sz_compressed};
+  const unsigned char *const secp[3] = {cur, cur + zl[0], cur + zl[0] + zl[1]};
+  const size_t rawn[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
+  size_t ix_off = (size_t)zl[0] + zl[1] + zl[2];
+#ifdef USE_QTABLE
+  ix_off += BLK_SZ * ts;
+#endif
+  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
+  size_t chunk = 0;
+  const int indexed = zl[0] >= 8 && zl[1] >= 8 && zl[2] >= 8 && secp[0][1] == 0x5E && secp[1][1] == 0x5E && secp[2][1] == 0x5E &&
+                      read_index(secp, zl, rawn, cur + ix_off, &chunk, ix_sizes);
+  const void *qtable = NULL;
+#ifdef USE_QTABLE
+  double qd[BLK_SZ];
+  float qf[BLK_SZ];
+  if (is_d) { memcpy(qd, cur + zl[0] + zl[1] + zl[2], sizeof(qd)); qtable = qd; } /* :193-199 */
+  else { memcpy(qf, cur + zl[0] + zl[1] + zl[2], sizeof(qf)); qtable = qf; }
+#endif
+  int ret = -1;
+  unsigned char *hp[3];
+  size_t want[3] = {need[0], need[1], need[2]};
+  uint32_t ac_need = 0;
+  double t_zlib = 0.0, t_h2d = 0.0, t0;
+  for (int i = 0; i < 3; i++) {
+    if (i == 2) {                                            /* idx[t1] of the prefix's index = idx[t1] of the whole array's */
+      t0 = now_s();
+      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(need[0]) * sizeof(uint32_t));
+      if (dctzhip_ac_index(c, g_dev.bin, need[0], (uint32_t *)g_dev.idx, &ac_need) != DCTZHIP_OK) die("dctzhip_ac_index");
+      if (ac_need > cnt) goto out;                           /* the bin ids flag more than the header counts */
+      want[2] = (size_t)ac_need * sizeof(float);
+      t_h2d += now_s() - t0;
+    }
+    t0 = now_s();
+    const size_t room = indexed ? MIN(rawn[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
+    hp[i] = (unsigned char *)host_buf(i, room);
+    if (inflate_prefix(secp[i], zl[i], rawn[i], want[i], hp[i], chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
+    t_zlib += now_s() - t0;
+    t0 = now_s();
+    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
+    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
+    grow(dp, cp, i == 1 ? dc_dev * sizeof(float) : (want[i] ? want[i] : 4));
+    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp[i], want[i]) != DCTZHIP_OK) die("H2D section prefix");
+    t_h2d += now_s() - t0;
+  }
+  t0 = now_s();
+  grow(&g_dev.out, &g_dev.out_cap, (hi - lo) * ts);
+  const double sf = is_d ? h.scaling_factor.d : (double)h.scaling_factor.f;
+  const int rc = dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need, (const uint32_t *)g_dev.idx,
+                                          qtable, n, dtype, h.error_bound, sf, DCTZ_MODE, lo, hi, g_dev.out);
+  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  if (rc != DCTZHIP_OK) die("dctzhip_decompress_range");
+  const double t1s = now_s();
+  void *host_out = is_d ? (void *)var_r->buf.d : (void *)var_r->buf.f;
+  if (dctzhip_memcpy_d2h(c, host_out, g_dev.out, (hi - lo) * ts) != DCTZHIP_OK) die("D2H output");
+  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
+  g_times.total_s = now_s() - t_begin;
+  ret = 1;
+out:
+  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  return ret;
 }
 
 /* ------------------------------------------------------ calc_data_stat ----- */

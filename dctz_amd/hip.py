@@ -98,6 +98,11 @@ _PROTOS = {
     "dctzhip_decompress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                      C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int,
                                      C.c_void_p]),
+    "dctzhip_ac_index_len": (C.c_size_t, [C.c_size_t]),
+    "dctzhip_ac_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "dctzhip_decompress_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_size_t,
+                                           C.c_size_t, C.c_void_p]),
     "dctzhip_set_blocking": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_compress_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BatchCItem), C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_decompress_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BatchDItem), C.c_int, C.POINTER(C.c_int)]),
@@ -343,6 +348,35 @@ class Context:
             int(cnt), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype),
             float(eb), float(sf), mode, dst.data_ptr())
         self._check(rc, "dctzhip_decompress")
+        return dst
+
+    # ---- random access on decode (include/dctz_hip.h: dctzhip_ac_index / dctzhip_decompress_range) ----
+    def ac_index(self, out, n):
+        """Exception index of the streams `out` (their bin_index) of an n-element array: (index, total), index an int32
+        CUDA tensor of ceil(n / 4096) + 1 entries (idx[i] = exact coefficients in front of element 4096 i), total = idx[-1]."""
+        self._bind_stream()
+        idx = self.torch.empty(int(self.lib.dctzhip_ac_index_len(n)), dtype=self.torch.int32, device=self.device)
+        tot = C.c_uint32(0)
+        rc = self.lib.dctzhip_ac_index(self.h, out["bin_index"].data_ptr(), n, idx.data_ptr(), C.byref(tot))
+        self._check(rc, "dctzhip_ac_index")
+        return idx, tot.value
+
+    def decompress_range(self, out, cnt, n, dtype, eb, sf, lo, hi, index, mode=EC, qtable=None, dst=None):
+        """Elements [lo, hi) of what decompress() rebuilds from the same arguments, bit for bit; `index` from ac_index().
+        Returns dst (hi - lo elements)."""
+        t = self.torch
+        self._bind_stream()
+        if dst is None:
+            dst = t.empty(max(int(hi) - int(lo), 0), dtype=dtype, device=self.device)
+        q = None
+        if mode == QT:
+            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
+            assert q.size == 64
+        rc = self.lib.dctzhip_decompress_range(
+            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
+            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb), float(sf),
+            mode, int(lo), int(hi), dst.data_ptr())
+        self._check(rc, "dctzhip_decompress_range")
         return dst
 
     # ---- batches of arrays (include/dctz_hip.h: dctzhip_compress_batch / dctzhip_decompress_batch) ----

@@ -143,6 +143,17 @@ int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r);
  * target, DCTZHIP_E_ARG (-1) for bad arguments, a constant array or a NaN (PSNR undefined), pending multi-dimensional
  * blocks (flat blocks only), and always in the QT library (its bin widths come from a whole-array table). */
 int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double target_psnr, double *error_bound_used);
+/* Part of a container (ADDITION, EC and QT builds): elements [lo, hi), 0 <= lo < hi <= N, of what dctz_decompress(var_z,
+ * ...) reconstructs, bit for bit, into var_r->buf (allocated by the caller: at least hi - lo elements of the container's
+ * type).  Returns 1 like dctz_decompress, or -1 for a bad range, a multi-dimensional (DZND) container -- its element
+ * order is not the block order --, and a container whose sections do not inflate as far as the range needs or whose bin
+ * ids disagree with tot_AC_exact_count.  It inflates no more than the range needs: bin_index up to min(N, 4096 t1)
+ * (t1 = ceil(hi / 4096): the flags in front give the range's place in AC_exact), DC up to the range's last block,
+ * AC_exact up to the exception index's idx[t1] (include/dctz_hip.h: dctzhip_ac_index, built on the device from that
+ * bin_index prefix).  Plain zlib sections go through a streaming inflate that stops there; in a container with the DZIX
+ * chunk index the chunks that lie wholly beyond it are not inflated at all.  Nothing of the container is validated
+ * beyond that. */
+int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

@@ -261,6 +261,41 @@ int dctzhip_decompress(dctzhip_ctx *ctx, const void *d_bin_index, const float *d
                        const void *qtable_host, size_t n, int dtype,
                        double error_bound, double sf, int mode, void *d_out);
 
+/* ---- random access on decode ------------------------------------------------ */
+/* The blocks of a stream are independent but for the running position `pos` in AC_exact (dctz-decomp-lib.c:370,
+ * :402-412): the number of "stored exactly" flags in front of a block.  The exception index holds it every
+ * DCTZHIP_INDEX_STRIDE elements.  With m = ceil(n / 4096), for 0 <= i <= m
+ *   idx[i] = number of bin ids equal to 255 at an in-block position j, 1 <= j < block length, in elements
+ *            [0, min(n, 4096 i))
+ * (the DC slot does not count, nor anything past the short last block): idx[i] is the reference's pos at block 64 i and
+ * idx[m] is tot_AC_exact_count.  Built from bin_index alone, so it serves any streams -- this library's or those
+ * inflated from a reference container -- and EC and QT alike.  Nothing is written into containers.
+ *   dctzhip_ac_index_len  entries of the index: ceil(n / 4096) + 1
+ *   dctzhip_ac_index      d_bin_index (n bytes, 16-byte aligned) -> d_index (dctzhip_ac_index_len(n) words, 4-byte
+ *                         aligned, not overlapping bin_index); *total (or NULL) receives idx[m].  1 <= n <= INT_MAX.
+ *                         Host-synchronous, like dctzhip_stats. */
+#define DCTZHIP_INDEX_STRIDE 4096   /* elements per index entry (64 blocks) */
+size_t dctzhip_ac_index_len(size_t n);
+int dctzhip_ac_index(dctzhip_ctx *ctx, const void *d_bin_index, size_t n, uint32_t *d_index, uint32_t *total);
+/* Elements [lo, hi) of the array, 0 <= lo < hi <= n, any alignment.  The streams and d_index describe the WHOLE array and
+ * are passed as pointers to its start, exactly as for dctzhip_decompress (ac_count, qtable_host, n, dtype, error_bound,
+ * sf and mode mean what they mean there).
+ *   d_out       receives hi - lo elements: d_out[k] is, bit for bit, element lo + k of what dctzhip_decompress writes for
+ *               the same arguments (EC and QT, fp32 and fp64, the short last block included)
+ *   locality    with t0 = lo / 4096 and t1 = ceil(hi / 4096) the call reads only the bin ids and DC values of tiles
+ *               [t0, t1), the index entries idx[t0 .. t1] and AC_exact[idx[t0], idx[t1]); it writes nothing outside
+ *               d_out[0, hi - lo).  Its cost follows the range, not n.
+ *   refusals    before any launch, DCTZHIP_E_ARG for a range outside [0, n), a null or misaligned pointer (bin_index and
+ *               d_out 16-byte aligned, DC, AC_exact and the index 4-byte aligned), and a d_out that overlaps what the call
+ *               reads (bin ids and DC of the range's tiles, their index entries, AC_exact[0, ac_count)).  On the device:
+ *               the flags of every tile t of the range must number idx[t + 1] - idx[t], and idx[t1] <= ac_count; if not,
+ *               DCTZHIP_E_ARG as for dctzhip_decompress's under-run, the output is undefined and the context stays usable.
+ * Returns once that check is known; the output is complete in stream order on the context's stream (and the call has
+ * synchronised the stream). */
+int dctzhip_decompress_range(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                             uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
+                             double error_bound, double sf, int mode, size_t lo, size_t hi, void *d_out);
+
 /* ---- batches of arrays ------------------------------------------------------ */
 /* The reference's own workloads are LISTS of small arrays, one dctz_compress() call and one process each
  * (tests/test-dctz.sh:13-56 over tests/list-msst19.txt:1-6: 12 960 ... 37 024 doubles; tests/list-CESM-ATM-tylor.txt:1-5).

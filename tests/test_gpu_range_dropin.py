@@ -1,0 +1,152 @@
+"""dctz_decompress_range (include/dctz.h) through the drop-in libraries, EC and QT builds: elements [lo, hi) of what
+dctz_decompress reconstructs, bit for bit, from a container with the reference's zlib tail and from one with the DZIX
+chunk index (DCTZ_ZLIB_GPU=1).  On the indexed container, every compressed chunk that lies wholly beyond what the range
+needs is zeroed first: the result does not change, so those chunks are not inflated.  A DZND container and bad ranges
+are refused with -1."""
+import ctypes as C
+import os
+import struct
+import zlib
+
+import numpy as np
+import pytest
+
+from tests import workloads as W
+
+pytestmark = pytest.mark.gpu
+LIBDIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dctz_amd", "lib")
+TILE = 4096
+IX_MAGIC = 0x58495A44                                  # "DZIX"
+
+
+class TVarBuf(C.Union):
+    _fields_ = [("f", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_double))]
+
+
+class TVar(C.Structure):   # dctz.h:49-59
+    _fields_ = [("datatype", C.c_int), ("err_bound", C.c_double), ("var_name", C.c_char_p), ("buf", TVarBuf)]
+
+
+def _lib(mode):
+    os.environ["DCTZ_QUIET"] = "1"
+    lib = C.CDLL(os.path.join(LIBDIR, f"libdctz-{mode}.so"))
+    lib.dctz_compress.restype = C.c_int
+    lib.dctz_compress.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(TVar), C.c_double]
+    lib.dctz_decompress.restype = C.c_int
+    lib.dctz_decompress.argtypes = [C.POINTER(TVar), C.POINTER(TVar)]
+    lib.dctz_decompress_range.restype = C.c_int
+    lib.dctz_decompress_range.argtypes = [C.POINTER(TVar), C.c_size_t, C.c_size_t, C.POINTER(TVar)]
+    lib.dctz_set_block_dims.restype = C.c_int
+    lib.dctz_set_block_dims.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
+    return lib
+
+
+def _tvar(arr):
+    v = TVar()
+    v.datatype = 1 if arr.dtype == np.float64 else 0
+    if arr.dtype == np.float64:
+        v.buf.d = arr.ctypes.data_as(C.POINTER(C.c_double))
+    else:
+        v.buf.f = arr.ctypes.data_as(C.POINTER(C.c_float))
+    return v
+
+
+def _container(lib, x, eb, gpu_tail):
+    """(container bytes as a uint8 array, the full dctz_decompress result)."""
+    if gpu_tail:
+        os.environ["DCTZ_ZLIB_GPU"] = "1"
+    try:
+        xin = x.copy()                                  # (dctz_compress scales its input in place)
+        z = np.zeros(x.size * x.itemsize + (1 << 16), np.uint8)
+        zv = _tvar(z.view(x.dtype)[: z.size // x.itemsize])
+        sz = C.c_size_t(0)
+        assert lib.dctz_compress(C.byref(_tvar(xin)), x.size, C.byref(sz), C.byref(zv), eb) == 1
+    finally:
+        os.environ.pop("DCTZ_ZLIB_GPU", None)
+    full = np.empty_like(x)
+    assert lib.dctz_decompress(C.byref(zv), C.byref(_tvar(full))) == 1
+    return z, full
+
+
+def _range(lib, z, dtype, lo, hi):
+    out = np.full(max(hi - lo, 1), np.nan, dtype)
+    rc = lib.dctz_decompress_range(C.byref(_tvar(z.view(dtype)[: z.size // np.dtype(dtype).itemsize])), lo, hi, C.byref(_tvar(out)))
+    return rc, out[: hi - lo]
+
+
+def _same(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+N = 64 * 20000 + 37                                    # 1.28 M elements: many 4096-element tiles, a short last block
+RANGES = [(0, 1), (0, N), (N - 1, N), (5, 9), (TILE - 3, TILE + 70), (100, 5000), (N // 2, N // 2 + (1 << 16) + 3),
+          (N - 45, N), (N - 64 * 100 - 7, N), (7 * TILE, 9 * TILE), (123457, 123458)]
+
+
+@pytest.mark.parametrize("mode", ["ec", "qt"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("gpu_tail", [False, True], ids=["zlib_tail", "dzix"])
+def test_range_is_the_slice_of_dctz_decompress(mode, dtype, gpu_tail):
+    lib = _lib(mode)
+    x = W.ragged(N, dtype, scale=37.0)
+    z, full = _container(lib, x, 1e-3, gpu_tail)
+    for lo, hi in RANGES:
+        rc, r = _range(lib, z, dtype, lo, hi)
+        assert rc == 1 and _same(r, full[lo:hi]), (lo, hi)
+
+
+def _sections(z, dtype, qt):
+    dt, n, eb, cnt = struct.unpack_from("<IIdI", z, 0)
+    sizes = struct.unpack_from("<III", z, 40)
+    offs = [56, 56 + sizes[0], 56 + sizes[0] + sizes[1]]
+    end = offs[2] + sizes[2] + (64 * np.dtype(dtype).itemsize if qt else 0)
+    return n, cnt, sizes, offs, end
+
+
+@pytest.mark.parametrize("mode", ["ec", "qt"])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_dzix_chunks_beyond_the_range_are_not_inflated(mode, dtype):
+    lib = _lib(mode)
+    x = W.ragged(N, dtype, scale=37.0)
+    z, full = _container(lib, x, 1e-3, True)
+    n, cnt, sizes, offs, end = _sections(z, dtype, mode == "qt")
+    assert all(z[o + 1] == 0x5E for o in offs)          # the GPU entropy stage's mark
+    magic, chunk, c0, c1, c2 = struct.unpack_from("<5I", z, end)
+    assert magic == IX_MAGIC
+    csz = np.frombuffer(bytes(z[end + 20:end + 20 + 2 * (c0 + c1 + c2)]), np.uint16).astype(np.int64)
+    per = [csz[:c0], csz[c0:c0 + c1], csz[c0 + c1:]]
+    bins = np.frombuffer(zlib.decompress(bytes(z[offs[0]:offs[0] + sizes[0]])), np.uint8)
+    flags = (bins == 255) & (np.arange(n) % 64 != 0)
+    for lo, hi in [(100, 5000), (0, 1), (3 * TILE + 5, 6 * TILE - 1), (N // 3, N // 3 + 20000)]:
+        t1 = -(-hi // TILE)
+        need = [min(n, TILE * t1), -(-hi // 64) * 4, int(flags[:min(n, TILE * t1)].sum()) * 4]
+        zz = z.copy()
+        zeroed = 0
+        for i in range(3):
+            off = offs[i] + 2
+            for j, s in enumerate(per[i]):
+                if j * chunk >= need[i]:                  # wholly beyond what the range needs
+                    zz[off:off + s] = 0
+                    zeroed += 1
+                off += s
+        assert zeroed > 0
+        rc, r = _range(lib, zz, dtype, lo, hi)
+        assert rc == 1 and _same(r, full[lo:hi]), (lo, hi)
+
+
+@pytest.mark.parametrize("mode", ["ec", "qt"])
+def test_dznd_and_bad_ranges_are_refused(mode):
+    lib = _lib(mode)
+    x = W.ragged(N, np.float64, scale=37.0)
+    z, full = _container(lib, x, 1e-3, False)
+    for lo, hi in [(5, 5), (6, 5), (0, N + 1), (N, N + 1)]:
+        assert _range(lib, z, np.float64, lo, hi)[0] == -1, (lo, hi)
+    shape = (96, 80)
+    y = W.ragged(shape[0] * shape[1], np.float64, scale=37.0)
+    assert lib.dctz_set_block_dims(2, (C.c_size_t * 2)(*shape)) == 0
+    zn, _ = _container(lib, y, 1e-3, False)
+    assert (struct.unpack_from("<I", zn, 0)[0] >> 8) & 0xFF == 2
+    assert _range(lib, zn, np.float64, 0, 10)[0] == -1
+    # and the library still decodes a flat container afterwards
+    rc, r = _range(lib, z, np.float64, 10, 5000)
+    assert rc == 1 and _same(r, full[10:5000])

@@ -1,0 +1,128 @@
+#!/usr/bin/env python3
+"""Random access on decode, measured: the exception index and range decodes of the C4 shard
+(synthetic fp64 512^3, EC, eb 1e-3) next to the whole-array decode in the same process.
+
+  --what index   dctzhip_ac_index               (k_ac_index*)
+  --what range   2^21 contiguous elements       (k_decompress_range)
+  --what one     one element                    (wall clock of the call)
+  --what full    [0, n)
+  --what dropin  dctz_decompress_range of 2^21 elements from the shard's 1 GiB DZIX container (DCTZ_ZLIB_GPU=1)
+                 against dctz_decompress of the whole container (wall clock, host buffers)
+Every other run also times dctzhip_decompress of the whole shard.  Wall-clock medians go to stdout as one JSON line; for device
+times run one --what per process under `rocprofv3 --kernel-trace --stats -- python tools/range_bench.py --what ...`."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin"], required=True)
+    ap.add_argument("--n", type=int, default=512, help="edge of the cube")
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    import dctz_amd
+    from tests import workloads as W
+
+    if a.what == "dropin":
+        return dropin(a, W)
+    ctx = dctz_amd.Context(0)
+    x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device)
+    n = x.numel()
+    eb = 1e-3
+    out, info = ctx.compress(x, eb, dctz_amd.EC)
+    del x
+    full = torch.empty(n, dtype=torch.float64, device=ctx.device)
+    idx, tot = ctx.ac_index(out, n)
+    assert tot == info.cnt
+    lo = n // 2 + 12345
+    rng = {"range": (lo, lo + (1 << 21)), "one": (lo, lo + 1), "full": (0, n), "index": None}[a.what]
+    dst = None if rng is None else torch.empty(rng[1] - rng[0], dtype=torch.float64, device=ctx.device)
+
+    def t_full():
+        ctx.decompress(out, info.cnt, n, torch.float64, eb, info.sf, dctz_amd.EC, dst=full)
+
+    def t_what():
+        if rng is None:
+            ctx.ac_index(out, n)
+        else:
+            ctx.decompress_range(out, info.cnt, n, torch.float64, eb, info.sf, rng[0], rng[1], idx, dctz_amd.EC, dst=dst)
+
+    def med(f):
+        ts = []
+        for _ in range(a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    for f in (t_full, t_what):                      # warm-up
+        f()
+    ms_full, ms_what = med(t_full), med(t_what)
+    if rng is not None:                             # and the result is the slice of the full decode
+        assert torch.equal(dst.view(torch.int64), full[rng[0]:rng[1]].view(torch.int64))
+    print(json.dumps({"what": a.what, "n": n, "cnt": info.cnt, "range": rng, "wall_ms_decompress": round(ms_full, 4),
+                      "wall_ms_" + a.what: round(ms_what, 4)}))
+    ctx.close()
+
+
+def dropin(a, W):
+    import ctypes as C
+    import numpy as np
+
+    class Buf(C.Union):
+        _fields_ = [("f", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_double))]
+
+    class TVar(C.Structure):                        # include/dctz.h: t_var
+        _fields_ = [("datatype", C.c_int), ("err_bound", C.c_double), ("var_name", C.c_char_p), ("buf", Buf)]
+
+    def tv(arr):
+        v = TVar()
+        v.datatype = 1
+        v.buf.d = arr.ctypes.data_as(C.POINTER(C.c_double))
+        return v
+
+    os.environ["DCTZ_QUIET"] = "1"
+    lib = C.CDLL(os.path.join(ROOT, "dctz_amd", "lib", "libdctz-ec.so"))
+    lib.dctz_compress.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(TVar), C.c_double]
+    lib.dctz_decompress.argtypes = [C.POINTER(TVar), C.POINTER(TVar)]
+    lib.dctz_decompress_range.argtypes = [C.POINTER(TVar), C.c_size_t, C.c_size_t, C.POINTER(TVar)]
+    x = W.c3(a.n, seed=512)
+    n = x.size
+    z = np.empty(n + (1 << 20), np.float64)
+    sz = C.c_size_t(0)
+    os.environ["DCTZ_ZLIB_GPU"] = "1"
+    assert lib.dctz_compress(C.byref(tv(x)), n, C.byref(sz), C.byref(tv(z)), 1e-3) == 1
+    del os.environ["DCTZ_ZLIB_GPU"]
+    full = np.empty(n, np.float64)
+    lo = n // 2 + 12345
+    hi = lo + (1 << 21)
+    part = np.empty(hi - lo, np.float64)
+
+    def med(f):
+        f()
+        ts = []
+        for _ in range(max(3, a.reps // 4)):
+            t0 = time.perf_counter()
+            f()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    ms_full = med(lambda: lib.dctz_decompress(C.byref(tv(z)), C.byref(tv(full))))
+    ms_part = med(lambda: lib.dctz_decompress_range(C.byref(tv(z)), lo, hi, C.byref(tv(part))))
+    assert np.array_equal(part.view(np.uint64), full[lo:hi].view(np.uint64))
+    print(json.dumps({"what": "dropin", "n": n, "container_bytes": sz.value, "range": [lo, hi],
+                      "wall_ms_dctz_decompress": round(ms_full, 3), "wall_ms_dctz_decompress_range": round(ms_part, 3)}))
+
+
+if __name__ == "__main__":
+    main()
