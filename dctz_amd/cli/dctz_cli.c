@@ -23,7 +23,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "dctz.h"
+#include "../csrc/dctz_container.h"
 
 #ifdef USE_QTABLE
 #define VARIANT "qt"
@@ -122,14 +122,14 @@ int main(int argc, char *argv[]) {
   printf("outsize = %zu\n", out_size);
 
   /* the library scaled the caller's array in place: undo it with the header's factor */
-  struct header h;
-  memcpy(&h, comp, sizeof(h));
+  dzc_view z;
+  dzc_header(&z, comp, 0, (int)dt);
   if (dt == DOUBLE) {
-    if (h.scaling_factor.d != 1.0)
-      for (int i = 0; i < N; i++) var.buf.d[i] *= h.scaling_factor.d;
+    if (z.h.scaling_factor.d != 1.0)
+      for (int i = 0; i < N; i++) var.buf.d[i] *= z.h.scaling_factor.d;
   } else {
-    if (h.scaling_factor.f != 1.0)
-      for (int i = 0; i < N; i++) var.buf.f[i] *= h.scaling_factor.f;
+    if (z.h.scaling_factor.f != 1.0)
+      for (int i = 0; i < N; i++) var.buf.f[i] *= z.h.scaling_factor.f;
   }
 
   if (!write_file(zpath, comp, out_size)) {

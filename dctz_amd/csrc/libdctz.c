@@ -36,6 +36,7 @@
 #include <sys/time.h>
 
 #include "dctz_hip.h"
+#include "dctz_container.h"
 
 #ifndef USE_TRUNCATE
 #error "build with -DUSE_TRUNCATE (every reference target does, Makefile:13-24)"
@@ -48,6 +49,7 @@
 #else
 #define DCTZ_MODE DCTZHIP_EC
 #endif
+#define DCTZ_QT (DCTZ_MODE == DCTZHIP_QT)     /* the variant, as csrc/dctz_container.h takes it */
 
 /* ------------------------------------------------------------------ state -- */
 static dctzhip_ctx *g_ctx = NULL;
@@ -354,6 +356,8 @@ static void *inflate_main(void *arg) {
   return NULL;
 }
 
+static void put_be32(unsigned char *p, uLong v) { p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v; }
+static uLong get_be32(const unsigned char *p) { return ((uLong)p[0] << 24) | ((uLong)p[1] << 16) | ((uLong)p[2] << 8) | (uLong)p[3]; }
 /* ---- sections whose deflate blocks are independent chunks ("DZIX" trailer, dctz.h): inflated side by side ---- */
 typedef struct {
   const unsigned char *src;   /* chunk bytes (raw deflate, byte aligned) */
@@ -394,32 +398,6 @@ static void *ix_worker(void *arg) {
   }
   return NULL;
 }
-/* The chunk index of a container ("DZIX", dctz.h) as three arrays of compressed sizes.  Returns 1 when the sections
- * carry the mark (78 5E), the trailer is there and describes them exactly -- chunk counts that follow from the raw sizes,
- * sizes that tile every stream up to its 03 00 + adler32 --, else 0 (nothing allocated): the caller then takes the
- * ordinary inflate. */
-static int read_index(const unsigned char *const sec[3], const unsigned int zlen[3], const size_t raw[3], const unsigned char *trailer,
-                      size_t *chunk_out, uint32_t *sizes[3]) {
-  for (int i = 0; i < 3; i++) { sizes[i] = NULL; if (zlen[i] < 8 || sec[i][0] != 0x78 || sec[i][1] != 0x5E) return 0; }
-  unsigned int hd[5];
-  memcpy(hd, trailer, sizeof(hd));
-  if (hd[0] != DCTZ_IX_MAGIC || hd[1] < 1024 || hd[1] > 65535) return 0;
-  const size_t chunk = hd[1];
-  for (int i = 0; i < 3; i++) if (hd[2 + i] != (raw[i] + chunk - 1) / chunk) return 0;
-  const unsigned char *e = trailer + sizeof(hd);
-  int ok = 1;
-  for (int i = 0; i < 3 && ok; i++) {
-    sizes[i] = (uint32_t *)malloc((hd[2 + i] ? hd[2 + i] : 1) * sizeof(uint32_t));
-    if (!sizes[i]) { ok = 0; break; }
-    size_t off = 2;
-    for (size_t j = 0; j < hd[2 + i]; j++, e += 2) { unsigned short z; memcpy(&z, e, 2); sizes[i][j] = z; off += z; }
-    if (off + 6 != zlen[i] || sec[i][off] != 0x03 || sec[i][off + 1] != 0x00) ok = 0;      /* the sizes must tile the stream */
-  }
-  if (!ok) { for (int i = 0; i < 3; i++) { free(sizes[i]); sizes[i] = NULL; } return 0; }
-  *chunk_out = chunk;
-  return 1;
-}
-
 /* Inflates a list of independent chunks side by side on DCTZ_ZLIB_THREADS host threads (default: the cores, at most 32). */
 static void ix_run(ix_chunk *chunks, size_t total) {
   int threads = zlib_threads();
@@ -437,12 +415,14 @@ static void ix_run(ix_chunk *chunks, size_t total) {
   pthread_mutex_destroy(&q.mu);
 }
 
-/* The three sections of an indexed container inflated chunk by chunk on host threads (sizes / chunk from read_index).
+/* The three sections of an indexed container inflated chunk by chunk on host threads (sizes / chunk from dzc_read_index).
  * Returns 1, or 0 when a chunk does not inflate or the content's adler32 is not the stream's: the caller then hands the
  * sections to the ordinary inflate, which treats damage the way the reference's reader does (dctz-decomp-lib.c:244-322
  * ignores inflate's return code). */
-static int inflate_indexed(const unsigned char *const sec[3], const unsigned int zlen[3], unsigned char *const dst[3], const size_t raw[3],
-                            size_t chunk, uint32_t *const sizes[3]) {
+static int inflate_indexed(const dzc_view *v, unsigned char *const dst[3], size_t chunk, uint32_t *const sizes[3]) {
+  const unsigned char *const *sec = v->sec;
+  const unsigned int *zlen = v->zlen;
+  const size_t *raw = v->raw;
   size_t nch[3], total = 0;
   for (int i = 0; i < 3; i++) { nch[i] = (raw[i] + chunk - 1) / chunk; total += nch[i]; }
   ix_chunk *chunks = (ix_chunk *)calloc(total ? total : 1, sizeof(ix_chunk));
@@ -463,9 +443,7 @@ static int inflate_indexed(const unsigned char *const sec[3], const unsigned int
   for (int i = 0; i < 3 && ok; i++) {                   /* what inflate() checks at the end of a stream: the adler32 of the content */
     uLong a = adler32(0L, Z_NULL, 0);
     for (size_t j = 0; j < nch[i]; j++, k++) { if (chunks[k].err) ok = 0; a = adler32_combine(a, chunks[k].adler, (z_off_t)chunks[k].len); }
-    const unsigned char *t = sec[i] + zlen[i] - 4;
-    const uLong want = ((uLong)t[0] << 24) | ((uLong)t[1] << 16) | ((uLong)t[2] << 8) | (uLong)t[3];
-    if (a != want) ok = 0;
+    if (a != get_be32(sec[i] + zlen[i] - 4)) ok = 0;
   }
   free(chunks);
   if (!ok) fprintf(stderr, "libdctz: a chunk of an indexed section does not inflate; falling back to the one-stream inflate\n");
@@ -670,8 +648,6 @@ static void *track_main(void *arg) {            /* releases the groups to the fo
   }
   return NULL;
 }
-static void put_be32(unsigned char *p, uLong v) { p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v; }
-static uLong get_be32(const unsigned char *p) { return ((uLong)p[0] << 24) | ((uLong)p[1] << 16) | ((uLong)p[2] << 8) | (uLong)p[3]; }
 /* the drainer: compressed pieces of finished groups, device -> host, in order, beside the calling thread */
 typedef struct {
   const unsigned char *src;     /* device: a piece's stream (78 5E | chunks | 03 00 | adler32) */
@@ -762,7 +738,7 @@ static int compress_pipelined(dctzhip_ctx *c, t_var *var, void *host_in, size_t 
   unsigned char *dcz = (unsigned char *)host_buf(1, G * bound[1]), *acz = (unsigned char *)host_buf(2, G * bound[2]);
   drain_piece *pieces = (drain_piece *)malloc((3 * G + 3) * sizeof(drain_piece));
   if (!ix[0] || !ix[1] || !ix[2] || !pieces) { fprintf(stderr, "Out of memory: chunk index\n"); exit(1); }
-  unsigned char *zc = (is_d ? (unsigned char *)var_z->buf.d : (unsigned char *)var_z->buf.f) + sizeof(struct header);
+  unsigned char *zc = dzc_sections(var_bytes(var_z));
 
   const double t0 = now_s();
   if (dctzhip_h2d_pipe_begin(c, g_dev.in, host_in, n * ts, gel * ts) != DCTZHIP_OK) die("H2D pipe");
@@ -896,31 +872,13 @@ static int compress_pipelined(dctzhip_ctx *c, t_var *var, void *host_in, size_t 
     if (dctzhip_memcpy_d2h(c, host_in, g_dev.in, n * ts) != DCTZHIP_OK) die("D2H scaled input");
   }
 
-  /* container: header | bin_indexz | DCz | AC_exactz | "DZIX"  (:775-820) */
-  struct header h;
-  memset(&h, 0, sizeof(h));
-  h.datatype = var->datatype;
-  h.num_elements = (unsigned int)n;
-  h.error_bound = error_bound;
-  h.tot_AC_exact_count = (unsigned int)S;
-  if (is_d) { h.scaling_factor.d = sf; h.mean.d = sum / (double)(int)n; }           /* util.c:28 / :41, on a tree-order sum (DCTZ_FAST_MEAN) */
-  else { h.scaling_factor.f = (float)sf; h.mean.f = (float)sum / (float)(int)n; }
-  h.bindex_sz_compressed = (unsigned int)z0;
-  h.DC_sz_compressed = (unsigned int)z1;
-  h.AC_exact_sz_compressed = (unsigned int)z2;
-  memcpy(zc - sizeof(h), &h, sizeof(h));
-  const size_t ix_bytes = (20 + 2 * (ix_n[0] + ix_n[1] + ix_n[2]) + 3) & ~(size_t)3;
-  unsigned char *cur = zc + z0 + z1 + z2;
-  const unsigned int hd[5] = {DCTZ_IX_MAGIC, (unsigned int)chunk, (unsigned int)ix_n[0], (unsigned int)ix_n[1], (unsigned int)ix_n[2]};
-  memset(cur, 0, ix_bytes);
-  memcpy(cur, hd, sizeof(hd));
-  unsigned short *e = (unsigned short *)(cur + sizeof(hd));
-  for (int i = 0; i < 3; i++) {
-    for (size_t k = 0; k < ix_n[i]; k++) *e++ = (unsigned short)ix[i][k];
-    free(ix[i]);
-  }
+  /* container: header | bin_indexz | DCz | AC_exactz | "DZIX"; the mean is util.c:28 / :41 on a tree-order sum (DCTZ_FAST_MEAN) */
+  const dzc_desc d = {.type = var->datatype, .n = n, .npos = n, .error_bound = error_bound, .sf = sf, .cnt = (unsigned int)S,
+                      .mean = is_d ? sum / (double)(int)n : (double)((float)sum / (float)(int)n), .zlen = {z0, z1, z2},
+                      .chunk = chunk, .ix_n = ix_n, .ix = ix};
+  *outSize = dzc_finish(var_bytes(var_z), &d);
+  for (int i = 0; i < 3; i++) free(ix[i]);
   free(firsts); free(pieces);
-  *outSize = sizeof(struct header) + z0 + z1 + z2 + ix_bytes;
   const double t_end = now_s();
   /* the stages overlap: h2d_s is the span up to the last group's kernels, gpu_s / zlib_s what the calling thread spent in the
    * groups' kernels / entropy stage, d2h_s what was left behind the last group (drain, assembly, the follower) */
@@ -938,7 +896,7 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
   const int is_d = (var->datatype == DOUBLE);
   const size_t ts = is_d ? sizeof(double) : sizeof(float);
   const int dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  void *host_in = is_d ? (void *)var->buf.d : (void *)var->buf.f;
+  void *host_in = var_bytes(var);
 
   if (error_bound < 1E-6) { /* dctz-comp-lib.c:135-138 */
     printf("ERROR BOUND is not acceptable");
@@ -1044,7 +1002,7 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
     const unsigned gflags[3] = {0u, DCTZHIP_DEFLATE_LITERALS, DCTZHIP_DEFLATE_LITERALS};   /* DC and AC_exact are bytes of floats */
     if (dctzhip_deflate_ex(c, 3, gsrc, sec_bytes, (void *const *)g_dev.z, gcap, gz_len, (uint32_t *const *)ix, gflags) != DCTZHIP_OK) die("dctzhip_deflate");
     /* the sections go straight from the device into the caller's container, behind the header (:775-820) */
-    unsigned char *zc = (is_d ? (unsigned char *)var_z->buf.d : (unsigned char *)var_z->buf.f) + sizeof(struct header);
+    unsigned char *zc = dzc_sections(var_bytes(var_z));
     for (int i = 0; i < 3; i++) {
       if (dctzhip_memcpy_d2h(c, zc, g_dev.z[i], gz_len[i]) != DCTZHIP_OK) die("D2H compressed section");
       zc += gz_len[i];
@@ -1093,56 +1051,17 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
   pthread_attr_destroy(&attr);
   double t4 = now_s();
 
-  /* container: header | bin_indexz | DCz | AC_exactz | [qtable]  (:775-820) */
-  struct header h;
-  memset(&h, 0, sizeof(h));
-  h.datatype = (t_datatype)((unsigned)var->datatype | ((unsigned)nd << DCTZ_GEOM_SHIFT));
-  h.num_elements = (unsigned int)N;
-  h.error_bound = error_bound;
-  h.tot_AC_exact_count = info.cnt;
-  if (is_d) { h.scaling_factor.d = info.sf; h.mean.d = mean_serial; }
-  else { h.scaling_factor.f = (float)info.sf; h.mean.f = (float)mean_serial; }
-  h.bindex_sz_compressed = (unsigned int)zsz[0];
-  h.DC_sz_compressed = (unsigned int)zsz[1];
-  h.AC_exact_sz_compressed = (unsigned int)zsz[2];
-#ifdef USE_QTABLE
-  h.bindex_count = (unsigned int)npos;
-#endif
-  *outSize = sizeof(struct header) + zsz[0] + zsz[1] + zsz[2];
-#ifdef USE_QTABLE
-  *outSize += BLK_SZ * ts;
-#endif
-  if (nd) *outSize += 16;                      /* "DZND" + the extents */
-  const size_t ix_bytes = gpu_tail ? ((20 + 2 * (ix_n[0] + ix_n[1] + ix_n[2]) + 3) & ~(size_t)3) : 0;
-  *outSize += ix_bytes;                        /* "DZIX" chunk index (dctz.h) */
-  unsigned char *cur = is_d ? (unsigned char *)var_z->buf.d : (unsigned char *)var_z->buf.f;
-  memcpy(cur, &h, sizeof(h)); cur += sizeof(h);
-  if (gpu_tail) cur += zsz[0] + zsz[1] + zsz[2];         /* already in place */
-  else {
-    memcpy(cur, jb[0].dst, zsz[0]); cur += zsz[0];
-    memcpy(cur, jb[1].dst, zsz[1]); cur += zsz[1];
-    memcpy(cur, jb[2].dst, zsz[2]); cur += zsz[2];
+  /* container: header | bin_indexz | DCz | AC_exactz | [qtable] | ["DZND"] | ["DZIX"]  (:775-820) */
+  if (!gpu_tail) {                             /* (the device's sections are already in place) */
+    unsigned char *cur = dzc_sections(var_bytes(var_z));
+    for (int i = 0; i < 3; i++) { memcpy(cur, jb[i].dst, zsz[i]); cur += zsz[i]; }
   }
-#ifdef USE_QTABLE
-  if (is_d) memcpy(cur, info.qtable, BLK_SZ * sizeof(double));
-  else { float q[BLK_SZ]; for (int j = 0; j < BLK_SZ; j++) q[j] = (float)info.qtable[j]; memcpy(cur, q, sizeof(q)); }
-  cur += BLK_SZ * ts;
-#endif
-  if (nd) {
-    const unsigned int tr[4] = {DCTZ_ND_MAGIC, (unsigned int)dims[0], (unsigned int)dims[1], (unsigned int)(nd == 3 ? dims[2] : 0)};
-    memcpy(cur, tr, sizeof(tr));
-    cur += sizeof(tr);
-  }
-  if (gpu_tail) {
-    const unsigned int hd[5] = {DCTZ_IX_MAGIC, (unsigned int)dctzhip_deflate_chunk_bytes(), (unsigned int)ix_n[0], (unsigned int)ix_n[1], (unsigned int)ix_n[2]};
-    memset(cur, 0, ix_bytes);
-    memcpy(cur, hd, sizeof(hd));
-    unsigned short *e = (unsigned short *)(cur + sizeof(hd));
-    for (int i = 0; i < 3; i++) {
-      for (size_t k = 0; k < ix_n[i]; k++) *e++ = (unsigned short)ix[i][k];
-      free(ix[i]);
-    }
-  }
+  const dzc_desc d = {.type = var->datatype, .nd = nd, .dims = dims, .n = n, .npos = npos, .error_bound = error_bound, .sf = info.sf,
+                      .mean = mean_serial, .cnt = info.cnt, .zlen = {zsz[0], zsz[1], zsz[2]},
+                      .qtable = DCTZ_QT ? info.qtable : NULL,
+                      .chunk = dctzhip_deflate_chunk_bytes(), .ix_n = ix_n, .ix = gpu_tail ? ix : NULL};
+  *outSize = dzc_finish(var_bytes(var_z), &d);
+  for (int i = 0; i < 3; i++) free(ix[i]);
   for (int i = 0; i < 3; i++) free(jb[i].dst);
 
   g_times.h2d_s = t1 - t0; g_times.gpu_s = t2 - t1; g_times.d2h_s = t3 - t2; g_times.zlib_s = t4 - t3;
@@ -1234,7 +1153,7 @@ int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double 
   if (g_nd || (getenv("DCTZ_BLOCK_DIMS") && *getenv("DCTZ_BLOCK_DIMS"))) return DCTZHIP_E_ARG;   /* flat blocks only */
   const int is_d = (var->datatype == DOUBLE);
   if (!is_d && var->datatype != FLOAT) return DCTZHIP_E_ARG;
-  const void *host_in = is_d ? (const void *)var->buf.d : (const void *)var->buf.f;
+  const void *host_in = var_bytes(var);
   if (!host_in) return DCTZHIP_E_ARG;
   const size_t n = (size_t)N, ts = is_d ? sizeof(double) : sizeof(float);
   dctzhip_ctx *c = ctx();
@@ -1280,7 +1199,7 @@ static int batch_inputs_overlap(int k, t_var *const *vars, const int *N) {
   if (!r) { fprintf(stderr, "Out of memory: batch\n"); exit(1); }
   for (int i = 0; i < k; i++) {
     const int is_d = vars[i]->datatype == DOUBLE;
-    r[i].lo = (uintptr_t)(is_d ? (void *)vars[i]->buf.d : (void *)vars[i]->buf.f);
+    r[i].lo = (uintptr_t)var_bytes(vars[i]);
     r[i].hi = r[i].lo + (size_t)(N[i] > 0 ? N[i] : 0) * (is_d ? 8 : 4);
   }
   qsort(r, (size_t)k, sizeof(*r), brange_cmp);
@@ -1324,7 +1243,7 @@ int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSize
   for (int i = 0; i < k; i++) {
     const int is_d = vars[i]->datatype == DOUBLE;
     const size_t ts = is_d ? 8 : 4;
-    memcpy(hp + off_in[i], is_d ? (void *)vars[i]->buf.d : (void *)vars[i]->buf.f, (size_t)N[i] * ts);
+    memcpy(hp + off_in[i], var_bytes(vars[i]), (size_t)N[i] * ts);
     items[i].d_in = dp + off_in[i]; items[i].n = (size_t)N[i]; items[i].dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
     items[i].error_bound = error_bounds[i];
     items[i].d_bin_index = dp + off_bin[i]; items[i].d_dc = (float *)(dp + off_dc[i]); items[i].d_ac_exact = (float *)(dp + off_ac[i]);
@@ -1344,7 +1263,7 @@ int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSize
       j->arr = i;
       if (pass == 3) {
         const int is_d = vars[i]->datatype == DOUBLE;
-        j->kind = 1; j->x = is_d ? (void *)vars[i]->buf.d : (void *)vars[i]->buf.f; j->nx = n; j->is_d = is_d; j->sf = infos[i].sf;
+        j->kind = 1; j->x = var_bytes(vars[i]); j->nx = n; j->is_d = is_d; j->sf = infos[i].sf;
       } else {
         const int sec = pass == 0 ? 2 : pass - 1;
         const size_t bytes = sec == 0 ? n : (sec == 1 ? nblk * sizeof(float) : (size_t)infos[i].cnt * sizeof(float));
@@ -1360,35 +1279,15 @@ int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSize
   bpool_run(jobs, nj);
   /* containers: header | bin_indexz | DCz | AC_exactz | [qtable]  (:775-820) */
   for (int i = 0; i < k; i++) {
-    const int is_d = vars[i]->datatype == DOUBLE;
-    const size_t ts = is_d ? 8 : 4;
     const bjob *jz[3] = {NULL, NULL, NULL}, *js = NULL;
     for (size_t q = 0; q < nj; q++) if (jobs[q].arr == i) { if (jobs[q].kind == 1) js = &jobs[q]; else jz[jobs[q].sec] = &jobs[q]; }
     for (int s3 = 0; s3 < 3; s3++) if (jz[s3]->rc) { fprintf(stderr, "libdctz: deflate failed\n"); exit(1); }
-    struct header h;
-    memset(&h, 0, sizeof(h));
-    h.datatype = vars[i]->datatype;
-    h.num_elements = (unsigned int)N[i];
-    h.error_bound = error_bounds[i];
-    h.tot_AC_exact_count = infos[i].cnt;
-    if (is_d) { h.scaling_factor.d = infos[i].sf; h.mean.d = js->mean; }
-    else { h.scaling_factor.f = (float)infos[i].sf; h.mean.f = (float)js->mean; }
-    h.bindex_sz_compressed = (unsigned int)jz[0]->out;
-    h.DC_sz_compressed = (unsigned int)jz[1]->out;
-    h.AC_exact_sz_compressed = (unsigned int)jz[2]->out;
-#ifdef USE_QTABLE
-    h.bindex_count = (unsigned int)N[i];
-#endif
-    unsigned char *cur = is_d ? (unsigned char *)vars_z[i]->buf.d : (unsigned char *)vars_z[i]->buf.f;
-    size_t out = sizeof(h) + jz[0]->out + jz[1]->out + jz[2]->out;
-    memcpy(cur, &h, sizeof(h)); cur += sizeof(h);
+    unsigned char *cur = dzc_sections(var_bytes(vars_z[i]));
     for (int s3 = 0; s3 < 3; s3++) { memcpy(cur, jz[s3]->dst, jz[s3]->out); cur += jz[s3]->out; }
-#ifdef USE_QTABLE
-    if (is_d) memcpy(cur, infos[i].qtable, BLK_SZ * sizeof(double));
-    else { float qf[BLK_SZ]; for (int j = 0; j < BLK_SZ; j++) qf[j] = (float)infos[i].qtable[j]; memcpy(cur, qf, sizeof(qf)); }
-    out += BLK_SZ * ts;
-#endif
-    (void)ts;
+    const dzc_desc d = {.type = vars[i]->datatype, .n = (size_t)N[i], .npos = (size_t)N[i], .error_bound = error_bounds[i], .sf = infos[i].sf,
+                        .mean = js->mean, .cnt = infos[i].cnt, .zlen = {jz[0]->out, jz[1]->out, jz[2]->out},
+                        .qtable = DCTZ_QT ? infos[i].qtable : NULL};
+    const size_t out = dzc_finish(var_bytes(vars_z[i]), &d);
     outSizes[i] = out;
     if (!quiet()) printf("outSize = %zu\n", out); /* :841-843 */
   }
@@ -1400,50 +1299,38 @@ int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSize
 int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r) {
   if (k <= 0) return 1;
   dctzhip_ctx *c = ctx();
-  struct header *hs = (struct header *)malloc((size_t)k * sizeof(struct header));
+  dzc_view *vs = (dzc_view *)malloc((size_t)k * sizeof(dzc_view));
   size_t *off_bin = (size_t *)malloc(4 * (size_t)k * sizeof(size_t));
   dctzhip_batch_ditem *items = (dctzhip_batch_ditem *)calloc((size_t)k, sizeof(*items));
   bjob *jobs = (bjob *)calloc(3 * (size_t)k, sizeof(bjob));
   double *qtabs = (double *)malloc((size_t)k * BLK_SZ * sizeof(double));
-  if (!hs || !off_bin || !items || !jobs || !qtabs) { fprintf(stderr, "Out of memory: batch\n"); exit(1); }
+  if (!vs || !off_bin || !items || !jobs || !qtabs) { fprintf(stderr, "Out of memory: batch\n"); exit(1); }
   size_t *off_dc = off_bin + k, *off_ac = off_bin + 2 * k, *off_out = off_bin + 3 * k;
   size_t total = 0, in_bytes;
   for (int i = 0; i < k; i++) {
-    const unsigned char *cur = vars_z[i]->datatype == DOUBLE ? (const unsigned char *)vars_z[i]->buf.d : (const unsigned char *)vars_z[i]->buf.f;
-    memcpy(&hs[i], cur, sizeof(struct header));                       /* dctz-decomp-lib.c:84-94 */
-    if (hs[i].num_elements == 0) { fprintf(stderr, "libdctz: empty stream\n"); exit(1); }
-    if (DCTZ_GEOM_OF(hs[i].datatype)) { fprintf(stderr, "libdctz: dctz_decompress_batch takes flat containers\n"); exit(1); }
+    dzc_header(&vs[i], var_bytes(vars_z[i]), DCTZ_QT, (int)vars_z[i]->datatype);
+    if (vs[i].n == 0) { fprintf(stderr, "libdctz: empty stream\n"); exit(1); }
+    if (vs[i].nd) { fprintf(stderr, "libdctz: dctz_decompress_batch takes flat containers\n"); exit(1); }
   }
-  for (int i = 0; i < k; i++) { off_bin[i] = total; total += up256(hs[i].num_elements); }
-  for (int i = 0; i < k; i++) { off_dc[i] = total; total += up256(CEIL((size_t)hs[i].num_elements, BLK_SZ) * sizeof(float)); }
-  for (int i = 0; i < k; i++) { off_ac[i] = total; total += up256(((size_t)hs[i].tot_AC_exact_count + 4) * sizeof(float)); }
+  for (int i = 0; i < k; i++) { off_bin[i] = total; total += up256(vs[i].raw[0]); }
+  for (int i = 0; i < k; i++) { off_dc[i] = total; total += up256(vs[i].raw[1]); }
+  for (int i = 0; i < k; i++) { off_ac[i] = total; total += up256(vs[i].raw[2] + 4 * sizeof(float)); }
   in_bytes = total;
-  for (int i = 0; i < k; i++) { off_out[i] = total; total += up256((size_t)hs[i].num_elements * (vars_z[i]->datatype == DOUBLE ? 8 : 4)); }
+  for (int i = 0; i < k; i++) { off_out[i] = total; total += up256(vs[i].n * vs[i].ts); }
   batch_buffers(c, total, total);
   unsigned char *hp = (unsigned char *)g_batch.pin, *dp = (unsigned char *)g_batch.dev;
   size_t nj = 0;
   for (int i = 0; i < k; i++) {
-    const int is_d = vars_z[i]->datatype == DOUBLE;
-    const size_t ts = is_d ? 8 : 4, n = hs[i].num_elements, nblk = CEIL(n, BLK_SZ);
-    const unsigned char *cur = (is_d ? (const unsigned char *)vars_z[i]->buf.d : (const unsigned char *)vars_z[i]->buf.f) + sizeof(struct header);
-    const unsigned int zl[3] = {hs[i].bindex_sz_compressed, hs[i].DC_sz_compressed, hs[i].AC_exact_sz_compressed};
-    const size_t raw[3] = {n, nblk * sizeof(float), (size_t)hs[i].tot_AC_exact_count * sizeof(float)};
+    const dzc_view *v = &vs[i];
     const size_t offs[3] = {off_bin[i], off_dc[i], off_ac[i]};
     for (int s3 = 0; s3 < 3; s3++) {                                   /* three inflates per array (dctz-decomp-lib.c:244-322) */
       bjob *j = &jobs[nj++];
-      j->kind = 2; j->arr = i; j->sec = s3; j->src = cur; j->n = zl[s3]; j->dst = hp + offs[s3]; j->cap = (uLong)raw[s3];
-      cur += zl[s3];
+      j->kind = 2; j->arr = i; j->sec = s3; j->src = v->sec[s3]; j->n = v->zlen[s3]; j->dst = hp + offs[s3]; j->cap = (uLong)v->raw[s3];
     }
-    const void *qt = NULL;
-#ifdef USE_QTABLE
-    memcpy(qtabs + (size_t)i * BLK_SZ, cur, BLK_SZ * ts);              /* :193-199 */
-    qt = qtabs + (size_t)i * BLK_SZ;
-#endif
-    (void)ts;
     items[i].d_bin_index = dp + off_bin[i]; items[i].d_dc = (const float *)(dp + off_dc[i]); items[i].d_ac_exact = (const float *)(dp + off_ac[i]);
-    items[i].ac_count = hs[i].tot_AC_exact_count; items[i].qtable_host = qt;
-    items[i].n = n; items[i].dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32; items[i].error_bound = hs[i].error_bound;
-    items[i].sf = is_d ? hs[i].scaling_factor.d : (double)hs[i].scaling_factor.f;
+    items[i].ac_count = v->cnt; items[i].qtable_host = dzc_qtable(v, qtabs + (size_t)i * BLK_SZ);
+    items[i].n = v->n; items[i].dtype = v->is_d ? DCTZHIP_F64 : DCTZHIP_F32; items[i].error_bound = v->h.error_bound;
+    items[i].sf = v->sf;
     items[i].d_out = dp + off_out[i];
   }
   bpool_run(jobs, nj);
@@ -1451,11 +1338,8 @@ int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r) {
   if (dctzhip_memcpy_h2d(c, dp, hp, in_bytes) != DCTZHIP_OK) die("H2D (batch)");
   if (dctzhip_decompress_batch(c, k, items, DCTZ_MODE, NULL) != DCTZHIP_OK) die("dctzhip_decompress_batch");
   if (dctzhip_memcpy_d2h(c, hp + in_bytes, dp + in_bytes, total - in_bytes) != DCTZHIP_OK) die("D2H (batch)");
-  for (int i = 0; i < k; i++) {
-    const int is_d = vars_z[i]->datatype == DOUBLE;
-    memcpy(is_d ? (void *)vars_r[i]->buf.d : (void *)vars_r[i]->buf.f, hp + off_out[i], (size_t)hs[i].num_elements * (is_d ? 8 : 4));
-  }
-  free(hs); free(off_bin); free(items); free(jobs); free(qtabs);
+  for (int i = 0; i < k; i++) memcpy(var_bytes(vars_r[i]), hp + off_out[i], vs[i].n * vs[i].ts);
+  free(vs); free(off_bin); free(items); free(jobs); free(qtabs);
   return 1;
 }
 
@@ -1466,70 +1350,30 @@ int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r) {
  * against `zbytes`, the plausibility of the header fields, and -- deep != 0 -- that the three
  * sections really inflate to N, 4*nblk and 4*cnt bytes (no GPU involved). */
 int dctz_check_container(const void *z, size_t zbytes, int max_elements, int deep) {
-  struct header h;
-  if (!z || zbytes < sizeof(h)) return DCTZ_CHECK_TRUNCATED;
-  memcpy(&h, z, sizeof(h));
-  const t_datatype base = DCTZ_TYPE_OF(h.datatype);
-  const unsigned geom = DCTZ_GEOM_OF(h.datatype);
-  if ((base != FLOAT && base != DOUBLE) || ((unsigned)h.datatype >> 16) || (geom != 0 && geom != 2 && geom != 3)) return DCTZ_CHECK_BAD_HEADER;
-  if (h.num_elements == 0 || h.num_elements > 0x7FFFFFFFu) return DCTZ_CHECK_BAD_HEADER;     /* N is an int, dctz.h:126 */
-  if (max_elements > 0 && h.num_elements > (unsigned int)max_elements) return DCTZ_CHECK_TOO_LARGE;
-  if (!(h.error_bound >= 1E-6) || h.error_bound != h.error_bound) return DCTZ_CHECK_BAD_HEADER;   /* :135-138 */
-  const size_t n = h.num_elements, ts = base == DOUBLE ? sizeof(double) : sizeof(float);
-  const size_t body = (size_t)h.bindex_sz_compressed + h.DC_sz_compressed + h.AC_exact_sz_compressed;
-  size_t want = sizeof(h) + body;
-#ifdef USE_QTABLE
-  want += BLK_SZ * ts;
-#else
-  (void)ts;
-#endif
-  size_t nblk = CEIL(n, BLK_SZ), npos = n;
-  if (geom) {                                           /* multi-dimensional blocks: the extents follow the last section */
-    if (zbytes < want + 16) return DCTZ_CHECK_TRUNCATED;
-    unsigned int tr[4];
-    memcpy(tr, (const unsigned char *)z + want, sizeof(tr));
-    want += 16;
-    size_t dims[3] = {tr[1], tr[2], tr[3]};
-    if (tr[0] != DCTZ_ND_MAGIC || (geom == 2 && tr[3] != 0)) return DCTZ_CHECK_BAD_HEADER;
-    nblk = dctzhip_nd_blocks((int)geom, dims);
-    size_t prod = 1;
-    for (unsigned i = 0; i < geom; i++) prod *= dims[i];
-    if (!nblk || prod != n) return DCTZ_CHECK_BAD_HEADER;
-    npos = nblk * BLK_SZ;
+  if (!z || zbytes < DZC_HEADER_BYTES) return DCTZ_CHECK_TRUNCATED;
+  dzc_view v;
+  dzc_header(&v, z, DCTZ_QT, DZC_TYPE_IN_HEADER);
+  if ((v.base != FLOAT && v.base != DOUBLE) || ((unsigned)v.h.datatype >> 16) || (v.nd != 0 && v.nd != 2 && v.nd != 3)) return DCTZ_CHECK_BAD_HEADER;
+  if (v.n == 0 || v.n > 0x7FFFFFFFu) return DCTZ_CHECK_BAD_HEADER;                             /* N is an int, dctz.h:126 */
+  if (max_elements > 0 && v.n > (unsigned int)max_elements) return DCTZ_CHECK_TOO_LARGE;
+  if (!(v.h.error_bound >= 1E-6) || v.h.error_bound != v.h.error_bound) return DCTZ_CHECK_BAD_HEADER;   /* :135-138 */
+  if (v.nd) {                                           /* multi-dimensional blocks: the extents follow the last section */
+    if (zbytes < v.ix_off) return DCTZ_CHECK_TRUNCATED;
+    if (dzc_geometry(&v) != 0 || (v.nd == 2 && v.dims[2] != 0)) return DCTZ_CHECK_BAD_HEADER;
   }
-  if ((size_t)h.tot_AC_exact_count > npos - nblk) return DCTZ_CHECK_BAD_HEADER;                /* at most 63 per block */
-#ifdef USE_QTABLE
-  if (h.bindex_count != npos) return DCTZ_CHECK_BAD_HEADER;                                     /* :798 */
-#endif
-  if (zbytes < want) return DCTZ_CHECK_TRUNCATED;
-  const unsigned char *cur = (const unsigned char *)z + sizeof(h);
-  const size_t raw[3] = {npos, nblk * sizeof(float), (size_t)h.tot_AC_exact_count * sizeof(float)};
-  const unsigned int zs[3] = {h.bindex_sz_compressed, h.DC_sz_compressed, h.AC_exact_sz_compressed};
-  {
-    /* Sections that carry the mark of the GPU entropy stage (78 5E): dctz_decompress will look for the "DZIX" chunk index
-     * BEHIND the container -- it has no size to check that against, this function has.  The index must be there in full
-     * and describe the sections exactly (the same test as the reader's), or the container is refused: a foreign stream
-     * that merely starts 78 5E (zlib at levels 2 .. 5 writes those bytes too) would make the reader look past the buffer. */
-    const unsigned char *sp[3] = {cur, cur + zs[0], cur + (size_t)zs[0] + zs[1]};
-    int marked = 1;
-    for (int i = 0; i < 3; i++) if (zs[i] < 8 || sp[i][0] != 0x78 || sp[i][1] != 0x5E) marked = 0;
-    if (marked) {
-      if (zbytes < want + 20) return DCTZ_CHECK_TRUNCATED;
-      unsigned int hd[5];
-      memcpy(hd, (const unsigned char *)z + want, sizeof(hd));
-      if (hd[0] != DCTZ_IX_MAGIC || hd[1] < 1024 || hd[1] > 65535) return DCTZ_CHECK_BAD_STREAM;
-      size_t entries = 0;
-      for (int i = 0; i < 3; i++) {
-        if (hd[2 + i] != (raw[i] + hd[1] - 1) / hd[1]) return DCTZ_CHECK_BAD_STREAM;
-        entries += hd[2 + i];
-      }
-      if (zbytes < want + 20 + 2 * entries) return DCTZ_CHECK_TRUNCATED;
-      uint32_t *sizes[3];
-      size_t chunk = 0;
-      if (!read_index(sp, zs, raw, (const unsigned char *)z + want, &chunk, sizes)) return DCTZ_CHECK_BAD_STREAM;
-      for (int i = 0; i < 3; i++) free(sizes[i]);
-    }
-  }
+  if ((size_t)v.cnt > v.npos - v.nblk) return DCTZ_CHECK_BAD_HEADER;                            /* at most 63 per block */
+  if (v.qtable && v.bindex_count != v.npos) return DCTZ_CHECK_BAD_HEADER;                       /* :798 */
+  if (zbytes < v.ix_off) return DCTZ_CHECK_TRUNCATED;
+  /* Sections that carry the mark of the GPU entropy stage (78 5E): dctz_decompress will look for the "DZIX" chunk index
+   * BEHIND the container -- it has no size to check that against, this function has.  The index must be there in full
+   * and describe the sections exactly (the same test as the reader's), or the container is refused: a foreign stream
+   * that merely starts 78 5E (zlib at levels 2 .. 5 writes those bytes too) would make the reader look past the buffer. */
+  uint32_t *sizes[3];
+  size_t chunk = 0;
+  const int ix = dzc_read_index(&v, zbytes, &chunk, sizes);
+  for (int i = 0; i < 3; i++) free(sizes[i]);
+  if (ix == DZC_IX_CUT) return DCTZ_CHECK_TRUNCATED;
+  if (ix == DZC_IX_BAD) return DCTZ_CHECK_BAD_STREAM;
   if (!deep) return DCTZ_CHECK_OK;
   for (int i = 0; i < 3; i++) {
     /* inflate into a small window, counting: the section must end exactly at `raw[i]` bytes */
@@ -1537,17 +1381,16 @@ int dctz_check_container(const void *z, size_t zbytes, int max_elements, int dee
     unsigned char win[65536];
     memset(&st, 0, sizeof(st));
     if (inflateInit(&st) != Z_OK) return DCTZ_CHECK_BAD_STREAM;
-    st.next_in = (Bytef *)cur; st.avail_in = zs[i];
+    st.next_in = (Bytef *)v.sec[i]; st.avail_in = v.zlen[i];
     size_t produced = 0;
     int rc;
     do {
       st.next_out = win; st.avail_out = sizeof(win);
       rc = inflate(&st, Z_NO_FLUSH);
       produced += sizeof(win) - st.avail_out;
-    } while (rc == Z_OK && produced <= raw[i]);
+    } while (rc == Z_OK && produced <= v.raw[i]);
     inflateEnd(&st);
-    if (rc != Z_STREAM_END || produced != raw[i]) return DCTZ_CHECK_BAD_STREAM;
-    cur += zs[i];
+    if (rc != Z_STREAM_END || produced != v.raw[i]) return DCTZ_CHECK_BAD_STREAM;
   }
   return DCTZ_CHECK_OK;
 }
@@ -1610,17 +1453,17 @@ static void *pp_worker(void *arg) {
 }
 /* returns 1: done; 0: not applicable / something does not inflate -- the caller takes the serial path (and its way of
  * reporting damage) */
-static int decompress_pipelined(dctzhip_ctx *c, const struct header *h, const unsigned char *const sec[3], const unsigned int zl[3],
-                                size_t chunk, uint32_t *const sizes[3], const void *qtable, t_var *var_r, size_t *got_out) {
-  const int is_d = ((h->datatype & 0xff) == DOUBLE);
-  const size_t ts = is_d ? sizeof(double) : sizeof(float);
-  const int dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const size_t n = h->num_elements, nblk = CEIL(n, BLK_SZ), cnt = h->tot_AC_exact_count;
+static int decompress_pipelined(dctzhip_ctx *c, const dzc_view *v, size_t chunk, uint32_t *const sizes[3], t_var *var_r, size_t *got_out) {
+  const size_t ts = v->ts, n = v->n, cnt = v->cnt;
+  const int dtype = v->is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const unsigned char *const *sec = v->sec;
+  const size_t *raw = v->raw;
+  double qbuf[BLK_SZ];
+  const void *qtable = dzc_qtable(v, qbuf);               /* :193-199 */
   const size_t gel = pipe_group();
   if (gel % (16 * chunk) != 0 || n < 2 * gel) return 0;
   const size_t G = (n + gel - 1) / gel;
   if (G > DCTZHIP_D2H_PIPE_MAX_MARKS) return 0;           /* (more groups than the D2H pipe has marks -> the serial path) */
-  const size_t raw[3] = {n, nblk * sizeof(float), cnt * sizeof(float)};
   size_t nch[3], total = 0;
   for (int i = 0; i < 3; i++) { nch[i] = (raw[i] + chunk - 1) / chunk; total += nch[i]; }
   unsigned char *const dst[3] = {(unsigned char *)host_buf(0, raw[0]), (unsigned char *)host_buf(1, raw[1]), (unsigned char *)host_buf(2, raw[2])};
@@ -1654,9 +1497,7 @@ static int decompress_pipelined(dctzhip_ctx *c, const struct header *h, const un
   if (th) for (int t = 0; t < threads; t++) { if (pthread_create(&th[started], NULL, pp_worker, &q)) break; started++; }
 
   grow(&g_dev.out, &g_dev.out_cap, n * ts);
-  unsigned char *host_out = is_d ? (unsigned char *)var_r->buf.d : (unsigned char *)var_r->buf.f;
-  if (dctzhip_d2h_pipe_begin(c, host_out, g_dev.out, n * ts) != DCTZHIP_OK) die("D2H pipe");
-  const double sf = is_d ? h->scaling_factor.d : (double)h->scaling_factor.f;
+  if (dctzhip_d2h_pipe_begin(c, var_bytes(var_r), g_dev.out, n * ts) != DCTZHIP_OK) die("D2H pipe");
   int ok = 1;
   size_t S = 0, ac_up = 0;                               /* exact coefficients consumed so far; bytes of AC_exact on the device */
   const int dbg = getenv("DCTZ_PIPE_DEBUG") != NULL;
@@ -1704,7 +1545,7 @@ static int decompress_pipelined(dctzhip_ctx *c, const struct header *h, const un
     }
     const double tg2 = now_s();
     if (dctzhip_decompress(c, (unsigned char *)g_dev.bin + e0, (const float *)g_dev.dc + b0, (const float *)g_dev.ac + S, (uint32_t)(cnt - S), qtable, ne, dtype,
-                           h->error_bound, sf, DCTZ_MODE, (unsigned char *)g_dev.out + e0 * ts) != DCTZHIP_OK) die("dctzhip_decompress");
+                           v->h.error_bound, v->sf, DCTZ_MODE, (unsigned char *)g_dev.out + e0 * ts) != DCTZHIP_OK) die("dctzhip_decompress");
     if (dbg) fprintf(stderr, "[pipe] group %zu: start %.2f ms, waited %.2f for its chunks, H2D %.2f, call %.2f\n", g, (tg0 - tp0) * 1e3, (tg1 - tg0) * 1e3, (tg2 - tg1) * 1e3, (now_s() - tg2) * 1e3);
     S = S1;
     if (dctzhip_d2h_pipe_advance(c, (e0 + ne) * ts) != DCTZHIP_OK) die("D2H pipe");     /* the group's bytes: complete behind its kernels */
@@ -1718,9 +1559,7 @@ static int decompress_pipelined(dctzhip_ctx *c, const struct header *h, const un
   for (int i = 0; i < 3 && ok; i++) {
     uLong a = adler32(0L, Z_NULL, 0);
     for (size_t j = 0; j < nch[i]; j++) { const pp_chunk *pc = &chunks[first[i][j]]; if (pc->done != 1) ok = 0; a = adler32_combine(a, pc->adler, (z_off_t)pc->len); }
-    const unsigned char *t = sec[i] + zl[i] - 4;
-    const uLong want = ((uLong)t[0] << 24) | ((uLong)t[1] << 16) | ((uLong)t[2] << 8) | (uLong)t[3];
-    if (a != want) ok = 0;
+    if (a != get_be32(sec[i] + v->zlen[i] - 4)) ok = 0;
   }
   free(th); free(chunks); free(goff); free(gbytes);
   for (int i = 0; i < 3; i++) free(first[i]);
@@ -1731,65 +1570,33 @@ static int decompress_pipelined(dctzhip_ctx *c, const struct header *h, const un
 
 int dctz_decompress(t_var *var_z, t_var *var_r) {
   const double t_begin = now_s();
-  const int is_d = (var_z->datatype == DOUBLE);
-  const size_t ts = is_d ? sizeof(double) : sizeof(float);
+  dzc_view v;
+  const int bad_nd = dzc_open(&v, var_z, DCTZ_QT); /* dctz-decomp-lib.c:84-94 */
+  const int is_d = v.is_d, nd = v.nd;
+  const size_t ts = v.ts, n = v.n, nblk = v.nblk, npos = v.npos;
   const int dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const unsigned char *cur = is_d ? (const unsigned char *)var_z->buf.d : (const unsigned char *)var_z->buf.f;
-  struct header h;
-  memcpy(&h, cur, sizeof(h)); /* dctz-decomp-lib.c:84-94 */
-  cur += sizeof(h);
-  const size_t n = h.num_elements;
-  const unsigned int cnt = h.tot_AC_exact_count;
+  const unsigned int cnt = v.cnt;
   if (n == 0) { fprintf(stderr, "libdctz: empty stream\n"); exit(1); }
   /* multi-dimensional blocks (dctz.h: dctz_set_block_dims): the extents sit behind the last section */
-  const int nd = (int)DCTZ_GEOM_OF(h.datatype);
-  size_t dims[3] = {0, 0, 0};
-  size_t nblk = CEIL(n, BLK_SZ);
-  if (nd) {
-    size_t off = (size_t)h.bindex_sz_compressed + h.DC_sz_compressed + h.AC_exact_sz_compressed;
-#ifdef USE_QTABLE
-    off += BLK_SZ * ts;
-#endif
-    unsigned int tr[4];
-    memcpy(tr, cur + off, sizeof(tr));
-    dims[0] = tr[1]; dims[1] = tr[2]; dims[2] = tr[3];
-    nblk = (tr[0] == DCTZ_ND_MAGIC && (nd == 2 || nd == 3)) ? dctzhip_nd_blocks(nd, dims) : 0;
-    if (!nblk || dims[0] * dims[1] * (nd == 3 ? dims[2] : 1) != n) { fprintf(stderr, "libdctz: bad multi-dimensional container\n"); exit(1); }
-  }
-  const size_t npos = nd ? nblk * BLK_SZ : n;
+  if (bad_nd) { fprintf(stderr, "libdctz: bad multi-dimensional container\n"); exit(1); }
 
   double t0 = now_s();
   dctzhip_ctx *c = ctx();
-  const unsigned int zl[3] = {h.bindex_sz_compressed, h.DC_sz_compressed, h.AC_exact_sz_compressed};
-  const unsigned char *const secp[3] = {cur, cur + zl[0], cur + zl[0] + zl[1]};
-  const size_t rawn[3] = {npos, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
-  size_t ix_off = (size_t)zl[0] + zl[1] + zl[2] + (nd ? 16 : 0);
-#ifdef USE_QTABLE
-  ix_off += BLK_SZ * ts;
-#endif
   /* sections written by the GPU entropy stage start 78 5E and bring a chunk index: only then are the bytes behind the
    * container looked at.  On request (DCTZ_INFLATE_GPU=1) they are inflated on the device, one lane per chunk -- the
    * compressed sections go over PCIe instead of the raw streams, no host core inflates (include/dctz_hip.h:
    * dctzhip_inflate); otherwise by host threads, chunks side by side. */
   uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
   size_t ix_chunk_bytes = 0;
-  const int indexed = zl[0] >= 8 && zl[1] >= 8 && zl[2] >= 8 && secp[0][1] == 0x5E && secp[1][1] == 0x5E && secp[2][1] == 0x5E &&
-                      read_index(secp, zl, rawn, cur + ix_off, &ix_chunk_bytes, ix_sizes);
+  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &ix_chunk_bytes, ix_sizes) == DZC_IX_OK;
   int on_device = 0;
   double t_h2d_z = 0.0;
   grow(&g_dev.bin, &g_dev.bin_cap, npos);
   grow(&g_dev.dc, &g_dev.dc_cap, nblk * sizeof(float));
   grow(&g_dev.ac, &g_dev.ac_cap, (cnt ? cnt : 4) * sizeof(float));
   if (indexed && !nd && !inflate_gpu() && pipeline_on()) {
-    const void *qt_p = NULL;
-#ifdef USE_QTABLE
-    double qd_p[BLK_SZ];
-    float qf_p[BLK_SZ];
-    if (is_d) { memcpy(qd_p, cur + zl[0] + zl[1] + zl[2], sizeof(qd_p)); qt_p = qd_p; } /* :193-199 */
-    else { memcpy(qf_p, cur + zl[0] + zl[1] + zl[2], sizeof(qf_p)); qt_p = qf_p; }
-#endif
     size_t got_p = 0;
-    if (decompress_pipelined(c, &h, secp, zl, ix_chunk_bytes, ix_sizes, qt_p, var_r, &got_p)) {
+    if (decompress_pipelined(c, &v, ix_chunk_bytes, ix_sizes, var_r, &got_p)) {
       for (int i = 0; i < 3; i++) free(ix_sizes[i]);
       if (!quiet()) printf("uncompressed bin_index size is: %lu\n", (unsigned long)got_p); /* :260-262 */
       g_times.zlib_s = 0.0; g_times.h2d_s = 0.0; g_times.gpu_s = 0.0; g_times.d2h_s = 0.0;   /* (the stages overlap: only the total means something) */
@@ -1800,14 +1607,14 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   if (indexed && inflate_gpu() && ix_chunk_bytes == dctzhip_deflate_chunk_bytes()) {
     size_t zlen[3];
     for (int i = 0; i < 3; i++) {
-      zlen[i] = zl[i];
-      grow(&g_dev.z[i], &g_dev.z_cap[i], zl[i]);
-      if (dctzhip_memcpy_h2d(c, g_dev.z[i], secp[i], zl[i]) != DCTZHIP_OK) die("H2D compressed section");
+      zlen[i] = v.zlen[i];
+      grow(&g_dev.z[i], &g_dev.z_cap[i], v.zlen[i]);
+      if (dctzhip_memcpy_h2d(c, g_dev.z[i], v.sec[i], v.zlen[i]) != DCTZHIP_OK) die("H2D compressed section");
     }
     t_h2d_z = now_s() - t0;
     void *const ddst[3] = {g_dev.bin, g_dev.dc, g_dev.ac};
     int ok = 0;
-    if (dctzhip_inflate(c, 3, (const void *const *)g_dev.z, zlen, (const uint32_t *const *)ix_sizes, rawn, ddst, &ok) != DCTZHIP_OK) die("dctzhip_inflate");
+    if (dctzhip_inflate(c, 3, (const void *const *)g_dev.z, zlen, (const uint32_t *const *)ix_sizes, v.raw, ddst, &ok) != DCTZHIP_OK) die("dctzhip_inflate");
     on_device = ok;            /* 0: inconsistent -- the host path below decides, and reports damage like the reference */
   }
 
@@ -1820,13 +1627,12 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   AC_exact = (float *)host_buf(2, (size_t)cnt * sizeof(float));
   /* three inflates, in order (dctz-decomp-lib.c:244-322) */
   unsigned char *const rawp[3] = {(unsigned char *)bin_index, (unsigned char *)DC, (unsigned char *)AC_exact};
-  if (indexed && inflate_indexed(secp, zl, rawp, rawn, ix_chunk_bytes, ix_sizes)) {   /* chunks side by side on host threads */
+  if (indexed && inflate_indexed(&v, rawp, ix_chunk_bytes, ix_sizes)) {   /* chunks side by side on host threads */
     got = (uLong)npos;
   } else if (zlib_threads() == 0 || zlib_threads() > 3) {   /* the sections are independent streams: inflate them side by side
                                                                (DCTZ_ZLIB_THREADS=1..3 keeps the reference's one-after-the-other) */
-    inflate_job ij[3] = {{secp[0], zl[0], (uLong)npos, 0, bin_index},
-                         {secp[1], zl[1], (uLong)(nblk * sizeof(float)), 0, DC},
-                         {secp[2], zl[2], (uLong)((size_t)cnt * sizeof(float)), 0, AC_exact}};
+    inflate_job ij[3] = {{v.sec[0], v.zlen[0], (uLong)v.raw[0], 0, bin_index}, {v.sec[1], v.zlen[1], (uLong)v.raw[1], 0, DC},
+                         {v.sec[2], v.zlen[2], (uLong)v.raw[2], 0, AC_exact}};
     pthread_t th[2];
     int started = 0;
     for (int i = 1; i < 3; i++) { if (pthread_create(&th[started], NULL, inflate_main, &ij[i])) inflate_main(&ij[i]); else started++; }
@@ -1834,21 +1640,15 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
     for (int i = 0; i < started; i++) pthread_join(th[i], NULL);
     got = ij[0].produced;
   } else {
-    got = inflate_into(secp[0], zl[0], bin_index, npos);
-    inflate_into(secp[1], zl[1], DC, nblk * sizeof(float));
-    inflate_into(secp[2], zl[2], AC_exact, (size_t)cnt * sizeof(float));
+    got = inflate_into(v.sec[0], v.zlen[0], bin_index, v.raw[0]);
+    inflate_into(v.sec[1], v.zlen[1], DC, v.raw[1]);
+    inflate_into(v.sec[2], v.zlen[2], AC_exact, v.raw[2]);
   }
   }
-  cur += (size_t)zl[0] + zl[1] + zl[2];
   for (int i = 0; i < 3; i++) free(ix_sizes[i]);
   if (!quiet()) printf("uncompressed bin_index size is: %lu\n", got); /* :260-262 */
-  const void *qtable = NULL;
-#ifdef USE_QTABLE
-  double qd[BLK_SZ];
-  float qf[BLK_SZ];
-  if (is_d) { memcpy(qd, cur, sizeof(qd)); qtable = qd; } /* :193-199 */
-  else { memcpy(qf, cur, sizeof(qf)); qtable = qf; }
-#endif
+  double qbuf[BLK_SZ];
+  const void *qtable = dzc_qtable(&v, qbuf);             /* :193-199 */
   double t1 = now_s();
 
   grow(&g_dev.out, &g_dev.out_cap, n * ts);
@@ -1859,16 +1659,14 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   }
   double t2 = now_s();
 
-  const double sf = is_d ? h.scaling_factor.d : (double)h.scaling_factor.f;
-  int rc = nd ? dctzhip_decompress_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, cnt, qtable, nd, dims,
-                                      dtype, h.error_bound, sf, DCTZ_MODE, g_dev.out)
+  int rc = nd ? dctzhip_decompress_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, cnt, qtable, nd, v.dims,
+                                      dtype, v.h.error_bound, v.sf, DCTZ_MODE, g_dev.out)
               : dctzhip_decompress(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, cnt, qtable, n, dtype,
-                                   h.error_bound, sf, DCTZ_MODE, g_dev.out);
+                                   v.h.error_bound, v.sf, DCTZ_MODE, g_dev.out);
   if (rc != DCTZHIP_OK) die("dctzhip_decompress");
   if (dctzhip_sync(c) != DCTZHIP_OK) die("sync");   /* (stage timers: the call returns while the reconstruction is being written) */
   double t3 = now_s();
-  void *host_out = is_d ? (void *)var_r->buf.d : (void *)var_r->buf.f;
-  if (dctzhip_memcpy_d2h(c, host_out, g_dev.out, n * ts) != DCTZHIP_OK) die("D2H output");
+  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, n * ts) != DCTZHIP_OK) die("D2H output");
   double t4 = now_s();
 
   g_times.zlib_s = t1 - t0; g_times.h2d_s = t2 - t1; g_times.gpu_s = t3 - t2; g_times.d2h_s = t4 - t3;
@@ -1922,17 +1720,13 @@ static size_t inflate_prefix(const unsigned char *sec, unsigned int zlen, size_t
 
 int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
   const double t_begin = now_s();
-  const int is_d = (var_z->datatype == DOUBLE);
-  const size_t ts = is_d ? sizeof(double) : sizeof(float);
-  const int dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const unsigned char *cur = is_d ? (const unsigned char *)var_z->buf.d : (const unsigned char *)var_z->buf.f;
-  struct header h;
-  memcpy(&h, cur, sizeof(h)); /* dctz-decomp-lib.c:84-94 */
-  cur += sizeof(h);
-  const size_t n = h.num_elements;
-  const unsigned int cnt = h.tot_AC_exact_count;
-  if (DCTZ_GEOM_OF(h.datatype) != 0 || n == 0 || lo >= hi || hi > n) return -1;   /* DZND: element order is not block order */
-  const size_t S = DCTZHIP_INDEX_STRIDE, nblk = (n + BLK_SZ - 1) / BLK_SZ;
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
+  const size_t ts = v.ts, n = v.n, nblk = v.nblk;
+  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const unsigned int cnt = v.cnt;
+  if (v.nd != 0 || n == 0 || lo >= hi || hi > n) return -1;   /* DZND: element order is not block order */
+  const size_t S = DCTZHIP_INDEX_STRIDE;
   const size_t t1 = (hi + S - 1) / S;                        /* the range's tiles end here */
   const size_t need[3] = {MIN(n, S * t1),                    /* bin ids: the flags in front give AC_exact's position */
                           (hi + BLK_SZ - 1) / BLK_SZ * sizeof(float),   /* DC up to the range's last block */
@@ -1940,24 +1734,11 @@ int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
   const size_t dc_dev = MIN(nblk, t1 * (S / BLK_SZ));        /* DC words the range's tiles cover on the device */
 
   dctzhip_ctx *c = ctx();
-  const unsigned int zl[3] = {h.bindex_sz_compressed, h.DC_sz_compressed, h.AC_exact_sz_compressed};
-  const unsigned char *const secp[3] = {cur, cur + zl[0], cur + zl[0] + zl[1]};
-  const size_t rawn[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
-  size_t ix_off = (size_t)zl[0] + zl[1] + zl[2];
-#ifdef USE_QTABLE
-  ix_off += BLK_SZ * ts;
-#endif
   uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
   size_t chunk = 0;
-  const int indexed = zl[0] >= 8 && zl[1] >= 8 && zl[2] >= 8 && secp[0][1] == 0x5E && secp[1][1] == 0x5E && secp[2][1] == 0x5E &&
-                      read_index(secp, zl, rawn, cur + ix_off, &chunk, ix_sizes);
-  const void *qtable = NULL;
-#ifdef USE_QTABLE
-  double qd[BLK_SZ];
-  float qf[BLK_SZ];
-  if (is_d) { memcpy(qd, cur + zl[0] + zl[1] + zl[2], sizeof(qd)); qtable = qd; } /* :193-199 */
-  else { memcpy(qf, cur + zl[0] + zl[1] + zl[2], sizeof(qf)); qtable = qf; }
-#endif
+  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
+  double qbuf[BLK_SZ];
+  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
   int ret = -1;
   unsigned char *hp[3];
   size_t want[3] = {need[0], need[1], need[2]};
@@ -1973,9 +1754,9 @@ int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
       t_h2d += now_s() - t0;
     }
     t0 = now_s();
-    const size_t room = indexed ? MIN(rawn[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
+    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
     hp[i] = (unsigned char *)host_buf(i, room);
-    if (inflate_prefix(secp[i], zl[i], rawn[i], want[i], hp[i], chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
+    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp[i], chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
     t_zlib += now_s() - t0;
     t0 = now_s();
     void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
@@ -1986,14 +1767,12 @@ int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
   }
   t0 = now_s();
   grow(&g_dev.out, &g_dev.out_cap, (hi - lo) * ts);
-  const double sf = is_d ? h.scaling_factor.d : (double)h.scaling_factor.f;
   const int rc = dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need, (const uint32_t *)g_dev.idx,
-                                          qtable, n, dtype, h.error_bound, sf, DCTZ_MODE, lo, hi, g_dev.out);
+                                          qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi, g_dev.out);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
   if (rc != DCTZHIP_OK) die("dctzhip_decompress_range");
   const double t1s = now_s();
-  void *host_out = is_d ? (void *)var_r->buf.d : (void *)var_r->buf.f;
-  if (dctzhip_memcpy_d2h(c, host_out, g_dev.out, (hi - lo) * ts) != DCTZHIP_OK) die("D2H output");
+  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, (hi - lo) * ts) != DCTZHIP_OK) die("D2H output");
   g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
   g_times.total_s = now_s() - t_begin;
   ret = 1;
@@ -2011,7 +1790,7 @@ void calc_data_stat(t_var *in, t_bstat *bs, int N) {
   const size_t n = (size_t)N;
   dctzhip_ctx *c = ctx();
   grow(&g_dev.in, &g_dev.in_cap, n * ts);
-  if (dctzhip_memcpy_h2d(c, g_dev.in, is_d ? (void *)in->buf.d : (void *)in->buf.f, n * ts) != DCTZHIP_OK) die("H2D");
+  if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(in), n * ts) != DCTZHIP_OK) die("H2D");
   dctzhip_cinfo info;
   double mean = 0.0;
   if (dctzhip_serial_mean_begin(c, g_dev.in, n, is_d ? DCTZHIP_F64 : DCTZHIP_F32) != DCTZHIP_OK) die("serial mean");
@@ -2058,8 +1837,7 @@ double calc_psnr(t_var *var, t_var *var_r, int N, double error_bound) {
     double t[4];
     grow(&g_dev.in, &g_dev.in_cap, bytes);
     grow(&g_dev.out, &g_dev.out_cap, bytes);
-    if (dctzhip_memcpy_h2d(c, g_dev.in, is_d ? (void *)var->buf.d : (void *)var->buf.f, bytes) != DCTZHIP_OK ||
-        dctzhip_memcpy_h2d(c, g_dev.out, is_d ? (void *)var_r->buf.d : (void *)var_r->buf.f, bytes) != DCTZHIP_OK)
+    if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var), bytes) != DCTZHIP_OK || dctzhip_memcpy_h2d(c, g_dev.out, var_bytes(var_r), bytes) != DCTZHIP_OK)
       die("H2D");
     if (dctzhip_psnr_terms(c, g_dev.in, g_dev.out, (size_t)N, is_d ? DCTZHIP_F64 : DCTZHIP_F32, t) != DCTZHIP_OK)
       die("dctzhip_psnr_terms");

@@ -10,6 +10,7 @@ import pytest
 
 from oracle import oracle as O
 from tests import workloads as W
+from tests.containers import container as _container
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "dctz_amd", "bin")
@@ -19,26 +20,6 @@ def _ensure_built():
     if not os.path.exists(os.path.join(BIN, "dctz-dump")):
         import __graft_entry__ as g
         g.build()
-
-
-def _container(x, eb, mode):
-    """A .z file assembled from the oracle's streams (dctz-comp-lib.c:775-820)."""
-    c = O.compress(x, eb, mode, O.FAST)
-    z = [zlib.compress(c.bin_index.tobytes()), zlib.compress(c.dc.tobytes()), zlib.compress(c.ac_exact.tobytes())]
-    is_d = x.dtype == np.float64
-    h = bytearray(56)
-    struct.pack_into("<II", h, 0, 1 if is_d else 0, x.size)
-    struct.pack_into("<d", h, 8, eb)
-    struct.pack_into("<I", h, 16, c.cnt)
-    struct.pack_into("<d" if is_d else "<f", h, 24, c.sf)
-    struct.pack_into("<d" if is_d else "<f", h, 32, c.mean)
-    struct.pack_into("<III", h, 40, len(z[0]), len(z[1]), len(z[2]))
-    if mode == O.QT:
-        struct.pack_into("<I", h, 52, x.size)
-    blob = bytes(h) + b"".join(z)
-    if mode == O.QT:
-        blob += c.qtable.tobytes()
-    return blob, c
 
 
 def test_usage_texts():

@@ -14,41 +14,10 @@ import pytest
 
 from oracle import oracle as O
 from tests import workloads as W
+from tests.containers import twin, twin_deflate
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = 128 * 128
-
-
-def twin():
-    so = os.path.join(ROOT, "tests", "emu", "emu_deflate.so")
-    src = os.path.join(ROOT, "tests", "emu", "emu_deflate.cpp")
-    hdr = os.path.join(ROOT, "dctz_amd", "csrc", "deflate_chunk.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "dctz_amd", "csrc"), src, "-o", so], check=True)
-    L = C.CDLL(so)
-    L.emu_deflate.restype = C.c_size_t
-    L.emu_deflate.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
-    L.emu_deflate_index.restype = C.c_size_t
-    L.emu_deflate_index.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    L.emu_deflate_literals.restype = C.c_size_t
-    L.emu_deflate_literals.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    L.emu_deflate_bound.restype = C.c_size_t
-    L.emu_deflate_bound.argtypes = [C.c_size_t, C.c_int]
-    return L
-
-
-def twin_deflate(L, data, nthr=128, want_index=False, literals=False):
-    a = np.frombuffer(data, dtype=np.uint8)
-    cap = L.emu_deflate_bound(len(data), nthr)
-    out = np.zeros(cap, dtype=np.uint8)
-    chunk = nthr * 128
-    sizes = np.zeros(max(1, (len(data) + chunk - 1) // chunk), np.uint32)
-    n = (L.emu_deflate_literals if literals else L.emu_deflate_index)(a.ctypes.data if len(data) else None, len(data), out.ctypes.data, cap, nthr,
-                                                                     sizes.ctypes.data)
-    assert n > 0
-    if want_index:
-        return out[:n].tobytes(), sizes[:(len(data) + chunk - 1) // chunk]
-    return out[:n].tobytes()
 
 
 def inflate_by_index(z, sizes, n, chunk=CHUNK):

@@ -15,6 +15,7 @@ import pytest
 from scipy.fft import dctn, idctn
 
 from oracle import oracle as O
+from tests.containers import container as _nd_container
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "emu", "emu_dct64.so")
@@ -211,31 +212,6 @@ def test_hip_nd_rejects_bad_shapes(ctx):
 ROOT = os.path.dirname(HERE)
 LIBDIR = os.path.join(ROOT, "dctz_amd", "lib")
 BIN = os.path.join(ROOT, "dctz_amd", "bin")
-
-
-def _nd_container(x, eb, mode):
-    """A multi-dimensional .z assembled from the oracle's streams: the reference's layout (dctz-comp-lib.c:775-820)
-    with the geometry in bits 8..15 of `datatype` and "DZND" + three extents behind the last section (include/dctz.h)."""
-    import struct
-    import zlib
-    c = O.compress_nd(x, eb, mode, O.FAST)
-    z = [zlib.compress(c.bin_index.tobytes()), zlib.compress(c.dc.tobytes()), zlib.compress(c.ac_exact.tobytes())]
-    is_d = x.dtype == np.float64
-    h = bytearray(56)
-    struct.pack_into("<II", h, 0, (1 if is_d else 0) | (x.ndim << 8), x.size)
-    struct.pack_into("<d", h, 8, eb)
-    struct.pack_into("<I", h, 16, c.cnt)
-    struct.pack_into("<d" if is_d else "<f", h, 24, c.sf)
-    struct.pack_into("<d" if is_d else "<f", h, 32, c.mean)
-    struct.pack_into("<III", h, 40, len(z[0]), len(z[1]), len(z[2]))
-    if mode == O.QT:
-        struct.pack_into("<I", h, 52, c.bin_index.size)
-    blob = bytes(h) + b"".join(z)
-    if mode == O.QT:
-        blob += c.qtable.tobytes()
-    dims = list(x.shape) + [0] * (3 - x.ndim)
-    blob += struct.pack("<IIII", 0x444E5A44, *dims)
-    return blob, c
 
 
 @pytest.mark.parametrize("mode,variant", [(O.EC, "ec"), (O.QT, "qt")])
