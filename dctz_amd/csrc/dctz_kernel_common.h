@@ -320,18 +320,26 @@ struct StatAcc {
   double sum;                                      // raw-domain sum (or correction term)
   double dcs;                                      // fused path: sum of the blocks' DC coefficients (see k_compress)
   __device__ __forceinline__ void init() { mx = T(0); mn = Traits<T>::huge(); sum = 0.0; dcs = 0.0; }
-  // one v_max / v_min with the |x| source modifier each (a NaN operand is skipped, like `a > mx ? a : mx`)
+  // A NaN element is passed over, like `a > mx ? a : mx`.  Kernels run in IEEE mode, where v_max /
+  // v_min skip a QUIET NaN operand but answer a SIGNALLING one with a quiet NaN -- which the next element then replaces:
+  // the lane has lost its maximum so far (seen on an MI355X: sf a decade or two short when signalling NaNs followed the
+  // array's largest value in its block).  So |x| is canonicalised first -- v_max(|x|, |x|) quiets a signalling NaN and
+  // leaves everything else as it is -- and the running values meet quiet NaNs only: three instructions per element for
+  // what were two.
   __device__ __forceinline__ void add(T e, bool in_sum) {
     minmax(e);
     if (in_sum) sum += (double)e;
   }
   __device__ __forceinline__ void minmax(T e) {
+    T a;
     if constexpr (sizeof(T) == 8) {
-      asm("v_max_f64 %0, %1, |%2|" : "=v"(mx) : "v"(mx), "v"(e));
-      asm("v_min_f64 %0, %1, |%2|" : "=v"(mn) : "v"(mn), "v"(e));
+      asm("v_max_f64 %0, |%1|, |%1|" : "=v"(a) : "v"(e));
+      asm("v_max_f64 %0, %1, %2" : "=v"(mx) : "v"(mx), "v"(a));
+      asm("v_min_f64 %0, %1, %2" : "=v"(mn) : "v"(mn), "v"(a));
     } else {
-      asm("v_max_f32 %0, %1, |%2|" : "=v"(mx) : "v"(mx), "v"(e));
-      asm("v_min_f32 %0, %1, |%2|" : "=v"(mn) : "v"(mn), "v"(e));
+      asm("v_max_f32 %0, |%1|, |%1|" : "=v"(a) : "v"(e));
+      asm("v_max_f32 %0, %1, %2" : "=v"(mx) : "v"(mx), "v"(a));
+      asm("v_min_f32 %0, %1, %2" : "=v"(mn) : "v"(mn), "v"(a));
     }
   }
   // workgroup reduction -> part[3*slot .. 3*slot+2]; `s` is scratch for 3 * (threads/64) doubles

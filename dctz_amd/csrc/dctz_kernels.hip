@@ -596,6 +596,7 @@ __device__ __forceinline__ void compress_rem_body(const FwdParams<T>& p, const i
   const T q = bwd.ok ? bwd.core(u) : u / bwd.d;
   const int t = (int)q;                                            // (t_bin_id) cast: truncation
   unsigned b = out ? 255u : (unsigned)(t <= 127 ? 254 - 2 * t : 2 * t - 255);   // conv_tbl :27-43 (t == 255 -> 255)
+  if (coef != coef) b = 0u;                                        // a NaN coefficient: bin id 0, like bin_value()
   bool exc = false;
   if (k == 0) b = 255u; else exc = (b == 255u);
   if (k >= l) exc = false;

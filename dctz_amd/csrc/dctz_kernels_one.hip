@@ -315,9 +315,11 @@ __device__ __forceinline__ void compress_one_body(const OneFwd<T>& a, const unsi
     {
       double s0 = 0.0, s1 = 0.0;
       if (active) {
+        // (x[0] is left out, not added and taken back: a non-finite x[0] must not reach a sum it is no part of)
+        s0 = (tile == 0 && lane == 0) ? 0.0 : 0.0 + (double)x[0];
+        s1 = 0.0 + (double)x[1];
 #pragma unroll
-        for (int j = 0; j < 64; j += 2) { s0 += (double)x[j]; s1 += (double)x[j + 1]; }
-        if (tile == 0 && lane == 0) s0 -= (double)x[0];
+        for (int j = 2; j < 64; j += 2) { s0 += (double)x[j]; s1 += (double)x[j + 1]; }
       }
       rsum = wave_sum_f64(s0 + s1);
     }
@@ -552,6 +554,7 @@ __device__ __forceinline__ void compress_one_body(const OneFwd<T>& a, const unsi
       const T q = bwd.ok ? bwd.core(u) : u / bwd.d;
       const int t = (int)q;                                          // (t_bin_id) cast: truncation
       rbin = out ? 255u : (unsigned)(t <= 127 ? 254 - 2 * t : 2 * t - 255);   // conv_tbl :27-43 (t == 255 -> 255)
+      if (rcoef != rcoef) rbin = 0u;                                 // a NaN coefficient: bin id 0, like bin_value()
       if (k == 0) rbin = 255u; else rexc = (rbin == 255u);
       if (k >= l) rexc = false;
       const unsigned long long m = __builtin_amdgcn_ballot_w64(rexc);

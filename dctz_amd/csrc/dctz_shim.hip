@@ -779,7 +779,7 @@ extern "C" int dctzhip_sync(dctzhip_ctx* c) {
 
 // FastDiv's divisor window (dctz_kernels.hip): |d| in [2^-250, 2^250] (f64) / [2^-30, 2^30] (f32)
 static unsigned divisor_in_window(int dtype, double d) {
-  if (!(d == d) || d == 0.0) return 0;
+  if (!(d == d) || d == 0.0 || std::isinf(d)) return 0;      // (inf: sf of an array that holds an infinity; frexp says nothing about it)
   int e = 0;
   (void)frexp(fabs(d), &e);                      // |d| = m * 2^e, m in [0.5, 1)
   return (dtype == DCTZHIP_F64) ? (e - 1 >= -250 && e - 1 < 250) : (e - 1 >= -30 && e - 1 < 30);
@@ -1034,7 +1034,7 @@ static int build_sf_tables(dctzhip_ctx* c) {
     for (int i = 0; i < nk && ok; i++) {
       const double probes[2] = {thr[i], dt == DCTZHIP_F64 ? nextafter(thr[i], INFINITY) : (double)nextafterf((float)thr[i], INFINITY)};
       for (double v : probes) {
-        if (!(v > 0) || std::isinf(v)) continue;
+        if (!(v > 0)) continue;                  // (v = inf is probed too: an array that holds an infinity gets sf = inf, util.c:29)
         int below = 0;
         for (int j = 0; j < nk; j++) below += thr[j] < v;
         const double want = scaling_factor(dt, v);
@@ -1388,6 +1388,9 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   return DCTZHIP_OK;
 }
 
+template <typename T>
+static int stats_impl(dctzhip_ctx* c, const T* d_in, size_t n, double* max_abs, double* min_abs, double* sum);
+
 // geom != GEOM_1D, nd == NULL: d_in is the block-linear layout of a multi-dimensional array (n = nblk * 64) and the
 // statistics partials of the ORIGINAL array (n_orig elements) are already in c->part[0 .. pre_parts) -- k_gather_nd.
 // geom != GEOM_1D, nd != NULL: d_in is the array itself, read in place by k_compress (no padding: n = nblk * 64 = N).
@@ -1560,6 +1563,15 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
       rc = run(st, false);
       if (rc) return rc;
     }
+  }
+  // The fused sum is 8 sf times the sum of the blocks' DCs.  A non-finite x[0] -- which util.c:22 never adds -- makes block
+  // 0's DC and with it that whole sum NaN where the reference's is finite, so a fused sum that is not finite is taken again
+  // by the plain pass, which leaves x[0] out (one more read, for arrays that hold a NaN or an infinity only).
+  if (spec && !std::isfinite(st.sum)) {
+    double mx2 = 0.0, mn2 = 0.0, sum2 = 0.0;
+    int rc = stats_impl<T>(c, d_in, n, &mx2, &mn2, &sum2);
+    if (rc) return rc;
+    st.sum = sum2;
   }
   // dctz-comp-lib.c:193-216: the reference divides the caller's array by sf in place; here on request, into
   // d_scaled (which may be d_in itself), once sf is final
@@ -1746,7 +1758,10 @@ extern "C" int dctzhip_compress_part(dctzhip_ctx* c, const void* d_in, size_t n,
   if (!aligned16(d_in) || !aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u))
     return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned (DC, AC_exact: 4)");
   if (eb < 1E-6) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
-  if (!(max_abs >= min_abs) || !(min_abs >= 0.0)) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_part: statistics are not a max|x| >= min|x| >= 0 pair");
+  // (max|x| = 0 with min|x| = the largest finite value is what the statistics say of an array that holds nothing but NaNs)
+  const bool nothing_ordered = max_abs == 0.0 && min_abs == (dtype == DCTZHIP_F64 ? 1.79769313486231570815e308 : (double)3.40282346638528859812e38f);
+  if (!nothing_ordered && (!(max_abs >= min_abs) || !(min_abs >= 0.0)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_part: statistics are not a max|x| >= min|x| >= 0 pair");
   HIPCHK(c, hipSetDevice(c->device));
   rc = ensure_scratch(c, n, dtype, DCTZHIP_EC);
   if (rc) return rc;

@@ -161,7 +161,9 @@ inline void decade_tables(int kmin, int kmax, double* thr, double* pw) {
     pw[k - kmin] = (double)p10(k - 1);
     // largest m with ceil(log10(m)) <= k: bisection over the bit patterns (log10 is monotonic)
     if (cl(val(bmin)) > (double)k) { thr[k - kmin] = 0.0; continue; }               // the decade lies below the smallest subnormal
-    if (cl(val(bmax)) <= (double)k) { thr[k - kmin] = (double)INFINITY; continue; } // ... reaches past the largest finite value
+    // ... reaches past the largest finite value: that value is the threshold, so that max = inf still counts as "above" and
+    // takes pw[nk] = 10^kmax = inf in the data type -- util.c:29 / :43 on an array that holds an infinity
+    if (cl(val(bmax)) <= (double)k) { thr[k - kmin] = (double)big; continue; }
     Bits lo = bmin, hi = bmax;                         // invariant: cl(lo) <= k < cl(hi)
     while (hi - lo > 1) {
       const Bits mid = lo + (hi - lo) / 2;

@@ -921,6 +921,21 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
   grow(&g_dev.dc, &g_dev.dc_cap, nblk * sizeof(float));
   grow(&g_dev.ac, &g_dev.ac_cap, npos * sizeof(float));
 
+  /* util.c:18-19 starts max and min from |x[0]|: a NaN there stays (no comparison against it is true), sf = NaN, and the
+   * in-place x /= sf (dctz-comp-lib.c:193-216) has made the whole array NaN before the first block is transformed.  The
+   * drop-in keeps that rule (the device ABI passes a NaN over wherever it stands), the way the
+   * reference gets there: the mean of the array as it came (util.c:22 never adds x[0]), then the division -- the device
+   * compresses the array of NaNs, and the header says sf = NaN. */
+  const int nan_first = is_d ? isnan(((const double *)host_in)[0]) : isnan(((const float *)host_in)[0]);
+  double nan_first_mean = 0.0;
+  if (nan_first) {
+    host_mean_job m0 = {host_in, n, is_d, 0.0, 0};
+    (void)host_mean_main(&m0);
+    nan_first_mean = m0.mean;
+    if (is_d) { double *x = (double *)host_in; for (size_t i = 0; i < n; i++) x[i] /= (double)NAN; }
+    else { float *x = (float *)host_in; for (size_t i = 0; i < n; i++) x[i] /= (float)NAN; }
+  }
+
   double t0 = now_s();
   if (dctzhip_memcpy_h2d(c, g_dev.in, host_in, n * ts) != DCTZHIP_OK) die("H2D");
   double t1 = now_s();
@@ -941,6 +956,7 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
               : dctzhip_compress(c, g_dev.in, n, dtype, error_bound, DCTZ_MODE, g_dev.bin, (float *)g_dev.dc,
                                  (float *)g_dev.ac, NULL, NULL, &info);
   if (rc != DCTZHIP_OK) die("dctzhip_compress");
+  if (nan_first) info.sf = (double)NAN;             /* (the array is all NaN by now: the device said sf = 1 and scaled nothing) */
   if (dctzhip_sync(c) != DCTZHIP_OK) die("sync");   /* (the call returns while its last kernels drain: keep the stage timers honest) */
   double t2 = now_s();
 
@@ -984,7 +1000,7 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
   double t_gz = 0.0;                        /* end of the device entropy stage (the write-back of x/sf follows it) */
   uint32_t *ix[3] = {NULL, NULL, NULL};     /* compressed bytes per chunk, for the "DZIX" trailer */
   size_t ix_n[3] = {0, 0, 0};
-  const int host_scale = scale_on_host(gpu_tail) && info.sf != 1.0;
+  const int host_scale = scale_on_host(gpu_tail) && info.sf != 1.0 && !nan_first;
   pthread_t scale_thread;
   scale_mgr sm = {host_in, n, is_d, host_threads(), info.sf, mean_on_host ? &mean_thread : NULL, mean_on_host ? &mj : NULL, 0};
   int scale_started = 0;
@@ -1031,7 +1047,8 @@ int dctz_compress(t_var *var, int N, size_t *outSize, t_var *var_z, double error
   if (tree_mean) mean_serial = info.mean;
   else if (mean_on_host) mean_serial = mj.mean;
   else if (dctzhip_serial_mean_end(c, &mean_serial) != DCTZHIP_OK) die("serial mean");
-  if (info.sf != 1.0 && !scale_started) {   /* only now may the device copy of the input change */
+  if (nan_first) mean_serial = nan_first_mean;
+  if (info.sf != 1.0 && !scale_started && !nan_first) {   /* only now may the device copy of the input change */
     if (dctzhip_scale_inplace(c, g_dev.in, n, dtype, info.sf) != DCTZHIP_OK) die("scale");
     if (dctzhip_memcpy_d2h(c, host_in, g_dev.in, n * ts) != DCTZHIP_OK) die("D2H scaled input");
   }
@@ -1220,6 +1237,13 @@ int dctz_compress_batch(int k, t_var *const *vars, const int *N, size_t *outSize
     for (int i = 0; i < k; i++) if (dctz_compress(vars[i], N[i], &outSizes[i], vars_z[i], error_bounds[i]) != 1) return 0;
     return 1;
   }
+  /* an array whose first element is a NaN: dctz_compress keeps util.c's rule for it (max = sf = NaN);
+   * a list that holds one goes call by call */
+  for (int i = 0; i < k; i++)
+    if (N[i] > 0 && (vars[i]->datatype == DOUBLE ? isnan(((const double *)var_bytes(vars[i]))[0]) : isnan(((const float *)var_bytes(vars[i]))[0]))) {
+      for (int q = 0; q < k; q++) if (dctz_compress(vars[q], N[q], &outSizes[q], vars_z[q], error_bounds[q]) != 1) return 0;
+      return 1;
+    }
   dctzhip_ctx *c = ctx();
   /* layout of the staging area (host, pinned) and of its device twin: inputs | bin_index | DC | AC_exact, array after array */
   size_t *off_in = (size_t *)malloc(4 * (size_t)k * sizeof(size_t));
@@ -1796,6 +1820,8 @@ void calc_data_stat(t_var *in, t_bstat *bs, int N) {
   if (dctzhip_serial_mean_begin(c, g_dev.in, n, is_d ? DCTZHIP_F64 : DCTZHIP_F32) != DCTZHIP_OK) die("serial mean");
   if (dctzhip_stats(c, g_dev.in, n, is_d ? DCTZHIP_F64 : DCTZHIP_F32, &info) != DCTZHIP_OK) die("dctzhip_stats");
   if (dctzhip_serial_mean_end(c, &mean) != DCTZHIP_OK) die("serial mean");
+  /* util.c:18-19: max and min start from |x[0]|, and a NaN there stays (dctzhip_stats passes a NaN over wherever it stands) */
+  if (is_d ? isnan(in->buf.d[0]) : isnan(in->buf.f[0])) { info.max_abs = info.min_abs = (double)NAN; info.sf = (double)NAN; }
   if (is_d) { bs->max.d = info.max_abs; bs->min.d = info.min_abs; bs->mean.d = mean; bs->sf.d = info.sf; }
   else { bs->max.f = (float)info.max_abs; bs->min.f = (float)info.min_abs; bs->mean.f = (float)mean; bs->sf.f = (float)info.sf; }
 }

@@ -221,7 +221,9 @@ int dctzhip_compress(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype,
  * coefficients go -- AC_exact + the counts of the parts in front; *cnt: the part's count; part_stats (or NULL): max|x|,
  * min|x| of the part and the sum of its elements from the SECOND on (util.c:22 starts at i = 1: the caller adds a part's
  * first element unless the part is the array's first); *sf (or NULL): the scaling factor used.  A part whose own extremes
- * lie outside [min_abs, max_abs] is refused (DCTZHIP_E_ARG: the statistics are not this array's). */
+ * lie outside [min_abs, max_abs] is refused (DCTZHIP_E_ARG: the statistics are not this array's).  NaN elements are passed
+ * over by the statistics wherever they stand: the pair of an array that holds nothing else is
+ * max_abs = 0, min_abs = the largest finite value of the element type, as dctzhip_stats reports it, and is accepted. */
 int dctzhip_compress_part(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, double error_bound, double max_abs,
                           double min_abs, void *d_bin, float *d_dc, float *d_ac, uint32_t *cnt, double *part_stats, double *sf);
 

@@ -60,6 +60,13 @@ typedef struct {
 
 void orc_stats_f64(const double *x, size_t n, orc_stats *st);
 void orc_stats_f32(const float *x, size_t n, orc_stats *st);
+/* The same with the NaN rule spelled out (see the definition):
+ * ORC_NAN_REFERENCE is util.c's loop as it stands (a NaN x[0] stays: sf = NaN), ORC_NAN_SKIP
+ * the device ABI's (a NaN is passed over wherever it stands).  orc_stats_* / orc_compress_*
+ * are the ORC_NAN_REFERENCE forms. */
+enum { ORC_NAN_REFERENCE = 0, ORC_NAN_SKIP = 1 };
+void orc_stats_rule_f64(const double *x, size_t n, orc_stats *st, int nan_rule);
+void orc_stats_rule_f32(const float *x, size_t n, orc_stats *st, int nan_rule);
 
 /* In-place scaling x[i] /= sf when sf != 1 (dctz-comp-lib.c:188-217). */
 void orc_scale_f64(double *x, size_t n, double sf);
@@ -90,6 +97,7 @@ void orc_gen_bins_f32(float *bin_center, int nbins, float error_bound);
  *                slot 0 = last block's DC; EC: untouched)
  *   qtable_raw : optional, 64 elements, the table before clamping (qtable.bin)
  *   coef       : optional, n elements: DCT coefficients a_x after pass 1
+ * A NaN coefficient gets bin id 0: not in ac_exact, not in the table.
  * returns 0, or -1 if error_bound < 1e-6 (dctz-comp-lib.c:135-138). */
 int orc_compress_f64(double *x, size_t n, double error_bound, int mode, int impl,
                      orc_stats *st, uint8_t *bin_index, float *dc,
@@ -99,6 +107,15 @@ int orc_compress_f32(float *x, size_t n, double error_bound, int mode, int impl,
                      orc_stats *st, uint8_t *bin_index, float *dc,
                      float *ac_exact, uint32_t *cnt, float *qtable,
                      float *qtable_raw, float *coef);
+
+int orc_compress_rule_f64(double *x, size_t n, double error_bound, int mode, int impl,
+                          orc_stats *st, uint8_t *bin_index, float *dc,
+                          float *ac_exact, uint32_t *cnt, double *qtable,
+                          double *qtable_raw, double *coef, int nan_rule);
+int orc_compress_rule_f32(float *x, size_t n, double error_bound, int mode, int impl,
+                          orc_stats *st, uint8_t *bin_index, float *dc,
+                          float *ac_exact, uint32_t *cnt, float *qtable,
+                          float *qtable_raw, float *coef, int nan_rule);
 
 /* Decompress hot path a11..a15 (dctz-decomp-lib.c:358-511).  sf is the header's
  * scaling factor (as double; f32 passes an exactly representable float). */

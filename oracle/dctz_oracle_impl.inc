@@ -13,8 +13,27 @@
 /* ------------------------------------------------------------------------- */
 /* statistics + scaling factor: util.c:12-44                                  */
 /* ------------------------------------------------------------------------- */
-void SUF(orc_stats)(const T *x, size_t n, orc_stats *st) {
-  T mx = M_FABS(x[0]), mn = M_FABS(x[0]);
+/* nan_rule (DESIGN.md section 4 row 7) -- what a NaN does to max|x| / min|x|:
+ *   ORC_NAN_REFERENCE  util.c's own loop: `max = min = |x[0]|` to start with, so a
+ *                      NaN x[0] stays (every later `>` / `<` against it is false:
+ *                      sf = NaN), while a NaN anywhere else is passed over.  The
+ *                      drop-in dctz_compress keeps this rule.
+ *   ORC_NAN_SKIP       the device ABI: a NaN is passed over wherever it stands, x[0]
+ *                      included (max starts at 0, min at the largest finite value),
+ *                      so one NaN costs one block and never the array.
+ * Both rules give the same numbers for an array without a NaN in x[0].  `sum`
+ * is the same under both (x[0] is never added, util.c:22).                    */
+void SUF(orc_stats_rule)(const T *x, size_t n, orc_stats *st, int nan_rule) {
+  T mx, mn;
+  if (nan_rule == ORC_NAN_SKIP) {
+    mx = (T)0.0;
+    mn = IS_F64 ? (T)1.79769313486231570815e308 : (T)3.40282346638528859812e38f;
+    T v = M_FABS(x[0]);
+    if (v > mx) mx = v;
+    if (v < mn) mn = v;
+  } else {
+    mx = M_FABS(x[0]); mn = M_FABS(x[0]);
+  }
   T sum = (T)0.0;                       /* util.c:18 / :31 -- sum in type T  */
   for (size_t i = 1; i < n; i++) {      /* util.c:22-26 starts at 1: x[0] is */
     T v = M_FABS(x[i]);                 /* never added to `sum`              */
@@ -33,6 +52,9 @@ void SUF(orc_stats)(const T *x, size_t n, orc_stats *st) {
    * sf = 0 for an all-zero array and divides by it; we define sf = 1.        */
   if (mx == (T)0.0) sf = (T)1.0;
   st->max = mx; st->min = mn; st->sum = sum; st->mean = mean; st->sf = sf;
+}
+void SUF(orc_stats)(const T *x, size_t n, orc_stats *st) {
+  SUF(orc_stats_rule)(x, n, st, ORC_NAN_REFERENCE);
 }
 
 /* dctz-comp-lib.c:193-216 */
@@ -542,12 +564,12 @@ static inline uint8_t SUF(conv_bin)(unsigned t) {
 /* ------------------------------------------------------------------------- */
 /* compress hot path: dctz-comp-lib.c:186-544                                 */
 /* ------------------------------------------------------------------------- */
-int SUF(orc_compress)(T *x, size_t n, double error_bound, int mode, int impl,
-                      orc_stats *st, uint8_t *bin_index, float *dc,
-                      float *ac_exact, uint32_t *cnt_out, T *qtable,
-                      T *qtable_raw, T *coef) {
+int SUF(orc_compress_rule)(T *x, size_t n, double error_bound, int mode, int impl,
+                           orc_stats *st, uint8_t *bin_index, float *dc,
+                           float *ac_exact, uint32_t *cnt_out, T *qtable,
+                           T *qtable_raw, T *coef, int nan_rule) {
   if (error_bound < 1E-6) return -1;          /* :135-138 */
-  SUF(orc_stats)(x, n, st);                   /* :186 */
+  SUF(orc_stats_rule)(x, n, st, nan_rule);    /* :186 */
   T sf = (T)st->sf;
   SUF(orc_scale)(x, n, sf);                   /* :193-216 */
 
@@ -574,7 +596,14 @@ int SUF(orc_compress)(T *x, size_t n, double error_bound, int mode, int impl,
     for (int j = 1; j < l; j++) {             /* :363-414 */
       T item = ax[i * ORC_BLK + j];
       uint8_t bin_id;
-      if (item < range_min || item > range_max) {
+      if (item != item) {
+        /* DESIGN.md section 4 row 7: a NaN coefficient gets bin id 0.  The reference
+         * falls through to the cast below, which is undefined for a NaN; the
+         * kernels' saturating conversion gives 0, and that is the rule.  Id 0 is
+         * not "stored exactly": nothing goes to AC_exact or into the QT table,
+         * and the block decodes to NaN through its NaN DC.                     */
+        bin_id = 0;
+      } else if (item < range_min || item > range_max) {
         bin_id = ORC_NBINS;
         if (M_FABS(item) >= q[j]) q[j] = M_FABS(item);   /* :371-372 */
       } else {
@@ -617,6 +646,13 @@ int SUF(orc_compress)(T *x, size_t n, double error_bound, int mode, int impl,
   *cnt_out = cnt;
   if (!coef) free(ax);
   return 0;
+}
+int SUF(orc_compress)(T *x, size_t n, double error_bound, int mode, int impl,
+                      orc_stats *st, uint8_t *bin_index, float *dc,
+                      float *ac_exact, uint32_t *cnt_out, T *qtable,
+                      T *qtable_raw, T *coef) {
+  return SUF(orc_compress_rule)(x, n, error_bound, mode, impl, st, bin_index, dc, ac_exact, cnt_out,
+                                qtable, qtable_raw, coef, ORC_NAN_REFERENCE);
 }
 
 /* ------------------------------------------------------------------------- */

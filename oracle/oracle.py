@@ -16,6 +16,10 @@ _SO = os.path.join(_HERE, "libdctz_oracle.so")
 F32, F64 = 0, 1
 EC, QT = 0, 1
 NAIVE, FAST = 0, 1
+# What a NaN does to max|x| / min|x|: NAN_REFERENCE is util.c's loop as it stands (it starts
+# from |x[0]|, so a NaN there stays and sf = NaN; the drop-in dctz_compress keeps it), NAN_SKIP the device ABI's (a NaN
+# is passed over wherever it stands).  The two agree on every array whose first element is not a NaN.
+NAN_REFERENCE, NAN_SKIP = 0, 1
 BLK = 64
 
 
@@ -57,10 +61,10 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-def stats(x):
+def stats(x, nan_rule=NAN_REFERENCE):
     x = np.ascontiguousarray(x)
     st = Stats()
-    getattr(lib(), "orc_stats_" + _suf(x.dtype))(_p(x), C.c_size_t(x.size), C.byref(st))
+    getattr(lib(), "orc_stats_rule_" + _suf(x.dtype))(_p(x), C.c_size_t(x.size), C.byref(st), C.c_int(nan_rule))
     return st
 
 
@@ -101,8 +105,8 @@ class Compressed:
                  "ac_exact", "cnt", "qtable", "qtable_raw", "coef", "scaled")
 
 
-def compress(x, eb, mode=EC, impl=FAST, want_coef=False):
-    """Runs a2..a9 on a COPY of x; the scaled copy is returned as .scaled."""
+def compress(x, eb, mode=EC, impl=FAST, want_coef=False, nan_rule=NAN_REFERENCE):
+    """Runs a2..a9 on a COPY of x; the scaled copy is returned as .scaled.  nan_rule: NAN_REFERENCE | NAN_SKIP."""
     x = np.array(x, copy=True, order="C")
     suf = _suf(x.dtype)
     n = x.size
@@ -117,10 +121,10 @@ def compress(x, eb, mode=EC, impl=FAST, want_coef=False):
     out.coef = np.zeros(n, x.dtype) if want_coef else None
     st = Stats()
     cnt = C.c_uint32(0)
-    rc = getattr(lib(), "orc_compress_" + suf)(
+    rc = getattr(lib(), "orc_compress_rule_" + suf)(
         _p(x), C.c_size_t(n), C.c_double(eb), C.c_int(mode), C.c_int(impl), C.byref(st),
         _p(out.bin_index), _p(out.dc), _p(ac), C.byref(cnt), _p(out.qtable),
-        _p(out.qtable_raw), _p(out.coef) if want_coef else None)
+        _p(out.qtable_raw), _p(out.coef) if want_coef else None, C.c_int(nan_rule))
     if rc != 0:
         raise ValueError("error bound not acceptable (dctz-comp-lib.c:135-138)")
     out.cnt = cnt.value
@@ -186,12 +190,12 @@ def nd_scatter(lin, shape):
     return np.ascontiguousarray(t[tuple(slice(0, d) for d in shape)])
 
 
-def compress_nd(x, eb, mode=EC, impl=FAST, want_coef=False):
+def compress_nd(x, eb, mode=EC, impl=FAST, want_coef=False, nan_rule=NAN_REFERENCE):
     """x: 2-D or 3-D array.  Streams over the block-linear layout; statistics (sf, mean) over the ORIGINAL array."""
     x = np.asarray(x)
-    c = compress(nd_gather(x), eb, mode, geom_impl(x.ndim, impl), want_coef)
-    st = stats(np.ascontiguousarray(x).reshape(-1))
-    assert st.sf == c.sf                      # the padding repeats samples: max|x| is unchanged
+    c = compress(nd_gather(x), eb, mode, geom_impl(x.ndim, impl), want_coef, nan_rule)
+    st = stats(np.ascontiguousarray(x).reshape(-1), nan_rule)
+    assert st.sf == c.sf or (st.sf != st.sf and c.sf != c.sf)     # the padding repeats samples: max|x| is unchanged
     c.stats, c.mean = st, st.mean
     return c
 

@@ -97,7 +97,7 @@ def test_decade_tables_reproduce_the_host_scaling_factor(emu, dtype, code, kmin,
 
     probes = []
     for t in thr:
-        if 0 < t < np.inf:
+        if 0 < t < float(np.finfo(dtype).max):            # (the last threshold is the largest finite value: nothing above it to probe)
             probes += [t, float(np.nextafter(dtype(t), dtype(np.inf))), float(np.nextafter(dtype(t), dtype(0)))]
     probes += [float(dtype(10.0) ** k) for k in range(-20, 21)] + [1.0, 0.1, 0.5, 37.5, 999.9999, 1000.0, 1000.0001]
     rng = np.random.default_rng(9)
@@ -108,6 +108,10 @@ def test_decade_tables_reproduce_the_host_scaling_factor(emu, dtype, code, kmin,
         if not (0 < v <= fin.max):
             continue
         assert dev(v) == emu.emu_scaling_factor(code, v), v
+    # an array that holds an infinity: sf = inf (util.c:29 / :43), through the table as through the host's expression --
+    # the last threshold is the largest finite value, not inf, so that max = inf counts as above it
+    assert np.all(np.isfinite(thr)) and thr[-1] == float(fin.max)
+    assert dev(np.inf) == np.inf == emu.emu_scaling_factor(code, np.inf)
     # ... and scaling_factor() itself is the oracle's (util.c:29 / :43 through the same libm)
     for v in (0.37, 1.0, 9.99, 10.0, 10.01, 37.5, 1e-7, 123456.0):
         assert emu.emu_scaling_factor(code, float(dtype(v))) == O.stats(np.array([0.0, v], dtype)).sf

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import nonfinite as NF
 from tests import workloads as W
 
 pytestmark = pytest.mark.gpu
@@ -61,6 +62,35 @@ def _parse(z, dtype, qt):
                 bindex_count=struct.unpack_from("<I", z, 52)[0] if qt else None)
 
 
+def _feq(a, b):
+    """Equal, or both NaN (the header of an array with a NaN in it: DESIGN.md section 4 row 7)."""
+    return a == b or (a != a and b != b)
+
+
+def _poison(x, kind):
+    """The non-finite kinds of the drop-in's tests, on an array of any magnitude (tests/nonfinite.py has the bit patterns).
+    The drop-in keeps util.c's first-element rule: a NaN x[0] makes max, sf and the whole result NaN."""
+    n, dt = x.size, x.dtype
+    p = (n // 2) // 64 * 64 + 4
+    if kind == "qnan_one":
+        NF.put_bits(x, p + 1, NF._QNAN[dt])
+    elif kind == "snan_after_max":                          # the array's largest |x|, signalling NaNs behind it in its block
+        x[p] = -10.0 * float(np.abs(x).max())
+        NF.put_bits(x, np.array([p + 1, p + 2, p + 3, p + 16, p + 59]), NF._SNAN[dt])
+    elif kind == "nan_first":
+        NF.put_bits(x, 0, NF._QNAN[dt])
+    elif kind == "nans_behind_finite_first":                # x[0] finite, everything else NaN: max = min = |x[0]|
+        NF.put_bits(x, np.arange(1, n), NF._QNAN[dt])
+    elif kind == "pos_inf":
+        x[p + 1] = np.inf
+    else:
+        raise KeyError(kind)
+    return x
+
+
+NONFINITE = ["qnan_one", "snan_after_max", "nan_first", "nans_behind_finite_first", "pos_inf"]
+
+
 @pytest.fixture(params=[0, 8, "gpu", "gpu_device_inflate"], ids=["zlib_ref_3threads", "zlib_chunked_8threads", "deflate_on_gpu", "deflate_and_inflate_on_gpu"])
 def zthreads(request):
     """0: the reference's tail (three single-shot deflates); 8: chunked deflate (pdeflate.c); "gpu": the entropy stage
@@ -80,14 +110,17 @@ def zthreads(request):
 
 
 @pytest.mark.parametrize("mode", ["ec", "qt"])
-@pytest.mark.parametrize("case", ["c1", "ragged_f32", "ragged_f64_rem"])
+@pytest.mark.parametrize("case", ["c1", "ragged_f32", "ragged_f64_rem", "qnan_one"])
 def test_dropin_compress_decompress(mode, case, zthreads):
     lib = _lib(mode)
     qt = mode == "qt"
+    bad = None
     if case == "c1":
         x = W.c1(); eb = 1e-3
     elif case == "ragged_f32":
         x = W.ragged(64 * 700 + 17, np.float32, scale=37.0); eb = 1e-4
+    elif case == "qnan_one":                              # one NaN costs one block
+        x, bad = NF.make("qnan_one", 64 * 700 + 17, np.float64); eb = 1e-3
     else:
         x = W.ragged(37024, np.float64, scale=410.0); eb = 1e-3
     n = x.size
@@ -104,13 +137,16 @@ def test_dropin_compress_decompress(mode, case, zthreads):
     h = _parse(zbuf[:out_size.value], x.dtype, qt)
     assert (h["dt"], h["n"], h["eb"], h["cnt"]) == (var.datatype, n, eb, c.cnt)
     assert h["sf"] == c.sf
-    assert h["mean"] == x.dtype.type(c.mean)              # serial-order mean: bit-exact
+    assert _feq(h["mean"], x.dtype.type(c.mean))          # serial-order mean: bit-exact
     assert h["streams"][0] == c.bin_index.tobytes()
-    assert h["streams"][1] == c.dc.tobytes()
-    assert h["streams"][2] == c.ac_exact.tobytes()
+    # (same_with_nans: bit-identical, but for the payload of a NaN where the oracle has a NaN -- nowhere in clean data)
+    assert NF.same_with_nans(np.frombuffer(h["streams"][1], np.float32), c.dc)
+    assert NF.same_with_nans(np.frombuffer(h["streams"][2], np.float32), c.ac_exact)
     if qt:
-        assert h["bindex_count"] == n and np.array_equal(h["q"].view(np.uint8), c.qtable.view(np.uint8))
-    assert np.array_equal(x.view(np.uint8), c.scaled.view(np.uint8)), "caller's buffer must hold x/sf"
+        assert h["bindex_count"] == n and NF.same_with_nans(h["q"], c.qtable)
+    assert NF.same_with_nans(x, c.scaled), "caller's buffer must hold x/sf"
+    if bad is None:
+        assert not np.isnan(c.dc).any() and not np.isnan(c.scaled).any()
     body = 56 + sum(h["sizes"]) + (64 * x.itemsize if qt else 0)
     if zthreads in ("gpu", "gpu_device_inflate"):          # "DZIX" chunk index behind the container (include/dctz.h)
         nblk = (n + 63) // 64
@@ -126,8 +162,18 @@ def test_dropin_compress_decompress(mode, case, zthreads):
     if case == "c1" and mode == "ec" and zthreads == 0 and zlib.ZLIB_VERSION.startswith("1.2.11"):
         assert out_size.value == 3763394                   # survey known answer (zlib 1.2.11)
 
+    if bad is not None:                                    # the container of an array with a NaN is a well-formed one
+        lib.dctz_check_container.restype = C.c_int
+        lib.dctz_check_container.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+        assert lib.dctz_check_container(zbuf.ctypes.data_as(C.c_void_p), out_size.value, n, 1) == 0
     assert lib.dctz_decompress(C.byref(var_z), C.byref(var_r)) == 1
-    assert np.array_equal(rec.view(np.uint8), O.decompress(c, O.FAST).view(np.uint8))
+    assert NF.same_with_nans(rec, O.decompress(c, O.FAST))
+    if bad is None:
+        assert not np.isnan(rec).any()
+    else:                                                  # ... and decodes to NaN on exactly one block
+        want = np.zeros(n, bool)
+        want[64 * bad[0]:64 * bad[0] + 64] = True
+        assert bad.size == 1 and np.array_equal(np.isnan(rec), want)
     if case == "c1" and mode == "ec":
         p = O.psnr((orig / c.sf) * c.sf, rec)
         assert abs(p["psnr"] - 96.383701092386) < 1e-6 and abs(p["maxdiff"] - 9.232739551845448e-05) < 1e-10
@@ -232,9 +278,12 @@ def test_dct_test_style_loop_is_not_a_pcie_round_trip_per_block():
     assert worst < 1e-12
 
 
-@pytest.mark.parametrize("mode", ["ec", "qt"])
-@pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_pipelined_decompress_is_the_serial_one(mode, dtype, monkeypatch):
+_PD_CASES = [(m, d, k) for k in [None] + NONFINITE for m in ("ec", "qt") for d in (np.float64, np.float32)]
+
+
+@pytest.mark.parametrize("mode,dtype,kind", _PD_CASES,
+                         ids=[f"{np.dtype(d).name}-{m}" + (f"-{k}" if k else "") for m, d, k in _PD_CASES])
+def test_pipelined_decompress_is_the_serial_one(mode, dtype, kind, monkeypatch):
     """dctz_decompress of an indexed container works group by group (inflate of the groups ahead, H2D, kernels and D2H of
     finished groups overlapping): the reconstruction must be the bytes of the serial path and of the oracle -- here with
     a small group (DCTZ_PIPE_GROUP) so that an array of a few MB is six groups, a remainder block in the last one, and
@@ -244,6 +293,8 @@ def test_pipelined_decompress_is_the_serial_one(mode, dtype, monkeypatch):
     n = (1 << 18) * 5 + 64 * 1000 + 37
     x = W.ragged(n, dtype, scale=37.0)
     x[: 1 << 18] += (np.random.default_rng(3).standard_normal(1 << 18) * 3.0).astype(dtype)   # a noisy first group: most of AC_exact
+    if kind:                                              # NaN / Inf kinds: NaN where the oracle's is, else the same bits
+        _poison(x, kind)
     orig = x.copy()
     eb = 1e-3
     monkeypatch.setenv("DCTZ_ZLIB_GPU", "1")
@@ -254,6 +305,7 @@ def test_pipelined_decompress_is_the_serial_one(mode, dtype, monkeypatch):
     out_size = C.c_size_t(0)
     assert lib.dctz_compress(C.byref(var), n, C.byref(out_size), C.byref(var_z), eb) == 1
     ref = O.decompress(O.compress(orig, eb, O.QT if qt else O.EC, O.FAST), O.FAST)
+    assert bool(np.isnan(ref).any()) == bool(kind)
     recs = {}
     for name, env in (("pipelined", {"DCTZ_PIPE_GROUP": str(1 << 18)}), ("serial", {"DCTZ_PIPELINE": "0"})):
         for k, v in env.items():
@@ -265,7 +317,7 @@ def test_pipelined_decompress_is_the_serial_one(mode, dtype, monkeypatch):
         for k in env:
             monkeypatch.delenv(k)
     assert np.array_equal(recs["pipelined"].view(np.uint8), recs["serial"].view(np.uint8))
-    assert np.array_equal(recs["pipelined"].view(np.uint8), ref.view(np.uint8))
+    assert NF.same_with_nans(recs["pipelined"], ref)
     # a damaged chunk in the middle: the pipelined reader notices and hands the container to the one-stream inflate,
     # which treats damage the way the reference's reader does (no crash, the call returns)
     monkeypatch.setenv("DCTZ_PIPE_GROUP", str(1 << 18))
@@ -279,7 +331,7 @@ def test_pipelined_decompress_is_the_serial_one(mode, dtype, monkeypatch):
     assert lib.dctz_decompress(C.byref(var_b), C.byref(var_r)) == 1
 
 
-@pytest.mark.parametrize("kind", ["ragged", "flat", "short_last_group"])
+@pytest.mark.parametrize("kind", ["ragged", "flat", "short_last_group"] + NONFINITE)
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_pipelined_compress_is_the_serial_one(dtype, kind, monkeypatch):
     """dctz_compress of a large array with the entropy stage on the device works group by group (H2D of the groups ahead,
@@ -297,6 +349,11 @@ def test_pipelined_compress_is_the_serial_one(dtype, kind, monkeypatch):
         x = W.ragged(n, dtype, scale=37.0)
         x[: 1 << 18] += (np.random.default_rng(3).standard_normal(1 << 18) * 3.0).astype(dtype)
         x[n - 70] = 5432.0
+    if kind in NONFINITE:
+        # NaN / Inf kinds.  The host's max|x| loops (mm_range_avx2 / mm_main) meet a NaN in every
+        # worker's range in "nans_behind_finite_first" and signalling NaNs behind the maximum in "snan_after_max"; a NaN x[0]
+        # sends the call to the serial path, which keeps util.c's rule (max = NaN, everything NaN).
+        _poison(x, kind)
     orig = x.copy()
     eb = 1e-3
     monkeypatch.setenv("DCTZ_ZLIB_GPU", "1")
@@ -321,19 +378,29 @@ def test_pipelined_compress_is_the_serial_one(dtype, kind, monkeypatch):
     assert np.array_equal(np.delete(zp, np.r_[MEAN]), np.delete(zs, np.r_[MEAN]))
     mp = zp[MEAN].view(np.float64)[0] if dtype == np.float64 else zp[32:36].view(np.float32)[0]
     ms = zs[MEAN].view(np.float64)[0] if dtype == np.float64 else zs[32:36].view(np.float32)[0]
-    assert abs(mp - ms) <= 1e-6 * max(1.0, abs(ms))
+    c = O.compress(orig, eb, O.EC, O.FAST)                 # (util.c's first-element rule: the drop-in's)
+    if np.isfinite(c.mean):
+        assert abs(mp - ms) <= 1e-6 * max(1.0, abs(ms))
+    else:
+        assert kind in NONFINITE and not np.isfinite(mp) and not np.isfinite(ms)
     assert np.array_equal(xp.view(np.uint8), xs.view(np.uint8))
-    sf = 10.0 ** (np.ceil(np.log10(np.abs(orig).max())) - 1)
-    assert np.array_equal(xp, orig / dtype(sf))
+    hsf = zp[24:32].view(np.float64)[0] if dtype == np.float64 else zp[24:28].view(np.float32)[0]
+    assert _feq(float(hsf), c.sf) and int(zp[16:20].view(np.uint32)[0]) == c.cnt
+    if kind in NONFINITE:
+        assert NF.same_with_nans(xp, c.scaled)
+    else:
+        sf = 10.0 ** (np.ceil(np.log10(np.abs(orig).max())) - 1)
+        assert sf == c.sf and np.array_equal(xp, orig / dtype(sf))
     # ... and it decodes to the oracle's reconstruction
-    ref = O.decompress(O.compress(orig, eb, O.EC, O.FAST), O.FAST)
+    ref = O.decompress(c, O.FAST)
+    assert bool(np.isnan(ref).any()) == (kind in NONFINITE)
     var_z = TVar()
     var_z.datatype = _tvar(orig).datatype
     var_z.buf.d = zp.ctypes.data_as(C.POINTER(C.c_double))
     rec = np.zeros(n, dtype)
     var_r = _tvar(rec)
     assert lib.dctz_decompress(C.byref(var_z), C.byref(var_r)) == 1
-    assert np.array_equal(rec.view(np.uint8), ref.view(np.uint8))
+    assert NF.same_with_nans(rec, ref)
 
 
 @pytest.mark.parametrize("mode", ["ec", "qt"])
@@ -432,6 +499,18 @@ def test_calc_data_stat_and_gen_bins():
         st = O.stats(x)
         got = (bs.mean.d, bs.min.d, bs.max.d, bs.sf.d) if dtype == np.float64 else (bs.mean.f, bs.min.f, bs.max.f, bs.sf.f)
         assert got == tuple(dtype(v) for v in (st.mean, st.min, st.max, st.sf))
+        # NaN / Inf: util.c's loop as it stands -- a NaN is passed over, except in x[0], where it stays
+        for kind in NONFINITE:
+            y = _poison(W.ragged(100003, dtype, scale=512.0), kind)
+            bs = BStat()
+            var = _tvar(y)
+            lib.calc_data_stat(C.byref(var), C.byref(bs), y.size)
+            st = O.stats(y)
+            got = (bs.min.d, bs.max.d, bs.sf.d) if dtype == np.float64 else (bs.min.f, bs.max.f, bs.sf.f)
+            want = tuple(dtype(v) for v in (st.min, st.max, st.sf))
+            assert all(_feq(g, w) for g, w in zip(got, want)), (kind, got, want)
+            m = bs.mean.d if dtype == np.float64 else bs.mean.f
+            assert _feq(m, dtype(st.mean)) if np.isfinite(st.mean) else not np.isfinite(m), (kind, m, st.mean)
     bc = np.zeros(255)
     lib.gen_bins(C.c_double(0), C.c_double(0), bc.ctypes.data_as(C.c_void_p), 255, C.c_double(1e-3))
     assert np.array_equal(bc, O.gen_bins(1e-3, np.float64))

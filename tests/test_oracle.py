@@ -197,3 +197,107 @@ def test_block_transform_against_fftw_generated_values(impl, key, dtype, tol):
         ref = y3 / 2.0 * np.sqrt(2.0 / n)
         got = O.dct_inv(x, impl).astype(np.float64)
         assert np.abs(got - ref).max() <= tol * np.abs(ref).max(), (n, "inverse")
+
+
+# ---- NaN / Inf inputs: DESIGN.md section 4 row 7, stated by the oracle ------------------------------------------------
+from tests import nonfinite as NF   # noqa: E402
+
+
+def _block_slices(c):
+    """AC_exact as one slice per block (the exceptions are emitted block-major, dctz-comp-lib.c:478-544)."""
+    nblk = (c.n + 63) // 64
+    flags = c.bin_index == 255
+    flags[::64] = False
+    per = np.add.reduceat(flags.astype(np.int64), np.arange(0, c.n, 64))
+    assert per.size == nblk and int(per.sum()) == c.cnt
+    off = np.concatenate([[0], np.cumsum(per)])
+    return [c.ac_exact[off[b]:off[b + 1]] for b in range(nblk)]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", [O.EC, O.QT])
+@pytest.mark.parametrize("kind,n", [(k_, n_) for k_ in ("qnan_one", "snan_one", "neg_nan", "nan_last_short", "nan_tile", "nan_sprinkled")
+                                    for n_ in (647, 64 * 64 * 3 + 64 * 9 + 21) if (k_, n_) != ("nan_tile", 647)])   # (647: one tile, no other block)
+def test_nan_coefficient_gets_bin_zero_and_stays_in_its_block(dtype, mode, kind, n):
+    """Row 7: a NaN coefficient -> bin id 0 (not the reference's undefined cast, which gives 254 on x86), nothing of it in
+    AC_exact or in the QT table, and CONTAINMENT: every other block's bin ids, DC and slice of AC_exact are, bit for bit,
+    those of the same array with the NaN blocks replaced by finite values (a constant, which like a NaN block puts
+    nothing into the QT table: the table, and with it the normalised values of the other blocks, must not move)."""
+    eb = 1e-3
+    x, bad = NF.make(kind, n, dtype)
+    clean = x.copy()
+    for b in bad:
+        clean[64 * b:64 * b + 64] = 1.0
+    c, k = O.compress(x, eb, mode, O.FAST), O.compress(clean, eb, mode, O.FAST)
+    assert c.sf == k.sf == 10.0 and c.stats.max == k.stats.max
+    nblk = (n + 63) // 64
+    other = np.setdiff1d(np.arange(nblk), bad)
+    assert other.size >= 1
+    for b in bad:
+        lo, hi = 64 * b, min(64 * b + 64, n)
+        assert c.bin_index[lo] == 255 and np.all(c.bin_index[lo + 1:hi] == 0), c.bin_index[lo:hi]
+        assert np.isnan(c.dc[b])
+    sc, sk = _block_slices(c), _block_slices(k)
+    for b in bad:
+        assert sc[b].size == 0
+    keep = np.ones(n, bool)
+    for b in bad:
+        keep[64 * b:64 * b + 64] = False
+    assert np.array_equal(c.bin_index[keep], k.bin_index[keep])
+    assert np.array_equal(c.dc[other].view(np.uint32), k.dc[other].view(np.uint32))
+    for b in other:
+        assert np.array_equal(sc[b].view(np.uint32), sk[b].view(np.uint32)), b
+    assert not np.isnan(c.ac_exact).any() and c.cnt == k.cnt - sum(sk[b].size for b in bad)
+    if mode == O.QT:
+        assert np.array_equal(c.qtable[1:].view(np.uint8), k.qtable[1:].view(np.uint8)) and not np.isnan(c.qtable_raw[1:]).any()
+    r, rk = O.decompress(c), O.decompress(k)
+    assert np.array_equal(np.isnan(r), ~keep), "the decode is NaN on exactly the poisoned blocks"
+    assert NF.same_with_nans(r[keep], rk[keep])
+    NF.contained_budget(c, r, bad.size)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", [O.EC, O.QT])
+def test_nan_in_the_first_element_under_both_rules(dtype, mode):
+    """The switch of O.compress: util.c's loop starts from |x[0]| (a NaN there stays: sf = NaN, everything NaN -- the
+    drop-in's rule), the device ABI passes a NaN over wherever it stands (one NaN costs one block)."""
+    n = 647
+    x, bad = NF.make("nan_first", n, dtype)
+    ref = O.compress(x, 1e-3, mode, O.FAST)                              # NAN_REFERENCE is the default
+    assert np.isnan(ref.sf) and np.isnan(ref.stats.max) and np.isnan(ref.stats.min) and ref.cnt == 0
+    assert np.isnan(O.decompress(ref)).all()
+    assert np.isfinite(ref.mean)                                         # util.c:22: x[0] is never added
+    dev = O.compress(x, 1e-3, mode, O.FAST, nan_rule=O.NAN_SKIP)
+    clean = x.copy(); clean[:64] = 1.0
+    k = O.compress(clean, 1e-3, mode, O.FAST)
+    assert dev.sf == k.sf == 10.0 and dev.stats.max == k.stats.max and dev.mean == ref.mean
+    assert np.array_equal(dev.bin_index[64:], k.bin_index[64:]) and np.all(dev.bin_index[1:64] == 0) and dev.bin_index[0] == 255
+    assert np.isnan(dev.dc[0]) and np.array_equal(dev.dc[1:].view(np.uint32), k.dc[1:].view(np.uint32))
+    r = O.decompress(dev)
+    assert np.isnan(r[:64]).all() and not np.isnan(r[64:]).any()
+    # the two rules are the same function wherever x[0] is not a NaN
+    for kind in ("qnan_one", "snan_after_max", "all_nan", "pos_inf", "inf_first"):
+        y, _ = NF.make(kind, n, dtype)
+        a, b = O.compress(y, 1e-3, mode, O.FAST), O.compress(y, 1e-3, mode, O.FAST, nan_rule=O.NAN_SKIP)
+        if kind == "all_nan":                                            # (x[0] is a NaN here too)
+            assert np.isnan(a.sf) and b.sf == 1.0 and b.stats.max == 0.0 and b.cnt == 0
+            continue
+        assert a.sf == b.sf and a.cnt == b.cnt and a.stats.max == b.stats.max and a.stats.min == b.stats.min
+        assert np.array_equal(a.bin_index, b.bin_index) and NF.same_with_nans(a.dc, b.dc)
+    s, _ = NF.make("snan_after_max", n, dtype)
+    assert O.compress(s, 1e-3, mode, O.FAST).sf == 1000.0                # the decade of the spike in front of the NaNs
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("mode", [O.EC, O.QT])
+@pytest.mark.parametrize("kind", NF.INF_KINDS)
+def test_an_infinity_gives_sf_inf_and_an_all_nan_decode(dtype, mode, kind):
+    """util.c:29 on max = inf: sf = inf.  x / inf is 0 (NaN for the infinity itself), so nothing is out of range
+    (cnt = 0), and the decode multiplies by inf: every element NaN.  Same under both first-element rules."""
+    n = 647
+    x, bad = NF.make(kind, n, dtype)
+    for rule in (O.NAN_REFERENCE, O.NAN_SKIP):
+        c = O.compress(x, 1e-3, mode, O.FAST, nan_rule=rule)
+        assert c.sf == np.inf and c.stats.max == np.inf and c.cnt == 0
+        assert np.isnan(c.dc[bad[0]]) and int(np.isnan(c.dc).sum()) == 1
+        assert np.isnan(O.decompress(c)).all()
