@@ -130,6 +130,18 @@ template <typename T, int MODE> struct Sub {
 template <typename T> struct Phases { static constexpr int C = DCTZ_PHC32, D = DCTZ_PHD32; };
 template <> struct Phases<double> { static constexpr int C = DCTZ_PHC64, D = DCTZ_PHD64; };
 
+// Run time -> compile time, written once: f is called with the mode (or the flag) as an integral_constant, so that M() is
+// a template argument inside it; with_mode_bool does both steps and calls f(M, B).  Every launcher picks its kernel
+// through these (the selectors in the kernel files: one function per kernel family that returns the instantiation's
+// handle, for the launch AND for the occupancy query).
+template <typename F> auto with_mode(int mode, F&& f) {
+  return mode == DCTZHIP_EC ? f(std::integral_constant<int, DCTZHIP_EC>{}) : f(std::integral_constant<int, DCTZHIP_QT>{});
+}
+template <typename F> auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <typename F> auto with_mode_bool(int mode, bool b, F&& f) {
+  return with_mode(mode, [&](auto M) { return with_bool(b, [&](auto B) { return f(decltype(M){}, B); }); });
+}
+
 // Per-call control block in device memory; zeroed by the first kernel of every compress call (k_stats_final) --
 // a decode call only ever sets `error`, and the host clears the block after a failed call.
 struct Ctl {
@@ -266,6 +278,11 @@ struct InvParams {
   T sf, bin_width, range_min, range_max;
   double eb;
 };
+
+// Which variant a launch takes: asked by the launcher, and by the shim for the kernel name it reports
+// (dctzhip_debug_last_kernel).  The scaled variant of k_compress and the tile-interleaved decoder exist for flat blocks only.
+template <typename T> inline bool takes_scaled(const FwdParams<T>& p, int geom) { return geom == GEOM_1D && p.scaled != nullptr; }
+template <typename T> inline bool takes_interleaved(const InvParams<T>& p, int geom) { return geom == GEOM_1D && p.tile_pre != nullptr; }
 
 // ---- batches of arrays (dctzhip_compress_batch / dctzhip_decompress_batch) -------------------------------------
 // k arrays of ONE element type go through ONE launch sequence: every kernel of the single-array path has a batch
@@ -511,7 +528,7 @@ size_t deflate_bound(size_t n);
 hipError_t launch_deflate(const void* src, size_t n, void* dst, void* scratch, unsigned long long* box_len, uint32_t* host_sizes, bool literals_only,
                           hipStream_t st);
 hipError_t launch_inflate(const void* sec, const uint32_t* offs, size_t nch, size_t n, void* dst, unsigned long long* adler, uint32_t* status, hipStream_t st);
-template <typename T> int compress_occupancy(int mode, bool stats, int geom, bool scaled = false);
+template <typename T> int compress_occupancy(int mode, bool stats, int geom, bool scaled);
 template <typename T> int decompress_occupancy(int mode, int geom);
 template <typename T> size_t compress_lds_bytes(int mode);
 template <typename T> size_t decompress_lds_bytes();

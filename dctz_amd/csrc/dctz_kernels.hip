@@ -1515,75 +1515,61 @@ void launch_finish(Ctl* ctl, const double* part, int nparts, HostBox* box, unsig
 }
 #endif
 
+// The k_compress instantiation for (mode, stats, geom, scaled): the one place that decides it, for the launch and for the
+// occupancy query.  Exactly the instantiations that exist: SC = true for flat blocks only.
+template <typename T>
+auto compress_kernel(int mode, bool stats, int geom, bool scaled) -> void (*)(FwdParams<T>) {
+  return with_mode_bool(mode, stats, [=](auto M, auto S) -> void (*)(FwdParams<T>) {
+    constexpr int PH = Phases<T>::C;
+    if (geom == GEOM_1D && scaled) return k_compress<T, M(), S(), PH, GEOM_1D, true>;   // the variant that writes x / sf back as well
+    if (geom == GEOM_1D) return k_compress<T, M(), S(), PH, GEOM_1D>;
+    if (geom == GEOM_2D) return k_compress<T, M(), S(), PH, GEOM_2D>;
+    return k_compress<T, M(), S(), PH, GEOM_3D>;
+  });
+}
 template <typename T>
 void launch_compress(const FwdParams<T>& p, int mode, bool stats, int grid, int geom, hipStream_t s) {
-  if (geom == GEOM_1D && p.scaled != nullptr) {        // the variant that writes x / sf back as well
-    if (mode == DCTZHIP_EC) {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, true, Phases<T>::C, GEOM_1D, true>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, false, Phases<T>::C, GEOM_1D, true>), dim3(grid), dim3(WG), 0, s, p);
-    } else {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, true, Phases<T>::C, GEOM_1D, true>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, false, Phases<T>::C, GEOM_1D, true>), dim3(grid), dim3(WG), 0, s, p);
-    }
-  } else if (geom == GEOM_1D) {
-    if (mode == DCTZHIP_EC) {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, true, Phases<T>::C, GEOM_1D>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, false, Phases<T>::C, GEOM_1D>), dim3(grid), dim3(WG), 0, s, p);
-    } else {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, true, Phases<T>::C, GEOM_1D>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, false, Phases<T>::C, GEOM_1D>), dim3(grid), dim3(WG), 0, s, p);
-    }
-  } else if (geom == GEOM_2D) {
-    if (mode == DCTZHIP_EC) {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, true, Phases<T>::C, GEOM_2D>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, false, Phases<T>::C, GEOM_2D>), dim3(grid), dim3(WG), 0, s, p);
-    } else {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, true, Phases<T>::C, GEOM_2D>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, false, Phases<T>::C, GEOM_2D>), dim3(grid), dim3(WG), 0, s, p);
-    }
-  } else {
-    if (mode == DCTZHIP_EC) {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, true, Phases<T>::C, GEOM_3D>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_EC, false, Phases<T>::C, GEOM_3D>), dim3(grid), dim3(WG), 0, s, p);
-    } else {
-      if (stats) hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, true, Phases<T>::C, GEOM_3D>), dim3(grid), dim3(WG), 0, s, p);
-      else hipLaunchKernelGGL((k_compress<T, DCTZHIP_QT, false, Phases<T>::C, GEOM_3D>), dim3(grid), dim3(WG), 0, s, p);
-    }
-  }
+  hipLaunchKernelGGL(compress_kernel<T>(mode, stats, geom, takes_scaled(p, geom)), dim3(grid), dim3(WG), 0, s, p);
 }
-
-// Resident workgroups per CU of the k_compress instantiation a launch would pick (registers AND LDS: the persistent
-// grid must not exceed what is resident at once, or its tail runs as a second round)
+// Resident workgroups per CU of that instantiation (registers AND LDS: the persistent grid must not exceed what is
+// resident at once, or its tail runs as a second round)
 template <typename T>
 int compress_occupancy(int mode, bool stats, int geom, bool scaled) {
   int n = 0;
-  hipError_t e;
-#define OCC(M, S, G) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress<T, M, S, Phases<T>::C, G>, WG, 0)
-#define OCCS(M, S) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress<T, M, S, Phases<T>::C, GEOM_1D, true>, WG, 0)
-  if (geom == GEOM_1D && scaled) { if (mode == DCTZHIP_EC) { if (stats) OCCS(DCTZHIP_EC, true); else OCCS(DCTZHIP_EC, false); } else { if (stats) OCCS(DCTZHIP_QT, true); else OCCS(DCTZHIP_QT, false); } }
-  else if (geom == GEOM_1D) { if (mode == DCTZHIP_EC) { if (stats) OCC(DCTZHIP_EC, true, GEOM_1D); else OCC(DCTZHIP_EC, false, GEOM_1D); } else { if (stats) OCC(DCTZHIP_QT, true, GEOM_1D); else OCC(DCTZHIP_QT, false, GEOM_1D); } }
-  else if (geom == GEOM_2D) { if (mode == DCTZHIP_EC) { if (stats) OCC(DCTZHIP_EC, true, GEOM_2D); else OCC(DCTZHIP_EC, false, GEOM_2D); } else { if (stats) OCC(DCTZHIP_QT, true, GEOM_2D); else OCC(DCTZHIP_QT, false, GEOM_2D); } }
-  else { if (mode == DCTZHIP_EC) { if (stats) OCC(DCTZHIP_EC, true, GEOM_3D); else OCC(DCTZHIP_EC, false, GEOM_3D); } else { if (stats) OCC(DCTZHIP_QT, true, GEOM_3D); else OCC(DCTZHIP_QT, false, GEOM_3D); } }
-#undef OCC
-#undef OCCS
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)compress_kernel<T>(mode, stats, geom, scaled), WG, 0);
   return e == hipSuccess ? n : 0;
 }
+
+// k_decompress / k_decompress_il likewise (k_decompress_il has no geometry: flat blocks only).  Tile-interleaved workgroups
+// where the shim sets tile_pre (takes_interleaved): by default fp64 EC only.  Measured on one box, builds alternating
+// (tools/r04_il.sh, r04_il2.sh): fp64 EC 220 -> 200-206 us, fp64 EC at p = 0.69 316-335 -> 313-320; fp64 QT 245 -> 257 and
+// fp32 119 -> 125 the OTHER way (kernels their arithmetic holds, not their store stream: they only pay for the scattered
+// reads and the per-tile descriptors), so those keep a contiguous range per workgroup.
+template <typename T>
+auto decompress_kernel(int mode, int geom, bool interleaved) -> void (*)(InvParams<T>, FinArgs) {
+  return with_mode(mode, [=](auto M) -> void (*)(InvParams<T>, FinArgs) {
+    constexpr int PH = Phases<T>::D;
+    if (geom == GEOM_1D && interleaved) return k_decompress_il<T, M(), PH>;   // (the shim chooses: fp64 EC by default, everything with DCTZHIP_DEC_IL=2)
+    if (geom == GEOM_1D) return k_decompress<T, M(), PH, GEOM_1D>;
+    if (geom == GEOM_2D) return k_decompress<T, M(), PH, GEOM_2D>;
+    return k_decompress<T, M(), PH, GEOM_3D>;
+  });
+}
+template <typename T>
+void launch_decompress(const InvParams<T>& p, int mode, int grid, const FinArgs& fin, int geom, hipStream_t s) {
+  hipLaunchKernelGGL(decompress_kernel<T>(mode, geom, takes_interleaved(p, geom)), dim3(grid), dim3(WG), 0, s, p, fin);
+}
+// (of the contiguous kernel: an interleaved launch is sized by it too -- the shim asks before it decides on tile_pre)
 template <typename T>
 int decompress_occupancy(int mode, int geom) {
   int n = 0;
-  hipError_t e;
-#define OCC(M, G) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress<T, M, Phases<T>::D, G>, WG, 0)
-  if (geom == GEOM_1D) { if (mode == DCTZHIP_EC) OCC(DCTZHIP_EC, GEOM_1D); else OCC(DCTZHIP_QT, GEOM_1D); }
-  else if (geom == GEOM_2D) { if (mode == DCTZHIP_EC) OCC(DCTZHIP_EC, GEOM_2D); else OCC(DCTZHIP_QT, GEOM_2D); }
-  else { if (mode == DCTZHIP_EC) OCC(DCTZHIP_EC, GEOM_3D); else OCC(DCTZHIP_QT, GEOM_3D); }
-#undef OCC
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)decompress_kernel<T>(mode, geom, false), WG, 0);
   return e == hipSuccess ? n : 0;
 }
 
 template <typename T>
 void launch_compress_rem(const FwdParams<T>& p, int mode, int l, hipStream_t s) {
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_compress_rem<T, DCTZHIP_EC>), dim3(1), dim3(64), 0, s, p, l);
-  else hipLaunchKernelGGL((k_compress_rem<T, DCTZHIP_QT>), dim3(1), dim3(64), 0, s, p, l);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_compress_rem<T, M()>; }), dim3(1), dim3(64), 0, s, p, l);
 }
 
 #if DCTZ_PART == 0
@@ -1602,40 +1588,12 @@ void launch_compact_ac(const FwdParams<T>& p, int mode, double eb, unsigned nlis
   // (grid = nlists; second dimension: chunks of COMPACT_TPW tiles of the longest list)
   const unsigned per_list = p.nlists_main ? (p.ntiles + p.nlists_main - 1) / p.nlists_main : 0u;
   const unsigned chunks = per_list ? (per_list + COMPACT_TPW - 1) / COMPACT_TPW : 1u;
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_compact_ac<T, DCTZHIP_EC>), dim3(grid, chunks), dim3(SWG), 0, s, p, eb, nlists, fin);
-  else hipLaunchKernelGGL((k_compact_ac<T, DCTZHIP_QT>), dim3(grid, chunks), dim3(SWG), 0, s, p, eb, nlists, fin);
-}
-
-template <typename T>
-void launch_decompress(const InvParams<T>& p, int mode, int grid, const FinArgs& fin, int geom, hipStream_t s) {
-  // tile-interleaved workgroups where the shim sets tile_pre: by default fp64 EC only.  Measured on one box, builds
-  // alternating (tools/r04_il.sh, r04_il2.sh): fp64 EC 220 -> 200-206 us, fp64 EC at p = 0.69 316-335 -> 313-320; fp64 QT
-  // 245 -> 257 and fp32 119 -> 125 the OTHER way (kernels their arithmetic holds, not their store stream: they only pay for
-  // the scattered reads and the per-tile descriptors), so those keep a contiguous range per workgroup.
-  if (geom == GEOM_1D && p.tile_pre != nullptr) {     // (the shim chooses: fp64 EC by default, everything with DCTZHIP_DEC_IL=2)
-    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_il<T, DCTZHIP_EC, Phases<T>::D>), dim3(grid), dim3(WG), 0, s, p, fin);
-    else hipLaunchKernelGGL((k_decompress_il<T, DCTZHIP_QT, Phases<T>::D>), dim3(grid), dim3(WG), 0, s, p, fin);
-  } else if (geom == GEOM_1D) {
-    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress<T, DCTZHIP_EC, Phases<T>::D, GEOM_1D>), dim3(grid), dim3(WG), 0, s, p, fin);
-    else hipLaunchKernelGGL((k_decompress<T, DCTZHIP_QT, Phases<T>::D, GEOM_1D>), dim3(grid), dim3(WG), 0, s, p, fin);
-  } else if (geom == GEOM_2D) {
-    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress<T, DCTZHIP_EC, Phases<T>::D, GEOM_2D>), dim3(grid), dim3(WG), 0, s, p, fin);
-    else hipLaunchKernelGGL((k_decompress<T, DCTZHIP_QT, Phases<T>::D, GEOM_2D>), dim3(grid), dim3(WG), 0, s, p, fin);
-  } else {
-    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress<T, DCTZHIP_EC, Phases<T>::D, GEOM_3D>), dim3(grid), dim3(WG), 0, s, p, fin);
-    else hipLaunchKernelGGL((k_decompress<T, DCTZHIP_QT, Phases<T>::D, GEOM_3D>), dim3(grid), dim3(WG), 0, s, p, fin);
-  }
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_compact_ac<T, M()>; }), dim3(grid, chunks), dim3(SWG), 0, s, p, eb, nlists, fin);
 }
 
 template <typename T>
 void launch_decompress_rem(const InvParams<T>& p, int mode, bool scale, int l, hipStream_t s) {
-  if (mode == DCTZHIP_EC) {
-    if (scale) hipLaunchKernelGGL((k_decompress_rem<T, DCTZHIP_EC, true>), dim3(1), dim3(64), 0, s, p, l);
-    else hipLaunchKernelGGL((k_decompress_rem<T, DCTZHIP_EC, false>), dim3(1), dim3(64), 0, s, p, l);
-  } else {
-    if (scale) hipLaunchKernelGGL((k_decompress_rem<T, DCTZHIP_QT, true>), dim3(1), dim3(64), 0, s, p, l);
-    else hipLaunchKernelGGL((k_decompress_rem<T, DCTZHIP_QT, false>), dim3(1), dim3(64), 0, s, p, l);
-  }
+  hipLaunchKernelGGL(with_mode_bool(mode, scale, [](auto M, auto SC) { return k_decompress_rem<T, M(), SC()>; }), dim3(1), dim3(64), 0, s, p, l);
 }
 
 // ================================================================== batches ==
@@ -1827,24 +1785,16 @@ __global__ __launch_bounds__(64) void k_decompress_rem_batch(const BatchInv<T>* 
 
 template <typename T>
 void launch_compress_batch(const BatchFwd<T>* items, const unsigned* first, unsigned k, unsigned grid, int mode, bool stats, hipStream_t s) {
-  if (mode == DCTZHIP_EC) {
-    if (stats) hipLaunchKernelGGL((k_compress_batch<T, DCTZHIP_EC, true>), dim3(grid), dim3(WG), 0, s, items, first, k);
-    else hipLaunchKernelGGL((k_compress_batch<T, DCTZHIP_EC, false>), dim3(grid), dim3(WG), 0, s, items, first, k);
-  } else {
-    if (stats) hipLaunchKernelGGL((k_compress_batch<T, DCTZHIP_QT, true>), dim3(grid), dim3(WG), 0, s, items, first, k);
-    else hipLaunchKernelGGL((k_compress_batch<T, DCTZHIP_QT, false>), dim3(grid), dim3(WG), 0, s, items, first, k);
-  }
+  hipLaunchKernelGGL(with_mode_bool(mode, stats, [](auto M, auto S) { return k_compress_batch<T, M(), S()>; }), dim3(grid), dim3(WG), 0, s, items, first, k);
 }
 template <typename T>
 void launch_compress_rem_batch(const BatchFwd<T>* items, const unsigned* rem_items, unsigned nrem, int mode, hipStream_t s) {
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_compress_rem_batch<T, DCTZHIP_EC>), dim3(nrem), dim3(64), 0, s, items, rem_items);
-  else hipLaunchKernelGGL((k_compress_rem_batch<T, DCTZHIP_QT>), dim3(nrem), dim3(64), 0, s, items, rem_items);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_compress_rem_batch<T, M()>; }), dim3(nrem), dim3(64), 0, s, items, rem_items);
 }
 template <typename T>
 void launch_compact_batch(const BatchFwd<T>* items, const unsigned* first, unsigned k, unsigned grid, unsigned chunks, int mode, const double* bstats,
                           const BatchFin& fin, hipStream_t s) {
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_compact_batch<T, DCTZHIP_EC>), dim3(grid, chunks), dim3(SWG), 0, s, items, first, k, bstats, fin);
-  else hipLaunchKernelGGL((k_compact_batch<T, DCTZHIP_QT>), dim3(grid, chunks), dim3(SWG), 0, s, items, first, k, bstats, fin);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_compact_batch<T, M()>; }), dim3(grid, chunks), dim3(SWG), 0, s, items, first, k, bstats, fin);
 }
 template <typename T>
 void launch_count_batch(const BatchInv<T>* items_src, const unsigned* first_src, unsigned k, unsigned grid, const void* blob_src, void* blob_dst,
@@ -1854,13 +1804,11 @@ void launch_count_batch(const BatchInv<T>* items_src, const unsigned* first_src,
 }
 template <typename T>
 void launch_decompress_batch(const BatchInv<T>* items, const unsigned* first, unsigned k, unsigned grid, int mode, const BatchFin& fin, hipStream_t s) {
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_batch<T, DCTZHIP_EC>), dim3(grid), dim3(WG), 0, s, items, first, k, fin);
-  else hipLaunchKernelGGL((k_decompress_batch<T, DCTZHIP_QT>), dim3(grid), dim3(WG), 0, s, items, first, k, fin);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_decompress_batch<T, M()>; }), dim3(grid), dim3(WG), 0, s, items, first, k, fin);
 }
 template <typename T>
 void launch_decompress_rem_batch(const BatchInv<T>* items, const unsigned* rem_items, unsigned nrem, int mode, hipStream_t s) {
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_rem_batch<T, DCTZHIP_EC>), dim3(nrem), dim3(64), 0, s, items, rem_items);
-  else hipLaunchKernelGGL((k_decompress_rem_batch<T, DCTZHIP_QT>), dim3(nrem), dim3(64), 0, s, items, rem_items);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_decompress_rem_batch<T, M()>; }), dim3(nrem), dim3(64), 0, s, items, rem_items);
 }
 
 // explicit instantiations used by dctz_shim.hip
@@ -1875,126 +1823,92 @@ void launch_decompress_rem_batch(const BatchInv<T>* items, const unsigned* rem_i
 // this file down to the n-th kernel of the list below, the main build (DCTZ_PART = 0) declares them `extern template` and
 // keeps everything else, launchers included (the host side needs only the kernel's handle, a link-time symbol).
 #define DCTZ_PARTS 24
-#if DCTZ_PART == 1
-template __global__ void k_compress<double, DCTZHIP_EC, true, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_EC, true, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
+#if DCTZ_PART > DCTZ_PARTS
+#error "DCTZ_PART names a hot kernel that is not in the list (dctz_amd/Makefile: NPARTS must equal DCTZ_PARTS)"
 #endif
-#if DCTZ_PART == 2
-template __global__ void k_compress<double, DCTZHIP_EC, true, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_EC, true, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
+// one entry per hot kernel: instantiated in its own unit, declared `extern template` in the main one
+#if DCTZ_PART == 0
+#define HOT extern template __global__ void
+#else
+#define HOT template __global__ void
 #endif
-#if DCTZ_PART == 3
-template __global__ void k_compress<double, DCTZHIP_EC, false, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_EC, false, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
+#define HOT_COMPRESS(T, MODE, STATS, SC) HOT k_compress<T, MODE, STATS, Phases<T>::C, GEOM_1D, SC>(FwdParams<T>);
+#define HOT_BATCH(T, MODE, STATS) HOT k_compress_batch<T, MODE, STATS>(const BatchFwd<T>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 1
+HOT_COMPRESS(double, DCTZHIP_EC, true, false)
 #endif
-#if DCTZ_PART == 4
-template __global__ void k_compress<double, DCTZHIP_EC, false, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_EC, false, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
+#if DCTZ_PART == 0 || DCTZ_PART == 2
+HOT_COMPRESS(double, DCTZHIP_EC, true, true)
 #endif
-#if DCTZ_PART == 5
-template __global__ void k_compress<double, DCTZHIP_QT, true, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_QT, true, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
+#if DCTZ_PART == 0 || DCTZ_PART == 3
+HOT_COMPRESS(double, DCTZHIP_EC, false, false)
 #endif
-#if DCTZ_PART == 6
-template __global__ void k_compress<double, DCTZHIP_QT, true, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_QT, true, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
+#if DCTZ_PART == 0 || DCTZ_PART == 4
+HOT_COMPRESS(double, DCTZHIP_EC, false, true)
 #endif
-#if DCTZ_PART == 7
-template __global__ void k_compress<double, DCTZHIP_QT, false, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_QT, false, Phases<double>::C, GEOM_1D, false>(FwdParams<double>);
+#if DCTZ_PART == 0 || DCTZ_PART == 5
+HOT_COMPRESS(double, DCTZHIP_QT, true, false)
 #endif
-#if DCTZ_PART == 8
-template __global__ void k_compress<double, DCTZHIP_QT, false, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<double, DCTZHIP_QT, false, Phases<double>::C, GEOM_1D, true>(FwdParams<double>);
+#if DCTZ_PART == 0 || DCTZ_PART == 6
+HOT_COMPRESS(double, DCTZHIP_QT, true, true)
 #endif
-#if DCTZ_PART == 9
-template __global__ void k_compress<float, DCTZHIP_EC, true, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_EC, true, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 7
+HOT_COMPRESS(double, DCTZHIP_QT, false, false)
 #endif
-#if DCTZ_PART == 10
-template __global__ void k_compress<float, DCTZHIP_EC, true, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_EC, true, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 8
+HOT_COMPRESS(double, DCTZHIP_QT, false, true)
 #endif
-#if DCTZ_PART == 11
-template __global__ void k_compress<float, DCTZHIP_EC, false, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_EC, false, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 9
+HOT_COMPRESS(float, DCTZHIP_EC, true, false)
 #endif
-#if DCTZ_PART == 12
-template __global__ void k_compress<float, DCTZHIP_EC, false, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_EC, false, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 10
+HOT_COMPRESS(float, DCTZHIP_EC, true, true)
 #endif
-#if DCTZ_PART == 13
-template __global__ void k_compress<float, DCTZHIP_QT, true, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_QT, true, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 11
+HOT_COMPRESS(float, DCTZHIP_EC, false, false)
 #endif
-#if DCTZ_PART == 14
-template __global__ void k_compress<float, DCTZHIP_QT, true, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_QT, true, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 12
+HOT_COMPRESS(float, DCTZHIP_EC, false, true)
 #endif
-#if DCTZ_PART == 15
-template __global__ void k_compress<float, DCTZHIP_QT, false, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_QT, false, Phases<float>::C, GEOM_1D, false>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 13
+HOT_COMPRESS(float, DCTZHIP_QT, true, false)
 #endif
-#if DCTZ_PART == 16
-template __global__ void k_compress<float, DCTZHIP_QT, false, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress<float, DCTZHIP_QT, false, Phases<float>::C, GEOM_1D, true>(FwdParams<float>);
+#if DCTZ_PART == 0 || DCTZ_PART == 14
+HOT_COMPRESS(float, DCTZHIP_QT, true, true)
 #endif
-#if DCTZ_PART == 17
-template __global__ void k_compress_batch<double, DCTZHIP_EC, false>(const BatchFwd<double>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<double, DCTZHIP_EC, false>(const BatchFwd<double>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 15
+HOT_COMPRESS(float, DCTZHIP_QT, false, false)
 #endif
-#if DCTZ_PART == 18
-template __global__ void k_compress_batch<double, DCTZHIP_QT, false>(const BatchFwd<double>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<double, DCTZHIP_QT, false>(const BatchFwd<double>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 16
+HOT_COMPRESS(float, DCTZHIP_QT, false, true)
 #endif
-#if DCTZ_PART == 19
-template __global__ void k_compress_batch<float, DCTZHIP_EC, false>(const BatchFwd<float>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<float, DCTZHIP_EC, false>(const BatchFwd<float>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 17
+HOT_BATCH(double, DCTZHIP_EC, false)
 #endif
-#if DCTZ_PART == 20
-template __global__ void k_compress_batch<float, DCTZHIP_QT, false>(const BatchFwd<float>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<float, DCTZHIP_QT, false>(const BatchFwd<float>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 18
+HOT_BATCH(double, DCTZHIP_QT, false)
 #endif
-#if DCTZ_PART == 21
-template __global__ void k_compress_batch<double, DCTZHIP_EC, true>(const BatchFwd<double>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<double, DCTZHIP_EC, true>(const BatchFwd<double>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 19
+HOT_BATCH(float, DCTZHIP_EC, false)
 #endif
-#if DCTZ_PART == 22
-template __global__ void k_compress_batch<double, DCTZHIP_QT, true>(const BatchFwd<double>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<double, DCTZHIP_QT, true>(const BatchFwd<double>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 20
+HOT_BATCH(float, DCTZHIP_QT, false)
 #endif
-#if DCTZ_PART == 23
-template __global__ void k_compress_batch<float, DCTZHIP_EC, true>(const BatchFwd<float>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<float, DCTZHIP_EC, true>(const BatchFwd<float>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 21
+HOT_BATCH(double, DCTZHIP_EC, true)
 #endif
-#if DCTZ_PART == 24
-template __global__ void k_compress_batch<float, DCTZHIP_QT, true>(const BatchFwd<float>*, const unsigned*, unsigned);
-#elif DCTZ_PART == 0
-extern template __global__ void k_compress_batch<float, DCTZHIP_QT, true>(const BatchFwd<float>*, const unsigned*, unsigned);
+#if DCTZ_PART == 0 || DCTZ_PART == 22
+HOT_BATCH(double, DCTZHIP_QT, true)
 #endif
+#if DCTZ_PART == 0 || DCTZ_PART == 23
+HOT_BATCH(float, DCTZHIP_EC, true)
+#endif
+#if DCTZ_PART == 0 || DCTZ_PART == 24
+HOT_BATCH(float, DCTZHIP_QT, true)
+#endif
+#undef HOT_COMPRESS
+#undef HOT_BATCH
+#undef HOT
 #ifdef DCTZ_DEV_ONE
 template __global__ void DCTZ_DEV_ONE(DCTZ_DEV_ARGS);
 #elif DCTZ_PART > 0

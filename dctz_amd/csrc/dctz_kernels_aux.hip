@@ -553,14 +553,12 @@ void launch_dct_blocks(const T* x, T* out, const T* gtab, const T* rtab, size_t 
   const int l = (int)(n % 64);
   if (nfull) {
     const int g = (int)min((unsigned)grid, (nfull + WG - 1) / WG);
-    if (inverse) hipLaunchKernelGGL((k_dct_blocks<T, true>), dim3(g), dim3(WG), 0, s, x, out, gtab, nfull);
-    else hipLaunchKernelGGL((k_dct_blocks<T, false>), dim3(g), dim3(WG), 0, s, x, out, gtab, nfull);
+    hipLaunchKernelGGL(with_bool(inverse, [](auto INV) { return k_dct_blocks<T, INV()>; }), dim3(g), dim3(WG), 0, s, x, out, gtab, nfull);
   }
   if (l) {
     const T* xr = x + (size_t)nfull * 64;
     T* orr = out + (size_t)nfull * 64;
-    if (inverse) hipLaunchKernelGGL((k_dct_rem<T, true>), dim3(1), dim3(64), 0, s, xr, orr, rtab, l);
-    else hipLaunchKernelGGL((k_dct_rem<T, false>), dim3(1), dim3(64), 0, s, xr, orr, rtab, l);
+    hipLaunchKernelGGL(with_bool(inverse, [](auto INV) { return k_dct_rem<T, INV()>; }), dim3(1), dim3(64), 0, s, xr, orr, rtab, l);
   }
 }
 

@@ -621,30 +621,22 @@ __global__ __launch_bounds__(EO_WG) __attribute__((amdgpu_waves_per_eu(DCTZ_EO_W
   else compress_eo_role<MODE, STATS, EO_ODD, DIRECT>(p, blockIdx.x, gridDim.x, L);
 }
 
+// the instantiation for (mode, stats, direct), for the launch and for the occupancy query; DIRECT exists in EC mode only
+static auto compress_eo_kernel(int mode, bool stats, bool direct) -> void (*)(FwdParams<double>) {
+  return with_bool(stats, [=](auto S) -> void (*)(FwdParams<double>) {
+    if (mode == DCTZHIP_EC) return direct ? k_compress_eo<DCTZHIP_EC, S(), true> : k_compress_eo<DCTZHIP_EC, S(), false>;
+    return k_compress_eo<DCTZHIP_QT, S(), false>;
+  });
+}
 void launch_compress_eo(const FwdParams<double>& p, int mode, bool stats, int grid, hipStream_t s) {
-  if (mode == DCTZHIP_EC && p.direct) {
-    if (stats) hipLaunchKernelGGL((k_compress_eo<DCTZHIP_EC, true, true>), dim3(grid), dim3(EO_WG), 0, s, p);
-    else hipLaunchKernelGGL((k_compress_eo<DCTZHIP_EC, false, true>), dim3(grid), dim3(EO_WG), 0, s, p);
-  } else if (mode == DCTZHIP_EC) {
-    if (stats) hipLaunchKernelGGL((k_compress_eo<DCTZHIP_EC, true, false>), dim3(grid), dim3(EO_WG), 0, s, p);
-    else hipLaunchKernelGGL((k_compress_eo<DCTZHIP_EC, false, false>), dim3(grid), dim3(EO_WG), 0, s, p);
-  } else {
-    if (stats) hipLaunchKernelGGL((k_compress_eo<DCTZHIP_QT, true, false>), dim3(grid), dim3(EO_WG), 0, s, p);
-    else hipLaunchKernelGGL((k_compress_eo<DCTZHIP_QT, false, false>), dim3(grid), dim3(EO_WG), 0, s, p);
-  }
+  hipLaunchKernelGGL(compress_eo_kernel(mode, stats, p.direct != 0), dim3(grid), dim3(EO_WG), 0, s, p);
 }
 
 // resident workgroups (of two waves) per CU: registers and LDS
 int compress_eo_occupancy(int mode, bool stats, bool direct) {
   int n = 0;
-  hipError_t e;
-  if (mode == DCTZHIP_EC && direct) e = stats ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_eo<DCTZHIP_EC, true, true>, EO_WG, 0)
-                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_eo<DCTZHIP_EC, false, true>, EO_WG, 0);
-  else if (mode == DCTZHIP_EC) e = stats ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_eo<DCTZHIP_EC, true, false>, EO_WG, 0)
-                                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_eo<DCTZHIP_EC, false, false>, EO_WG, 0);
-  else e = stats ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_eo<DCTZHIP_QT, true, false>, EO_WG, 0)
-                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_eo<DCTZHIP_QT, false, false>, EO_WG, 0);
-  if (e != hipSuccess || n <= 0) n = (int)((size_t)160 * 1024 / (mode == DCTZHIP_EC ? eo_lds_bytes<DCTZHIP_EC>() : eo_lds_bytes<DCTZHIP_QT>()));
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)compress_eo_kernel(mode, stats, direct), EO_WG, 0);
+  if (e != hipSuccess || n <= 0) n = (int)((size_t)160 * 1024 / with_mode(mode, [](auto M) { return eo_lds_bytes<M()>(); }));
   return n;
 }
 

@@ -1037,53 +1037,39 @@ __global__ __launch_bounds__(OTW * 64) __attribute__((amdgpu_waves_per_eu(one_wa
 // ================================================================= launchers ==
 template <typename T>
 void launch_compress_one_batch(const OneBatchC<T>& cm, unsigned grid, int mode, bool scaled, hipStream_t s) {
-  const dim3 g(grid), blk(OTW * 64);
-  if (mode == DCTZHIP_EC) {
-    if (scaled) hipLaunchKernelGGL((k_compress_one_batch<T, DCTZHIP_EC, true>), g, blk, 0, s, cm);
-    else hipLaunchKernelGGL((k_compress_one_batch<T, DCTZHIP_EC, false>), g, blk, 0, s, cm);
-  } else {
-    if (scaled) hipLaunchKernelGGL((k_compress_one_batch<T, DCTZHIP_QT, true>), g, blk, 0, s, cm);
-    else hipLaunchKernelGGL((k_compress_one_batch<T, DCTZHIP_QT, false>), g, blk, 0, s, cm);
-  }
+  hipLaunchKernelGGL(with_mode_bool(mode, scaled, [](auto M, auto SC) { return k_compress_one_batch<T, M(), SC()>; }), dim3(grid), dim3(OTW * 64), 0, s, cm);
 }
 template <typename T>
 void launch_decompress_one_batch(const OneBatchD<T>& cm, unsigned grid, int mode, hipStream_t s) {
-  const dim3 g(grid), blk(OTW * 64);
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_one_batch<T, DCTZHIP_EC>), g, blk, 0, s, cm);
-  else hipLaunchKernelGGL((k_decompress_one_batch<T, DCTZHIP_QT>), g, blk, 0, s, cm);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_decompress_one_batch<T, M()>; }), dim3(grid), dim3(OTW * 64), 0, s, cm);
+}
+// the single-array kernels: one selector each, for the launch and for the occupancy query
+template <typename T>
+auto compress_one_kernel(int mode, bool scaled) -> void (*)(OneFwd<T>) {
+  return with_mode_bool(mode, scaled, [](auto M, auto SC) { return k_compress_one<T, M(), SC()>; });
+}
+template <typename T>
+auto decompress_one_kernel(int mode) -> void (*)(OneInv<T>) {
+  return with_mode(mode, [](auto M) { return k_decompress_one<T, M()>; });
 }
 template <typename T>
 void launch_compress_one(const OneFwd<T>& a, int mode, bool scaled, hipStream_t s) {
-  const dim3 grid(a.b.nwg), blk(OTW * 64);
-  if (mode == DCTZHIP_EC) {
-    if (scaled) hipLaunchKernelGGL((k_compress_one<T, DCTZHIP_EC, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_compress_one<T, DCTZHIP_EC, false>), grid, blk, 0, s, a);
-  } else {
-    if (scaled) hipLaunchKernelGGL((k_compress_one<T, DCTZHIP_QT, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((k_compress_one<T, DCTZHIP_QT, false>), grid, blk, 0, s, a);
-  }
+  hipLaunchKernelGGL(compress_one_kernel<T>(mode, scaled), dim3(a.b.nwg), dim3(OTW * 64), 0, s, a);
 }
 template <typename T>
 void launch_decompress_one(const OneInv<T>& a, int mode, hipStream_t s) {
-  const dim3 grid(a.b.nwg), blk(OTW * 64);
-  if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_one<T, DCTZHIP_EC>), grid, blk, 0, s, a);
-  else hipLaunchKernelGGL((k_decompress_one<T, DCTZHIP_QT>), grid, blk, 0, s, a);
+  hipLaunchKernelGGL(decompress_one_kernel<T>(mode), dim3(a.b.nwg), dim3(OTW * 64), 0, s, a);
 }
 template <typename T>
 int compress_one_occupancy(int mode, bool scaled) {
   int n = 0;
-  hipError_t e;
-  if (mode == DCTZHIP_EC) e = scaled ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_one<T, DCTZHIP_EC, true>, OTW * 64, 0)
-                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_one<T, DCTZHIP_EC, false>, OTW * 64, 0);
-  else e = scaled ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_one<T, DCTZHIP_QT, true>, OTW * 64, 0)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_compress_one<T, DCTZHIP_QT, false>, OTW * 64, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)compress_one_kernel<T>(mode, scaled), OTW * 64, 0);
   return e == hipSuccess ? n : 0;
 }
 template <typename T>
 int decompress_one_occupancy(int mode) {
   int n = 0;
-  const hipError_t e = mode == DCTZHIP_EC ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress_one<T, DCTZHIP_EC>, OTW * 64, 0)
-                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress_one<T, DCTZHIP_QT>, OTW * 64, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)decompress_one_kernel<T>(mode), OTW * 64, 0);
   return e == hipSuccess ? n : 0;
 }
 

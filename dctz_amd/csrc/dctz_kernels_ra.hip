@@ -332,24 +332,20 @@ __global__ __launch_bounds__(64) void k_decompress_range_rem(RangeParams<T> p) {
 }
 
 template <typename T>
+auto range_kernel(int mode) -> void (*)(RangeParams<T>) {
+  return with_mode(mode, [](auto M) { return k_decompress_range<T, M()>; });
+}
+template <typename T>
 int range_occupancy(int mode) {
   int n = 0;
-  const hipError_t e = mode == DCTZHIP_EC
-      ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress_range<T, DCTZHIP_EC>, 64, 0)
-      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k_decompress_range<T, DCTZHIP_QT>, 64, 0);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)range_kernel<T>(mode), 64, 0);
   return e == hipSuccess ? n : 0;
 }
 
 template <typename T>
 void launch_decompress_range(const RangeParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s) {
-  if (grid > 0) {
-    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_range<T, DCTZHIP_EC>), dim3(grid), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL((k_decompress_range<T, DCTZHIP_QT>), dim3(grid), dim3(64), 0, s, p);
-  }
-  if (with_rem) {
-    if (mode == DCTZHIP_EC) hipLaunchKernelGGL((k_decompress_range_rem<T, DCTZHIP_EC>), dim3(1), dim3(64), 0, s, p);
-    else hipLaunchKernelGGL((k_decompress_range_rem<T, DCTZHIP_QT>), dim3(1), dim3(64), 0, s, p);
-  }
+  if (grid > 0) hipLaunchKernelGGL(range_kernel<T>(mode), dim3(grid), dim3(64), 0, s, p);
+  if (with_rem) hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_decompress_range_rem<T, M()>; }), dim3(1), dim3(64), 0, s, p);
 }
 template int range_occupancy<double>(int);
 template int range_occupancy<float>(int);

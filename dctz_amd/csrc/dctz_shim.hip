@@ -1070,13 +1070,16 @@ static int read_timings(dctzhip_ctx* c, int nev_main_start) {
 struct HostStats { double max_abs, min_abs, sum; };
 
 // resident single-wave workgroups per CU of the two big kernels: what the runtime's occupancy calculator says for the
-// very instantiation (registers and LDS; k_compress: 8 for fp64, 12 for fp32 EC; k_decompress: 4 / 7), cached
+// instantiation (registers and LDS; k_compress: 8 for fp64, 12 for fp32 EC; k_decompress: 4 / 7), cached.
+// A launch that takes the scaled variant of k_compress (takes_scaled) is sized by its UNSCALED twin's occupancy: the
+// query passes scaled = false and the cache has no slot for it, although the scaled variants need a few registers more.
+// Asking for the variant that runs would change grid sizes: a change of its own, to be measured before it is made.
 template <typename T>
 static int wg_per_cu(dctzhip_ctx* c, bool decode, int mode, bool stats = false, int geom = GEOM_1D) {
   if (c->wg_per_cu) return c->wg_per_cu;
   int& slot = c->occ[sizeof(T) == 8][decode ? 1 : 0][mode == DCTZHIP_QT][stats ? 1 : 0][geom];
   if (slot == 0) {
-    int v = decode ? decompress_occupancy<T>(mode, geom) : compress_occupancy<T>(mode, stats, geom);
+    int v = decode ? decompress_occupancy<T>(mode, geom) : compress_occupancy<T>(mode, stats, geom, false);
     if (v <= 0) {                                   // (no answer: the LDS bound alone)
       const size_t lds = decode ? decompress_lds_bytes<T>() : compress_lds_bytes<T>(mode);
       v = (int)((size_t)160 * 1024 / lds);
@@ -1363,7 +1366,7 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   }
   if (ntiles && !eo) {
     launch_compress<T>(p, mode, fused, grid, geom, s);
-    SET_LAST(c, 0, "k_compress<%s, %d, %s, %d, %d, %s>", tname<T>(), mode, bname(fused), Phases<T>::C, geom, bname(geom == GEOM_1D && p.scaled != nullptr));
+    SET_LAST(c, 0, "k_compress<%s, %d, %s, %d, %d, %s>", tname<T>(), mode, bname(fused), Phases<T>::C, geom, bname(takes_scaled(p, geom)));
   }
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], s));
   if (rem) launch_compress_rem<T>(p, mode, rem, s);
@@ -1833,7 +1836,7 @@ static int decompress_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_
   const FinArgs fin = {c->ctl, nullptr, 0, early ? c->box_dev : nullptr, seq, nullptr};
   if (ntiles) {
     launch_decompress<T>(p, mode, grid, fin, geom, s);
-    if (geom == GEOM_1D && p.tile_pre != nullptr) SET_LAST(c, 1, "k_decompress_il<%s, %d, %d>", tname<T>(), mode, Phases<T>::D);
+    if (takes_interleaved(p, geom)) SET_LAST(c, 1, "k_decompress_il<%s, %d, %d>", tname<T>(), mode, Phases<T>::D);
     else SET_LAST(c, 1, "k_decompress<%s, %d, %d, %d>", tname<T>(), mode, Phases<T>::D, geom);
   }
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], s));
