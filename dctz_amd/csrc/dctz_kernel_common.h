@@ -1,6 +1,7 @@
 // dctz_kernel_common.h -- device helpers shared by the two kernel files: streaming accesses, the wave scan, the exact
 // division by a launch constant (FastDiv), the tile range of a workgroup, the tile image in LDS (TileMap, LDS-DMA issue,
-// LDS <-> registers), the statistics accumulator, the QT (de-)normalisation, the mailbox publish, small reductions.
+// LDS <-> registers), the statistics accumulator, the QT (de-)normalisation, the mailbox publish, small reductions,
+// binning / bin centres, the "stored exactly" flags, the de-quantise step of every decoder, the short last block.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -483,6 +484,207 @@ __device__ __forceinline__ T bin_centre(const unsigned w1, const unsigned nw, co
   const float t = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, mag) | sgn);
   if constexpr (sizeof(T) == 8) return __builtin_fma((double)t, bin_width, 0.0);
   else return __builtin_fmaf(t, bin_width, 0.0f);
+}
+// gen_bins' own expression, for the table and for the short block
+template <typename T>
+__device__ __forceinline__ T bin_centre_ref(const unsigned b, const T bin_width) {
+  const int ti = (b & 1u) ? (int)(b >> 1) + 1 : -(int)(b >> 1);
+  return (T)ti * bin_width;
+}
+// Where a decoder takes the centre of byte i of a dword of bin ids from: computed (bin_centre), or looked up in a table
+// in LDS that the workgroup fills first (fp32 of the whole-array decoders: computing measured 6 % slower there).
+// (BinDword: what bin_centre needs of a dword, made once per dword -- made per position, the compiler does not merge the
+// four and k_decompress_il<double, EC> grows by 140 instructions)
+struct BinDword { unsigned w, w1, nw; };                               // four bin ids, their magnitudes (b + 1) >> 1, their complement
+__device__ __forceinline__ BinDword bin_dword(const unsigned w) { return {w, ((w >> 1) & 0x7F7F7F7Fu) + (w & 0x01010101u), ~w}; }
+template <typename T, bool ARITH> struct BinCentres {
+  T bin_width;
+  const T* tab;                                                        // !ARITH: 256 entries, fill_bin_centres
+  __device__ __forceinline__ T at(const BinDword& d, const int i) const {                        // :416 / :462
+    if constexpr (ARITH) return bin_centre<T>(d.w1, d.nw, i, bin_width);
+    else return tab[(d.w >> (8 * i)) & 255u];
+  }
+};
+template <typename T>
+__device__ __forceinline__ void fill_bin_centres(T* tab, const T bin_width, const int tid, const int nthreads) {
+  for (int b = tid; b < 256; b += nthreads) tab[b] = bin_centre_ref<T>((unsigned)b, bin_width);
+}
+
+// --------------------------------------------- "stored exactly" flags, de-quantise --
+// Bit 7 of byte i set <=> byte i of w, a dword of four bin ids, is 255: the coefficient is stored exactly (:400 / :446)
+__device__ __forceinline__ unsigned exact_flags(const unsigned w) {
+  const unsigned v = ~w;                                               // a zero byte of v <=> bin id 255
+  const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;            // bit 7 of a byte set <=> that byte of v is non-zero
+  return ~z & 0x80808080u;
+}
+// (dword g of a block's sixteen: j = 0 is the DC slot, never an exact coefficient, :392 / :438)
+__device__ __forceinline__ unsigned block_flags(const unsigned (&w)[16], const int g) {
+  return g == 0 ? exact_flags(w[0]) & ~0x80u : exact_flags(w[g]);
+}
+__device__ __forceinline__ unsigned block_flag_count(const unsigned (&w)[16]) {
+  unsigned n = 0;
+#pragma unroll
+  for (int g = 0; g < 16; g++) n += (unsigned)__popc(block_flags(w, g));
+  return n;
+}
+
+// De-quantise one block (dctz-decomp-lib.c:389-417 / :438-463): the sixteen dwords of bin ids `w`, the block's DC and the
+// tile's piece of AC_exact staged in LDS (`stage`, this lane's first coefficient at `ptr`, reads clamped to `stage_last`)
+// -> x[64].  `qtab(j)` is the QT table's entry j (QT only; EC callers pass anything).  The callers keep loading,
+// staging, waits, prefetch and stores.  Two forms, because two measured:
+//
+// GROUPED (fp64, one wave per SIMD, every LDS round trip exposed).  Four coefficients = one dword of bin ids at a time:
+// the (up to four) exact coefficients of the group are fetched together -- their places follow from the flag bits alone
+// -- so that a tile pays one LDS round trip per GROUP that has a flag somewhere in the wave (16 at most), not one per
+// flagged POSITION (63 on noisy data: at p = 17 % the serialised round trips were a third of the kernel; 512^3 fp64:
+// 0.33 -> 0.28 ms there, 0.245 -> 0.235 at p = 5 %).
+// QT_TRAILING: dctz-decomp-lib.c:404-409 in a pass of its own over the flagged positions.  Inside the loop every division
+// sits right behind the LDS read of its coefficient, one exposed round trip per flagged group (with one wave per SIMD the
+// QT decoder spent 76 % more cycles waiting than its EC twin for FEWER vector instructions, profiles/r04_pmc_qt.txt);
+// behind it the coefficients are in registers already and the reads of all sixteen groups overlap as they do in EC mode.
+template <typename T, int MODE, bool QT_TRAILING, typename Centre, typename QTab>
+__device__ __forceinline__ void dequantise_grouped(T (&x)[64], const unsigned (&w)[16], const float dc, unsigned& ptr, const float* stage,
+                                                   const unsigned stage_last, const Centre centre, QTab&& qtab, const double eb,
+                                                   const T range_min, const T range_max) {
+#pragma unroll
+  for (int g = 0; g < 16; g++) {
+    const unsigned m = block_flags(w, g);
+    const BinDword d = bin_dword(w[g]);
+    float e[4] = {0.f, 0.f, 0.f, 0.f};
+    if (__builtin_amdgcn_ballot_w64(m != 0u)) {                        // :400 / :446 somewhere in the wave
+      unsigned at[4];
+      at[0] = ptr;
+      at[1] = at[0] + ((m >> 7) & 1u);
+      at[2] = at[1] + ((m >> 15) & 1u);
+      at[3] = at[2] + ((m >> 23) & 1u);
+      ptr = at[3] + (m >> 31);
+#pragma unroll
+      for (int i = 0; i < 4; i++) e[i] = stage[min(at[i], stage_last)];        // (all lanes read: predicating the reads on the flag measured slower)
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int j = 4 * g + i;
+      if (j == 0) { x[0] = (T)dc; continue; }                          // :392 / :438
+      T v = centre.at(d, i);
+      if ((m >> (8 * i + 7)) & 1u) {
+        v = (T)e[i];
+        if (MODE == DCTZHIP_QT && !QT_TRAILING) v = qt_restore(v, qtab(j), eb, T(10), range_min, range_max);
+      }
+      x[j] = v;
+    }
+  }
+  if constexpr (MODE == DCTZHIP_QT && QT_TRAILING) {
+#pragma unroll
+    for (int g = 0; g < 16; g++) {
+      const unsigned m = block_flags(w, g);
+      if (__builtin_amdgcn_ballot_w64(m != 0u)) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int j = 4 * g + i;
+          if (j != 0 && ((m >> (8 * i + 7)) & 1u)) x[j] = qt_restore(x[j], qtab(j), eb, T(10), range_min, range_max);
+        }
+      }
+    }
+  }
+}
+// POSITIONAL (fp32: several waves per SIMD hide the round trips, the grouped form measured 10 % slower; the range decoder).
+// Written as sixteen dwords of four: as ONE loop of 63 trips the compiler leaves it partly rolled in k_decompress_one<float>,
+// and the bin ids and the block then live in scratch memory -- 144 bytes per lane, stored and read back per tile: 15 MB of
+// the 41 MB that kernel wrote for a 26 MB array (profiles/r05_c2_raw_traffic.txt).
+// PIN: each value through a register of its own (same kernel, same file: paired into <2 x float> stores by the vectoriser,
+// the first 33 elements of the block stayed an array in scratch memory).
+template <typename T, int MODE, bool PIN, typename Centre, typename QTab>
+__device__ __forceinline__ void dequantise_positional(T (&x)[64], const unsigned (&w)[16], const float dc, unsigned& ptr, const float* stage,
+                                                      const unsigned stage_last, const Centre centre, QTab&& qtab, const double eb,
+                                                      const T range_min, const T range_max) {
+#pragma unroll
+  for (int g = 0; g < 16; g++) {
+    const BinDword d = bin_dword(w[g]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int j = 4 * g + i;
+      if (j == 0) { x[0] = (T)dc; continue; }                          // :392 / :438
+      T v = centre.at(d, i);
+      if (((w[g] >> (8 * i)) & 255u) == 255u) {                        // :400 / :446
+        const float e = stage[min(ptr, stage_last)];
+        ptr++;
+        v = (T)e;
+        if (MODE == DCTZHIP_QT) v = qt_restore(v, qtab(j), eb, T(10), range_min, range_max);
+      }
+      if (PIN) asm volatile("" : "+v"(v));
+      x[j] = v;
+    }
+  }
+}
+
+// ------------------------------------------------------- the short last block --
+// Length l = N % 64: the reference re-plans a length-l (l even) or 2l (l odd) FFT for it (dctz-comp-lib.c:326-340,
+// dct.c:59-72); here a definition-order DFT with host-built roots `rt`, lane k = element / coefficient k, one wave.  The
+// phases exchange through LDS: the caller puts its own barrier between them (a workgroup of one wave: __syncthreads;
+// one wave of several: its LDS operations are in order, s_waitcnt lgkmcnt(0)) and guards each with k < l.
+// Forward: element a -> its mirrored place(s) in v[N]; then coefficient k.
+template <typename T>
+__device__ __forceinline__ void short_fwd_fill(T* v, const int l, const int k, const T a) {
+  if (l & 1) { v[k] = a; v[l + (l - 1 - k)] = a; }                     // dct.c:61-64
+  else if (k & 1) v[l - 1 - (k >> 1)] = a;                             // dct.c:75-83
+  else v[k >> 1] = a;
+}
+// (N = short_dft_len(l) comes from the caller, computed in front of its k < l branches as it always was: with N derived in
+// here k_compress_one<double, EC> spilled 11 VGPRs for 8)
+__device__ __forceinline__ int short_dft_len(const int l) { return (l & 1) ? 2 * l : l; }
+template <typename T>
+__device__ __forceinline__ T short_fwd_sum(const T* v, const T* rt, const int N, const int k) {
+  T sr = T(0), si = T(0);
+  for (int j = 0; j < N; j++) {
+    const int tt = (j * k) % N;
+    sr = sr + v[j] * rt[RTAB_WR + tt];
+    si = si + v[j] * rt[RTAB_WI + tt];
+  }
+  return rt[RTAB_AS + k] * sr + rt[RTAB_AX + k] * si;                  // dct.c:100-102 (Im V = -si)
+}
+// pass-1 binning of its coefficients, the reference's own form (:363-414)
+template <typename T>
+__device__ __forceinline__ unsigned bin_short(const T coef, const T range_min, const T range_max, const FastDiv<T>& bwd) {
+  const bool out = fabs(coef) > range_max;                             // == (item < range_min || item > range_max)
+  const T u = coef - range_min;
+  const T q = bwd.ok ? bwd.core(u) : u / bwd.d;
+  const int t = (int)q;                                                // (t_bin_id) cast: truncation
+  unsigned b = out ? 255u : (unsigned)(t <= 127 ? 254 - 2 * t : 2 * t - 255);   // conv_tbl :27-43 (t == 255 -> 255)
+  if (coef != coef) b = 0u;                                            // a NaN coefficient: bin id 0, like bin_value()
+  return b;
+}
+// Inverse (dctz-decomp-lib.c:423-428, dct.c:144-199): coefficient k from its bin id b, the DC, or -- `exc` -- the exact
+// value the caller fetched; then a[] -> cr[] / ci[] (128 entries each, cleared first: a barrier between the two as well);
+// then element k.
+template <typename T, int MODE, typename QTab>
+__device__ __forceinline__ T short_inv_value(const unsigned b, const bool exc, const int k, const float dc, T exact, const T bin_width,
+                                             QTab&& qtab, const double eb, const T range_min, const T range_max) {
+  if (k == 0) return (T)dc;
+  if (!exc) return bin_centre_ref<T>(b, bin_width);
+  if (MODE == DCTZHIP_QT) exact = qt_restore(exact, qtab(k), eb, T(10), range_min, range_max);
+  return exact;
+}
+template <typename T>
+__device__ __forceinline__ void short_inv_clear(T* cr, T* ci, const int k) { cr[k] = T(0); ci[k] = T(0); cr[k + 64] = T(0); ci[k + 64] = T(0); }
+template <typename T>
+__device__ __forceinline__ void short_inv_spread(T* cr, T* ci, const T* a, const T* rt, const int l, const int k) {
+  cr[k] = rt[RTAB_IAS + k] * a[k];                                     // dct.c:146-151 / :166-172
+  ci[k] = rt[RTAB_IAX + k] * a[k];
+  if ((l & 1) && k >= 1) {                                             // dct.c:152-153
+    cr[l + k] = rt[RTAB_IAX + k] * a[l - k];
+    ci[l + k] = -(rt[RTAB_IAS + k] * a[l - k]);
+  }
+}
+template <typename T>
+__device__ __forceinline__ T short_inv_sum(const T* cr, const T* ci, const T* rt, const int l, const int k) {
+  const int N = short_dft_len(l);
+  const int s = (l & 1) ? k : ((k & 1) ? l - 1 - (k >> 1) : (k >> 1)); // dct.c:189-199
+  T acc = T(0);
+  for (int j = 0; j < N; j++) {
+    const int tt = (s * j) % N;
+    acc = acc + (cr[j] * rt[RTAB_WR + tt] - ci[j] * rt[RTAB_WI + tt]);
+  }
+  return (l & 1) ? (acc / (T)l) / T(2) : acc / (T)l;                   // dct.c:163 / :185
 }
 
 

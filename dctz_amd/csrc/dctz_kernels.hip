@@ -434,8 +434,7 @@ __device__ __forceinline__ void compress_body(const FwdParams<T>& p, const unsig
         w[g] = wgd;                                  // last group and keeps 64 fp64 bin values alive (128 registers) until then
         // "stored exactly" = id 255: bit 7 of byte i of mm.  A group is only looked at further when SOME lane of the wave
         // has such a coefficient in it (the high-frequency groups of a smooth field never do)
-        const unsigned nw = ~wgd;
-        const unsigned mm = ~(((nw & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nw) & 0x80808080u;
+        const unsigned mm = exact_flags(wgd);
         if (__builtin_amdgcn_ballot_w64(mm != 0u))
           m |= (((mm >> 7) | (mm >> 14) | (mm >> 21) | (mm >> 28)) & 0xFu) << (4 * gg);
         __builtin_amdgcn_sched_barrier(0);           // keep the groups apart: hoisting all 64 quotients first costs 128 registers
@@ -557,8 +556,6 @@ __device__ __forceinline__ void compress_rem_body(const FwdParams<T>& p, const i
   __shared__ T v[128];
   const int k = threadIdx.x;
   const size_t base = (size_t)p.nfull * 64;
-  const T* rt = p.rtab;
-  const int N = (l & 1) ? 2 * l : l;
   const T sf = p.guess ? (T)p.guess->sf : p.sf;
   const bool SCALE = (sf != T(1));                                 // dctz-comp-lib.c:193 / :208
   FastDiv<T> sfd, bwd;
@@ -575,28 +572,12 @@ __device__ __forceinline__ void compress_rem_body(const FwdParams<T>& p, const i
     T a = p.x[base + k];
     if (SCALE) a = sfd.div(a);
     if (p.scaled != nullptr) p.scaled[base + k] = a;               // (dctz-comp-lib.c:193-216, when k_compress writes the scaled copy)
-    if (l & 1) { v[k] = a; v[l + (l - 1 - k)] = a; }               // dct.c:61-64
-    else if (k & 1) v[l - 1 - (k >> 1)] = a;                       // dct.c:75-83
-    else v[k >> 1] = a;
+    short_fwd_fill(v, l, k, a);
   }
   __syncthreads();
   T coef = T(0);
-  if (k < l) {
-    T sr = T(0), si = T(0);
-    for (int j = 0; j < N; j++) {
-      const int tt = (j * k) % N;
-      sr = sr + v[j] * rt[RTAB_WR + tt];
-      si = si + v[j] * rt[RTAB_WI + tt];
-    }
-    coef = rt[RTAB_AS + k] * sr + rt[RTAB_AX + k] * si;            // dct.c:100-102 (Im V = -si)
-  }
-  // pass-1 binning, the reference's own form (:363-414)
-  const bool out = fabs(coef) > p.range_max;                       // == (item < range_min || item > range_max)
-  const T u = coef - p.range_min;
-  const T q = bwd.ok ? bwd.core(u) : u / bwd.d;
-  const int t = (int)q;                                            // (t_bin_id) cast: truncation
-  unsigned b = out ? 255u : (unsigned)(t <= 127 ? 254 - 2 * t : 2 * t - 255);   // conv_tbl :27-43 (t == 255 -> 255)
-  if (coef != coef) b = 0u;                                        // a NaN coefficient: bin id 0, like bin_value()
+  if (k < l) coef = short_fwd_sum(v, p.rtab, short_dft_len(l), k);
+  unsigned b = bin_short(coef, p.range_min, p.range_max, bwd);
   bool exc = false;
   if (k == 0) b = 255u; else exc = (b == 255u);
   if (k >= l) exc = false;
@@ -887,9 +868,7 @@ __device__ __forceinline__ void count_tiles_body(const uint8_t* __restrict__ bin
         const unsigned w[4] = {wv[h][i].x, wv[h][i].y, wv[h][i].z, wv[h][i].w};
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-          const unsigned v = ~w[k];                                      // a zero byte of v <=> bin id 255
-          const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;      // bit 7 of a byte set <=> that byte of v is non-zero
-          unsigned m = ~z & 0x80808080u;
+          unsigned m = exact_flags(w[k]);
           if (k == 0 && (lane & 3) == 0) m &= ~0x80u;                    // byte 0 of every 64: j = 0, the DC slot (:392 / :438)
           c += (unsigned)__popc(m);
         }
@@ -950,7 +929,49 @@ size_t decompress_lds_bytes() { return (size_t)Geo<T, Phases<T>::D>::PHB + 256 *
 #ifndef DCTZ_DEC_STORE_AUX
 #define DCTZ_DEC_STORE_AUX 2     /* cache policy of k_decompress's row stores: 2 = nt */
 #endif
-// (bin_centre: dctz_kernel_common.h)
+// The image's rows of phase PHASE -> HBM, one 1 KiB row (8 whole 128-byte lines) per instruction; blocks beyond the end
+// fall outside r_out.  `vbase`: byte offset of the tile behind r_out (flat blocks); `tile`: its number (blocks written in
+// place in a multi-dimensional array).  (Sending the second half of a tile's rows one stage later, behind the next tile's
+// de-quantisation, so that the 32 stores -- 7 K cycles at the issue port -- come in two bursts, measured slower: 0.287
+// against 0.260 ms at p = 17 %, no gain at 5 %.)
+template <typename T, int PH, int GEOM, int PHASE>
+__device__ __forceinline__ void store_rows(const unsigned char* outbuf, const TileMap<T, PH>& tm, const __amdgpu_buffer_rsrc_t r_out,
+                                           const int vbase, const bool nd_direct, const NdDirect& nd, const unsigned tile, const int lane) {
+  using G = Geo<T, PH>;
+#pragma unroll
+  for (int jg = 0; jg < 8; jg++) {
+    unsigned org = 0;
+    int cg = 0;
+    if (GEOM != GEOM_1D && nd_direct) {              // this lane's piece of row (jg, s): a chunk of block 8 jg + beta of the tile
+      const int beta = lane >> 3, gam = lane & 7;
+      org = nd_block_origin<T>(nd, tile * (unsigned)TILE_BLKS + (unsigned)(8 * jg + beta));
+      cg = swz_row_chunk(beta, gam, jg);
+    }
+    const int vo = vbase + jg * 8 * G::BLKB + tm.g_of(jg);
+#pragma unroll
+    for (int s = 0; s < G::SEGP; s++) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(outbuf + (jg * G::SEGP + s) * 1024 + lane * 16);
+      int at = vo + (PHASE * G::SEGP + s) * 128;
+      if (GEOM != GEOM_1D && nd_direct) at = (int)(org >= 0xFFFFFFF0u ? org : org + nd_chunk_offset<T>(nd, 8 * (PHASE * G::SEGP + s) + cg));
+      __builtin_amdgcn_raw_buffer_store_b128(v, r_out, at, 0, DCTZ_DEC_STORE_AUX);
+    }
+  }
+}
+// The one thing the host waits for on decode: does the stream promise more exact coefficients than the caller provides
+// (all counts are in: k_count_tiles)?  Known before the first block is rebuilt -> workgroup 0 hands it over at once.
+template <typename T>
+__device__ __forceinline__ void decompress_handoff(const InvParams<T>& p, const FinArgs& fin) {
+  if (fin.box == nullptr || blockIdx.x != 0) return;
+  unsigned all = 0;
+  for (unsigned i = threadIdx.x; i < p.nwg; i += WG) all += p.wg_cnt[i];
+  all = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(all), 63);
+  FinBody f;
+  f.ctl = fin.ctl; f.part = nullptr; f.nparts = 0; f.box = fin.box; f.seq = fin.seq; f.guess = nullptr;
+  f.cnt_known = true; f.cnt_total = all;
+  f.err_known = true; f.error = all > p.ac_count ? 2u : 0u;
+  finish_body<false>(f);
+}
+// (bin_centre, the de-quantise step: dctz_kernel_common.h)
 template <typename T, int MODE, int PH, int GEOM, typename Handoff>
 __device__ __forceinline__ void decompress_body(const InvParams<T>& p, const unsigned wg, const unsigned nwg, Handoff&& handoff) {
   using G = Geo<T, PH>;
@@ -989,11 +1010,8 @@ __device__ __forceinline__ void decompress_body(const InvParams<T>& p, const uns
   tm.init(lane);
   const CTab<T> tab = as_ctab<T>(p.tab);
   // gen_bins / gen_bins_f (binning.c:17-23 / :37-43): bin_center[b] = (b odd ? b/2 + 1 : -(b/2)) * bin_width
-  if (!BC_ARITH)
-    for (int b = lane; b < 256; b += WG) {
-      const int ti = (b & 1) ? (b >> 1) + 1 : -(b >> 1);
-      bctab[b] = (T)ti * p.bin_width;
-    }
+  if (!BC_ARITH) fill_bin_centres(bctab, p.bin_width, lane, WG);
+  const BinCentres<T, BC_ARITH> centre{p.bin_width, bctab};
   QtLanes<T> qtl{};
   if (MODE == DCTZHIP_QT) qtl.load(p.qtab, lane);
   const bool scale = (p.sf != T(1));                 // dctz-decomp-lib.c:496 / :505
@@ -1038,32 +1056,6 @@ __device__ __forceinline__ void decompress_body(const InvParams<T>& p, const uns
     if constexpr (sizeof(T) == 8) asm volatile("" :: "v"(dcv));      // (the youngest of the reads: the others came back before it)
   };
 
-  // The image's rows -> HBM, one 1 KiB row (8 whole 128-byte lines) per instruction; blocks beyond the end fall outside
-  // r_out.  (Sending the second half of a tile's rows one stage later, behind the next tile's de-quantisation, so that
-  // the 32 stores -- 7 K cycles at the issue port -- come in two bursts, measured slower: 0.287 against 0.260 ms at
-  // p = 17 %, no gain at 5 %.)
-  auto store_rows = [&](auto phase, unsigned tile_s) {
-    constexpr int PHASE = decltype(phase)::value;
-    const int vbase = (int)((tile_s - tr.lo) * (unsigned)G::TILEB);
-#pragma unroll
-    for (int jg = 0; jg < 8; jg++) {
-      unsigned org = 0;
-      int cg = 0;
-      if (GEOM != GEOM_1D && nd_direct) {              // this lane's piece of row (jg, s): a chunk of block 8 jg + beta of the tile
-        const int beta = lane >> 3, gam = lane & 7;
-        org = nd_block_origin<T>(p.nd, tile_s * (unsigned)TILE_BLKS + (unsigned)(8 * jg + beta));
-        cg = swz_row_chunk(beta, gam, jg);
-      }
-      const int vo = vbase + jg * 8 * G::BLKB + tm.g_of(jg);
-#pragma unroll
-      for (int s = 0; s < G::SEGP; s++) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(outbuf + (jg * G::SEGP + s) * 1024 + lane * 16);
-        int at = vo + (PHASE * G::SEGP + s) * 128;
-        if (GEOM != GEOM_1D && nd_direct) at = (int)(org >= 0xFFFFFFF0u ? org : org + nd_chunk_offset<T>(p.nd, 8 * (PHASE * G::SEGP + s) + cg));
-        __builtin_amdgcn_raw_buffer_store_b128(v, r_out, at, 0, DCTZ_DEC_STORE_AUX);
-      }
-    }
-  };
   if (tr.lo < tr.hi) { prefetch(tr.lo); landed(); }
   for (unsigned tile = tr.lo; tile < tr.hi; tile++) {
     const unsigned rel = tile - tr.lo;
@@ -1086,92 +1078,14 @@ __device__ __forceinline__ void decompress_body(const InvParams<T>& p, const uns
                       bw[2].x, bw[2].y, bw[2].z, bw[2].w, bw[3].x, bw[3].y, bw[3].z, bw[3].w};
     const float dc_t = dcv;
     // where this lane's exact coefficients start: count the flags of the block (byte == 255, j != 0), scan over the wave
-    unsigned n = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const unsigned v = ~w[i];                                        // a zero byte of v <=> bin id 255
-      const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;        // bit 7 of a byte set <=> that byte of v is non-zero
-      unsigned m = ~z & 0x80808080u;
-      if (i == 0) m &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
-      n += (unsigned)__popc(m);
-    }
-    if (!active) n = 0;
+    const unsigned n = active ? block_flag_count(w) : 0u;
     unsigned ptr = wave_incl_scan(n) - n;                              // index inside the tile's piece of AC_exact
     if (S_t + total_t > p.ac_count) underrun = true;                  // the stream promises more than the caller provides
     T x[64];
-    if constexpr (sizeof(T) == 8) {
-    // Four coefficients = one dword of bin ids at a time: the (up to four) exact coefficients of the group are fetched
-    // together -- their places follow from the flag bits alone -- so that a tile pays one LDS round trip per GROUP that
-    // has a flag somewhere in the wave (16 at most), not one per flagged POSITION (63 on noisy data: at p = 17 % the
-    // serialised round trips were a third of the kernel; 512^3 fp64: 0.33 -> 0.28 ms there, 0.245 -> 0.235 at p = 5 %).
-#pragma unroll
-    for (int g = 0; g < 16; g++) {
-      const unsigned wg = w[g];
-      const unsigned nv = ~wg;                                         // a zero byte of nv <=> bin id 255
-      unsigned m = ~(((nv & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nv) & 0x80808080u;
-      if (g == 0) m &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
-      const unsigned w1 = ((wg >> 1) & 0x7F7F7F7Fu) + (wg & 0x01010101u);   // four magnitudes (b + 1) >> 1
-      float e[4] = {0.f, 0.f, 0.f, 0.f};
-      if (__builtin_amdgcn_ballot_w64(m != 0u)) {                      // :400 / :446 somewhere in the wave
-        unsigned at[4];
-        at[0] = ptr;
-        at[1] = at[0] + ((m >> 7) & 1u);
-        at[2] = at[1] + ((m >> 15) & 1u);
-        at[3] = at[2] + ((m >> 23) & 1u);
-        ptr = at[3] + (m >> 31);
-#pragma unroll
-        for (int i = 0; i < 4; i++) e[i] = stage[min(at[i], stage_last)];      // (all lanes read: predicating the reads on the flag measured slower)
-      }
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int j = 4 * g + i;
-        if (j == 0) { x[0] = (T)dc_t; continue; }                      // :392 / :438
-        T v;
-        if constexpr (BC_ARITH) v = bin_centre<T>(w1, nv, i, p.bin_width);
-        else v = bctab[(wg >> (8 * i)) & 255u];                        // :416 / :462
-        if ((m >> (8 * i + 7)) & 1u) v = (T)e[i];
-        x[j] = v;
-      }
-    }
-    if constexpr (MODE == DCTZHIP_QT) {
-      // dctz-decomp-lib.c:404-409 in a pass of its own over the flagged positions: inside the loop above every division sat
-      // right behind the LDS read of its coefficient, one exposed round trip per flagged group (with one wave per SIMD the
-      // QT decoder spent 76 % more cycles waiting than its EC twin for FEWER vector instructions, profiles/r04_pmc_qt.txt);
-      // here the coefficients are in registers already and the reads of all sixteen groups overlap as they do in EC mode
-#pragma unroll
-      for (int g = 0; g < 16; g++) {
-        const unsigned nv = ~w[g];
-        unsigned m = ~(((nv & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nv) & 0x80808080u;
-        if (g == 0) m &= ~0x80u;
-        if (__builtin_amdgcn_ballot_w64(m != 0u)) {
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const int j = 4 * g + i;
-            if (j != 0 && ((m >> (8 * i + 7)) & 1u)) x[j] = qt_restore(x[j], qtl.at(j), p.eb, T(10), p.range_min, p.range_max);
-          }
-        }
-      }
-    }
-    } else {
-    // fp32 (seven waves per CU hide the round trips; the grouped form measured 10 % slower here): position by position
-    x[0] = (T)dc_t;                                                    // :392 / :438
-#pragma unroll
-    for (int j = 1; j < 64; j++) {
-      const unsigned b = (w[j >> 2] >> (8 * (j & 3))) & 255u;
-      T v;
-      if constexpr (BC_ARITH) {
-        const unsigned wj = w[j >> 2];
-        v = bin_centre<T>(((wj >> 1) & 0x7F7F7F7Fu) + (wj & 0x01010101u), ~wj, j & 3, p.bin_width);
-      } else v = bctab[b];                                             // :416 / :462
-      if (b == 255u) {                                                 // :400 / :446
-        const float e = stage[min(ptr, stage_last)];
-        ptr++;
-        v = (T)e;
-        if (MODE == DCTZHIP_QT) v = qt_restore(v, qtl.at(j), p.eb, T(10), p.range_min, p.range_max);
-      }
-      x[j] = v;
-    }
-    }
+    const auto qtab = [&](int j) { return qtl.at(j); };
+    // fp64: grouped, QT in a trailing pass; fp32 (seven waves per CU hide the round trips): position by position
+    if constexpr (sizeof(T) == 8) dequantise_grouped<T, MODE, true>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
+    else dequantise_positional<T, MODE, false>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // the staged coefficients are consumed: the strip is free
     if (tile + 1 < tr.hi) prefetch(tile + 1);
     block_inv<T, CTab<T>, GEOM, (PH > 1)>(x, tab);
@@ -1185,7 +1099,7 @@ __device__ __forceinline__ void decompress_body(const InvParams<T>& p, const uns
     auto store_phase = [&](auto phase) {
       constexpr int PHASE = decltype(phase)::value;
       write_phase<T, PH, PHASE>(x, outbuf, tm);
-      store_rows(phase, tile);
+      store_rows<T, PH, GEOM, PHASE>(outbuf, tm, r_out, (int)(rel * (unsigned)G::TILEB), nd_direct, p.nd, tile, lane);
     };
     store_phase(std::integral_constant<int, 0>{});
     if (PH == 2) store_phase(std::integral_constant<int, PH - 1>{});
@@ -1196,21 +1110,7 @@ __device__ __forceinline__ void decompress_body(const InvParams<T>& p, const uns
 
 template <typename T, int MODE, int PH, int GEOM>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((sizeof(T) == 4 && DCTZ_WPED32) ? DCTZ_WPED32 : PH, (sizeof(T) == 4 && DCTZ_WPED32) ? DCTZ_WPED32 : PH))) void k_decompress(InvParams<T> p, FinArgs fin) {
-  decompress_body<T, MODE, PH, GEOM>(p, blockIdx.x, gridDim.x, [&]() {
-    if (fin.box != nullptr && blockIdx.x == 0) {
-      // the one thing the host waits for on decode: does the stream promise more exact coefficients than the caller
-      // provides (all counts are in: k_count_tiles)?  Known before the first block is rebuilt -> hand it over now.
-      const int lane = threadIdx.x;
-      unsigned all = 0;
-      for (unsigned i = (unsigned)lane; i < p.nwg; i += WG) all += p.wg_cnt[i];
-      all = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(all), 63);
-      FinBody f;
-      f.ctl = fin.ctl; f.part = nullptr; f.nparts = 0; f.box = fin.box; f.seq = fin.seq; f.guess = nullptr;
-      f.cnt_known = true; f.cnt_total = all;
-      f.err_known = true; f.error = all > p.ac_count ? 2u : 0u;
-      finish_body<false>(f);
-    }
-  });
+  decompress_body<T, MODE, PH, GEOM>(p, blockIdx.x, gridDim.x, [&]() { decompress_handoff(p, fin); });
 }
 
 // ---- the same kernel with TILE-INTERLEAVED workgroups (flat blocks, one array) -------------------------------------------
@@ -1270,11 +1170,8 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
   TileMap<T, PH> tm;
   tm.init(lane);
   const CTab<T> tab = as_ctab<T>(p.tab);
-  if (!BC_ARITH)
-    for (int b = lane; b < 256; b += WG) {
-      const int ti = (b & 1) ? (b >> 1) + 1 : -(b >> 1);
-      bctab[b] = (T)ti * p.bin_width;
-    }
+  if (!BC_ARITH) fill_bin_centres(bctab, p.bin_width, lane, WG);
+  const BinCentres<T, BC_ARITH> centre{p.bin_width, bctab};
   QtLanes<T> qtl{};
   if (MODE == DCTZHIP_QT) qtl.load(p.qtab, lane);
   const bool scale = (p.sf != T(1));                 // dctz-decomp-lib.c:496 / :505
@@ -1324,87 +1221,13 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
     unsigned w[16] = {bw[0].x, bw[0].y, bw[0].z, bw[0].w, bw[1].x, bw[1].y, bw[1].z, bw[1].w,
                       bw[2].x, bw[2].y, bw[2].z, bw[2].w, bw[3].x, bw[3].y, bw[3].z, bw[3].w};
     const float dc_t = dcv;
-    unsigned n = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const unsigned v = ~w[i];                                        // a zero byte of v <=> bin id 255
-      const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;        // bit 7 of a byte set <=> that byte of v is non-zero
-      unsigned m = ~z & 0x80808080u;
-      if (i == 0) m &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
-      n += (unsigned)__popc(m);
-    }
-    if (!active) n = 0;
+    const unsigned n = active ? block_flag_count(w) : 0u;
     unsigned ptr = wave_incl_scan(n) - n;                              // index inside the tile's piece of AC_exact
     if (S_t + total_t > p.ac_count) underrun = true;                  // the stream promises more than the caller provides
     T x[64];
-    if constexpr (sizeof(T) == 8) {
-#pragma unroll
-    for (int g = 0; g < 16; g++) {
-      const unsigned wgd = w[g];
-      const unsigned nv = ~wgd;                                        // a zero byte of nv <=> bin id 255
-      unsigned m = ~(((nv & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nv) & 0x80808080u;
-      if (g == 0) m &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
-      const unsigned w1 = ((wgd >> 1) & 0x7F7F7F7Fu) + (wgd & 0x01010101u);   // four magnitudes (b + 1) >> 1
-      float e[4] = {0.f, 0.f, 0.f, 0.f};
-      if (__builtin_amdgcn_ballot_w64(m != 0u)) {                      // :400 / :446 somewhere in the wave
-        unsigned at[4];
-        at[0] = ptr;
-        at[1] = at[0] + ((m >> 7) & 1u);
-        at[2] = at[1] + ((m >> 15) & 1u);
-        at[3] = at[2] + ((m >> 23) & 1u);
-        ptr = at[3] + (m >> 31);
-#pragma unroll
-        for (int i = 0; i < 4; i++) e[i] = stage[min(at[i], stage_last)];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int j = 4 * g + i;
-        if (j == 0) { x[0] = (T)dc_t; continue; }                      // :392 / :438
-        T v;
-        if constexpr (BC_ARITH) v = bin_centre<T>(w1, nv, i, p.bin_width);
-        else v = bctab[(wgd >> (8 * i)) & 255u];                       // :416 / :462
-        if ((m >> (8 * i + 7)) & 1u) v = (T)e[i];
-        x[j] = v;
-      }
-    }
-    if constexpr (MODE == DCTZHIP_QT) {
-      // dctz-decomp-lib.c:404-409 in a pass of its own over the flagged positions: inside the loop above every division sat
-      // right behind the LDS read of its coefficient, one exposed round trip per flagged group (with one wave per SIMD the
-      // QT decoder spent 76 % more cycles waiting than its EC twin for FEWER vector instructions, profiles/r04_pmc_qt.txt);
-      // here the coefficients are in registers already and the reads of all sixteen groups overlap as they do in EC mode
-#pragma unroll
-      for (int g = 0; g < 16; g++) {
-        const unsigned nv = ~w[g];
-        unsigned m = ~(((nv & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nv) & 0x80808080u;
-        if (g == 0) m &= ~0x80u;
-        if (__builtin_amdgcn_ballot_w64(m != 0u)) {
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const int j = 4 * g + i;
-            if (j != 0 && ((m >> (8 * i + 7)) & 1u)) x[j] = qt_restore(x[j], qtl.at(j), p.eb, T(10), p.range_min, p.range_max);
-          }
-        }
-      }
-    }
-    } else {
-    x[0] = (T)dc_t;                                                    // :392 / :438
-#pragma unroll
-    for (int j = 1; j < 64; j++) {
-      const unsigned b = (w[j >> 2] >> (8 * (j & 3))) & 255u;
-      T v;
-      if constexpr (BC_ARITH) {
-        const unsigned wj = w[j >> 2];
-        v = bin_centre<T>(((wj >> 1) & 0x7F7F7F7Fu) + (wj & 0x01010101u), ~wj, j & 3, p.bin_width);
-      } else v = bctab[b];                                             // :416 / :462
-      if (b == 255u) {                                                 // :400 / :446
-        const float e = stage[min(ptr, stage_last)];
-        ptr++;
-        v = (T)e;
-        if (MODE == DCTZHIP_QT) v = qt_restore(v, qtl.at(j), p.eb, T(10), p.range_min, p.range_max);
-      }
-      x[j] = v;
-    }
-    }
+    const auto qtab = [&](int j) { return qtl.at(j); };
+    if constexpr (sizeof(T) == 8) dequantise_grouped<T, MODE, true>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
+    else dequantise_positional<T, MODE, false>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // the staged coefficients are consumed: the strip is free
     if (r + 1 < my_tiles) prefetch(tile + nwg, r + 1);
     block_inv<T, CTab<T>, GEOM_1D, (PH > 1)>(x, tab);
@@ -1416,15 +1239,7 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
     auto store_phase = [&](auto phase) {
       constexpr int PHASE = decltype(phase)::value;
       write_phase<T, PH, PHASE>(x, outbuf, tm);
-#pragma unroll
-      for (int jg = 0; jg < 8; jg++) {
-        const int vo = jg * 8 * G::BLKB + tm.g_of(jg);
-#pragma unroll
-        for (int sg = 0; sg < G::SEGP; sg++) {
-          const u32x4 v = *reinterpret_cast<const u32x4*>(outbuf + (jg * G::SEGP + sg) * 1024 + lane * 16);
-          __builtin_amdgcn_raw_buffer_store_b128(v, r_out, vo + (PHASE * G::SEGP + sg) * 128, 0, DCTZ_DEC_STORE_AUX);
-        }
-      }
+      store_rows<T, PH, GEOM_1D, PHASE>(outbuf, tm, r_out, 0, false, p.nd, tile, lane);
     };
     store_phase(std::integral_constant<int, 0>{});
     if (PH == 2) store_phase(std::integral_constant<int, PH - 1>{});
@@ -1433,19 +1248,7 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
 }
 template <typename T, int MODE, int PH>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((sizeof(T) == 4 && DCTZ_WPED32) ? DCTZ_WPED32 : PH, (sizeof(T) == 4 && DCTZ_WPED32) ? DCTZ_WPED32 : PH))) void k_decompress_il(InvParams<T> p, FinArgs fin) {
-  decompress_il_body<T, MODE, PH>(p, blockIdx.x, gridDim.x, [&]() {
-    if (fin.box != nullptr && blockIdx.x == 0) {
-      const int lane = threadIdx.x;
-      unsigned all = 0;
-      for (unsigned i = (unsigned)lane; i < p.nwg; i += WG) all += p.wg_cnt[i];
-      all = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(all), 63);
-      FinBody f;
-      f.ctl = fin.ctl; f.part = nullptr; f.nparts = 0; f.box = fin.box; f.seq = fin.seq; f.guess = nullptr;
-      f.cnt_known = true; f.cnt_total = all;
-      f.err_known = true; f.error = all > p.ac_count ? 2u : 0u;
-      finish_body<false>(f);
-    }
-  });
+  decompress_il_body<T, MODE, PH>(p, blockIdx.x, gridDim.x, [&]() { decompress_handoff(p, fin); });
 }
 
 // Last, short block on decode (dctz-decomp-lib.c:423-428, dct.c:144-199).
@@ -1456,8 +1259,6 @@ __device__ __forceinline__ void decompress_rem_body(const InvParams<T>& p, const
   __shared__ T ci[128];
   const int k = threadIdx.x;
   const size_t base = (size_t)p.nfull * 64;
-  const T* rt = p.rtab;
-  const int N = (l & 1) ? 2 * l : l;
   unsigned b = 0;
   if (k < l) b = p.bin[base + k];
   const bool exc = (k < l) && (k != 0) && (b == 255u);
@@ -1466,39 +1267,17 @@ __device__ __forceinline__ void decompress_rem_body(const InvParams<T>& p, const
   unsigned before = 0;                                             // everything the full blocks consumed
   for (unsigned i = (unsigned)k; i < p.nwg; i += 64) before += p.wg_cnt[i];
   const unsigned start = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(before), 63);
-  cr[k] = T(0); ci[k] = T(0); cr[k + 64] = T(0); ci[k + 64] = T(0);
+  short_inv_clear(cr, ci, k);
   if (k < l) {
-    T val;
-    if (k == 0) val = (T)p.dc[p.nfull];
-    else if (exc) {
-      T v = T(0);
-      if (start + rank < p.ac_count) v = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u);
-      if (MODE == DCTZHIP_QT) v = qt_restore(v, p.qtab[k], p.eb, T(10), p.range_min, p.range_max);
-      val = v;
-    } else {
-      const int ti = (b & 1u) ? (int)(b >> 1) + 1 : -(int)(b >> 1);
-      val = (T)ti * p.bin_width;
-    }
-    a[k] = val;
+    T e = T(0);
+    if (exc) { if (start + rank < p.ac_count) e = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u); }
+    a[k] = short_inv_value<T, MODE>(b, exc, k, k == 0 ? p.dc[p.nfull] : 0.f, e, p.bin_width, [&](int j) { return p.qtab[j]; }, p.eb, p.range_min, p.range_max);
   }
   __syncthreads();
-  if (k < l) {
-    cr[k] = rt[RTAB_IAS + k] * a[k];                               // dct.c:146-151 / :166-172
-    ci[k] = rt[RTAB_IAX + k] * a[k];
-    if ((l & 1) && k >= 1) {                                       // dct.c:152-153
-      cr[l + k] = rt[RTAB_IAX + k] * a[l - k];
-      ci[l + k] = -(rt[RTAB_IAS + k] * a[l - k]);
-    }
-  }
+  if (k < l) short_inv_spread(cr, ci, a, p.rtab, l, k);
   __syncthreads();
   if (k < l) {
-    const int s = (l & 1) ? k : ((k & 1) ? l - 1 - (k >> 1) : (k >> 1));   // dct.c:189-199
-    T acc = T(0);
-    for (int j = 0; j < N; j++) {
-      const int tt = (s * j) % N;
-      acc = acc + (cr[j] * rt[RTAB_WR + tt] - ci[j] * rt[RTAB_WI + tt]);
-    }
-    T val = (l & 1) ? (acc / (T)l) / T(2) : acc / (T)l;            // dct.c:163 / :185
+    T val = short_inv_sum(cr, ci, p.rtab, l, k);
     if (SCALE) val = val * p.sf;
     p.out[base + k] = val;
   }

@@ -328,45 +328,16 @@ __global__ __launch_bounds__(64) void k_dct_rem(const T* __restrict__ x, T* __re
   __shared__ T v[128];
   __shared__ T w[128];
   const int k = threadIdx.x;
-  const int N = (l & 1) ? 2 * l : l;
-  v[k] = T(0); v[k + 64] = T(0); w[k] = T(0); w[k + 64] = T(0);
+  short_inv_clear(v, w, k);
   __syncthreads();
   if (!INVERSE) {
-    if (k < l) {
-      const T a = x[k];
-      if (l & 1) { v[k] = a; v[l + (l - 1 - k)] = a; }
-      else if (k & 1) v[l - 1 - (k >> 1)] = a;
-      else v[k >> 1] = a;
-    }
+    if (k < l) short_fwd_fill(v, l, k, x[k]);
     __syncthreads();
-    if (k < l) {
-      T sr = T(0), si = T(0);
-      for (int j = 0; j < N; j++) {
-        const int tt = (j * k) % N;
-        sr = sr + v[j] * rt[RTAB_WR + tt];
-        si = si + v[j] * rt[RTAB_WI + tt];
-      }
-      out[k] = rt[RTAB_AS + k] * sr + rt[RTAB_AX + k] * si;
-    }
+    if (k < l) out[k] = short_fwd_sum(v, rt, short_dft_len(l), k);
   } else {
-    if (k < l) {
-      v[k] = rt[RTAB_IAS + k] * x[k];
-      w[k] = rt[RTAB_IAX + k] * x[k];
-      if ((l & 1) && k >= 1) {
-        v[l + k] = rt[RTAB_IAX + k] * x[l - k];
-        w[l + k] = -(rt[RTAB_IAS + k] * x[l - k]);
-      }
-    }
+    if (k < l) short_inv_spread(v, w, x, rt, l, k);
     __syncthreads();
-    if (k < l) {
-      const int s = (l & 1) ? k : ((k & 1) ? l - 1 - (k >> 1) : (k >> 1));
-      T acc = T(0);
-      for (int j = 0; j < N; j++) {
-        const int tt = (s * j) % N;
-        acc = acc + (v[j] * rt[RTAB_WR + tt] - w[j] * rt[RTAB_WI + tt]);
-      }
-      out[k] = (l & 1) ? (acc / (T)l) / T(2) : acc / (T)l;
-    }
+    if (k < l) out[k] = short_inv_sum(v, w, rt, l, k);
   }
 }
 

@@ -506,8 +506,7 @@ __device__ __forceinline__ void compress_one_body(const OneFwd<T>& a, const unsi
           for (int i = 0; i < 4; i++) wgd = __builtin_amdgcn_cvt_pk_u8_f32(h[i], i, wgd);
           asm volatile("" : "+v"(wgd));
           w[g] = wgd;
-          const unsigned nw = ~wgd;                    // "stored exactly" = id 255: bit 7 of byte i of mm
-          const unsigned mm = ~(((nw & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nw) & 0x80808080u;
+          const unsigned mm = exact_flags(wgd);        // "stored exactly" = id 255: bit 7 of byte i of mm
           const unsigned m4 = ((mm >> 7) | (mm >> 14) | (mm >> 21) | (mm >> 28)) & 0xFu;
           if (g < 8) mlo |= m4 << (4 * g); else mhi |= m4 << (4 * (g - 8));
           __builtin_amdgcn_sched_barrier(0);
@@ -526,7 +525,7 @@ __device__ __forceinline__ void compress_one_body(const OneFwd<T>& a, const unsi
       // (dctz-comp-lib.c:326-340, dct.c:59-72); definition-order DFT with host-built roots, lane k = output k
       T* const v = reinterpret_cast<T*>(tilebuf);
       const T* rt = p.rtab;
-      const int N = (l & 1) ? 2 * l : l;
+      const int N = (l & 1) ? 2 * l : l;                             // (short_dft_len, written out: through the call k_compress_one<double, EC> spills 11 VGPRs for 8)
       const int k = lane;
       FastDiv<T> sfd;
       sfd.init(sf, osf.fast != 0u);
@@ -534,27 +533,11 @@ __device__ __forceinline__ void compress_one_body(const OneFwd<T>& a, const unsi
         T e = raw;
         if (scale) e = sfd.div(e);
         if (p.scaled != nullptr) p.scaled[rbase + k] = e;
-        if (l & 1) { v[k] = e; v[l + (l - 1 - k)] = e; }             // dct.c:61-64
-        else if (k & 1) v[l - 1 - (k >> 1)] = e;                     // dct.c:75-83
-        else v[k >> 1] = e;
+        short_fwd_fill(v, l, k, e);
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // (one wave: its LDS operations are in order)
-      if (k < l) {
-        T sr = T(0), si = T(0);
-        for (int j = 0; j < N; j++) {
-          const int tt = (j * k) % N;
-          sr = sr + v[j] * rt[RTAB_WR + tt];
-          si = si + v[j] * rt[RTAB_WI + tt];
-        }
-        rcoef = rt[RTAB_AS + k] * sr + rt[RTAB_AX + k] * si;         // dct.c:100-102 (Im V = -si)
-      }
-      // pass-1 binning, the reference's own form (:363-414)
-      const bool out = fabs(rcoef) > rmax;                           // == (item < range_min || item > range_max)
-      const T u = rcoef - rmin;
-      const T q = bwd.ok ? bwd.core(u) : u / bwd.d;
-      const int t = (int)q;                                          // (t_bin_id) cast: truncation
-      rbin = out ? 255u : (unsigned)(t <= 127 ? 254 - 2 * t : 2 * t - 255);   // conv_tbl :27-43 (t == 255 -> 255)
-      if (rcoef != rcoef) rbin = 0u;                                 // a NaN coefficient: bin id 0, like bin_value()
+      if (k < l) rcoef = short_fwd_sum(v, rt, N, k);
+      rbin = bin_short(rcoef, rmin, rmax, bwd);
       if (k == 0) rbin = 255u; else rexc = (rbin == 255u);
       if (k >= l) rexc = false;
       const unsigned long long m = __builtin_amdgcn_ballot_w64(rexc);
@@ -797,11 +780,7 @@ __device__ __forceinline__ void decompress_one_body(const OneInv<T>& a, const un
   const size_t first_el = (size_t)tile * TILE_ELEMS;
   const int range_el = (int)(blks_here * 64u);
   const size_t rbase = (size_t)p.nfull * 64;
-  if (!BC_ARITH)
-    for (int b = threadIdx.x; b < 256; b += OTW * 64) {   // gen_bins / gen_bins_f (binning.c:17-23 / :37-43)
-      const int ti = (b & 1) ? (b >> 1) + 1 : -(b >> 1);
-      bctab[b] = (T)ti * p.bin_width;
-    }
+  if (!BC_ARITH) fill_bin_centres(bctab, p.bin_width, (int)threadIdx.x, OTW * 64);   // gen_bins / gen_bins_f (binning.c:17-23 / :37-43)
   if (MODE == DCTZHIP_QT && threadIdx.x < 64) qt[threadIdx.x] = qtab_src[threadIdx.x];
   // ---- the flags of the tile (dctz-decomp-lib.c:400 / :446) -------------------------------------------------------------
   one_stamp(a.b, 0);
@@ -820,16 +799,7 @@ __device__ __forceinline__ void decompress_one_body(const OneInv<T>& a, const un
     bw3 = __builtin_amdgcn_raw_buffer_load_b128(r_bin, lane * 64 + 48, 0, 0);
     dc_t = active ? p.dc[(size_t)tile * TILE_BLKS + lane] : 0.f;
     const unsigned w[16] = {bw0.x, bw0.y, bw0.z, bw0.w, bw1.x, bw1.y, bw1.z, bw1.w, bw2.x, bw2.y, bw2.z, bw2.w, bw3.x, bw3.y, bw3.z, bw3.w};
-    unsigned n = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      const unsigned v = ~w[i];                                        // a zero byte of v <=> bin id 255
-      const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;        // bit 7 of a byte set <=> that byte of v is non-zero
-      unsigned m = ~z & 0x80808080u;
-      if (i == 0) m &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
-      n += (unsigned)__popc(m);
-    }
-    if (!active) n = 0;
+    const unsigned n = active ? block_flag_count(w) : 0u;
     const unsigned incl = wave_incl_scan(n);
     tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
     ptr = incl - n;                                                    // index inside the tile's piece of AC_exact
@@ -887,68 +857,12 @@ __device__ __forceinline__ void decompress_one_body(const OneInv<T>& a, const un
     constexpr unsigned stage_last = (unsigned)(G::TILEB / 4) - 1u;
     const unsigned w[16] = {bw0.x, bw0.y, bw0.z, bw0.w, bw1.x, bw1.y, bw1.z, bw1.w, bw2.x, bw2.y, bw2.z, bw2.w, bw3.x, bw3.y, bw3.z, bw3.w};
     T x[64];
-    if constexpr (sizeof(T) == 8) {
-      // four coefficients = one dword of bin ids at a time (dctz_kernels.hip: decompress_body)
-#pragma unroll
-      for (int g = 0; g < 16; g++) {
-        const unsigned wgd = w[g];
-        const unsigned nv = ~wgd;                                      // a zero byte of nv <=> bin id 255
-        unsigned m = ~(((nv & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | nv) & 0x80808080u;
-        if (g == 0) m &= ~0x80u;                                       // j = 0 is the DC slot (:392 / :438)
-        const unsigned w1 = ((wgd >> 1) & 0x7F7F7F7Fu) + (wgd & 0x01010101u);   // four magnitudes (b + 1) >> 1
-        float e[4] = {0.f, 0.f, 0.f, 0.f};
-        if (__builtin_amdgcn_ballot_w64(m != 0u)) {                    // :400 / :446 somewhere in the wave
-          unsigned at[4];
-          at[0] = ptr;
-          at[1] = at[0] + ((m >> 7) & 1u);
-          at[2] = at[1] + ((m >> 15) & 1u);
-          at[3] = at[2] + ((m >> 23) & 1u);
-          ptr = at[3] + (m >> 31);
-#pragma unroll
-          for (int i = 0; i < 4; i++) e[i] = stage[min(at[i], stage_last)];
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int j = 4 * g + i;
-          if (j == 0) { x[0] = (T)dc_t; continue; }                    // :392 / :438
-          T v;
-          if constexpr (BC_ARITH) v = bin_centre<T>(w1, nv, i, p.bin_width);
-          else v = bctab[(wgd >> (8 * i)) & 255u];                     // :416 / :462
-          if ((m >> (8 * i + 7)) & 1u) {
-            v = (T)e[i];
-            if (MODE == DCTZHIP_QT) v = qt_restore(v, qt[j], p.eb, T(10), p.range_min, p.range_max);
-          }
-          x[j] = v;
-        }
-      }
-    } else {
-      // position by position (two workgroups per CU hide the round trips; the grouped form measured slower for fp32), written
-      // as sixteen dwords of four: as ONE loop of 63 trips the compiler leaves it partly rolled, and the bin ids and the
-      // block then live in scratch memory -- 144 bytes per lane, stored and read back per tile: 15 MB of the 41 MB that
-      // k_decompress_one<float> wrote for a 26 MB array (profiles/r05_c2_raw_traffic.txt)
-#pragma unroll
-      for (int g = 0; g < 16; g++) {
-        const unsigned wgd = w[g];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const int j = 4 * g + i;
-          if (j == 0) { x[0] = (T)dc_t; continue; }                    // :392 / :438
-          const unsigned b = (wgd >> (8 * i)) & 255u;
-          T v = bctab[b];                                              // :416 / :462
-          if (b == 255u) {                                             // :400 / :446
-            const float e = stage[min(ptr, stage_last)];
-            ptr++;
-            v = (T)e;
-            if (MODE == DCTZHIP_QT) v = qt_restore(v, qt[j], p.eb, T(10), p.range_min, p.range_max);
-          }
-          // (each value through a register of its own: paired into <2 x float> stores by the vectoriser, the first 33
-          // elements of the block stayed an array in scratch memory -- 144 bytes per lane, stored and read back per tile:
-          // 15 MB of the 41 MB that k_decompress_one<float> wrote for a 26 MB array, profiles/r05_c2_raw_traffic.txt)
-          asm volatile("" : "+v"(v));
-          x[j] = v;
-        }
-      }
-    }
+    const BinCentres<T, BC_ARITH> centre{p.bin_width, bctab};
+    const auto qtab = [&](int j) { return qt[j]; };
+    // fp64: grouped, QT restored in place; fp32 (two workgroups per CU hide the round trips; the grouped form measured slower):
+    // position by position, every value pinned (dctz_kernel_common.h)
+    if constexpr (sizeof(T) == 8) dequantise_grouped<T, MODE, false>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
+    else dequantise_positional<T, MODE, true>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
     one_stamp(a.b, 5);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                  // the staged coefficients are consumed: the array becomes the image
     block_inv<T, CTab<T>, GEOM_1D, true>(x, as_ctab<T>(p.tab));
@@ -972,42 +886,18 @@ __device__ __forceinline__ void decompress_one_body(const OneInv<T>& a, const un
     T* const av = reinterpret_cast<T*>(io);
     T* const cr = av + 64;
     T* const ci = cr + 128;
-    const T* rt = p.rtab;
-    const int N = (l & 1) ? 2 * l : l;
     const int k = lane;
-    cr[k] = T(0); ci[k] = T(0); cr[k + 64] = T(0); ci[k + 64] = T(0);
+    short_inv_clear(cr, ci, k);
     if (k < l) {
-      T val;
-      if (k == 0) val = (T)p.dc[p.nfull];
-      else if (rexc) {
-        T v = T(0);
-        if (S + rrank < p.ac_count) v = (T)p.ac[(size_t)S + rrank];
-        if (MODE == DCTZHIP_QT) v = qt_restore(v, qt[k], p.eb, T(10), p.range_min, p.range_max);
-        val = v;
-      } else {
-        const int ti = (rbin & 1u) ? (int)(rbin >> 1) + 1 : -(int)(rbin >> 1);
-        val = (T)ti * p.bin_width;
-      }
-      av[k] = val;
+      T e = T(0);
+      if (rexc && S + rrank < p.ac_count) e = (T)p.ac[(size_t)S + rrank];
+      av[k] = short_inv_value<T, MODE>(rbin, rexc, k, k == 0 ? p.dc[p.nfull] : 0.f, e, p.bin_width, [&](int j) { return qt[j]; }, p.eb, p.range_min, p.range_max);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (k < l) {
-      cr[k] = rt[RTAB_IAS + k] * av[k];                            // dct.c:146-151 / :166-172
-      ci[k] = rt[RTAB_IAX + k] * av[k];
-      if ((l & 1) && k >= 1) {                                     // dct.c:152-153
-        cr[l + k] = rt[RTAB_IAX + k] * av[l - k];
-        ci[l + k] = -(rt[RTAB_IAS + k] * av[l - k]);
-      }
-    }
+    if (k < l) short_inv_spread(cr, ci, av, p.rtab, l, k);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (k < l) {
-      const int s = (l & 1) ? k : ((k & 1) ? l - 1 - (k >> 1) : (k >> 1));   // dct.c:189-199
-      T accv = T(0);
-      for (int j = 0; j < N; j++) {
-        const int tt = (s * j) % N;
-        accv = accv + (cr[j] * rt[RTAB_WR + tt] - ci[j] * rt[RTAB_WI + tt]);
-      }
-      T val = (l & 1) ? (accv / (T)l) / T(2) : accv / (T)l;        // dct.c:163 / :185
+      T val = short_inv_sum(cr, ci, p.rtab, l, k);
       if (p.sf != T(1)) val = val * p.sf;                          // :496 / :505
       p.out[rbase + k] = val;
     }

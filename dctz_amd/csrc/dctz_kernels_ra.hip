@@ -20,13 +20,6 @@
 
 namespace dctz {
 
-// bit 7 of byte i set <=> byte i of w is 255 (a "stored exactly" flag)
-__device__ __forceinline__ unsigned ra_flags(unsigned w) {
-  const unsigned v = ~w;                                           // a zero byte of v <=> bin id 255
-  const unsigned z = ((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v;        // bit 7 of a byte set <=> that byte of v is non-zero
-  return ~z & 0x80808080u;
-}
-
 // ================================================================== the index ==
 // Workgroup g takes tiles [64 g, 64 g + 64): wave w the tiles w, w + 4, ..., IX_TF of them in flight, 16-byte loads as
 // k_count_tiles reads them.  The one 16-byte group that holds the array's last byte (n % 16 != 0) is read byte by byte:
@@ -63,7 +56,7 @@ __global__ __launch_bounds__(SWG) void k_ac_index(const uint8_t* __restrict__ bi
         const unsigned w[4] = {wv[h][i].x, wv[h][i].y, wv[h][i].z, wv[h][i].w};
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-          unsigned f = ra_flags(w[k]);
+          unsigned f = exact_flags(w[k]);
           if (k == 0 && (lane & 3) == 0) f &= ~0x80u;                    // byte 0 of every 64: j = 0, the DC slot
           c += (unsigned)__popc(f);
         }
@@ -172,12 +165,7 @@ __global__ __launch_bounds__(64) void k_decompress_range(RangeParams<T> p) {
       if (blk == p.nfull && rem)
         for (unsigned j = 1; j < rem; j++) cnt += p.bin[(size_t)full_end + j] == 255u ? 1u : 0u;
     }
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-      unsigned f = ra_flags(w[i]);
-      if (i == 0) f &= ~0x80u;                                         // j = 0 is the DC slot (:392 / :438)
-      cnt += (unsigned)__popc(f);
-    }
+    cnt += block_flag_count(w);
     const unsigned incl = wave_incl_scan(cnt);
     const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
     const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
@@ -187,19 +175,8 @@ __global__ __launch_bounds__(64) void k_decompress_range(RangeParams<T> p) {
     __syncthreads();
     unsigned ptr = incl - cnt;                                         // this block's first exact coefficient in the tile
     T x[64];
-    x[0] = (T)dcv;                                                     // :392 / :438
-#pragma unroll
-    for (int j = 1; j < 64; j++) {
-      const unsigned wj = w[j >> 2];
-      const unsigned b = (wj >> (8 * (j & 3))) & 255u;
-      T v = bin_centre<T>(((wj >> 1) & 0x7F7F7F7Fu) + (wj & 0x01010101u), ~wj, j & 3, p.bin_width);   // :416 / :462
-      if (b == 255u) {                                                 // :400 / :446
-        v = (T)stage[min(ptr, (unsigned)(63 * 64 - 1))];
-        ptr++;
-        if (MODE == DCTZHIP_QT) v = qt_restore(v, qtl.at(j), p.eb, T(10), p.range_min, p.range_max);
-      }
-      x[j] = v;
-    }
+    dequantise_positional<T, MODE, false>(x, w, dcv, ptr, stage, (unsigned)(63 * 64 - 1), BinCentres<T, true>{p.bin_width, nullptr},
+                                          [&](int j) { return qtl.at(j); }, p.eb, p.range_min, p.range_max);
     __syncthreads();                                                   // the staged coefficients are consumed
     block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
     if (scale) {
@@ -262,69 +239,40 @@ __global__ __launch_bounds__(64) void k_decompress_range_rem(RangeParams<T> p) {
   __shared__ T cr[128];
   __shared__ T ci[128];
   const int k = threadIdx.x;
-  const unsigned l = p.n - p.nfull * 64u;
+  const int l = (int)(p.n - p.nfull * 64u);
   const size_t base = (size_t)p.nfull * 64;
   const unsigned t = p.nfull / (unsigned)TILE_BLKS;                    // the tile that holds the short block
-  const T* rt = p.rtab;
-  const int N = (l & 1) ? 2 * (int)l : (int)l;
   // flags of the tile's whole blocks in front of the short block
   unsigned c = 0;
   const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)k;
   if (blk < p.nfull) {
     const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
+    unsigned w[16];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const u32x4 v = src[i];
-      const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        unsigned f = ra_flags(w[q]);
-        if (i == 0 && q == 0) f &= ~0x80u;
-        c += (unsigned)__popc(f);
-      }
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
     }
+    c = block_flag_count(w);
   }
   const unsigned start = p.idx[t] + (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(c), 63);
   const unsigned lim = min(p.ac_count, p.idx[t + 1]);
   unsigned b = 0;
-  if ((unsigned)k < l) b = p.bin[base + k];
-  const bool exc = ((unsigned)k < l) && (k != 0) && (b == 255u);
+  if (k < l) b = p.bin[base + k];
+  const bool exc = (k < l) && (k != 0) && (b == 255u);
   const unsigned long long msk = __ballot(exc);
   const unsigned rank = (unsigned)__popcll(msk & ((1ull << k) - 1ull));
-  cr[k] = T(0); ci[k] = T(0); cr[k + 64] = T(0); ci[k + 64] = T(0);
-  if ((unsigned)k < l) {
-    T val;
-    if (k == 0) val = (T)p.dc[p.nfull];
-    else if (exc) {
-      T v = T(0);
-      if (start + rank < lim) v = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u);
-      if (MODE == DCTZHIP_QT) v = qt_restore(v, p.qtab[k], p.eb, T(10), p.range_min, p.range_max);
-      val = v;
-    } else {
-      const int ti = (b & 1u) ? (int)(b >> 1) + 1 : -(int)(b >> 1);
-      val = (T)ti * p.bin_width;
-    }
-    a[k] = val;
+  short_inv_clear(cr, ci, k);
+  if (k < l) {
+    T e = T(0);
+    if (exc) { if (start + rank < lim) e = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u); }
+    a[k] = short_inv_value<T, MODE>(b, exc, k, k == 0 ? p.dc[p.nfull] : 0.f, e, p.bin_width, [&](int j) { return p.qtab[j]; }, p.eb, p.range_min, p.range_max);
   }
   __syncthreads();
-  if ((unsigned)k < l) {
-    cr[k] = rt[RTAB_IAS + k] * a[k];                                   // dct.c:146-151 / :166-172
-    ci[k] = rt[RTAB_IAX + k] * a[k];
-    if ((l & 1) && k >= 1) {                                           // dct.c:152-153
-      cr[l + k] = rt[RTAB_IAX + k] * a[l - k];
-      ci[l + k] = -(rt[RTAB_IAS + k] * a[l - k]);
-    }
-  }
+  if (k < l) short_inv_spread(cr, ci, a, p.rtab, l, k);
   __syncthreads();
-  if ((unsigned)k < l) {
-    const int L = (int)l;
-    const int s = (l & 1) ? k : ((k & 1) ? L - 1 - (k >> 1) : (k >> 1));   // dct.c:189-199
-    T acc = T(0);
-    for (int j = 0; j < N; j++) {
-      const int tt = (s * j) % N;
-      acc = acc + (cr[j] * rt[RTAB_WR + tt] - ci[j] * rt[RTAB_WI + tt]);
-    }
-    T val = (l & 1) ? (acc / (T)L) / T(2) : acc / (T)L;                // dct.c:163 / :185
+  if (k < l) {
+    T val = short_inv_sum(cr, ci, p.rtab, l, k);
     if (p.sf != T(1)) val = val * p.sf;
     const size_t e = base + (size_t)k;
     if (e >= p.lo && e < p.hi) p.out[e - p.lo] = val;

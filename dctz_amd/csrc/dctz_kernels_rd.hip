@@ -145,8 +145,6 @@ __global__ __launch_bounds__(64) void k_rd_probe_rem(RdParams<T> p, int l, unsig
   __shared__ T v[128];
   const int k = threadIdx.x;
   const size_t base = (size_t)p.nfull * 64;
-  const T* rt = p.rtab;
-  const int N = (l & 1) ? 2 * l : l;
   const T sf = p.sf;
   const bool SCALE = (sf != T(1));
   FastDiv<T> sfd;
@@ -156,21 +154,11 @@ __global__ __launch_bounds__(64) void k_rd_probe_rem(RdParams<T> p, int l, unsig
     T a = p.x[base + k];
     mn = (double)a; mx = (double)a;
     if (SCALE) a = sfd.div(a);
-    if (l & 1) { v[k] = a; v[l + (l - 1 - k)] = a; }               // dct.c:61-64
-    else if (k & 1) v[l - 1 - (k >> 1)] = a;                       // dct.c:75-83
-    else v[k >> 1] = a;
+    short_fwd_fill(v, l, k, a);
   }
   __syncthreads();
   T coef = T(0);
-  if (k < l) {
-    T sr = T(0), si = T(0);
-    for (int j = 0; j < N; j++) {
-      const int tt = (j * k) % N;
-      sr = sr + v[j] * rt[RTAB_WR + tt];
-      si = si + v[j] * rt[RTAB_WI + tt];
-    }
-    coef = rt[RTAB_AS + k] * sr + rt[RTAB_AX + k] * si;            // dct.c:100-102 (Im V = -si)
-  }
+  if (k < l) coef = short_fwd_sum(v, p.rtab, short_dft_len(l), k);
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) { mn = fmin(mn, __shfl_xor(mn, d)); mx = fmax(mx, __shfl_xor(mx, d)); }
   double* row = p.slab + (size_t)row_at * RD_SLOT;
