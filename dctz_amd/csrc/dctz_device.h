@@ -521,6 +521,67 @@ void launch_ac_index(const uint8_t* bin, unsigned n, unsigned* idx, unsigned* wg
 template <typename T> int range_occupancy(int mode);
 template <typename T> void launch_decompress_range(const RangeParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s);
 
+// A box of an array in C order, in its canonical form (dctz_shim.hip: canonical_box): at most BOX_ND dimensions, padded in
+// front with dimensions of size 1.  The flat order of the array restricted to the box IS the box's own C order, so the box
+// elements in front of a flat position p are exactly the output positions in front of its first element at or behind p:
+// rank() counts them, and the box elements of a flat interval [a, b) fill the output positions [rank(a), rank(b)).
+constexpr int BOX_ND = 4;
+struct BoxGeo {
+  unsigned dim[BOX_ND], lo[BOX_ND], ext[BOX_ND];
+  unsigned step[BOX_ND];           // 64 in the mixed radix of ext: what the box coordinates of an output position advance by per wave row
+  unsigned fstep, wrap[BOX_ND];    // ... and its flat position: by fstep, plus wrap[d] whenever coordinate d wraps and carries into d - 1
+                                   // (stride[d - 1] - ext[d] * stride[d]; modulo 2^32 like every sum of them; wrap[0] unused)
+  __host__ __device__ void coords(unsigned p, unsigned (&c)[BOX_ND]) const {      // p <= prod dim; c[0] = dim[0] at the end
+    for (int d = BOX_ND - 1; d > 0; d--) { const unsigned q = p / dim[d]; c[d] = p - q * dim[d]; p = q; }
+    c[0] = p;
+  }
+  __host__ __device__ unsigned rank(unsigned p) const {
+    unsigned c[BOX_ND];
+    coords(p, c);
+    unsigned r = 0;
+    bool on = true;                // the coordinates in front of d are all inside the box
+    for (int d = 0; d < BOX_ND; d++) {
+      unsigned k = c[d] > lo[d] ? c[d] - lo[d] : 0u;
+      const bool in = c[d] >= lo[d] && k < ext[d];
+      if (k > ext[d]) k = ext[d];
+      r = r * ext[d] + (on ? k : 0u);
+      on = on && in;
+    }
+    return r;
+  }
+  // flat position in the array of output position o (< prod ext), and o's box coordinates
+  __host__ __device__ unsigned flat_of(unsigned o, unsigned (&b)[BOX_ND]) const {
+    for (int d = BOX_ND - 1; d > 0; d--) { const unsigned q = o / ext[d]; b[d] = o - q * ext[d]; o = q; }
+    b[0] = o;
+    return flat(b);
+  }
+  __host__ __device__ unsigned flat(const unsigned (&b)[BOX_ND]) const {
+    unsigned f = 0;
+    for (int d = 0; d < BOX_ND; d++) f = f * dim[d] + lo[d] + b[d];
+    return f;
+  }
+};
+// Box decode (dctz_kernels_box.hip: k_decompress_box, k_decompress_box_rem).  The streams and the index describe the whole
+// array as for RangeParams; [t0, t1) are the candidate tiles (those of the first and the last box element).
+template <typename T>
+struct BoxParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[t], idx[t + 1] of hit tiles are read
+  T* out;                          // prod ext elements
+  const T* tab;
+  const T* rtab;
+  const T* qtab;
+  Ctl* ctl;                        // error = 2: as RangeParams
+  unsigned n, nfull, t0, t1, ac_count;
+  T sf, bin_width, range_min, range_max;
+  double eb;
+  BoxGeo box;
+};
+template <typename T> int box_occupancy(int mode);
+template <typename T> void launch_decompress_box(const BoxParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

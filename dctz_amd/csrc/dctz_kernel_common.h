@@ -687,6 +687,80 @@ __device__ __forceinline__ T short_inv_sum(const T* cr, const T* ci, const T* rt
   return (l & 1) ? (acc / (T)l) / T(2) : acc / (T)l;                   // dct.c:163 / :185
 }
 
+// ---- one tile for random access (k_decompress_range, k_decompress_box) ------------------------------------------------------
+// LDS image of a reconstructed tile: block b at elements [b * STRIDE, b * STRIDE + 64), one 16-byte pad behind every
+// block, so that the lanes' 16-byte writes of their own blocks (rows STRIDE elements apart) and the reads in output order
+// (consecutive elements across the lanes) both spread over the banks.  The tile's exact coefficients (up to 63 * 64
+// floats) are staged in the same array before the image is written.
+template <typename T> struct RaGeo {
+  static constexpr int EPV = Traits<T>::EPV;
+  static constexpr int STRIDE = 64 + EPV;
+  static constexpr int BYTES = TILE_BLKS * STRIDE * (int)sizeof(T);
+  static_assert(BYTES >= 63 * 64 * 4, "a dense tile's exact coefficients fit the image");
+  // element e of the tile in the image
+  __device__ static unsigned at(unsigned e) { return e + (e >> 6) * (unsigned)EPV; }
+};
+
+// Tile t of the array into the image, by one wave (lane b = block b): flags and wave scan, the index check, staging of
+// AC_exact[idx[t], idx[t + 1]), de-quantisation, inverse transform, de-scaling -- the whole-array decoders' functions in
+// their order.  P is RangeParams<T> or BoxParams<T>.  False: the index disagrees with the tile's own flags or leaves the
+// caller's AC_exact; nothing of AC_exact was read and the image is not written.  True: the image is complete behind the
+// closing barrier.  The short last block only contributes its flags (its elements are the _rem kernels').
+template <typename T, int MODE, typename P>
+__device__ __forceinline__ bool ra_tile_image(const P& p, const unsigned t, const int lane, const CTab<T> tab, const QtLanes<T>& qtl,
+                                              const bool scale, unsigned char* lds) {
+  using G = RaGeo<T>;
+  using Vec = typename Traits<T>::Vec;
+  constexpr int EPV = G::EPV;
+  float* const stage = reinterpret_cast<float*>(lds);
+  T* const img = reinterpret_cast<T*>(lds);
+  const unsigned rem = p.n - p.nfull * 64u;
+  const unsigned full_end = p.nfull * 64u;
+  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)lane;
+  const bool full = blk < p.nfull;
+  unsigned w[16];
+  float dcv = 0.f;
+  unsigned cnt = 0;
+  if (full) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u32x4 v = src[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    dcv = p.dc[blk];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] = 0u;
+    // the short block's flags count for the tile (its elements are the _rem kernel's: this lane stores nothing)
+    if (blk == p.nfull && rem)
+      for (unsigned j = 1; j < rem; j++) cnt += p.bin[(size_t)full_end + j] == 255u ? 1u : 0u;
+  }
+  cnt += block_flag_count(w);
+  const unsigned incl = wave_incl_scan(cnt);
+  const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+  const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
+  // the index must agree with the tile's own flags and stay inside the caller's AC_exact (else: refused, nothing read)
+  if (s1 < s0 || s1 - s0 != tot || s1 > p.ac_count) return false;
+  for (unsigned i = (unsigned)lane; i < tot; i += 64u) stage[i] = p.ac[s0 + i];
+  __syncthreads();
+  unsigned ptr = incl - cnt;                                           // this block's first exact coefficient in the tile
+  T x[64];
+  dequantise_positional<T, MODE, false>(x, w, dcv, ptr, stage, (unsigned)(63 * 64 - 1), BinCentres<T, true>{p.bin_width, nullptr},
+                                        [&](int j) { return qtl.at(j); }, p.eb, p.range_min, p.range_max);
+  __syncthreads();                                                     // the staged coefficients are consumed
+  block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
+  if (scale) {
+#pragma unroll
+    for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                   // dctz-decomp-lib.c:494-511
+  }
+#pragma unroll
+  for (int ch = 0; ch < 64 / EPV; ch++)
+    *reinterpret_cast<Vec*>(img + lane * G::STRIDE + ch * EPV) = Traits<T>::pack(&x[ch * EPV]);
+  __syncthreads();
+  return true;
+}
+
 
 // FastDiv's windows on the host's terms (dctz_shim.hip: divisor_in_window / value_in_window): unbiased exponent of a
 // finite non-zero double in [lo, hi)

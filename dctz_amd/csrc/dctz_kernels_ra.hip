@@ -115,78 +115,26 @@ void launch_ac_index(const uint8_t* bin, unsigned n, unsigned* idx, unsigned* wg
 }
 
 // ============================================================== range decode ==
-// LDS image of a reconstructed tile: block b at elements [b * STRIDE, b * STRIDE + 64), one 16-byte pad behind every
-// block, so that the lanes' 16-byte writes of their own blocks (rows STRIDE elements apart) and the reads in output order
-// (consecutive elements across the lanes) both spread over the banks.  The tile's exact coefficients (up to 63 * 64
-// floats) are staged in the same array before the image is written.
-template <typename T> struct RaGeo {
-  static constexpr int EPV = Traits<T>::EPV;
-  static constexpr int STRIDE = 64 + EPV;
-  static constexpr int BYTES = TILE_BLKS * STRIDE * (int)sizeof(T);
-  static_assert(BYTES >= 63 * 64 * 4, "a dense tile's exact coefficients fit the image");
-};
-
+// The tile itself (flags, index check, staging, de-quantisation, transform, LDS image) is ra_tile_image's
+// (dctz_kernel_common.h), shared with k_decompress_box.
 template <typename T, int MODE>
 __global__ __launch_bounds__(64) void k_decompress_range(RangeParams<T> p) {
   using G = RaGeo<T>;
   using Vec = typename Traits<T>::Vec;
   constexpr int EPV = G::EPV;
   __shared__ __attribute__((aligned(16))) unsigned char lds[G::BYTES];
-  float* const stage = reinterpret_cast<float*>(lds);
   T* const img = reinterpret_cast<T*>(lds);
   const int lane = threadIdx.x;
   const CTab<T> tab = as_ctab<T>(p.tab);
   QtLanes<T> qtl{};
   if (MODE == DCTZHIP_QT) qtl.load(p.qtab, lane);
   const bool scale = (p.sf != T(1));                                   // dctz-decomp-lib.c:496 / :505
-  const unsigned rem = p.n - p.nfull * 64u;
   const unsigned full_end = p.nfull * 64u;
   bool bad = false;
   for (unsigned t = p.t0 + blockIdx.x; t < p.t1; t += gridDim.x) {
     // (a compiler barrier per trip: keeps the transform's scalar constant loads inside the loop, as in k_rd_probe)
     asm volatile("" ::: "memory");
-    const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)lane;
-    const bool full = blk < p.nfull;
-    unsigned w[16];
-    float dcv = 0.f;
-    unsigned cnt = 0;
-    if (full) {
-      const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const u32x4 v = src[i];
-        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-      }
-      dcv = p.dc[blk];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; i++) w[i] = 0u;
-      // the short block's flags count for the tile (its elements are k_decompress_range_rem's: this lane stores nothing)
-      if (blk == p.nfull && rem)
-        for (unsigned j = 1; j < rem; j++) cnt += p.bin[(size_t)full_end + j] == 255u ? 1u : 0u;
-    }
-    cnt += block_flag_count(w);
-    const unsigned incl = wave_incl_scan(cnt);
-    const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-    const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
-    // the index must agree with the tile's own flags and stay inside the caller's AC_exact (else: refused, nothing read)
-    if (s1 < s0 || s1 - s0 != tot || s1 > p.ac_count) { bad = true; continue; }
-    for (unsigned i = (unsigned)lane; i < tot; i += 64u) stage[i] = p.ac[s0 + i];
-    __syncthreads();
-    unsigned ptr = incl - cnt;                                         // this block's first exact coefficient in the tile
-    T x[64];
-    dequantise_positional<T, MODE, false>(x, w, dcv, ptr, stage, (unsigned)(63 * 64 - 1), BinCentres<T, true>{p.bin_width, nullptr},
-                                          [&](int j) { return qtl.at(j); }, p.eb, p.range_min, p.range_max);
-    __syncthreads();                                                   // the staged coefficients are consumed
-    block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
-    if (scale) {
-#pragma unroll
-      for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                 // dctz-decomp-lib.c:494-511
-    }
-#pragma unroll
-    for (int ch = 0; ch < 64 / EPV; ch++)
-      *reinterpret_cast<Vec*>(img + lane * G::STRIDE + ch * EPV) = Traits<T>::pack(&x[ch * EPV]);
-    __syncthreads();
+    if (!ra_tile_image<T, MODE>(p, t, lane, tab, qtl, scale, lds)) { bad = true; continue; }
     // the tile's whole-block elements inside [lo, hi) -> d_out, in output order
     const unsigned ts = t * (unsigned)TILE_ELEMS;
     const unsigned A = max(p.lo, ts), B = min(p.hi, min(ts + (unsigned)TILE_ELEMS, full_end));
@@ -206,7 +154,7 @@ __global__ __launch_bounds__(64) void k_decompress_range(RangeParams<T> p) {
             const unsigned o = q * EPV + (unsigned)k;
             in[k] = o >= oa && o < ob;
             const unsigned e = in[k] ? o + p.lo - ts : 0u;             // element of the tile
-            v[k] = img[e + (e >> 6) * EPV];
+            v[k] = img[G::at(e)];
           }
           const int at = (int)((q - qf) * 16u);
           bool whole = true;

@@ -73,6 +73,8 @@ struct dctzhip_ctx {
   unsigned* ix_part = nullptr;      // dctzhip_ac_index: flag counts per workgroup of k_ac_index, then their exclusive prefix
   size_t ix_part_cap = 0;           // entries
   int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
+  int box_occ[2][2] = {{0, 0}, {0, 0}};  // dctzhip_decompress_box: the same of k_decompress_box
+  unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   int dec_il = 1;                   // 0: k_decompress with a contiguous tile range per workgroup; 1: interleaved for fp64 EC; 2: for all (DCTZHIP_DEC_IL)
   size_t qcnt_cap = 0;              // tiles the two hold
   void* qt_item = nullptr;
@@ -401,6 +403,8 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 8: *value = c->b_spec_items; break;         // batch items that took their scaling factor from a sample
     case 9: *value = c->b_spec_misses; break;        // ... whose guess the true statistics refused (done again on their own)
     case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
+    case 11: *value = c->box_grid; break;            // dctzhip_decompress_box, last call: workgroups of k_decompress_box
+    case 12: *value = c->box_tiles; break;           // ... candidate tiles (more than workgroups: the grid-stride loop ran)
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
   return DCTZHIP_OK;
@@ -1997,6 +2001,132 @@ extern "C" int dctzhip_decompress_range(dctzhip_ctx* c, const void* d_bin, const
                                              (double*)d_out)
              : decompress_range_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, lo, hi,
                                             (float*)d_out);
+}
+
+// ---- a box of an N-D array (include/dctz_hip.h; dctz_kernels_box.hip) -------------------------------------------
+// The box in its canonical form: dimensions of size 1 drop out, a dimension the box covers completely merges into the
+// one in front of it (coordinates (a, b) -> a D + b, the box's [lo, hi) x [0, D) -> [lo D, hi D): the runs become as long
+// as the box allows), the rest is padded in front with dimensions of size 1.  The arguments have been checked.
+static BoxGeo canonical_box(int ndim, const size_t* dims, const size_t* lo, const size_t* hi) {
+  size_t d[DCTZHIP_BOX_MAXDIM], l[DCTZHIP_BOX_MAXDIM], h[DCTZHIP_BOX_MAXDIM];
+  int k = 0;
+  for (int i = 0; i < ndim; i++) {
+    if (dims[i] == 1) continue;
+    if (k > 0 && lo[i] == 0 && hi[i] == dims[i]) { d[k - 1] *= dims[i]; l[k - 1] *= dims[i]; h[k - 1] *= dims[i]; continue; }
+    d[k] = dims[i]; l[k] = lo[i]; h[k] = hi[i]; k++;
+  }
+  BoxGeo g;
+  for (int i = 0; i < BOX_ND; i++) {
+    const int j = i - (BOX_ND - k);
+    g.dim[i] = j >= 0 ? (unsigned)d[j] : 1u;
+    g.lo[i] = j >= 0 ? (unsigned)l[j] : 0u;
+    g.ext[i] = j >= 0 ? (unsigned)(h[j] - l[j]) : 1u;
+  }
+  unsigned q = 64u;                                  // a wave row of output positions in the mixed radix of ext
+  for (int i = BOX_ND - 1; i > 0; i--) { g.step[i] = q % g.ext[i]; q /= g.ext[i]; }
+  g.step[0] = q;
+  unsigned stride[BOX_ND];
+  stride[BOX_ND - 1] = 1u;
+  for (int i = BOX_ND - 1; i > 0; i--) stride[i - 1] = stride[i] * g.dim[i];
+  g.fstep = 0u;
+  for (int i = 0; i < BOX_ND; i++) g.fstep += g.step[i] * stride[i];
+  g.wrap[0] = 0u;
+  for (int i = 1; i < BOX_ND; i++) g.wrap[i] = stride[i - 1] - g.ext[i] * stride[i];
+  return g;
+}
+
+template <typename T>
+static int decompress_box_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                               const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
+                               const BoxGeo& box, size_t first, size_t last, T* d_out) {
+  hipStream_t s = c->stream;
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  const unsigned t0 = (unsigned)(first / TILE_ELEMS), t1 = (unsigned)(last / TILE_ELEMS + 1);
+  const bool with_rem = rem && box.rank((unsigned)n) != box.rank(nfull * 64u);    // an element of the short block lies in the box
+  if (c->ctl_dirty) HIPCHK(c, hipMemsetAsync(c->ctl, 0, sizeof(Ctl), s));
+  c->ctl_dirty = 1;                                 // until this call's error word has been read back clean
+  if (mode == DCTZHIP_QT) {
+    // staged through pinned memory that the next call may rewrite: this call ends with a stream synchronisation
+    T* hq = reinterpret_cast<T*>(c->h_pin + PIN_TAB + sizeof(double) * RTAB_SIZE);
+    memcpy(hq, qtable_host, sizeof(T) * 64);
+    HIPCHK(c, hipMemcpyAsync(c->qtab, hq, sizeof(T) * 64, hipMemcpyHostToDevice, s));
+  }
+  if (with_rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+  BoxParams<T> p;
+  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index; p.out = d_out;
+  p.tab = tab_of<T>(c); p.rtab = reinterpret_cast<const T*>(c->rtab); p.qtab = reinterpret_cast<const T*>(c->qtab);
+  p.ctl = c->ctl;
+  p.n = (unsigned)n; p.nfull = nfull; p.t0 = t0; p.t1 = t1; p.ac_count = ac_count;
+  p.sf = (T)sf;
+  p.bin_width = (T)((T)eb * 2 * 1.0);               // as decompress_impl (binning.c:17 / :37)
+  p.range_max = (T)(eb * DCTZHIP_NBINS);
+  p.range_min = (T)(-eb * DCTZHIP_NBINS);
+  p.eb = eb;
+  p.box = box;
+  // one single-wave workgroup per candidate tile, persistent only beyond what is resident at once
+  int& occ = c->box_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
+  if (occ == 0) occ = std::max(box_occupancy<T>(mode), 1);
+  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+  const unsigned tiles = t1 - t0;
+  const int grid = (int)(tiles < resident ? tiles : resident);
+  c->box_grid = (unsigned)grid; c->box_tiles = tiles;
+  launch_decompress_box<T>(p, mode, grid, with_rem, s);
+  SET_LAST(c, 1, "k_decompress_box<%s, %d>", tname<T>(), mode);
+  HIPCHK(c, hipGetLastError());
+  Ctl* hc = reinterpret_cast<Ctl*>(c->h_pin + PIN_CTL);
+  HIPCHK(c, hipMemcpyAsync(hc, c->ctl, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (!hc->error) c->ctl_dirty = 0;
+  if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
+  if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                      const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf,
+                                      int mode, int ndim, const size_t* dims, const size_t* lo, const size_t* hi, void* d_out) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
+  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: null dims, lo or hi");
+  size_t prod = 1, cnt = 1, first = 0, last = 0;
+  for (int i = 0; i < ndim; i++) {
+    // (n <= INT_MAX: a product that stays <= n cannot overflow)
+    if (dims[i] == 0 || dims[i] > n / prod) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: the product of dims is not n = %zu", n);
+    prod *= dims[i];
+    if (lo[i] >= hi[i] || hi[i] > dims[i])
+      return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: [%zu, %zu) is not inside dimension %d of %zu", lo[i], hi[i], i, dims[i]);
+    cnt *= hi[i] - lo[i];
+    first = first * dims[i] + lo[i];
+    last = last * dims[i] + (hi[i] - 1);
+  }
+  if (prod != n) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: the product of dims is not n = %zu", n);
+  if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    // what the call may read: what dctzhip_decompress_range reads for [first box element, last box element + 1)
+    const size_t t0 = first / TILE_ELEMS, t1 = last / TILE_ELEMS + 1;
+    const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n, t1 * (size_t)TILE_ELEMS);
+    Span sp[5];
+    size_t m = 0;
+    add_span(sp, &m, (const uint8_t*)d_bin + b0, b1 - b0, SPAN_READ, 0);
+    add_span(sp, &m, d_dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_decompress_box", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const BoxGeo box = canonical_box(ndim, dims, lo, hi);
+  return (dtype == DCTZHIP_F64)
+             ? decompress_box_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, box, first,
+                                           last, (double*)d_out)
+             : decompress_box_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, box, first,
+                                          last, (float*)d_out);
 }
 
 // ---- multi-dimensional blocks (include/dctz_hip.h) -------------------------------------------------

@@ -1699,7 +1699,7 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   return 1;
 }
 
-/* ---------------------------------------------------- dctz_decompress_range -- */
+/* ------------------------------- dctz_decompress_range, dctz_decompress_box -- */
 /* The first `want` bytes of one section into dst.  Indexed (sizes != NULL): only the chunks that hold them, side by side
  * on host threads (dst has room for whole chunks: min(raw, chunks * chunk) bytes); a chunk that does not inflate sends the
  * section to the streaming inflate.  Otherwise one inflate that stops once `want` bytes are out.  Returns the bytes made. */
@@ -1742,13 +1742,33 @@ static size_t inflate_prefix(const unsigned char *sec, unsigned int zlen, size_t
   return done;
 }
 
-int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
+/* dctz_decompress_range (ndim == 0: elements [lo, hi)) and dctz_decompress_box (ndim >= 1: the box; [lo, hi) becomes
+ * [first box element, last box element + 1)): the prefix of the sections that span needs, its index, one device call,
+ * and only the wanted elements copied back. */
+static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, t_var *var_r) {
   const double t_begin = now_s();
   dzc_view v;
   dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
   const size_t ts = v.ts, n = v.n, nblk = v.nblk;
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   const unsigned int cnt = v.cnt;
+  size_t out_elems;
+  if (ndim != 0) {
+    if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM || !dims || !blo || !bhi || n == 0) return -1;
+    size_t prod = 1, last = 0;
+    lo = 0; out_elems = 1;
+    for (int i = 0; i < ndim; i++) {
+      if (dims[i] == 0 || dims[i] > n / prod || blo[i] >= bhi[i] || bhi[i] > dims[i]) return -1;
+      prod *= dims[i];
+      out_elems *= bhi[i] - blo[i];
+      lo = lo * dims[i] + blo[i];
+      last = last * dims[i] + (bhi[i] - 1);
+    }
+    if (prod != n) return -1;
+    hi = last + 1;
+  } else {
+    out_elems = hi - lo;
+  }
   if (v.nd != 0 || n == 0 || lo >= hi || hi > n) return -1;   /* DZND: element order is not block order */
   const size_t S = DCTZHIP_INDEX_STRIDE;
   const size_t t1 = (hi + S - 1) / S;                        /* the range's tiles end here */
@@ -1790,19 +1810,30 @@ int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) {
     t_h2d += now_s() - t0;
   }
   t0 = now_s();
-  grow(&g_dev.out, &g_dev.out_cap, (hi - lo) * ts);
-  const int rc = dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need, (const uint32_t *)g_dev.idx,
-                                          qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi, g_dev.out);
+  grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
+  const int rc = ndim == 0 ? dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
+                                                      (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi,
+                                                      g_dev.out)
+                           : dctzhip_decompress_box(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
+                                                    (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims,
+                                                    blo, bhi, g_dev.out);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
-  if (rc != DCTZHIP_OK) die("dctzhip_decompress_range");
+  if (rc != DCTZHIP_OK) die(ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
   const double t1s = now_s();
-  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, (hi - lo) * ts) != DCTZHIP_OK) die("D2H output");
+  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
   g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
   g_times.total_s = now_s() - t_begin;
   ret = 1;
 out:
   for (int i = 0; i < 3; i++) free(ix_sizes[i]);
   return ret;
+}
+
+int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) { return decompress_part(var_z, lo, hi, 0, NULL, NULL, NULL, var_r); }
+
+int dctz_decompress_box(t_var *var_z, int ndim, const size_t *dims, const size_t *lo, const size_t *hi, t_var *var_r) {
+  if (ndim == 0) return -1;
+  return decompress_part(var_z, 0, 0, ndim, dims, lo, hi, var_r);
 }
 
 /* ------------------------------------------------------ calc_data_stat ----- */

@@ -103,6 +103,9 @@ _PROTOS = {
     "dctzhip_decompress_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_size_t,
                                            C.c_size_t, C.c_void_p]),
+    "dctzhip_decompress_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "dctzhip_set_blocking": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_compress_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BatchCItem), C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_decompress_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BatchDItem), C.c_int, C.POINTER(C.c_int)]),
@@ -378,6 +381,30 @@ class Context:
             mode, int(lo), int(hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_range")
         return dst
+
+    def decompress_box(self, out, cnt, dims, dtype, eb, sf, lo, hi, index, mode=EC, qtable=None, dst=None):
+        """The box lo[i] <= c[i] < hi[i] of what decompress() rebuilds from the same arguments, seen as an array of shape
+        `dims` in C order (1 to 4 dimensions), bit for bit; `index` from ac_index().  Returns dst shaped hi - lo."""
+        t = self.torch
+        self._bind_stream()
+        dims, lo, hi = [int(v) for v in dims], [int(v) for v in lo], [int(v) for v in hi]
+        nd = len(dims)
+        assert len(lo) == nd and len(hi) == nd
+        n = int(np.prod(dims, dtype=np.int64)) if nd else 0
+        shape = [max(h - l, 0) for l, h in zip(lo, hi)]
+        if dst is None:
+            dst = t.empty(shape, dtype=dtype, device=self.device)
+        q = None
+        if mode == QT:
+            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
+            assert q.size == 64
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_decompress_box(
+            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
+            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb), float(sf),
+            mode, nd, arr(*dims), arr(*lo), arr(*hi), dst.data_ptr())
+        self._check(rc, "dctzhip_decompress_box")
+        return dst.view(shape)
 
     # ---- batches of arrays (include/dctz_hip.h: dctzhip_compress_batch / dctzhip_decompress_batch) ----
     def compress_batch(self, xs, ebs, mode=EC, outs=None, scaled=None, prepared=None):

@@ -154,6 +154,14 @@ int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double 
  * chunk index the chunks that lie wholly beyond it are not inflated at all.  Nothing of the container is validated
  * beyond that. */
 int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r);
+/* A box of a container (ADDITION, EC and QT builds): the array as an ndim-dimensional array in C order (1 <= ndim <= 4,
+ * prod dims = N, last dimension fastest), elements lo[i] <= c[i] < hi[i], dense and in C order into var_r->buf (allocated
+ * by the caller: prod (hi[i] - lo[i]) elements).  Each is bit for bit the element dctz_decompress reconstructs at those
+ * coordinates.  Returns 1, or -1 for a bad box (ndim, a null pointer, lo[i] >= hi[i], hi[i] > dims[i]), prod dims != N, a
+ * DZND container and streams that disagree with each other -- dctz_decompress_range's return values.  It inflates what
+ * dctz_decompress_range(first box element, last box element + 1) inflates and no more; on the device only the tiles that
+ * hold box elements are decoded, once each (include/dctz_hip.h: dctzhip_decompress_box), and only the box is copied back. */
+int dctz_decompress_box(t_var *var_z, int ndim, const size_t *dims, const size_t *lo, const size_t *hi, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

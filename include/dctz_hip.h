@@ -131,7 +131,8 @@ int dctzhip_set_split(dctzhip_ctx *ctx, int on);
 /* (tests and tools)  Counters of the context -- which: 0 one-launch calls, 1 one-launch launches that gave up (run again
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
- * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr -- and knobs that
+ * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr, 11 / 12 workgroups and
+ * candidate tiles of the last dctzhip_decompress_box call (12 > 11: its grid-stride loop ran) -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
  * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
@@ -297,6 +298,31 @@ int dctzhip_ac_index(dctzhip_ctx *ctx, const void *d_bin_index, size_t n, uint32
 int dctzhip_decompress_range(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
                              uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
                              double error_bound, double sf, int mode, size_t lo, size_t hi, void *d_out);
+/* A rectangular box of the array seen as an ndim-dimensional array in C order (last dimension fastest), 1 <= ndim <=
+ * DCTZHIP_BOX_MAXDIM, prod dims == n: the elements lo[i] <= c[i] < hi[i] in every dimension.  The streams, d_index,
+ * ac_count, qtable_host, n, dtype, error_bound, sf and mode are dctzhip_decompress_range's: they describe the WHOLE array,
+ * compressed in the ordinary flat 64-element blocks (dctzhip_compress), not in the tiles of dctzhip_compress_nd.
+ * Fortran order: reverse dims, lo and hi.
+ *   d_out       receives prod (hi[i] - lo[i]) elements, dense, in C order; each is, bit for bit, the element that
+ *               dctzhip_decompress writes at the same coordinates (EC and QT, fp32 and fp64, the short last block
+ *               included).  ndim == 1 gives the bytes of dctzhip_decompress_range(lo[0], hi[0]).
+ *   locality    a tile (4096 consecutive elements) is HIT if at least one of its elements lies in the box.  The call reads
+ *               the bin ids and DC values of hit tiles only, their index entries idx[t] and idx[t + 1] only, and
+ *               AC_exact[idx[t], idx[t + 1]) of hit tiles only; it writes nothing outside d_out[0, prod ext).  A hit tile
+ *               is decoded once however many rows of the box cross it: the cost follows the number of hit tiles, not n and
+ *               not the number of rows.
+ *   refusals    before any launch, DCTZHIP_E_ARG for ndim outside 1 .. 4, a null dims, lo or hi, a zero extent, prod dims
+ *               != n, lo[i] >= hi[i] or hi[i] > dims[i], the pointer and alignment rules of dctzhip_decompress_range, and
+ *               a d_out that overlaps what dctzhip_decompress_range may read for [first box element, last box element +
+ *               1).  On the device, for hit tiles only: the flags of tile t must number idx[t + 1] - idx[t], and idx[t +
+ *               1] <= ac_count; if not the tile reads no AC_exact and the call returns DCTZHIP_E_ARG, the output is
+ *               undefined and the context stays usable.
+ * Returns once that check is known, as dctzhip_decompress_range does. */
+#define DCTZHIP_BOX_MAXDIM 4
+int dctzhip_decompress_box(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                           uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
+                           double error_bound, double sf, int mode, int ndim, const size_t *dims, const size_t *lo,
+                           const size_t *hi, void *d_out);
 
 /* ---- batches of arrays ------------------------------------------------------ */
 /* The reference's own workloads are LISTS of small arrays, one dctz_compress() call and one process each

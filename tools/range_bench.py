@@ -8,6 +8,10 @@
   --what full    [0, n)
   --what dropin  dctz_decompress_range of 2^21 elements from the shard's 1 GiB DZIX container (DCTZ_ZLIB_GPU=1)
                  against dctz_decompress of the whole container (wall clock, host buffers)
+  --what box     a box of the shard through --via box (dctzhip_decompress_box: k_decompress_box), --via ranges (one
+                 dctzhip_decompress_range call per run of the box, into the right offsets) or --via slice (whole decode +
+                 torch slice copy); --box brick (64^3 at 224^3) | zplane ([100:101, :, :]) | xplane ([:, :, 100:101]) |
+                 full | c2 (the 1800 x 3600 fp32 field, window [600:856, 1200:1712])
 Every other run also times dctzhip_decompress of the whole shard.  Wall-clock medians go to stdout as one JSON line; for device
 times run one --what per process under `rocprofv3 --kernel-trace --stats -- python tools/range_bench.py --what ...`."""
 import argparse
@@ -22,7 +26,9 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin"], required=True)
+    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin", "box"], required=True)
+    ap.add_argument("--box", choices=["brick", "zplane", "xplane", "full", "c2"], default="brick")
+    ap.add_argument("--via", choices=["box", "ranges", "slice"], default="box")
     ap.add_argument("--n", type=int, default=512, help="edge of the cube")
     ap.add_argument("--reps", type=int, default=20)
     a = ap.parse_args()
@@ -33,6 +39,8 @@ def main():
 
     if a.what == "dropin":
         return dropin(a, W)
+    if a.what == "box":
+        return box(a, W)
     ctx = dctz_amd.Context(0)
     x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device)
     n = x.numel()
@@ -72,6 +80,82 @@ def main():
         assert torch.equal(dst.view(torch.int64), full[rng[0]:rng[1]].view(torch.int64))
     print(json.dumps({"what": a.what, "n": n, "cnt": info.cnt, "range": rng, "wall_ms_decompress": round(ms_full, 4),
                       "wall_ms_" + a.what: round(ms_what, 4)}))
+    ctx.close()
+
+
+def box(a, W):
+    import numpy as np
+    import torch
+    import dctz_amd
+
+    ctx = dctz_amd.Context(0)
+    if a.box == "c2":
+        x = torch.from_numpy(np.ascontiguousarray(W.c2(), dtype=np.float32).reshape(-1)).to(ctx.device)
+        dims, tdt = (1800, 3600), torch.float32
+        lo, hi = (600, 1200), (856, 1712)
+    else:
+        x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device).reshape(-1)
+        e, tdt = a.n, torch.float64
+        dims = (e, e, e)
+        lo, hi = {"brick": ((224 * e // 512,) * 3, (224 * e // 512 + 64,) * 3), "zplane": ((100, 0, 0), (101, e, e)),
+                  "xplane": ((0, 0, 100), (e, e, 101)), "full": ((0, 0, 0), dims)}[a.box]
+    n = x.numel()
+    eb = 1e-3
+    out, info = ctx.compress(x, eb, dctz_amd.EC)
+    del x
+    full = torch.empty(n, dtype=tdt, device=ctx.device)
+    idx, tot = ctx.ac_index(out, n)
+    ext = tuple(h - l for l, h in zip(lo, hi))
+    dst = torch.empty(ext, dtype=tdt, device=ctx.device)
+    sl = tuple(slice(l, h) for l, h in zip(lo, hi))
+    # the box as runs of the flat order: (flat start, length) per row of the box, the fastest dimension as long as it is
+    starts = np.ravel_multi_index(np.meshgrid(*[np.arange(l, h) for l, h in zip(lo[:-1], hi[:-1])], [lo[-1]], indexing="ij"), dims).reshape(-1)
+    run = ext[-1]
+    flat = dst.view(-1)
+
+    def t_full():
+        ctx.decompress(out, info.cnt, n, tdt, eb, info.sf, dctz_amd.EC, dst=full)
+
+    def t_box():
+        ctx.decompress_box(out, info.cnt, dims, tdt, eb, info.sf, lo, hi, idx, dctz_amd.EC, dst=dst)
+
+    def t_ranges():
+        for k, s0 in enumerate(starts):
+            ctx.decompress_range(out, info.cnt, n, tdt, eb, info.sf, int(s0), int(s0) + run, idx, dctz_amd.EC, dst=flat[k * run:(k + 1) * run])
+
+    def t_slice():
+        t_full()
+        dst.copy_(full.view(dims)[sl])
+
+    f_what = {"box": t_box, "ranges": t_ranges, "slice": t_slice}[a.via]
+    if a.via == "ranges" and (run * dst.element_size()) % 16:
+        raise SystemExit("the runs' outputs are not 16-byte aligned: dctzhip_decompress_range refuses them")
+
+    def med(f, reps):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    for f in (t_full, f_what):                      # warm-up
+        f()
+    reps = max(3, a.reps // 4) if a.via == "ranges" else a.reps
+    ms_full, ms_what = med(t_full, a.reps), med(f_what, reps)
+    it = torch.int64 if tdt == torch.float64 else torch.int32
+    assert torch.equal(dst.contiguous().view(it), full.view(dims)[sl].contiguous().view(it))
+    m = np.zeros(dims, bool)
+    m[sl] = True
+    fm = np.zeros(-(-n // 4096) * 4096, bool)
+    fm[:n] = m.reshape(-1)
+    hit = fm.reshape(-1, 4096).any(axis=1)
+    t = np.flatnonzero(hit)
+    print(json.dumps({"what": "box", "box": a.box, "via": a.via, "n": n, "cnt": info.cnt, "lo": lo, "hi": hi, "rows": int(starts.size),
+                      "hit_tiles": int(hit.sum()), "candidate_tiles": int(t[-1] - t[0] + 1), "wall_ms_decompress": round(ms_full, 4),
+                      "wall_ms_" + a.via: round(ms_what, 4)}))
     ctx.close()
 
 
