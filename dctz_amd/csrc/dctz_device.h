@@ -582,6 +582,30 @@ struct BoxParams {
 template <typename T> int box_occupancy(int mode);
 template <typename T> void launch_decompress_box(const BoxParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s);
 
+// Box decode of an array compressed in 8 x 8 / 4 x 4 x 4 tiles (dctz_kernels_ndbox.hip: k_decompress_ndbox).  The streams
+// and the index cover n = 64 nblk positions, nfull = nblk (no short block); [t0, t1) are the candidate STREAM tiles (64
+// consecutive blocks each), those of the first and the last block that intersects the box.  A 2-D array sits in the last
+// two axes, axis 0 has extent 1.
+template <typename T>
+struct NdBoxParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[t], idx[t + 1] of hit tiles are read
+  T* out;                          // prod ext elements
+  const T* tab;
+  const T* qtab;
+  Ctl* ctl;                        // error = 2: as RangeParams
+  unsigned n, nfull, t0, t1, ac_count;
+  T sf, bin_width, range_min, range_max;
+  double eb;
+  unsigned nb[3];                  // blocks per axis
+  unsigned lo[3], ext[3];          // the box, in elements
+  BoxGeo blocks;                   // the intersecting blocks, a box of the row-major block grid (dim = nb): rank() is the hit test
+};
+template <typename T> int ndbox_occupancy(int mode, int geom);
+template <typename T> void launch_decompress_ndbox(const NdBoxParams<T>& p, int mode, int geom, int grid, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

@@ -703,13 +703,13 @@ template <typename T> struct RaGeo {
 
 // Tile t of the array into the image, by one wave (lane b = block b): flags and wave scan, the index check, staging of
 // AC_exact[idx[t], idx[t + 1]), de-quantisation, inverse transform, de-scaling -- the whole-array decoders' functions in
-// their order.  P is RangeParams<T> or BoxParams<T>.  False: the index disagrees with the tile's own flags or leaves the
+// their order.  P is RangeParams<T>, BoxParams<T> or NdBoxParams<T>.  False: the index disagrees with the tile's own flags or leaves the
 // caller's AC_exact; nothing of AC_exact was read and the image is not written.  True: the image is complete behind the
 // closing barrier.  The short last block only contributes its flags (its elements are the _rem kernels').
-template <typename T, int MODE, typename P>
+// GEOM: the block transform (k_decompress_ndbox: the tiles of dctzhip_compress_nd); G: the image, RaGeo's members.
+template <typename T, int MODE, int GEOM = GEOM_1D, typename G = RaGeo<T>, typename P>
 __device__ __forceinline__ bool ra_tile_image(const P& p, const unsigned t, const int lane, const CTab<T> tab, const QtLanes<T>& qtl,
                                               const bool scale, unsigned char* lds) {
-  using G = RaGeo<T>;
   using Vec = typename Traits<T>::Vec;
   constexpr int EPV = G::EPV;
   float* const stage = reinterpret_cast<float*>(lds);
@@ -749,7 +749,7 @@ __device__ __forceinline__ bool ra_tile_image(const P& p, const unsigned t, cons
   dequantise_positional<T, MODE, false>(x, w, dcv, ptr, stage, (unsigned)(63 * 64 - 1), BinCentres<T, true>{p.bin_width, nullptr},
                                         [&](int j) { return qtl.at(j); }, p.eb, p.range_min, p.range_max);
   __syncthreads();                                                     // the staged coefficients are consumed
-  block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
+  block_inv<T, CTab<T>, GEOM, (sizeof(T) == 4)>(x, tab);
   if (scale) {
 #pragma unroll
     for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                   // dctz-decomp-lib.c:494-511

@@ -74,6 +74,7 @@ struct dctzhip_ctx {
   size_t ix_part_cap = 0;           // entries
   int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
   int box_occ[2][2] = {{0, 0}, {0, 0}};  // dctzhip_decompress_box: the same of k_decompress_box
+  int ndbox_occ[2][2][2] = {};      // dctzhip_decompress_box_nd: the same of k_decompress_ndbox, [fp64][QT][3-D]
   unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   int dec_il = 1;                   // 0: k_decompress with a contiguous tile range per workgroup; 1: interleaved for fp64 EC; 2: for all (DCTZHIP_DEC_IL)
   size_t qcnt_cap = 0;              // tiles the two hold
@@ -403,7 +404,7 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 8: *value = c->b_spec_items; break;         // batch items that took their scaling factor from a sample
     case 9: *value = c->b_spec_misses; break;        // ... whose guess the true statistics refused (done again on their own)
     case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
-    case 11: *value = c->box_grid; break;            // dctzhip_decompress_box, last call: workgroups of k_decompress_box
+    case 11: *value = c->box_grid; break;            // dctzhip_decompress_box / _box_nd, last call: workgroups of its kernel
     case 12: *value = c->box_tiles; break;           // ... candidate tiles (more than workgroups: the grid-stride loop ran)
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
@@ -1923,6 +1924,47 @@ extern "C" int dctzhip_ac_index(dctzhip_ctx* c, const void* d_bin, size_t n, uin
   return DCTZHIP_OK;
 }
 
+// What the three random-access calls (range, box, box of a tiled array) share around their launch.  ra_begin: the control
+// block is clean and the QT table staged; ra_fill: the fields every parameter block has; ra_finish: the error word read
+// back -- the call returns once the index check is known, and has synchronised the stream.
+template <typename T>
+static int ra_begin(dctzhip_ctx* c, int mode, const void* qtable_host) {
+  hipStream_t s = c->stream;
+  if (c->ctl_dirty) HIPCHK(c, hipMemsetAsync(c->ctl, 0, sizeof(Ctl), s));
+  c->ctl_dirty = 1;                                 // until this call's error word has been read back clean
+  if (mode == DCTZHIP_QT) {
+    // staged through pinned memory that the next call may rewrite: the call ends with a stream synchronisation
+    T* hq = reinterpret_cast<T*>(c->h_pin + PIN_TAB + sizeof(double) * RTAB_SIZE);
+    memcpy(hq, qtable_host, sizeof(T) * 64);
+    HIPCHK(c, hipMemcpyAsync(c->qtab, hq, sizeof(T) * 64, hipMemcpyHostToDevice, s));
+  }
+  return DCTZHIP_OK;
+}
+template <typename T, typename P>
+static void ra_fill(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_dc, const float* d_ac, const uint32_t* d_index, T* d_out,
+                    uint32_t ac_count, double eb, double sf) {
+  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index; p.out = d_out;
+  p.tab = tab_of<T>(c); p.qtab = reinterpret_cast<const T*>(c->qtab);
+  p.ctl = c->ctl;
+  p.ac_count = ac_count;
+  p.sf = (T)sf;
+  p.bin_width = (T)((T)eb * 2 * 1.0);               // as decompress_impl (binning.c:17 / :37)
+  p.range_max = (T)(eb * DCTZHIP_NBINS);
+  p.range_min = (T)(-eb * DCTZHIP_NBINS);
+  p.eb = eb;
+}
+static int ra_finish(dctzhip_ctx* c) {
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipGetLastError());
+  Ctl* hc = reinterpret_cast<Ctl*>(c->h_pin + PIN_CTL);
+  HIPCHK(c, hipMemcpyAsync(hc, c->ctl, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (!hc->error) c->ctl_dirty = 0;
+  if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
+  if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
+  return DCTZHIP_OK;
+}
+
 template <typename T>
 static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                  const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
@@ -1932,25 +1974,12 @@ static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const flo
   const int rem = (int)(n % 64);
   const unsigned t0 = (unsigned)(lo / TILE_ELEMS), t1 = (unsigned)((hi + TILE_ELEMS - 1) / TILE_ELEMS);
   const bool with_rem = rem && hi > (size_t)nfull * 64;
-  if (c->ctl_dirty) HIPCHK(c, hipMemsetAsync(c->ctl, 0, sizeof(Ctl), s));
-  c->ctl_dirty = 1;                                 // until this call's error word has been read back clean
-  if (mode == DCTZHIP_QT) {
-    // staged through pinned memory that the next call may rewrite: this call ends with a stream synchronisation
-    T* hq = reinterpret_cast<T*>(c->h_pin + PIN_TAB + sizeof(double) * RTAB_SIZE);
-    memcpy(hq, qtable_host, sizeof(T) * 64);
-    HIPCHK(c, hipMemcpyAsync(c->qtab, hq, sizeof(T) * 64, hipMemcpyHostToDevice, s));
-  }
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
   if (with_rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   RangeParams<T> p;
-  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index; p.out = d_out;
-  p.tab = tab_of<T>(c); p.rtab = reinterpret_cast<const T*>(c->rtab); p.qtab = reinterpret_cast<const T*>(c->qtab);
-  p.ctl = c->ctl;
-  p.n = (unsigned)n; p.nfull = nfull; p.lo = (unsigned)lo; p.hi = (unsigned)hi; p.t0 = t0; p.t1 = t1; p.ac_count = ac_count;
-  p.sf = (T)sf;
-  p.bin_width = (T)((T)eb * 2 * 1.0);               // as decompress_impl (binning.c:17 / :37)
-  p.range_max = (T)(eb * DCTZHIP_NBINS);
-  p.range_min = (T)(-eb * DCTZHIP_NBINS);
-  p.eb = eb;
+  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  p.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.n = (unsigned)n; p.nfull = nfull; p.lo = (unsigned)lo; p.hi = (unsigned)hi; p.t0 = t0; p.t1 = t1;
   // one single-wave workgroup per tile of the range, persistent only beyond what is resident at once
   int& occ = c->ra_occ[sizeof(T) == 8][mode == DCTZHIP_QT];    // (per context: the context's device)
   if (occ == 0) occ = std::max(range_occupancy<T>(mode), 1);
@@ -1960,14 +1989,7 @@ static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const flo
   // (no stage timings: dctzhip_last_timings keeps reporting the last compress / decompress call)
   launch_decompress_range<T>(p, mode, grid, with_rem, s);
   SET_LAST(c, 1, "k_decompress_range<%s, %d>", tname<T>(), mode);
-  HIPCHK(c, hipGetLastError());
-  Ctl* hc = reinterpret_cast<Ctl*>(c->h_pin + PIN_CTL);
-  HIPCHK(c, hipMemcpyAsync(hc, c->ctl, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (!hc->error) c->ctl_dirty = 0;
-  if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
-  if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
-  return DCTZHIP_OK;
+  return ra_finish(c);
 }
 
 extern "C" int dctzhip_decompress_range(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -2044,25 +2066,12 @@ static int decompress_box_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float
   const int rem = (int)(n % 64);
   const unsigned t0 = (unsigned)(first / TILE_ELEMS), t1 = (unsigned)(last / TILE_ELEMS + 1);
   const bool with_rem = rem && box.rank((unsigned)n) != box.rank(nfull * 64u);    // an element of the short block lies in the box
-  if (c->ctl_dirty) HIPCHK(c, hipMemsetAsync(c->ctl, 0, sizeof(Ctl), s));
-  c->ctl_dirty = 1;                                 // until this call's error word has been read back clean
-  if (mode == DCTZHIP_QT) {
-    // staged through pinned memory that the next call may rewrite: this call ends with a stream synchronisation
-    T* hq = reinterpret_cast<T*>(c->h_pin + PIN_TAB + sizeof(double) * RTAB_SIZE);
-    memcpy(hq, qtable_host, sizeof(T) * 64);
-    HIPCHK(c, hipMemcpyAsync(c->qtab, hq, sizeof(T) * 64, hipMemcpyHostToDevice, s));
-  }
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
   if (with_rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   BoxParams<T> p;
-  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index; p.out = d_out;
-  p.tab = tab_of<T>(c); p.rtab = reinterpret_cast<const T*>(c->rtab); p.qtab = reinterpret_cast<const T*>(c->qtab);
-  p.ctl = c->ctl;
-  p.n = (unsigned)n; p.nfull = nfull; p.t0 = t0; p.t1 = t1; p.ac_count = ac_count;
-  p.sf = (T)sf;
-  p.bin_width = (T)((T)eb * 2 * 1.0);               // as decompress_impl (binning.c:17 / :37)
-  p.range_max = (T)(eb * DCTZHIP_NBINS);
-  p.range_min = (T)(-eb * DCTZHIP_NBINS);
-  p.eb = eb;
+  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  p.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.n = (unsigned)n; p.nfull = nfull; p.t0 = t0; p.t1 = t1;
   p.box = box;
   // one single-wave workgroup per candidate tile, persistent only beyond what is resident at once
   int& occ = c->box_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
@@ -2073,14 +2082,7 @@ static int decompress_box_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float
   c->box_grid = (unsigned)grid; c->box_tiles = tiles;
   launch_decompress_box<T>(p, mode, grid, with_rem, s);
   SET_LAST(c, 1, "k_decompress_box<%s, %d>", tname<T>(), mode);
-  HIPCHK(c, hipGetLastError());
-  Ctl* hc = reinterpret_cast<Ctl*>(c->h_pin + PIN_CTL);
-  HIPCHK(c, hipMemcpyAsync(hc, c->ctl, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (!hc->error) c->ctl_dirty = 0;
-  if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
-  if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
-  return DCTZHIP_OK;
+  return ra_finish(c);
 }
 
 extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -2269,6 +2271,93 @@ extern "C" int dctzhip_decompress_nd(dctzhip_ctx* c, const void* d_bin, const fl
   HIPCHK(c, hipGetLastError());
   if (c->blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
   return DCTZHIP_OK;
+}
+
+// ---- a box of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndbox.hip) -------------------------
+template <typename T>
+static int decompress_box_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                  const uint32_t* d_index, const void* qtable_host, const NdShape& sh, double eb, double sf, int mode,
+                                  const size_t* lo, const size_t* hi, unsigned t0, unsigned t1, T* d_out) {
+  hipStream_t s = c->stream;
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  const unsigned edge = sh.nd == 2 ? 8u : 4u;
+  NdBoxParams<T> p;
+  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  p.n = (unsigned)(sh.nblk * 64); p.nfull = (unsigned)sh.nblk; p.t0 = t0; p.t1 = t1;
+  // the array in the last sh.nd of three axes; the intersecting blocks as a box of the block grid
+  memset(&p.blocks, 0, sizeof(p.blocks));
+  for (int i = 0; i < BOX_ND; i++) { p.blocks.dim[i] = 1u; p.blocks.lo[i] = 0u; p.blocks.ext[i] = 1u; }
+  for (int i = 0; i < 3; i++) { p.nb[i] = 1u; p.lo[i] = 0u; p.ext[i] = 1u; }
+  for (int i = 0; i < sh.nd; i++) {
+    const int a = 3 - sh.nd + i;
+    p.nb[a] = (unsigned)sh.nb[i]; p.lo[a] = (unsigned)lo[i]; p.ext[a] = (unsigned)(hi[i] - lo[i]);
+    const unsigned bl = (unsigned)lo[i] / edge, bh = (unsigned)(hi[i] - 1) / edge;
+    p.blocks.dim[a + 1] = (unsigned)sh.nb[i]; p.blocks.lo[a + 1] = bl; p.blocks.ext[a + 1] = bh - bl + 1u;
+  }
+  // one single-wave workgroup per candidate tile, persistent only beyond what is resident at once
+  const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
+  int& occ = c->ndbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3];
+  if (occ == 0) occ = std::max(ndbox_occupancy<T>(mode, geom), 1);
+  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+  const unsigned tiles = t1 - t0;
+  // A heuristic, measured on two boxes of one volume only: the stride of the loop over tiles is kept ODD.  The hit tiles
+  // of a box repeat with the tiles per block row and per block plane, even numbers for most shapes; with the even stride
+  // 1024 the x-plane of a 512^3 volume (every other tile is hit) left half of the workgroups without a single hit tile:
+  // 254 -> 142 us.  It does not balance the 64^3 brick (a workgroup still meets four hit tiles) and costs the full box
+  // 3.5 % (369 -> 382 us).  An assignment that follows the hit tiles instead of the candidates is the real fix (EXPERIMENTS
+  // section 22).
+  int grid = (int)(tiles < resident ? tiles : resident);
+  if (tiles > resident && grid > 1 && !(grid & 1)) grid--;
+  c->box_grid = (unsigned)grid; c->box_tiles = tiles;
+  launch_decompress_ndbox<T>(p, mode, geom, grid, s);
+  SET_LAST(c, 1, "k_decompress_ndbox<%s, %d, %d>", tname<T>(), mode, geom);
+  return ra_finish(c);
+}
+
+extern "C" int dctzhip_decompress_box_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                         const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype,
+                                         double eb, double sf, int mode, const size_t* lo, const size_t* hi, void* d_out) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64;
+  int rc = check_common(c, n_lin, dtype, mode);
+  if (rc) return rc;
+  if (!lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box_nd: null lo or hi");
+  const size_t edge = ndims == 2 ? 8 : 4;
+  size_t cnt = 1, first = 0, last = 0;              // first / last intersecting block of the row-major block grid
+  for (int i = 0; i < ndims; i++) {
+    if (lo[i] >= hi[i] || hi[i] > dims[i])
+      return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box_nd: [%zu, %zu) is not inside dimension %d of %zu", lo[i], hi[i], i, dims[i]);
+    cnt *= hi[i] - lo[i];
+    first = first * sh.nb[i] + lo[i] / edge;
+    last = last * sh.nb[i] + (hi[i] - 1) / edge;
+  }
+  if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  const size_t t0 = first / TILE_BLKS, t1 = last / TILE_BLKS + 1;
+  {
+    // what the call may read: bin ids, DC and index entries of the candidate tiles, AC_exact (all of it: where a tile's
+    // part starts is only known on the device)
+    const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n_lin, t1 * (size_t)TILE_ELEMS);
+    Span sp[5];
+    size_t m = 0;
+    add_span(sp, &m, (const uint8_t*)d_bin + b0, b1 - b0, SPAN_READ, 0);
+    add_span(sp, &m, d_dc + b0 / 64, (b1 / 64 - b0 / 64) * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_decompress_box_nd", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? decompress_box_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode, lo, hi,
+                                              (unsigned)t0, (unsigned)t1, (double*)d_out)
+             : decompress_box_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode, lo, hi,
+                                             (unsigned)t0, (unsigned)t1, (float*)d_out);
 }
 
 extern "C" int dctzhip_dct_blocks(dctzhip_ctx* c, const void* d_in, void* d_out, size_t n, int dtype, int inverse) {

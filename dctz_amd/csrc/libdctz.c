@@ -1699,7 +1699,7 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   return 1;
 }
 
-/* ------------------------------- dctz_decompress_range, dctz_decompress_box -- */
+/* ------------- dctz_decompress_range, dctz_decompress_box, dctz_decompress_box_nd -- */
 /* The first `want` bytes of one section into dst.  Indexed (sizes != NULL): only the chunks that hold them, side by side
  * on host threads (dst has room for whole chunks: min(raw, chunks * chunk) bytes); a chunk that does not inflate sends the
  * section to the streaming inflate.  Otherwise one inflate that stops once `want` bytes are out.  Returns the bytes made. */
@@ -1742,18 +1742,36 @@ static size_t inflate_prefix(const unsigned char *sec, unsigned int zlen, size_t
   return done;
 }
 
-/* dctz_decompress_range (ndim == 0: elements [lo, hi)) and dctz_decompress_box (ndim >= 1: the box; [lo, hi) becomes
- * [first box element, last box element + 1)): the prefix of the sections that span needs, its index, one device call,
- * and only the wanted elements copied back. */
+/* dctz_decompress_range (ndim == 0: elements [lo, hi)), dctz_decompress_box (ndim >= 1: the box; [lo, hi) becomes
+ * [first box element, last box element + 1)) and dctz_decompress_box_nd (ndim == PART_TILED: a DZND container, geometry and
+ * extents from the container; [lo, hi) becomes the stream positions [64 * first intersecting block, 64 * (last + 1))): the
+ * prefix of the sections that span needs, its index, one device call, and only the wanted elements copied back. */
+#define PART_TILED (-1)
 static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, t_var *var_r) {
   const double t_begin = now_s();
   dzc_view v;
   dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
-  const size_t ts = v.ts, n = v.n, nblk = v.nblk;
+  const int tiled = ndim == PART_TILED;
+  if (tiled && (v.nd == 0 || dzc_geometry(&v) != 0)) return -1;    /* a flat container, or extents that are no shape */
+  if (!tiled && v.nd != 0) return -1;                              /* DZND: element order is not block order */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;               /* n: positions of the streams (flat: the elements) */
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   const unsigned int cnt = v.cnt;
   size_t out_elems;
-  if (ndim != 0) {
+  if (tiled) {
+    if (!blo || !bhi || n == 0) return -1;
+    const size_t edge = v.nd == 2 ? 8 : 4;
+    size_t first = 0, last = 0;                                    /* intersecting blocks of the row-major block grid */
+    out_elems = 1;
+    for (int i = 0; i < v.nd; i++) {
+      if (blo[i] >= bhi[i] || bhi[i] > v.dims[i]) return -1;
+      const size_t nb = (v.dims[i] + edge - 1) / edge;
+      out_elems *= bhi[i] - blo[i];
+      first = first * nb + blo[i] / edge;
+      last = last * nb + (bhi[i] - 1) / edge;
+    }
+    lo = first * BLK_SZ; hi = (last + 1) * BLK_SZ;
+  } else if (ndim != 0) {
     if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM || !dims || !blo || !bhi || n == 0) return -1;
     size_t prod = 1, last = 0;
     lo = 0; out_elems = 1;
@@ -1769,7 +1787,7 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   } else {
     out_elems = hi - lo;
   }
-  if (v.nd != 0 || n == 0 || lo >= hi || hi > n) return -1;   /* DZND: element order is not block order */
+  if (n == 0 || lo >= hi || hi > n) return -1;
   const size_t S = DCTZHIP_INDEX_STRIDE;
   const size_t t1 = (hi + S - 1) / S;                        /* the range's tiles end here */
   const size_t need[3] = {MIN(n, S * t1),                    /* bin ids: the flags in front give AC_exact's position */
@@ -1811,14 +1829,17 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   }
   t0 = now_s();
   grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
-  const int rc = ndim == 0 ? dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
+  const int rc = tiled     ? dctzhip_decompress_box_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
+                                                       (const uint32_t *)g_dev.idx, qtable, v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE,
+                                                       blo, bhi, g_dev.out)
+                 : ndim == 0 ? dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
                                                       (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi,
                                                       g_dev.out)
                            : dctzhip_decompress_box(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
                                                     (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims,
                                                     blo, bhi, g_dev.out);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
-  if (rc != DCTZHIP_OK) die(ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
+  if (rc != DCTZHIP_OK) die(tiled ? "dctzhip_decompress_box_nd" : ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
   const double t1s = now_s();
   if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
   g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
@@ -1832,8 +1853,12 @@ out:
 int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) { return decompress_part(var_z, lo, hi, 0, NULL, NULL, NULL, var_r); }
 
 int dctz_decompress_box(t_var *var_z, int ndim, const size_t *dims, const size_t *lo, const size_t *hi, t_var *var_r) {
-  if (ndim == 0) return -1;
+  if (ndim < 1) return -1;
   return decompress_part(var_z, 0, 0, ndim, dims, lo, hi, var_r);
+}
+
+int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_var *var_r) {
+  return decompress_part(var_z, 0, 0, PART_TILED, NULL, lo, hi, var_r);
 }
 
 /* ------------------------------------------------------ calc_data_stat ----- */

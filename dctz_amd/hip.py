@@ -115,6 +115,9 @@ _PROTOS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CompressInfo)]),
     "dctzhip_decompress_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
                                         C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "dctzhip_decompress_box_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int,
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "dctzhip_dct_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dctzhip_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_serial_mean_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -505,6 +508,29 @@ class Context:
             mode, dst.data_ptr())
         self._check(rc, "dctzhip_decompress_nd")
         return dst
+
+    def decompress_box_nd(self, out, cnt, shape, dtype, eb, sf, lo, hi, index, mode=EC, qtable=None, dst=None):
+        """The box lo[i] <= c[i] < hi[i] of what decompress_nd() rebuilds from the same arguments, bit for bit; `index` from
+        ac_index(out, 64 * nd_blocks(shape)).  Returns dst shaped hi - lo."""
+        t = self.torch
+        self._bind_stream()
+        shape, lo, hi = [int(v) for v in shape], [int(v) for v in lo], [int(v) for v in hi]
+        nd = len(shape)
+        assert len(lo) == nd and len(hi) == nd
+        ext = [max(h - l, 0) for l, h in zip(lo, hi)]
+        if dst is None:
+            dst = t.empty(ext, dtype=dtype, device=self.device)
+        q = None
+        if mode == QT:
+            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
+            assert q.size == 64
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_decompress_box_nd(
+            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
+            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, nd, arr(*shape), _dt(dtype),
+            float(eb), float(sf), mode, arr(*lo), arr(*hi), dst.data_ptr())
+        self._check(rc, "dctzhip_decompress_box_nd")
+        return dst.view(ext)
 
     def psnr_terms(self, x, r):
         """calc_psnr's reductions (util.c:54-104) on the GPU: (min x, max x, max |x - r|, sum (x - r)^2)."""

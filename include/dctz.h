@@ -162,6 +162,17 @@ int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r);
  * dctz_decompress_range(first box element, last box element + 1) inflates and no more; on the device only the tiles that
  * hold box elements are decoded, once each (include/dctz_hip.h: dctzhip_decompress_box), and only the box is copied back. */
 int dctz_decompress_box(t_var *var_z, int ndim, const size_t *dims, const size_t *lo, const size_t *hi, t_var *var_r);
+/* A box of a container compressed in tiles (ADDITION, EC and QT builds): var_z is a DZND container (dctz_set_block_dims +
+ * dctz_compress); its geometry and extents come from the container.  Elements lo[i] <= c[i] < hi[i] (2 or 3 entries, as the
+ * container has dimensions), dense and in C order into var_r->buf (allocated by the caller); each is bit for bit the element
+ * dctz_decompress reconstructs at those coordinates.  Returns 1, or -1 for a flat container, a bad box (a null pointer,
+ * lo[i] >= hi[i], hi[i] > dims[i]) and streams that disagree with each other -- dctz_decompress_box's conventions.  The
+ * blocks that intersect the box are a box of the row-major block grid; the call inflates what the stream positions [64 *
+ * first such block, 64 * (last + 1)) need, exactly as dctz_decompress_range would for a flat container, and no more; on the
+ * device only the stream tiles (64 blocks) that hold such a block are decoded, once each (include/dctz_hip.h:
+ * dctzhip_decompress_box_nd), and only the box is copied back.  dctz_decompress_range and dctz_decompress_box keep
+ * refusing DZND containers. */
+int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

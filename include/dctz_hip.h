@@ -132,7 +132,7 @@ int dctzhip_set_split(dctzhip_ctx *ctx, int on);
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr, 11 / 12 workgroups and
- * candidate tiles of the last dctzhip_decompress_box call (12 > 11: its grid-stride loop ran) -- and knobs that
+ * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran) -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
  * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
@@ -301,7 +301,8 @@ int dctzhip_decompress_range(dctzhip_ctx *ctx, const void *d_bin_index, const fl
 /* A rectangular box of the array seen as an ndim-dimensional array in C order (last dimension fastest), 1 <= ndim <=
  * DCTZHIP_BOX_MAXDIM, prod dims == n: the elements lo[i] <= c[i] < hi[i] in every dimension.  The streams, d_index,
  * ac_count, qtable_host, n, dtype, error_bound, sf and mode are dctzhip_decompress_range's: they describe the WHOLE array,
- * compressed in the ordinary flat 64-element blocks (dctzhip_compress), not in the tiles of dctzhip_compress_nd.
+ * compressed in the ordinary flat 64-element blocks (dctzhip_compress); streams in the tiles of dctzhip_compress_nd have
+ * dctzhip_decompress_box_nd.
  * Fortran order: reverse dims, lo and hi.
  *   d_out       receives prod (hi[i] - lo[i]) elements, dense, in C order; each is, bit for bit, the element that
  *               dctzhip_decompress writes at the same coordinates (EC and QT, fp32 and fp64, the short last block
@@ -402,6 +403,30 @@ int dctzhip_decompress_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float
                           const float *d_ac_exact, uint32_t ac_count, const void *qtable_host,
                           int ndims, const size_t *dims, int dtype, double error_bound, double sf,
                           int mode, void *d_out);
+/* A rectangular box lo[i] <= c[i] < hi[i] of an array compressed by dctzhip_compress_nd(ndims, dims).  The streams,
+ * ac_count, qtable_host, ndims, dims, dtype, error_bound, sf and mode are dctzhip_decompress_nd's; they cover n_lin = 64 *
+ * dctzhip_nd_blocks(ndims, dims) positions, and d_index is dctzhip_ac_index(d_bin_index, n_lin).
+ *   d_out       receives prod (hi[i] - lo[i]) elements, dense, in C order; each is, bit for bit, the element that
+ *               dctzhip_decompress_nd writes at the same coordinates (EC and QT, fp32 and fp64, whether the full decode
+ *               writes the array in place or through its scatter pass).
+ *   locality    a STREAM TILE is 64 consecutive blocks of the stream (4096 positions, one index entry).  The blocks that
+ *               intersect the box are, per axis, [lo / e, (hi - 1) / e] (e = 8 | 4): a box of the block grid, which is
+ *               numbered row-major.  A stream tile is HIT if it holds at least one of them; candidate tiles run from the
+ *               first to the last intersecting block.  The call reads the bin ids and DC values of hit tiles only, their
+ *               index entries idx[t] and idx[t + 1] only, and AC_exact[idx[t], idx[t + 1]) of hit tiles only; it writes
+ *               nothing outside d_out[0, prod ext).  A hit tile is decoded once.
+ *   refusals    before any launch, DCTZHIP_E_ARG for a NULL ctx, whatever dctzhip_decompress_nd refuses for ndims / dims,
+ *               a null lo or hi, lo[i] >= hi[i] or hi[i] > dims[i], the pointer and alignment rules of
+ *               dctzhip_decompress_box, a QT call without a table, and a d_out that overlaps what the call may read for
+ *               the candidate tiles (their bin ids, DC values and index entries, AC_exact[0, ac_count)).  On the device,
+ *               for hit tiles only: the flags of tile t must number idx[t + 1] - idx[t], and idx[t + 1] <= ac_count; if
+ *               not the tile reads no AC_exact and the call returns DCTZHIP_E_ARG, the output is undefined and the
+ *               context stays usable.
+ * Returns once that check is known, as dctzhip_decompress_box does (the call has synchronised the stream). */
+int dctzhip_decompress_box_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                              uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                              const size_t *dims, int dtype, double error_bound, double sf, int mode,
+                              const size_t *lo, const size_t *hi, void *d_out);
 
 /* ---- transform only ------------------------------------------------------ */
 /* Batched drop-in for dct_init + per-block dct_fftw / ifft_idct (+ the

@@ -1,0 +1,29 @@
+"""Register budget of the box decode of tiled arrays (dctz_kernels_ndbox.hip): exactly the eight k_decompress_ndbox
+instantiations are built, and each runs without scratch and without spilled VGPRs (read from the code object's metadata)."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "dctz_amd", "lib", "libdctzhip.so")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    """A missing library is built, as tests/test_abi_cpu.py does; one that does not build fails the test."""
+    if not os.path.exists(LIB):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "dctz_amd"), "all"])
+
+
+def test_ndbox_kernels_have_no_scratch():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import kernels_of
+    ks = [k for k in kernels_of(LIB) if k.get("demangled", "").startswith("dctz::k_decompress_ndbox")]
+    names = sorted(k["demangled"].split("(")[0] for k in ks)
+    want = [f"dctz::k_decompress_ndbox<{t}, {m}, {g}>" for t in ("double", "float") for m in (0, 1) for g in (1, 2)]
+    assert names == sorted(want), names
+    for k in ks:
+        assert k.get("private_segment_fixed_size", 0) == 0, k
+        assert k.get("vgpr_spill_count", 0) == 0, k

@@ -12,6 +12,8 @@
                  dctzhip_decompress_range call per run of the box, into the right offsets) or --via slice (whole decode +
                  torch slice copy); --box brick (64^3 at 224^3) | zplane ([100:101, :, :]) | xplane ([:, :, 100:101]) |
                  full | c2 (the 1800 x 3600 fp32 field, window [600:856, 1200:1712])
+  --what ndbox   the same boxes (brick | zplane | xplane | full) of the shard compressed in 4 x 4 x 4 tiles (compress_nd)
+                 through dctzhip_decompress_box_nd (k_decompress_ndbox), beside that run's whole-array decompress_nd
 Every other run also times dctzhip_decompress of the whole shard.  Wall-clock medians go to stdout as one JSON line; for device
 times run one --what per process under `rocprofv3 --kernel-trace --stats -- python tools/range_bench.py --what ...`."""
 import argparse
@@ -26,7 +28,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin", "box"], required=True)
+    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin", "box", "ndbox"], required=True)
     ap.add_argument("--box", choices=["brick", "zplane", "xplane", "full", "c2"], default="brick")
     ap.add_argument("--via", choices=["box", "ranges", "slice"], default="box")
     ap.add_argument("--n", type=int, default=512, help="edge of the cube")
@@ -41,6 +43,8 @@ def main():
         return dropin(a, W)
     if a.what == "box":
         return box(a, W)
+    if a.what == "ndbox":
+        return ndbox(a, W)
     ctx = dctz_amd.Context(0)
     x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device)
     n = x.numel()
@@ -156,6 +160,63 @@ def box(a, W):
     print(json.dumps({"what": "box", "box": a.box, "via": a.via, "n": n, "cnt": info.cnt, "lo": lo, "hi": hi, "rows": int(starts.size),
                       "hit_tiles": int(hit.sum()), "candidate_tiles": int(t[-1] - t[0] + 1), "wall_ms_decompress": round(ms_full, 4),
                       "wall_ms_" + a.via: round(ms_what, 4)}))
+    ctx.close()
+
+
+def ndbox(a, W):
+    import numpy as np
+    import torch
+    import dctz_amd
+
+    if a.box == "c2":
+        raise SystemExit("--what ndbox runs the boxes of the cube: brick, zplane, xplane, full")
+    ctx = dctz_amd.Context(0)
+    e, tdt = a.n, torch.float64
+    dims = (e, e, e)
+    x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device).reshape(dims)
+    lo, hi = {"brick": ((224 * e // 512,) * 3, (224 * e // 512 + 64,) * 3), "zplane": ((100, 0, 0), (101, e, e)),
+              "xplane": ((0, 0, 100), (e, e, 101)), "full": ((0, 0, 0), dims)}[a.box]
+    eb = 1e-3
+    out, info = ctx.compress_nd(x, eb, dctz_amd.EC)
+    del x
+    nblk = ctx.nd_blocks(dims)
+    full = torch.empty(dims, dtype=tdt, device=ctx.device)
+    idx, tot = ctx.ac_index(out, 64 * nblk)
+    assert tot == info.cnt
+    ext = tuple(h - l for l, h in zip(lo, hi))
+    dst = torch.empty(ext, dtype=tdt, device=ctx.device)
+    sl = tuple(slice(l, h) for l, h in zip(lo, hi))
+
+    def t_full():
+        ctx.decompress_nd(out, info.cnt, dims, tdt, eb, info.sf, dctz_amd.EC, dst=full)
+
+    def t_box():
+        ctx.decompress_box_nd(out, info.cnt, dims, tdt, eb, info.sf, lo, hi, idx, dctz_amd.EC, dst=dst)
+
+    def med(f, reps):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    for f in (t_full, t_box):                       # warm-up
+        f()
+    ms_full, ms_what = med(t_full, a.reps), med(t_box, a.reps)
+    assert torch.equal(dst.contiguous().view(torch.int64), full[sl].contiguous().view(torch.int64))
+    nb = [-(-d // 4) for d in dims]                 # the intersecting blocks, 64 to a stream tile
+    m = np.zeros(nb, bool)
+    m[tuple(slice(l // 4, (h - 1) // 4 + 1) for l, h in zip(lo, hi))] = True
+    fm = np.zeros(-(-nblk // 64) * 64, bool)
+    fm[:nblk] = m.reshape(-1)
+    hit = fm.reshape(-1, 64).any(axis=1)
+    t = np.flatnonzero(hit)
+    print(json.dumps({"what": "ndbox", "box": a.box, "n": e ** 3, "cnt": info.cnt, "lo": lo, "hi": hi, "tiles": int(hit.size),
+                      "hit_tiles": int(hit.sum()), "candidate_tiles": int(t[-1] - t[0] + 1), "grid": ctx.counter(11),
+                      "kernel": ctx.last_kernel(1), "wall_ms_decompress_nd": round(ms_full, 4), "wall_ms_box_nd": round(ms_what, 4)}))
     ctx.close()
 
 
