@@ -582,6 +582,51 @@ struct BoxParams {
 template <typename T> int box_occupancy(int mode);
 template <typename T> void launch_decompress_box(const BoxParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s);
 
+// A list of boxes in one call (dctz_kernels_mbox.hip: k_boxlist_build, k_decompress_mbox, k_decompress_mbox_rem).  One record
+// per box; k_boxlist_build asks every (box, candidate) pair the hit test and compacts the hits into `items`, the decoder's
+// single-wave workgroups take items, so none of them ever meets a candidate that is not hit.
+// The builder needs a BoxGeo, the size of a candidate in the units rank() counts in, and the span only: `g` may as well be a
+// box of a block grid (NdBoxParams::blocks) with the stream tiles as candidates.
+struct BoxRec {
+  BoxGeo g;                        // canonical box (hit test by rank(), output positions)
+  unsigned t0, t1;                 // candidates [t0, t1)
+  unsigned cand0;                  // candidates of the boxes in front of this one: pair number cand0 + (t - t0)
+  void* out;                       // prod g.ext elements
+};
+static_assert(sizeof(BoxRec) == 104, "BoxRec is read word by word");
+struct BoxItem { unsigned box, tile; };
+struct BoxListParams {
+  const BoxRec* recs;
+  unsigned nbox;
+  unsigned total;                  // (box, candidate) pairs: cand0 + (t1 - t0) of the last record
+  unsigned unit;                   // what a candidate spans in rank()'s units (4096 elements for flat blocks)
+  unsigned end;                    // ... the last one ends here (n)
+  BoxItem* items;
+  unsigned cap;                    // the host's bound of the hits: nothing is stored at or beyond it
+  Ctl* ctl;                        // cnt_total: the hits (cleared in stream order before the launch); error = 4: more than cap
+};
+template <typename T>
+struct MBoxParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[t], idx[t + 1] of listed tiles are read
+  const T* tab;
+  const T* rtab;
+  const T* qtab;
+  Ctl* ctl;                        // cnt_total: items in the list (k_boxlist_build); error = 2: as RangeParams
+  const BoxRec* recs;
+  const BoxItem* items;
+  const unsigned* rem_boxes;       // k_decompress_mbox_rem: the boxes that reach into the short last block, one workgroup each
+  unsigned cap;                    // capacity of items
+  unsigned n, nfull, ac_count;
+  T sf, bin_width, range_min, range_max;
+  double eb;
+};
+void launch_boxlist_build(const BoxListParams& p, hipStream_t s);
+template <typename T> int mbox_occupancy(int mode);
+template <typename T> void launch_decompress_mbox(const MBoxParams<T>& p, int mode, int grid, int nrem, hipStream_t s);
+
 // Box decode of an array compressed in 8 x 8 / 4 x 4 x 4 tiles (dctz_kernels_ndbox.hip: k_decompress_ndbox).  The streams
 // and the index cover n = 64 nblk positions, nfull = nblk (no short block); [t0, t1) are the candidate STREAM tiles (64
 // consecutive blocks each), those of the first and the last block that intersects the box.  A 2-D array sits in the last

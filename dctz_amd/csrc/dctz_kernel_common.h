@@ -761,6 +761,52 @@ __device__ __forceinline__ bool ra_tile_image(const P& p, const unsigned t, cons
   return true;
 }
 
+// The short last block (length l = n % 64) of a box that reaches into it, by one wave (k_decompress_box_rem,
+// k_decompress_mbox_rem): k_decompress_range_rem with the box test and the box's output position in place of [lo, hi).
+// a: 64, cr / ci: 128 elements of LDS.
+template <typename T, int MODE, typename P>
+__device__ __forceinline__ void box_rem_block(const P& p, const BoxGeo& g, T* const out, const int k, T* a, T* cr, T* ci) {
+  const int l = (int)(p.n - p.nfull * 64u);
+  const size_t base = (size_t)p.nfull * 64;
+  const unsigned t = p.nfull / (unsigned)TILE_BLKS;                    // the tile that holds the short block
+  // flags of the tile's whole blocks in front of the short block
+  unsigned c = 0;
+  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)k;
+  if (blk < p.nfull) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
+    unsigned w[16];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u32x4 v = src[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    c = block_flag_count(w);
+  }
+  const unsigned start = p.idx[t] + (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(c), 63);
+  const unsigned lim = min(p.ac_count, p.idx[t + 1]);
+  unsigned b = 0;
+  if (k < l) b = p.bin[base + k];
+  const bool exc = (k < l) && (k != 0) && (b == 255u);
+  const unsigned long long msk = __ballot(exc);
+  const unsigned rank = (unsigned)__popcll(msk & ((1ull << k) - 1ull));
+  short_inv_clear(cr, ci, k);
+  if (k < l) {
+    T e = T(0);
+    if (exc) { if (start + rank < lim) e = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u); }
+    a[k] = short_inv_value<T, MODE>(b, exc, k, k == 0 ? p.dc[p.nfull] : 0.f, e, p.bin_width, [&](int j) { return p.qtab[j]; }, p.eb, p.range_min, p.range_max);
+  }
+  __syncthreads();
+  if (k < l) short_inv_spread(cr, ci, a, p.rtab, l, k);
+  __syncthreads();
+  if (k < l) {
+    T val = short_inv_sum(cr, ci, p.rtab, l, k);
+    if (p.sf != T(1)) val = val * p.sf;
+    const unsigned e = (unsigned)base + (unsigned)k;
+    const unsigned o = g.rank(e);
+    if (g.rank(e + 1u) != o) out[o] = val;                             // e lies in the box: it is output element o
+  }
+}
+
 
 // FastDiv's windows on the host's terms (dctz_shim.hip: divisor_in_window / value_in_window): unbiased exponent of a
 // finite non-zero double in [lo, hi)

@@ -11,7 +11,8 @@
 // dimension, the flat position by additions alone (BoxGeo::fstep, wrap); the element is read from the tile's LDS image and
 // stored through a buffer descriptor that covers exactly d_out[oa, ob).  Work per tile follows its elements in the box,
 // stores are consecutive across the lanes.
-// The short last block is k_decompress_box_rem's, as k_decompress_range_rem with the box test in place of [lo, hi).
+// The short last block is k_decompress_box_rem's (dctz_kernel_common.h: box_rem_block, shared with the list call), as
+// k_decompress_range_rem with the box test in place of [lo, hi).
 #include "dctz_kernel_common.h"
 
 namespace dctz {
@@ -79,46 +80,7 @@ __global__ __launch_bounds__(64) void k_decompress_box_rem(BoxParams<T> p) {
   __shared__ T a[64];
   __shared__ T cr[128];
   __shared__ T ci[128];
-  const int k = threadIdx.x;
-  const int l = (int)(p.n - p.nfull * 64u);
-  const size_t base = (size_t)p.nfull * 64;
-  const unsigned t = p.nfull / (unsigned)TILE_BLKS;                    // the tile that holds the short block
-  // flags of the tile's whole blocks in front of the short block
-  unsigned c = 0;
-  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)k;
-  if (blk < p.nfull) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
-    unsigned w[16];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const u32x4 v = src[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-    c = block_flag_count(w);
-  }
-  const unsigned start = p.idx[t] + (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(c), 63);
-  const unsigned lim = min(p.ac_count, p.idx[t + 1]);
-  unsigned b = 0;
-  if (k < l) b = p.bin[base + k];
-  const bool exc = (k < l) && (k != 0) && (b == 255u);
-  const unsigned long long msk = __ballot(exc);
-  const unsigned rank = (unsigned)__popcll(msk & ((1ull << k) - 1ull));
-  short_inv_clear(cr, ci, k);
-  if (k < l) {
-    T e = T(0);
-    if (exc) { if (start + rank < lim) e = (T)p.ac[start + rank]; else atomicExch(&p.ctl->error, 2u); }
-    a[k] = short_inv_value<T, MODE>(b, exc, k, k == 0 ? p.dc[p.nfull] : 0.f, e, p.bin_width, [&](int j) { return p.qtab[j]; }, p.eb, p.range_min, p.range_max);
-  }
-  __syncthreads();
-  if (k < l) short_inv_spread(cr, ci, a, p.rtab, l, k);
-  __syncthreads();
-  if (k < l) {
-    T val = short_inv_sum(cr, ci, p.rtab, l, k);
-    if (p.sf != T(1)) val = val * p.sf;
-    const unsigned e = (unsigned)base + (unsigned)k;
-    const unsigned o = p.box.rank(e);
-    if (p.box.rank(e + 1u) != o) p.out[o] = val;                       // e lies in the box: it is output element o
-  }
+  box_rem_block<T, MODE>(p, p.box, p.out, (int)threadIdx.x, a, cr, ci);
 }
 
 template <typename T>

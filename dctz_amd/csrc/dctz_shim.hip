@@ -76,6 +76,14 @@ struct dctzhip_ctx {
   int box_occ[2][2] = {{0, 0}, {0, 0}};  // dctzhip_decompress_box: the same of k_decompress_box
   int ndbox_occ[2][2][2] = {};      // dctzhip_decompress_box_nd: the same of k_decompress_ndbox, [fp64][QT][3-D]
   unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
+  // dctzhip_decompress_boxes: the box table (records, then the boxes of the short block) in pinned host memory and on the
+  // device, the list of hit (box, tile) items, resident workgroups per CU of k_decompress_mbox [fp64][QT]
+  unsigned char* mb_pin = nullptr;
+  unsigned char* mb_dev = nullptr;
+  BoxItem* mb_items = nullptr;
+  size_t mb_items_cap = 0;          // items
+  int mbox_occ[2][2] = {{0, 0}, {0, 0}};
+  unsigned mbox_items = 0, mbox_grid = 0, mbox_bound = 0;   // ... its last call: items listed, workgroups of the decode launch, the bound B (dctzhip_debug_counter 13 / 14 / 15)
   int dec_il = 1;                   // 0: k_decompress with a contiguous tile range per workgroup; 1: interleaved for fp64 EC; 2: for all (DCTZHIP_DEC_IL)
   size_t qcnt_cap = 0;              // tiles the two hold
   void* qt_item = nullptr;
@@ -323,10 +331,11 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
+  if (c->mb_pin) (void)hipHostFree(c->mb_pin);
   if (c->dfl_len) (void)hipHostFree(c->dfl_len);
   if (c->dfl_ev) (void)hipEventDestroy(c->dfl_ev);
   for (int i = 0; i < dctzhip_ctx::STAGE_WORKERS; i++) {
@@ -406,6 +415,9 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
     case 11: *value = c->box_grid; break;            // dctzhip_decompress_box / _box_nd, last call: workgroups of its kernel
     case 12: *value = c->box_tiles; break;           // ... candidate tiles (more than workgroups: the grid-stride loop ran)
+    case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes, last call: (box, hit tile) items in its list
+    case 14: *value = c->mbox_grid; break;           // ... workgroups of its decode launch (fewer than items: they took several each)
+    case 15: *value = c->mbox_bound; break;          // ... the host's bound B of the items, the list's capacity
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
   return DCTZHIP_OK;
@@ -941,13 +953,18 @@ static void add_span(Span* v, size_t* m, const void* p, size_t bytes, int kind, 
 // Sorted by start, a range overlaps an earlier one iff that one ends beyond its start: O(m log m).  shared (or null): set for
 // every item whose IN_PLACE range another item reads -- its division has to wait for every read of the call.  In-place
 // ranges are disjoint once the check passes, so the last one met is the only one that can cover a later start.
-static int check_spans(dctzhip_ctx* c, Span* v, size_t m, const char* what, char* shared) {
+// unit (or null: "array", and the item of the later range is named): what an item is called; then a range that runs into an
+// output names that output's item.
+static int check_spans(dctzhip_ctx* c, Span* v, size_t m, const char* what, char* shared, const char* unit = nullptr) {
   std::sort(v, v + m, [](const Span& a, const Span& b) { return a.lo < b.lo; });
   uintptr_t end_any = 0, end_written = 0, end_out = 0, end_read = 0, ip_hi = 0;
-  int ip_item = -1;
+  int ip_item = -1, out_item = -1;
   for (size_t i = 0; i < m; i++) {
     const Span& s = v[i];
     const uintptr_t end = s.kind == SPAN_OUT ? end_any : s.kind == SPAN_IN_PLACE ? end_written : end_out;
+    if (end > s.lo && unit)
+      return s.kind == SPAN_OUT ? fail(c, DCTZHIP_E_ARG, "%s: the output of %s %d overlaps another buffer of the call", what, unit, s.item)
+                                : fail(c, DCTZHIP_E_ARG, "%s: the output of %s %d overlaps what the call reads", what, unit, out_item);
     if (end > s.lo)
       return fail(c, DCTZHIP_E_ARG, "%s: a buffer of array %d overlaps %s of the call", what, s.item,
                   s.kind == SPAN_READ ? "an output" : s.kind == SPAN_IN_PLACE ? "an output or another in-place range" : "another buffer");
@@ -957,7 +974,7 @@ static int check_spans(dctzhip_ctx* c, Span* v, size_t m, const char* what, char
     }
     end_any = std::max(end_any, s.hi);
     if (s.kind != SPAN_READ) end_written = std::max(end_written, s.hi);
-    if (s.kind == SPAN_OUT) end_out = std::max(end_out, s.hi);
+    if (s.kind == SPAN_OUT && s.hi > end_out) { end_out = s.hi; out_item = s.item; }
     if (s.kind == SPAN_READ) end_read = std::max(end_read, s.hi);
     if (s.kind == SPAN_IN_PLACE) { ip_hi = s.hi; ip_item = s.item; }
   }
@@ -1941,9 +1958,9 @@ static int ra_begin(dctzhip_ctx* c, int mode, const void* qtable_host) {
   return DCTZHIP_OK;
 }
 template <typename T, typename P>
-static void ra_fill(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_dc, const float* d_ac, const uint32_t* d_index, T* d_out,
-                    uint32_t ac_count, double eb, double sf) {
-  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index; p.out = d_out;
+static void ra_fill_streams(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_dc, const float* d_ac, const uint32_t* d_index,
+                            uint32_t ac_count, double eb, double sf) {
+  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index;
   p.tab = tab_of<T>(c); p.qtab = reinterpret_cast<const T*>(c->qtab);
   p.ctl = c->ctl;
   p.ac_count = ac_count;
@@ -1953,14 +1970,23 @@ static void ra_fill(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_d
   p.range_min = (T)(-eb * DCTZHIP_NBINS);
   p.eb = eb;
 }
-static int ra_finish(dctzhip_ctx* c) {
+template <typename T, typename P>
+static void ra_fill(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_dc, const float* d_ac, const uint32_t* d_index, T* d_out,
+                    uint32_t ac_count, double eb, double sf) {
+  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  p.out = d_out;
+}
+// cnt_total (or null): the control block's counter of the same read-back; a call that used it leaves the block to be cleared
+static int ra_finish(dctzhip_ctx* c, unsigned* cnt_total = nullptr) {
   hipStream_t s = c->stream;
   HIPCHK(c, hipGetLastError());
   Ctl* hc = reinterpret_cast<Ctl*>(c->h_pin + PIN_CTL);
   HIPCHK(c, hipMemcpyAsync(hc, c->ctl, 16, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
-  if (!hc->error) c->ctl_dirty = 0;
+  if (cnt_total) *cnt_total = hc->cnt_total;
+  if (!hc->error && !cnt_total) c->ctl_dirty = 0;
   if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
+  if (hc->error == 4) return fail(c, DCTZHIP_E_ARG, "the boxes hit more tiles than the bound of the work list");
   if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
   return DCTZHIP_OK;
 }
@@ -2057,6 +2083,35 @@ static BoxGeo canonical_box(int ndim, const size_t* dims, const size_t* lo, cons
   return g;
 }
 
+// The extents of one box against the array (dims are checked with it): its element count, first and last flat element.
+static int box_extents(dctzhip_ctx* c, const char* what, size_t n, int ndim, const size_t* dims, const size_t* lo, const size_t* hi,
+                       size_t* cnt, size_t* first, size_t* last) {
+  size_t prod = 1;
+  *cnt = 1; *first = 0; *last = 0;
+  for (int i = 0; i < ndim; i++) {
+    // (n <= INT_MAX: a product that stays <= n cannot overflow)
+    if (dims[i] == 0 || dims[i] > n / prod) return fail(c, DCTZHIP_E_ARG, "%s: the product of dims is not n = %zu", what, n);
+    prod *= dims[i];
+    if (lo[i] >= hi[i] || hi[i] > dims[i])
+      return fail(c, DCTZHIP_E_ARG, "%s: [%zu, %zu) is not inside dimension %d of %zu", what, lo[i], hi[i], i, dims[i]);
+    *cnt *= hi[i] - lo[i];
+    *first = *first * dims[i] + lo[i];
+    *last = *last * dims[i] + (hi[i] - 1);
+  }
+  if (prod != n) return fail(c, DCTZHIP_E_ARG, "%s: the product of dims is not n = %zu", what, n);
+  return DCTZHIP_OK;
+}
+// what a box call may read of bin_index, DC and the index: what dctzhip_decompress_range reads for [first box element, last box
+// element + 1)
+static void box_read_spans(Span* sp, size_t* m, const uint8_t* d_bin, const float* d_dc, const uint32_t* d_index, size_t n, size_t first,
+                           size_t last, int item) {
+  const size_t t0 = first / TILE_ELEMS, t1 = last / TILE_ELEMS + 1;
+  const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n, t1 * (size_t)TILE_ELEMS);
+  add_span(sp, m, d_bin + b0, b1 - b0, SPAN_READ, item);
+  add_span(sp, m, d_dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, item);
+  add_span(sp, m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, item);
+}
+
 template <typename T>
 static int decompress_box_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
@@ -2092,32 +2147,19 @@ extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const f
   if (rc) return rc;
   if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
   if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: null dims, lo or hi");
-  size_t prod = 1, cnt = 1, first = 0, last = 0;
-  for (int i = 0; i < ndim; i++) {
-    // (n <= INT_MAX: a product that stays <= n cannot overflow)
-    if (dims[i] == 0 || dims[i] > n / prod) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: the product of dims is not n = %zu", n);
-    prod *= dims[i];
-    if (lo[i] >= hi[i] || hi[i] > dims[i])
-      return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: [%zu, %zu) is not inside dimension %d of %zu", lo[i], hi[i], i, dims[i]);
-    cnt *= hi[i] - lo[i];
-    first = first * dims[i] + lo[i];
-    last = last * dims[i] + (hi[i] - 1);
-  }
-  if (prod != n) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: the product of dims is not n = %zu", n);
+  size_t cnt = 1, first = 0, last = 0;
+  rc = box_extents(c, "dctzhip_decompress_box", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  if (rc) return rc;
   if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
     return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
   if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
   {
     // what the call may read: what dctzhip_decompress_range reads for [first box element, last box element + 1)
-    const size_t t0 = first / TILE_ELEMS, t1 = last / TILE_ELEMS + 1;
-    const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n, t1 * (size_t)TILE_ELEMS);
     Span sp[5];
     size_t m = 0;
-    add_span(sp, &m, (const uint8_t*)d_bin + b0, b1 - b0, SPAN_READ, 0);
-    add_span(sp, &m, d_dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, 0);
+    box_read_spans(sp, &m, (const uint8_t*)d_bin, d_dc, d_index, n, first, last, 0);
     add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, 0);
     add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
     rc = check_spans(c, sp, m, "dctzhip_decompress_box", nullptr);
     if (rc) return rc;
@@ -2129,6 +2171,118 @@ extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const f
                                            last, (double*)d_out)
              : decompress_box_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, box, first,
                                           last, (float*)d_out);
+}
+
+// ---- a list of boxes in one call (include/dctz_hip.h; dctz_kernels_mbox.hip) ------------------------------------
+static constexpr size_t MBOX_LIST_MAX = (size_t)1 << 24;                // items: the bound B of a call may not exceed it
+static constexpr size_t MBOX_TABLE_BYTES = (size_t)DCTZHIP_BOXES_MAX * (sizeof(BoxRec) + sizeof(unsigned));
+
+// recs[0, k) are complete but for the device side of the table; rem_boxes[0, nrem) reach into the short block; B bounds the hits.
+template <typename T>
+static int decompress_boxes_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                 const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
+                                 int k, const BoxRec* recs, const unsigned* rem_boxes, int nrem, unsigned total, size_t B) {
+  hipStream_t s = c->stream;
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  int rc;
+  if (!c->mb_pin) {
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mb_pin), MBOX_TABLE_BYTES, hipHostMallocDefault));
+    HIPCHK(c, hipMalloc(&c->mb_dev, MBOX_TABLE_BYTES));
+  }
+  if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
+  c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
+  if ((rc = ra_begin<T>(c, mode, qtable_host))) return rc;
+  if (nrem) { if ((rc = upload_rtab<T>(c, rem))) return rc; }
+  // the table in one transfer, on the call's stream, behind everything of the prologue that can fail: from here on the call
+  // reaches its synchronisation (ra_finish), or the stream is synchronised before the error is returned, so the pinned
+  // copy is never rewritten under a copy in flight
+  const size_t rec_bytes = (size_t)k * sizeof(BoxRec);
+  memcpy(c->mb_pin, recs, rec_bytes);
+  memcpy(c->mb_pin + rec_bytes, rem_boxes, (size_t)nrem * sizeof(unsigned));
+  {
+    const hipError_t e = hipMemcpyAsync(c->mb_dev, c->mb_pin, rec_bytes + (size_t)nrem * sizeof(unsigned), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);
+      return fail(c, DCTZHIP_E_HIP, "copy of the box table failed: %s", hipGetErrorString(e));
+    }
+  }
+  BoxListParams lp;
+  lp.recs = reinterpret_cast<const BoxRec*>(c->mb_dev);
+  lp.nbox = (unsigned)k; lp.total = total; lp.unit = (unsigned)TILE_ELEMS; lp.end = (unsigned)n;
+  lp.items = c->mb_items; lp.cap = (unsigned)B; lp.ctl = c->ctl;
+  MBoxParams<T> p;
+  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  p.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.recs = lp.recs; p.items = c->mb_items; p.rem_boxes = reinterpret_cast<const unsigned*>(c->mb_dev + rec_bytes);
+  p.cap = (unsigned)B; p.n = (unsigned)n; p.nfull = nfull;
+  // single-wave workgroups that take items: as many as are resident at once, at most one per item the list can hold
+  int& occ = c->mbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
+  if (occ == 0) occ = std::max(mbox_occupancy<T>(mode), 1);
+  const size_t resident = (size_t)c->num_cu * (size_t)occ;
+  const int grid = (int)std::min(resident, B);
+  c->mbox_grid = (unsigned)grid; c->mbox_bound = (unsigned)B; c->mbox_items = 0;
+  launch_boxlist_build(lp, s);
+  launch_decompress_mbox<T>(p, mode, grid, nrem, s);
+  SET_LAST(c, 1, "k_decompress_mbox<%s, %d>", tname<T>(), mode);
+  rc = ra_finish(c, &c->mbox_items);
+  if (rc == DCTZHIP_E_HIP) (void)hipStreamSynchronize(s);   // (a failed launch or read-back: the table's copy may still be in flight)
+  return rc;
+}
+
+extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                        const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf,
+                                        int mode, int ndim, const size_t* dims, int k, const dctzhip_box_item* boxes) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  if (k < 1 || k > DCTZHIP_BOXES_MAX) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: k must be in [1, %d]", DCTZHIP_BOXES_MAX);
+  if (!boxes) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: null boxes");
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
+  if (!dims) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: null dims");
+  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index and the outputs must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  const unsigned nfull = (unsigned)(n / 64);
+  const bool rem = n % 64 != 0;
+  std::vector<BoxRec> recs((size_t)k);
+  std::vector<unsigned> rem_boxes;
+  // every buffer of the call against every other: the outputs may overlap nothing, neither each other nor what any box reads
+  std::vector<Span> sp((size_t)k * 4 + 1);
+  size_t m = 0, B = 0, total = 0;
+  add_span(sp.data(), &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, -1);
+  for (int i = 0; i < k; i++) {
+    char what[48];
+    snprintf(what, sizeof(what), "dctzhip_decompress_boxes: box %d", i);
+    size_t cnt, first, last;
+    if ((rc = box_extents(c, what, n, ndim, dims, boxes[i].lo, boxes[i].hi, &cnt, &first, &last))) return rc;
+    if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", what);
+    if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", what);
+    box_read_spans(sp.data(), &m, (const uint8_t*)d_bin, d_dc, d_index, n, first, last, i);
+    add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(dtype), SPAN_OUT, i);
+    BoxRec& r = recs[(size_t)i];
+    r.g = canonical_box(ndim, dims, boxes[i].lo, boxes[i].hi);
+    r.t0 = (unsigned)(first / TILE_ELEMS); r.t1 = (unsigned)(last / TILE_ELEMS + 1);
+    r.cand0 = (unsigned)total;                      // (k <= 2^12 boxes of <= 2^19 candidates each)
+    r.out = boxes[i].d_out;
+    const size_t cand = r.t1 - r.t0;
+    total += cand;
+    // a run of L consecutive elements touches at most ceil((L - 1) / 4096) + 1 tiles
+    size_t runs = 1;
+    for (int d = 0; d < BOX_ND - 1; d++) runs *= r.g.ext[d];
+    const size_t runlen = r.g.ext[BOX_ND - 1];
+    B += std::min(cand, runs * ((runlen - 1 + TILE_ELEMS - 1) / TILE_ELEMS + 1));
+    if (rem && r.g.rank((unsigned)n) != r.g.rank(nfull * 64u)) rem_boxes.push_back((unsigned)i);
+  }
+  if ((rc = check_spans(c, sp.data(), m, "dctzhip_decompress_boxes", nullptr, "box"))) return rc;
+  if (B > MBOX_LIST_MAX)
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: the boxes may hit %zu tiles, more than the %zu a call lists", B, MBOX_LIST_MAX);
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? decompress_boxes_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, k,
+                                             recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B)
+             : decompress_boxes_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, k,
+                                            recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B);
 }
 
 // ---- multi-dimensional blocks (include/dctz_hip.h) -------------------------------------------------

@@ -1699,7 +1699,7 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   return 1;
 }
 
-/* ------------- dctz_decompress_range, dctz_decompress_box, dctz_decompress_box_nd -- */
+/* ------------- dctz_decompress_range, dctz_decompress_box, dctz_decompress_boxes, dctz_decompress_box_nd -- */
 /* The first `want` bytes of one section into dst.  Indexed (sizes != NULL): only the chunks that hold them, side by side
  * on host threads (dst has room for whole chunks: min(raw, chunks * chunk) bytes); a chunk that does not inflate sends the
  * section to the streaming inflate.  Otherwise one inflate that stops once `want` bytes are out.  Returns the bytes made. */
@@ -1747,7 +1747,26 @@ static size_t inflate_prefix(const unsigned char *sec, unsigned int zlen, size_t
  * extents from the container; [lo, hi) becomes the stream positions [64 * first intersecting block, 64 * (last + 1))): the
  * prefix of the sections that span needs, its index, one device call, and only the wanted elements copied back. */
 #define PART_TILED (-1)
-static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, t_var *var_r) {
+/* dctz_decompress_boxes: k boxes (rows of ndim entries) of one container through the same machinery ONCE -- the prefix of
+ * the sections up to the last element of any box, one index, one dctzhip_decompress_boxes into one device arena, k copies
+ * back. */
+typedef struct { int k; const size_t *lo, *hi; t_var *const *var_r; } part_list;
+/* A box against n elements seen as dims: 0 and its first and last flat element and its element count, or -1. */
+static int box_span(size_t n, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, size_t *first, size_t *last, size_t *elems) {
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM || !dims || !blo || !bhi || n == 0) return -1;
+  size_t prod = 1;
+  *first = 0; *last = 0; *elems = 1;
+  for (int i = 0; i < ndim; i++) {
+    if (dims[i] == 0 || dims[i] > n / prod || blo[i] >= bhi[i] || bhi[i] > dims[i]) return -1;
+    prod *= dims[i];
+    *elems *= bhi[i] - blo[i];
+    *first = *first * dims[i] + blo[i];
+    *last = *last * dims[i] + (bhi[i] - 1);
+  }
+  return prod == n ? 0 : -1;
+}
+static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, t_var *var_r,
+                           const part_list *list) {
   const double t_begin = now_s();
   dzc_view v;
   dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
@@ -1758,6 +1777,7 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   const unsigned int cnt = v.cnt;
   size_t out_elems;
+  dctzhip_box_item *items = NULL;
   if (tiled) {
     if (!blo || !bhi || n == 0) return -1;
     const size_t edge = v.nd == 2 ? 8 : 4;
@@ -1771,23 +1791,31 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
       last = last * nb + (bhi[i] - 1) / edge;
     }
     lo = first * BLK_SZ; hi = (last + 1) * BLK_SZ;
-  } else if (ndim != 0) {
-    if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM || !dims || !blo || !bhi || n == 0) return -1;
-    size_t prod = 1, last = 0;
-    lo = 0; out_elems = 1;
-    for (int i = 0; i < ndim; i++) {
-      if (dims[i] == 0 || dims[i] > n / prod || blo[i] >= bhi[i] || bhi[i] > dims[i]) return -1;
-      prod *= dims[i];
-      out_elems *= bhi[i] - blo[i];
-      lo = lo * dims[i] + blo[i];
-      last = last * dims[i] + (bhi[i] - 1);
+  } else if (list) {                                           /* [lo, hi): from the first element of any box to the last of any */
+    if (list->k < 1 || list->k > DCTZHIP_BOXES_MAX || !list->lo || !list->hi || !list->var_r) return -1;
+    items = (dctzhip_box_item *)calloc((size_t)list->k, sizeof(dctzhip_box_item));
+    if (!items) { fprintf(stderr, "Out of memory: box list\n"); exit(1); }
+    out_elems = 0;                                             /* the arena: every output at a multiple of 16 bytes */
+    for (int j = 0; j < list->k; j++) {
+      size_t first, last, elems;
+      if (!list->var_r[j] || box_span(n, ndim, dims, list->lo + (size_t)j * ndim, list->hi + (size_t)j * ndim, &first, &last, &elems) != 0) {
+        free(items);
+        return -1;
+      }
+      if (j == 0 || first < lo) lo = first;
+      if (j == 0 || last + 1 > hi) hi = last + 1;
+      for (int i = 0; i < ndim; i++) { items[j].lo[i] = list->lo[(size_t)j * ndim + i]; items[j].hi[i] = list->hi[(size_t)j * ndim + i]; }
+      items[j].d_out = (void *)(uintptr_t)(out_elems * ts);    /* offset for now: the arena may still move */
+      out_elems += (elems * ts + 15) / 16 * 16 / ts;
     }
-    if (prod != n) return -1;
+  } else if (ndim != 0) {
+    size_t last;
+    if (box_span(n, ndim, dims, blo, bhi, &lo, &last, &out_elems) != 0) return -1;
     hi = last + 1;
   } else {
     out_elems = hi - lo;
   }
-  if (n == 0 || lo >= hi || hi > n) return -1;
+  if (n == 0 || lo >= hi || hi > n) { free(items); return -1; }
   const size_t S = DCTZHIP_INDEX_STRIDE;
   const size_t t1 = (hi + S - 1) / S;                        /* the range's tiles end here */
   const size_t need[3] = {MIN(n, S * t1),                    /* bin ids: the flags in front give AC_exact's position */
@@ -1829,7 +1857,11 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   }
   t0 = now_s();
   grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
-  const int rc = tiled     ? dctzhip_decompress_box_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
+  if (list) for (int j = 0; j < list->k; j++) items[j].d_out = (unsigned char *)g_dev.out + (uintptr_t)items[j].d_out;
+  const int rc = list      ? dctzhip_decompress_boxes(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
+                                                      (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims,
+                                                      list->k, items)
+                 : tiled   ? dctzhip_decompress_box_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
                                                        (const uint32_t *)g_dev.idx, qtable, v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE,
                                                        blo, bhi, g_dev.out)
                  : ndim == 0 ? dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
@@ -1839,26 +1871,40 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
                                                     (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims,
                                                     blo, bhi, g_dev.out);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
-  if (rc != DCTZHIP_OK) die(tiled ? "dctzhip_decompress_box_nd" : ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
+  if (rc != DCTZHIP_OK)
+    die(list ? "dctzhip_decompress_boxes" : tiled ? "dctzhip_decompress_box_nd" : ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
   const double t1s = now_s();
-  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
+  if (list) {
+    for (int j = 0; j < list->k; j++) {
+      size_t elems = 1;
+      for (int i = 0; i < ndim; i++) elems *= items[j].hi[i] - items[j].lo[i];
+      if (dctzhip_memcpy_d2h(c, var_bytes(list->var_r[j]), items[j].d_out, elems * ts) != DCTZHIP_OK) die("D2H output");
+    }
+  } else if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
   g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
   g_times.total_s = now_s() - t_begin;
   ret = 1;
 out:
   for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  free(items);
   return ret;
 }
 
-int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) { return decompress_part(var_z, lo, hi, 0, NULL, NULL, NULL, var_r); }
+int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r) { return decompress_part(var_z, lo, hi, 0, NULL, NULL, NULL, var_r, NULL); }
 
 int dctz_decompress_box(t_var *var_z, int ndim, const size_t *dims, const size_t *lo, const size_t *hi, t_var *var_r) {
   if (ndim < 1) return -1;
-  return decompress_part(var_z, 0, 0, ndim, dims, lo, hi, var_r);
+  return decompress_part(var_z, 0, 0, ndim, dims, lo, hi, var_r, NULL);
+}
+
+int dctz_decompress_boxes(t_var *var_z, int ndim, const size_t *dims, int k, const size_t *lo, const size_t *hi, t_var *const *var_r) {
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return -1;
+  const part_list list = {k, lo, hi, var_r};
+  return decompress_part(var_z, 0, 0, ndim, dims, NULL, NULL, NULL, &list);
 }
 
 int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_var *var_r) {
-  return decompress_part(var_z, 0, 0, PART_TILED, NULL, lo, hi, var_r);
+  return decompress_part(var_z, 0, 0, PART_TILED, NULL, lo, hi, var_r, NULL);
 }
 
 /* ------------------------------------------------------ calc_data_stat ----- */

@@ -58,6 +58,14 @@ class RdPoint(C.Structure):          # dctzhip_rd_point
                 ("raw_bytes", C.c_uint64)]
 
 
+BOX_MAXDIM = 4                       # DCTZHIP_BOX_MAXDIM
+BOXES_MAX = 4096                     # DCTZHIP_BOXES_MAX: boxes per dctzhip_decompress_boxes call
+
+
+class BoxItem(C.Structure):          # dctzhip_box_item
+    _fields_ = [("lo", C.c_size_t * BOX_MAXDIM), ("hi", C.c_size_t * BOX_MAXDIM), ("d_out", C.c_void_p)]
+
+
 RD_MAXK = 16                         # DCTZHIP_RD_MAXK: bounds per dctzhip_rd_probe call
 
 
@@ -106,6 +114,9 @@ _PROTOS = {
     "dctzhip_decompress_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_decompress_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                           C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
     "dctzhip_set_blocking": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_compress_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BatchCItem), C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_decompress_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BatchDItem), C.c_int, C.POINTER(C.c_int)]),
@@ -408,6 +419,40 @@ class Context:
             mode, nd, arr(*dims), arr(*lo), arr(*hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_box")
         return dst.view(shape)
+
+    def decompress_boxes(self, out, cnt, dims, dtype, eb, sf, boxes, index, mode=EC, qtable=None, dsts=None):
+        """The boxes (lo, hi) of `boxes`, each what decompress_box() gives for it, in ONE call (one work list of the hit tiles
+        of all boxes, one decode launch, one synchronisation).  Boxes may overlap or repeat.  Returns the list of tensors
+        shaped hi - lo; `dsts` (or None: allocated) are the outputs, one per box."""
+        t = self.torch
+        self._bind_stream()
+        dims = [int(v) for v in dims]
+        nd = len(dims)
+        n = int(np.prod(dims, dtype=np.int64)) if nd else 0
+        boxes = [([int(v) for v in lo], [int(v) for v in hi]) for lo, hi in boxes]
+        shapes = []
+        for lo, hi in boxes:
+            assert len(lo) == nd and len(hi) == nd
+            shapes.append([max(h - l, 0) for l, h in zip(lo, hi)])
+        if dsts is None:
+            dsts = [t.empty(sh, dtype=dtype, device=self.device) for sh in shapes]
+        assert len(dsts) == len(boxes)
+        q = None
+        if mode == QT:
+            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
+            assert q.size == 64
+        items = (BoxItem * max(len(boxes), 1))()
+        for it, (lo, hi), d in zip(items, boxes, dsts):
+            for i in range(min(nd, BOX_MAXDIM)):
+                it.lo[i], it.hi[i] = lo[i], hi[i]
+            it.d_out = d.data_ptr()
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_decompress_boxes(
+            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
+            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb), float(sf),
+            mode, nd, arr(*dims), len(boxes), C.cast(items, C.c_void_p))
+        self._check(rc, "dctzhip_decompress_boxes")
+        return [d.view(sh) for d, sh in zip(dsts, shapes)]
 
     # ---- batches of arrays (include/dctz_hip.h: dctzhip_compress_batch / dctzhip_decompress_batch) ----
     def compress_batch(self, xs, ebs, mode=EC, outs=None, scaled=None, prepared=None):

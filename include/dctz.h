@@ -162,6 +162,16 @@ int dctz_decompress_range(t_var *var_z, size_t lo, size_t hi, t_var *var_r);
  * dctz_decompress_range(first box element, last box element + 1) inflates and no more; on the device only the tiles that
  * hold box elements are decoded, once each (include/dctz_hip.h: dctzhip_decompress_box), and only the box is copied back. */
 int dctz_decompress_box(t_var *var_z, int ndim, const size_t *dims, const size_t *lo, const size_t *hi, t_var *var_r);
+/* k boxes of ONE container in one call (ADDITION, EC and QT builds), 1 <= k <= 4096: lo and hi hold k rows of ndim entries,
+ * var_r[j]->buf (allocated by the caller) receives box j, the bytes dctz_decompress_box gives for it.  Boxes may overlap or
+ * repeat.  The container is gone through ONCE: the sections are inflated up to what the last element of any box needs (plain
+ * and DZIX, as dctz_decompress_range(smallest first box element, largest last box element + 1) would), one exception index
+ * is built, one device call (include/dctz_hip.h: dctzhip_decompress_boxes) decodes the hit tiles of every box into one
+ * device arena, and k copies bring the boxes back.  Return values and refusals are dctz_decompress_box's, for any box of
+ * the list (nothing is written then); a k outside 1 .. 4096 and a null lo, hi, var_r or var_r[j] return -1 as well. */
+int dctz_decompress_boxes(t_var *var_z, int ndim, const size_t *dims, int k,
+                          const size_t *lo, const size_t *hi,   /* k rows of ndim entries */
+                          t_var *const *var_r);                 /* k caller-allocated outputs */
 /* A box of a container compressed in tiles (ADDITION, EC and QT builds): var_z is a DZND container (dctz_set_block_dims +
  * dctz_compress); its geometry and extents come from the container.  Elements lo[i] <= c[i] < hi[i] (2 or 3 entries, as the
  * container has dimensions), dense and in C order into var_r->buf (allocated by the caller); each is bit for bit the element

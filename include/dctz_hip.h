@@ -132,14 +132,15 @@ int dctzhip_set_split(dctzhip_ctx *ctx, int on);
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr, 11 / 12 workgroups and
- * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran) -- and knobs that
+ * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran), 13 / 14 / 15 items
+ * in the list of the last dctzhip_decompress_boxes call, workgroups of its decode launch and the list's bound -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
  * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
 int dctzhip_debug_counter(dctzhip_ctx *ctx, int which, unsigned long long *value);
 int dctzhip_debug_knob(dctzhip_ctx *ctx, int key, int value);
 /* (tools) the name rocprofv3 lists the big kernel of the last call under, every template argument: which = 0 compress,
- * 1 decompress, 2 / 3 batch compress of the fp64 / fp32 arrays, 4 / 5 batch decompress ("" if none ran yet) */
+ * 1 decompress (the random-access calls included), 2 / 3 batch compress of the fp64 / fp32 arrays, 4 / 5 batch decompress ("" if none ran yet) */
 int dctzhip_debug_last_kernel(dctzhip_ctx *ctx, int which, char *buf, size_t cap);
 /* on != 0: every compress / decompress call ends with a synchronisation of the context's stream, i.e. its outputs are
  * complete for ANY observer when it returns (default off: complete in stream order, see the two calls below; env
@@ -324,6 +325,35 @@ int dctzhip_decompress_box(dctzhip_ctx *ctx, const void *d_bin_index, const floa
                            uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
                            double error_bound, double sf, int mode, int ndim, const size_t *dims, const size_t *lo,
                            const size_t *hi, void *d_out);
+/* k boxes of the SAME array in one call: one box table handed over in one transfer, one work list of (box, hit tile) pairs
+ * built on the device, one persistent decode launch whose workgroups take list items -- none of them ever meets a tile
+ * that is not hit -- and one synchronisation.  Everything but the last two arguments is dctzhip_decompress_box's; boxes is
+ * a HOST array of k items, entries of lo / hi at positions >= ndim are ignored.
+ *   boxes[i].d_out  receives exactly the bytes dctzhip_decompress_box writes for box i with the same remaining arguments
+ *               (EC and QT, fp32 and fp64, the short last block included)
+ *   overlap     boxes may overlap, nest or repeat.  A tile hit by two boxes is decoded once per box that hits it:
+ *               de-duplication is not part of this call.
+ *   locality    that of dctzhip_decompress_box over the union of the boxes' hit tiles: the call reads the bin ids, DC
+ *               values, idx[t], idx[t + 1] and AC_exact[idx[t], idx[t + 1]) of tiles hit by at least one box and nothing
+ *               else of the streams; it writes nothing outside the k outputs.
+ *   refusals    before anything is launched or written, all or nothing, DCTZHIP_E_ARG: k < 1, k > DCTZHIP_BOXES_MAX, a null
+ *               boxes; for any box whatever dctzhip_decompress_box refuses (the message names the box's index); an output
+ *               that overlaps another output or what any box of the call may read; boxes that may hit more than 2^24 tiles
+ *               in all (the bound of the work list: per box the smaller of its candidate tiles and the tiles its rows can
+ *               touch).  On the device, for hit tiles only, dctzhip_decompress_box's index check: a failing tile reads no
+ *               AC_exact, the call returns DCTZHIP_E_ARG, the outputs are undefined and the context stays usable.
+ * Returns once that check is known, having synchronised the context's stream once, as dctzhip_decompress_box does.
+ *   cost        the list builder runs one thread per (box, candidate tile), candidates being the tiles from a box's first
+ *               to its last element: cheap next to a decode (a rank computation each), but it follows the candidates, not the
+ *               hits.  Thousands of thin boxes that each span a large array (up to 2^31 pairs in all) pay for that span;
+ *               only the hits are bounded (2^24).
+ * dctzhip_debug_counter 13 / 14 / 15: items of the last call's list, workgroups of its decode launch, the list's bound. */
+#define DCTZHIP_BOXES_MAX 4096
+typedef struct { size_t lo[DCTZHIP_BOX_MAXDIM], hi[DCTZHIP_BOX_MAXDIM]; void *d_out; } dctzhip_box_item;
+int dctzhip_decompress_boxes(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                             uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
+                             double error_bound, double sf, int mode, int ndim, const size_t *dims,
+                             int k, const dctzhip_box_item *boxes /* host */);
 
 /* ---- batches of arrays ------------------------------------------------------ */
 /* The reference's own workloads are LISTS of small arrays, one dctz_compress() call and one process each
