@@ -148,7 +148,7 @@ struct Ctl {
   unsigned pad_ticket;
   unsigned cnt_total;              // exceptions emitted / consumed so far
   unsigned error;                  // 2: AC_exact underrun on decode
-  unsigned pad0;
+  unsigned memo_arrive;            // memo decode (k_decompress_il, MEMO): workgroups that have all their counts (low 16 bits) / that met a count the memo does not have (high 16); zero between calls
   unsigned long long qraw[64];     // max |coef| per position, raw bits of T (dctz-comp-lib.c:371-372)
   unsigned long long q0;           // bits of the last block's DC (qtable[0], :355-360)
   unsigned long long pad1;
@@ -268,9 +268,10 @@ struct InvParams {
   const T* tab;
   const T* rtab;
   const T* qtab;                   // QT: clamped table (device)
-  const unsigned* tile_cnt;        // per-TILE counts of "stored exactly" flags (k_count_tiles)
+  const unsigned* tile_cnt;        // per-TILE counts of "stored exactly" flags (k_count_tiles; memo decode: the last compress call's, FwdParams::ttot)
   const unsigned* wg_cnt;          // the same summed over the tile range of every workgroup of k_decompress (nwg entries)
-  const unsigned* tile_pre;        // tile-interleaved k_decompress: counts of the tiles of the same RANGE in front of a tile (k_count_tiles)
+  const unsigned* tile_pre;        // tile-interleaved k_decompress: counts of the tiles of the same RANGE in front of a tile (k_count_tiles);
+                                   // memo decode: every tile's first place in AC_exact[] as the last compress call left it (k_compact_ac)
   Ctl* ctl;
   unsigned nfull, ntiles, ac_count;
   unsigned nwg;                    // grid of k_decompress
@@ -444,6 +445,7 @@ constexpr unsigned LIST_IN_ORDER = 0x80000000u, LIST_LEN = 0x7FFFFFFFu;
 // lane of an "odd" wavefront (workgroups of two waves); same parameters, same outputs
 void launch_compress_eo(const FwdParams<double>& p, int mode, bool stats, int grid, hipStream_t s);
 int compress_eo_occupancy(int mode, bool stats, bool direct);
+constexpr unsigned DEC_ERR_MEMO_STALE = 6u;   // HostBox::error: a tile's flags do not add up to the count the last compress call left (the decode memo is stale: the host decodes again behind k_count_tiles)
 constexpr unsigned ONE_ERR_TIMEOUT = 3u;   // Ctl::error / HostBox::error: a sweep of the board gave up (a workgroup was not resident)
 template <typename T> void launch_compress_one(const OneFwd<T>& a, int mode, bool scaled, hipStream_t s);
 template <typename T> void launch_decompress_one(const OneInv<T>& a, int mode, hipStream_t s);
@@ -469,11 +471,12 @@ template <typename T> void launch_compress(const FwdParams<T>& p, int mode, bool
 template <typename T> void launch_gather_nd(const T* x, T* lin, const NdShape& sh, double* part, int nparts, hipStream_t s);
 template <typename T> void launch_scatter_nd(const T* lin, T* out, const NdShape& sh, int grid, hipStream_t s);
 template <typename T> void launch_compress_rem(const FwdParams<T>& p, int mode, int l, hipStream_t s);
-template <typename T> void launch_compact_ac(const FwdParams<T>& p, int mode, double eb, unsigned nlists, int grid, const FinArgs& fin, hipStream_t s);
+template <typename T> void launch_compact_ac(const FwdParams<T>& p, int mode, double eb, unsigned nlists, int grid, const FinArgs& fin, hipStream_t s,
+                                             unsigned* memo_start = nullptr);
 struct QtabArg { unsigned long long w[64]; };       // a QT table (64 values of either element type) as a kernel argument
 void launch_count_tiles(const uint8_t* bin, unsigned nfull, unsigned ntiles, unsigned nwg, unsigned* tile_cnt, unsigned* wg_cnt, hipStream_t s,
                         const void* qtab_host = nullptr, size_t qtab_bytes = 0, void* qtab_dev = nullptr, unsigned* tile_pre = nullptr);
-template <typename T> void launch_decompress(const InvParams<T>& p, int mode, int grid, const FinArgs& fin, int geom, hipStream_t s);
+template <typename T> void launch_decompress(const InvParams<T>& p, int mode, int grid, const FinArgs& fin, int geom, hipStream_t s, bool memo = false);
 template <typename T> void launch_decompress_rem(const InvParams<T>& p, int mode, bool scale, int l, hipStream_t s);
 template <typename T> void launch_dct_blocks(const T* x, T* out, const T* gtab, const T* rtab, size_t n,
                                              bool inverse, int grid, hipStream_t s);

@@ -635,7 +635,7 @@ __device__ __forceinline__ unsigned wave_incl_max_scan(unsigned v) {
 }
 template <typename T, int MODE>
 __device__ __forceinline__ void compact_ac_body(const FwdParams<T>& p, const double eb, const unsigned nlists, const unsigned l, const unsigned chunk,
-                                                unsigned* sh) {
+                                                unsigned* sh, unsigned* __restrict__ memo = nullptr) {
   using Bits = typename Traits<T>::Bits;
   using S = Sub<T, MODE>;
   constexpr int NQ = S::NQ, CB = S::CBITS, FB = S::FB, FPD = S::FPD, NPK = S::NPK;
@@ -692,6 +692,17 @@ __device__ __forceinline__ void compact_ac_body(const FwdParams<T>& p, const dou
   const size_t src = list_slot(l, G, p.ntiles);
   if (l >= G || (nraw & LIST_IN_ORDER)) {            // the remainder block's list, or a list that is in order as it is
     if (chunk == 0) {
+      // the decode memo (below) of a list nobody walks tile by tile: dst + the exclusive prefix of its tiles' totals
+      if (memo != nullptr && l < G && wave == 0) {
+        unsigned run = dst;
+        for (unsigned u0 = tr.lo; u0 < tr.hi; u0 += 64u) {
+          const unsigned u = u0 + lane;
+          const unsigned v = u < tr.hi ? p.ttot[u] : 0u;
+          const unsigned incl = wave_incl_scan(v);
+          if (u < tr.hi) memo[u] = run + incl - v;
+          run += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+        }
+      }
       for (unsigned i0 = threadIdx.x; i0 < n; i0 += 4 * SWG) {          // (four independent items in flight per thread)
         float v[4];
 #pragma unroll
@@ -704,6 +715,9 @@ __device__ __forceinline__ void compact_ac_body(const FwdParams<T>& p, const dou
   }
   if (!tile_here) return;
   pre = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(pre), 63);
+  // Decode memo: where the tile's piece of AC_exact[] starts.  A decode of these very streams (dctz_shim.hip: DecodeMemo)
+  // takes it, with ttot[t], in place of a pass over bin_index that counts the flags again (k_count_tiles).
+  if (memo != nullptr && part == 0u && lane == 0u) memo[t] = dst + pre;
   if (!__builtin_amdgcn_ballot_w64((c >> CB) != 0u)) {
     // only the first sub-list of the tile has items (a smooth field: what is stored exactly are the lowest
     // frequencies): block-major over its range of j IS the reference's order -- the tile's piece is copied as it is
@@ -809,7 +823,7 @@ __device__ __forceinline__ void compact_ac_body(const FwdParams<T>& p, const dou
   }
 }
 template <typename T, int MODE>
-__global__ __launch_bounds__(SWG) void k_compact_ac(FwdParams<T> p, double eb, unsigned nlists, FinArgs fin) {
+__global__ __launch_bounds__(SWG) void k_compact_ac(FwdParams<T> p, double eb, unsigned nlists, FinArgs fin, unsigned* memo) {
   __shared__ unsigned sh[SWG / 64];
   if (fin.box != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
     unsigned all = 0;
@@ -820,7 +834,7 @@ __global__ __launch_bounds__(SWG) void k_compact_ac(FwdParams<T> p, double eb, u
     f.err_known = true; f.error = 0;
     finish_body<true>(f);
   }
-  compact_ac_body<T, MODE>(p, eb, nlists, blockIdx.x, blockIdx.y, sh);
+  compact_ac_body<T, MODE>(p, eb, nlists, blockIdx.x, blockIdx.y, sh, memo);
 }
 
 // =============================================================== decompress ==
@@ -1121,7 +1135,19 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((sizeof(T) =
 // k_count_tiles RANGES in front of the tile's range (their exclusive prefix: built once per workgroup in the LDS array that
 // is still free then) + the counts of the range's tiles in front of it (tile_pre, left by k_count_tiles); a workgroup keeps
 // the start and the count of its next 64 tiles in a register pair, lane r = its r-th tile.
-template <typename T, int MODE, int PH, typename Handoff>
+//
+// MEMO: the streams are the ones the context's last compress call wrote (dctz_shim.hip: DecodeMemo), and that call has left
+// every tile's first place in AC_exact[] (k_compact_ac -> p.tile_pre here) and its count (k_compress: ttot -> p.tile_cnt
+// here), absolute and per tile: no k_count_tiles in front, no prefix over the ranges.  The memo is not trusted: every tile's
+// flags are counted here anyway (the wave scan that places the lanes in the tile's piece), and a count that differs from
+// the memo's marks the workgroup.  A workgroup has its last count at the top of its last trip; it then adds itself to
+// Ctl::memo_arrive -- ONE relaxed atomic, arrivals in the low half and marked workgroups in the high half -- and the
+// workgroup whose add completes the grid hands the verdict to the host (handoff(marked workgroups)) and leaves the word at
+// zero.  All it reports came back with its own atomic: no fence, nothing another workgroup wrote is read, nobody waits.
+// With every count equal to the memo's the starts are the true prefix sums, so the reconstruction is the classic one's
+// bit for bit; otherwise the host decodes again behind k_count_tiles.  Stale starts cannot fault: AC_exact is read through
+// descriptors that end at ac_count, and out of the LDS stage at bounded indices.
+template <typename T, int MODE, int PH, bool MEMO = false, typename Handoff>
 __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const unsigned wg, const unsigned nwg, Handoff&& handoff) {
   using G = Geo<T, PH>;
   constexpr int DEC_CAP = DecStage<T>::CAP;
@@ -1138,7 +1164,7 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
   // one load per trip was sixteen to twenty-eight dependent round trips, 8-14 us -- and are scanned out of LDS, 64 entries
   // = one conflict-free row per wave scan)
   unsigned* const rpre = reinterpret_cast<unsigned*>(io);
-  {
+  if constexpr (!MEMO) {
     for (unsigned i0 = 0; i0 < p.nwg; i0 += 512u) {
       unsigned v[8];
 #pragma unroll
@@ -1155,7 +1181,7 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
       run += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
     }
   }
-  handoff();
+  if constexpr (!MEMO) handoff();
   // the inverse of tile_range(): which range a tile lies in
   const unsigned rq = p.ntiles / p.nwg, rr = p.ntiles % p.nwg;
   auto range_of = [&](unsigned t) -> unsigned { return t < rr * (rq + 1u) ? t / (rq + 1u) : rr + (t - rr * (rq + 1u)) / rq; };
@@ -1163,7 +1189,7 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
   unsigned starts = 0, cnts = 0;                     // lane r: first exact coefficient / count of this workgroup's r-th tile
   if ((unsigned)lane < my_tiles) {
     const unsigned t = wg + (unsigned)lane * nwg;
-    starts = rpre[range_of(t)] + p.tile_pre[t];
+    if constexpr (MEMO) starts = p.tile_pre[t]; else starts = rpre[range_of(t)] + p.tile_pre[t];
     cnts = p.tile_cnt[t];
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (rpre is read: the array may be written now)
@@ -1202,6 +1228,21 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
   auto landed = [&]() {
     if constexpr (sizeof(T) == 8) asm volatile("" :: "v"(dcv));
   };
+  // MEMO: this workgroup's arrival (see above)
+  bool stale = false;
+  unsigned arr_add = 0, arr_old = 0;
+  auto arrive = [&]() {
+    arr_add = 1u | (stale ? 0x10000u : 0u);
+    if (lane == 0) arr_old = __hip_atomic_fetch_add(&p.ctl->memo_arrive, arr_add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  auto arrived = [&]() {                             // (the atomic's answer is first looked at here)
+    const unsigned v = (unsigned)__builtin_amdgcn_readfirstlane((int)arr_old) + arr_add;
+    if ((v & 0xFFFFu) == nwg) {
+      if (lane == 0) p.ctl->memo_arrive = 0u;
+      if constexpr (MEMO) handoff(v >> 16);
+    }
+  };
+  if constexpr (MEMO) { if (my_tiles == 0u) { arrive(); arrived(); } }
   if (my_tiles) { prefetch(wg, 0u); landed(); }
   for (unsigned r = 0; r < my_tiles; r++) {
     const unsigned tile = wg + r * nwg;
@@ -1222,8 +1263,14 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
                       bw[2].x, bw[2].y, bw[2].z, bw[2].w, bw[3].x, bw[3].y, bw[3].z, bw[3].w};
     const float dc_t = dcv;
     const unsigned n = active ? block_flag_count(w) : 0u;
-    unsigned ptr = wave_incl_scan(n) - n;                              // index inside the tile's piece of AC_exact
-    if (S_t + total_t > p.ac_count) underrun = true;                  // the stream promises more than the caller provides
+    const unsigned n_incl = wave_incl_scan(n);
+    unsigned ptr = n_incl - n;                                         // index inside the tile's piece of AC_exact
+    if constexpr (MEMO) {
+      if ((unsigned)__builtin_amdgcn_readlane((int)n_incl, 63) != total_t) stale = true;   // the tile's flags against the memo's count
+      if (r + 1 == my_tiles) arrive();
+    } else {
+      if (S_t + total_t > p.ac_count) underrun = true;                // the stream promises more than the caller provides
+    }
     T x[64];
     const auto qtab = [&](int j) { return qtl.at(j); };
     if constexpr (sizeof(T) == 8) dequantise_grouped<T, MODE, true>(x, w, dc_t, ptr, stage, stage_last, centre, qtab, p.eb, p.range_min, p.range_max);
@@ -1236,6 +1283,7 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
       for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                 // dctz-decomp-lib.c:494-511
     }
     if (r + 1 < my_tiles) landed();
+    if constexpr (MEMO) { if (r + 1 == my_tiles) arrived(); }           // (in front of the tile's row stores: behind them the answer would wait for all 32)
     auto store_phase = [&](auto phase) {
       constexpr int PHASE = decltype(phase)::value;
       write_phase<T, PH, PHASE>(x, outbuf, tm);
@@ -1246,9 +1294,22 @@ __device__ __forceinline__ void decompress_il_body(const InvParams<T>& p, const 
   }
   if (underrun) atomicExch(&p.ctl->error, 2u);
 }
-template <typename T, int MODE, int PH>
+template <typename T, int MODE, int PH, bool MEMO = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu((sizeof(T) == 4 && DCTZ_WPED32) ? DCTZ_WPED32 : PH, (sizeof(T) == 4 && DCTZ_WPED32) ? DCTZ_WPED32 : PH))) void k_decompress_il(InvParams<T> p, FinArgs fin) {
-  decompress_il_body<T, MODE, PH>(p, blockIdx.x, gridDim.x, [&]() { decompress_handoff(p, fin); });
+  if constexpr (MEMO) {
+    // the verdict of the memo's check, by the workgroup that arrived last: with every count the memo's, the stream asks for
+    // exactly the ac_count the tag was matched on (no under-run possible)
+    decompress_il_body<T, MODE, PH, true>(p, blockIdx.x, gridDim.x, [&](unsigned marked) {
+      if (fin.box == nullptr) return;
+      FinBody f;
+      f.ctl = fin.ctl; f.part = nullptr; f.nparts = 0; f.box = fin.box; f.seq = fin.seq; f.guess = nullptr;
+      f.cnt_known = true; f.cnt_total = p.ac_count;
+      f.err_known = true; f.error = marked ? DEC_ERR_MEMO_STALE : 0u;
+      finish_body<false>(f);
+    });
+  } else {
+    decompress_il_body<T, MODE, PH>(p, blockIdx.x, gridDim.x, [&]() { decompress_handoff(p, fin); });
+  }
 }
 
 // Last, short block on decode (dctz-decomp-lib.c:423-428, dct.c:144-199).
@@ -1324,10 +1385,14 @@ int compress_occupancy(int mode, bool stats, int geom, bool scaled) {
 // (tools/r04_il.sh, r04_il2.sh): fp64 EC 220 -> 200-206 us, fp64 EC at p = 0.69 316-335 -> 313-320; fp64 QT 245 -> 257 and
 // fp32 119 -> 125 the OTHER way (kernels their arithmetic holds, not their store stream: they only pay for the scattered
 // reads and the per-tile descriptors), so those keep a contiguous range per workgroup.
+// (memo: fp64 EC only -- the one combination the shim asks it for)
 template <typename T>
-auto decompress_kernel(int mode, int geom, bool interleaved) -> void (*)(InvParams<T>, FinArgs) {
+auto decompress_kernel(int mode, int geom, bool interleaved, bool memo = false) -> void (*)(InvParams<T>, FinArgs) {
   return with_mode(mode, [=](auto M) -> void (*)(InvParams<T>, FinArgs) {
     constexpr int PH = Phases<T>::D;
+    if constexpr (sizeof(T) == 8 && decltype(M)::value == DCTZHIP_EC) {
+      if (geom == GEOM_1D && interleaved && memo) return k_decompress_il<T, DCTZHIP_EC, PH, true>;
+    }
     if (geom == GEOM_1D && interleaved) return k_decompress_il<T, M(), PH>;   // (the shim chooses: fp64 EC by default, everything with DCTZHIP_DEC_IL=2)
     if (geom == GEOM_1D) return k_decompress<T, M(), PH, GEOM_1D>;
     if (geom == GEOM_2D) return k_decompress<T, M(), PH, GEOM_2D>;
@@ -1335,8 +1400,8 @@ auto decompress_kernel(int mode, int geom, bool interleaved) -> void (*)(InvPara
   });
 }
 template <typename T>
-void launch_decompress(const InvParams<T>& p, int mode, int grid, const FinArgs& fin, int geom, hipStream_t s) {
-  hipLaunchKernelGGL(decompress_kernel<T>(mode, geom, takes_interleaved(p, geom)), dim3(grid), dim3(WG), 0, s, p, fin);
+void launch_decompress(const InvParams<T>& p, int mode, int grid, const FinArgs& fin, int geom, hipStream_t s, bool memo) {
+  hipLaunchKernelGGL(decompress_kernel<T>(mode, geom, takes_interleaved(p, geom), memo), dim3(grid), dim3(WG), 0, s, p, fin);
 }
 // (of the contiguous kernel: an interleaved launch is sized by it too -- the shim asks before it decides on tile_pre)
 template <typename T>
@@ -1363,11 +1428,11 @@ void launch_count_tiles(const uint8_t* bin, unsigned nfull, unsigned ntiles, uns
 #endif
 
 template <typename T>
-void launch_compact_ac(const FwdParams<T>& p, int mode, double eb, unsigned nlists, int grid, const FinArgs& fin, hipStream_t s) {
+void launch_compact_ac(const FwdParams<T>& p, int mode, double eb, unsigned nlists, int grid, const FinArgs& fin, hipStream_t s, unsigned* memo_start) {
   // (grid = nlists; second dimension: chunks of COMPACT_TPW tiles of the longest list)
   const unsigned per_list = p.nlists_main ? (p.ntiles + p.nlists_main - 1) / p.nlists_main : 0u;
   const unsigned chunks = per_list ? (per_list + COMPACT_TPW - 1) / COMPACT_TPW : 1u;
-  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_compact_ac<T, M()>; }), dim3(grid, chunks), dim3(SWG), 0, s, p, eb, nlists, fin);
+  hipLaunchKernelGGL(with_mode(mode, [](auto M) { return k_compact_ac<T, M()>; }), dim3(grid, chunks), dim3(SWG), 0, s, p, eb, nlists, fin, memo_start);
 }
 
 template <typename T>
@@ -1697,8 +1762,8 @@ template __global__ void DCTZ_DEV_ONE(DCTZ_DEV_ARGS);
 #define INST(T)                                                                                         \
   template void launch_compress<T>(const FwdParams<T>&, int, bool, int, int, hipStream_t);              \
   template void launch_compress_rem<T>(const FwdParams<T>&, int, int, hipStream_t);                     \
-  template void launch_compact_ac<T>(const FwdParams<T>&, int, double, unsigned, int, const FinArgs&, hipStream_t); \
-  template void launch_decompress<T>(const InvParams<T>&, int, int, const FinArgs&, int, hipStream_t);  \
+  template void launch_compact_ac<T>(const FwdParams<T>&, int, double, unsigned, int, const FinArgs&, hipStream_t, unsigned*); \
+  template void launch_decompress<T>(const InvParams<T>&, int, int, const FinArgs&, int, hipStream_t, bool);  \
   template void launch_decompress_rem<T>(const InvParams<T>&, int, bool, int, hipStream_t);             \
   template void launch_compress_batch<T>(const BatchFwd<T>*, const unsigned*, unsigned, unsigned, int, bool, hipStream_t);                      \
   template void launch_compress_rem_batch<T>(const BatchFwd<T>*, const unsigned*, unsigned, int, hipStream_t);                              \

@@ -70,6 +70,23 @@ struct dctzhip_ctx {
   unsigned* qcnt = nullptr;         // k_compress -> k_compact_ac: per block, the counts of its tile's sub-lists (dctz_device.h: Sub)
   unsigned* ttot = nullptr;         // ... per tile, its "stored exactly" coefficients
   unsigned* tile_pre = nullptr;     // decode, tile-interleaved k_decompress: per tile, the counts of its range's tiles in front of it
+  // Decode memo.  A compress call on the chain of kernels leaves, beside ttot[] (every tile's count of exact coefficients),
+  // memo_start[]: every tile's first place in AC_exact[] (k_compact_ac).  `memo` names the streams those tables describe; a
+  // dctzhip_decompress of exactly these streams takes the tables in place of k_count_tiles' pass over bin_index, and the
+  // decoder checks every count against the flags it reads anyway (dctz_kernels.hip: k_decompress_il, MEMO).  Per tile and
+  // absolute: the partitions of the two sides do not matter.
+  unsigned* memo_start = nullptr;   // (allocated with ttot)
+  struct DecodeMemo {
+    bool valid = false;
+    const void* bin = nullptr; const void* dc = nullptr; const void* ac = nullptr;
+    size_t n = 0;
+    int dtype = 0, mode = 0;
+    unsigned cnt_total = 0;
+    hipStream_t stream = nullptr;
+  } memo;
+  bool memo_pass = false;           // the last compress_pass filled both tables (flat blocks through k_compress + k_compact_ac)
+  int dec_memo = 1;                 // 0: every decode counts its flags first (DCTZHIP_DEC_MEMO, dctzhip_set_decode_memo)
+  unsigned long long memo_decodes = 0, memo_redos = 0;   // decodes launched on the memo / of them found stale and done again (dctzhip_debug_counter 16 / 17)
   unsigned* ix_part = nullptr;      // dctzhip_ac_index: flag counts per workgroup of k_ac_index, then their exclusive prefix
   size_t ix_part_cap = 0;           // entries
   int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
@@ -305,6 +322,7 @@ extern "C" int dctzhip_ctx_create(dctzhip_ctx** out, int device) {
   if (const char* e = getenv("DCTZHIP_EO_LB_FAIL")) c->eo_lb_fail = atoi(e) != 0;
   if (const char* e = getenv("DCTZHIP_BLOCKING")) c->blocking = atoi(e) != 0;
   if (const char* e = getenv("DCTZHIP_STAGED_D2H")) c->staged_d2h = atoi(e) != 0;
+  if (const char* e = getenv("DCTZHIP_DEC_MEMO")) c->dec_memo = atoi(e) != 0;
   if (const char* e = getenv("DCTZHIP_DEC_IL")) c->dec_il = atoi(e);      // 0: never, 1: where it measured faster (fp64 EC), 2: every element type and mode
   if (const char* e = getenv("DCTZHIP_DEFLATE_SIDE")) c->dfl_side = atoi(e) != 0;
   if (int rc = build_sf_tables(c)) return rc;
@@ -331,7 +349,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -361,10 +379,17 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
 extern "C" int dctzhip_set_stream(dctzhip_ctx* c, void* s) {
   if (!c) return DCTZHIP_E_ARG;
   c->stream = (hipStream_t)s;
+  c->memo.valid = false;                            // (the tables were written in the order of the stream that is left)
+  return DCTZHIP_OK;
+}
+extern "C" int dctzhip_set_decode_memo(dctzhip_ctx* c, int on) {
+  if (!c) return DCTZHIP_E_ARG;
+  c->dec_memo = on != 0;
   return DCTZHIP_OK;
 }
 extern "C" int dctzhip_use_own_stream(dctzhip_ctx* c) {
   if (!c) return DCTZHIP_E_ARG;
+  c->memo.valid = false;
   c->stream = c->own_stream;
   return DCTZHIP_OK;
 }
@@ -418,6 +443,8 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes, last call: (box, hit tile) items in its list
     case 14: *value = c->mbox_grid; break;           // ... workgroups of its decode launch (fewer than items: they took several each)
     case 15: *value = c->mbox_bound; break;          // ... the host's bound B of the items, the list's capacity
+    case 16: *value = c->memo_decodes; break;        // dctzhip_decompress calls launched on the last compress call's tile counts (the decode memo)
+    case 17: *value = c->memo_redos; break;          // ... of them, found stale by the decoder and done again behind k_count_tiles
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
   return DCTZHIP_OK;
@@ -902,12 +929,15 @@ static int ensure_scratch(dctzhip_ctx* c, size_t n, int dtype, int mode, bool co
     if ((rc = regrow(c, &c->wg_cnt, &c->tile_cap, entries, sizeof(unsigned)))) return rc;
   }
   if (!compress) return DCTZHIP_OK;
+  c->memo.valid = false;                               // (every call that rewrites ttot / memo_start comes through here first)
   if (ntiles + 2 > c->qcnt_cap) {                      // one word per block / per tile
     if (c->qcnt) HIPCHK(c, hipFree(c->qcnt));
     if (c->ttot) HIPCHK(c, hipFree(c->ttot));
-    c->qcnt = nullptr; c->ttot = nullptr; c->qcnt_cap = 0;
+    if (c->memo_start) HIPCHK(c, hipFree(c->memo_start));
+    c->qcnt = nullptr; c->ttot = nullptr; c->memo_start = nullptr; c->qcnt_cap = 0;
     HIPCHK(c, hipMalloc(&c->qcnt, (ntiles + 2) * TILE_BLKS * sizeof(unsigned)));
     HIPCHK(c, hipMalloc(&c->ttot, (ntiles + 2) * sizeof(unsigned)));
+    HIPCHK(c, hipMalloc(&c->memo_start, (ntiles + 2) * sizeof(unsigned)));
     c->qcnt_cap = ntiles + 2;
   }
   const size_t slots = (ntiles + 1) * TILE_ELEMS;      // list of workgroup b at the slot of its first tile; the remainder block's behind them
@@ -1305,6 +1335,7 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   const unsigned ntiles = (nfull + TILE_BLKS - 1) / TILE_BLKS;
   const double sf = device_sf ? 1.0 : scaling_factor(dtype, st.max_abs);   // (device_sf: k_stats_final_sf has chosen it; read back after the call)
   *sf_out = sf;
+  c->memo.valid = false; c->memo_pass = false;       // (ttot / memo_start are about to be rewritten)
 
   // ---- bin ranges, dctz-comp-lib.c:271-281 (computed in double, stored in T) --
   const int half = DCTZHIP_NBINS / 2;
@@ -1405,7 +1436,10 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
     if (seq) launch_finish(c->ctl, c->part, fused ? (int)nlists : 0, c->box_dev, seq, s, p.guess, c->lb_ticket, 128u);
     else HIPCHK(c, hipMemsetAsync(c->lb_ticket, 0, 128 * sizeof(unsigned), s));
   } else {
-    launch_compact_ac<T>(p, mode, eb, nlists, (int)nlists, fin, s);
+    // (the decode memo: flat blocks through k_compress, which leaves ttot[] -- k_compress_eo does not)
+    const bool memo = geom == GEOM_1D && !nd && !eo && ntiles != 0;
+    launch_compact_ac<T>(p, mode, eb, nlists, (int)nlists, fin, s, memo ? c->memo_start : nullptr);
+    c->memo_pass = memo;
   }
   if (!seq && fused) launch_stats_final(c->part, (int)nlists, c->stats_out, s);
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[4], s));
@@ -1610,6 +1644,12 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   if (c->eo_lb_fallbacks > eof0) flags |= DCTZHIP_INFO_LB_FALLBACK;
   else if (c->eo_direct_calls > eod0) flags |= DCTZHIP_INFO_SINGLE_PASS;
   if (info) fill_cinfo(info, dtype, mode, sf, st, n_orig ? n_orig : n, hc->cnt_total, nblk, flags, hc->qraw, hc->q0);
+  // the decode memo: the tables of the pass that stands (after a respin: the second one's) describe these streams
+  if (c->memo_pass && geom == GEOM_1D && !nd && pre_parts == 0) {
+    c->memo.bin = d_bin; c->memo.dc = d_dc; c->memo.ac = d_ac; c->memo.n = n; c->memo.dtype = dtype; c->memo.mode = mode;
+    c->memo.cnt_total = hc->cnt_total; c->memo.stream = s;
+    c->memo.valid = true;
+  }
   return DCTZHIP_OK;
 }
 
@@ -1845,9 +1885,17 @@ static int decompress_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_
   // array of flat blocks whose workgroups take at most 64 tiles each
   if (c->dec_il && (c->dec_il == 2 || (sizeof(T) == 8 && mode == DCTZHIP_EC)) && geom == GEOM_1D && !nd && ntiles && (size_t)ntiles <= (size_t)64 * (size_t)grid && grid <= 4096)
     p.tile_pre = c->tile_pre;                       // (fp64 EC: the one combination it measured faster for, launch_decompress)
+  // The decode memo: these are the streams the context's last compress call wrote, and its per-tile tables still stand ->
+  // no pass over bin_index in front of the decoder, which checks the tables against the flags it reads (k_decompress_il,
+  // MEMO) and reports a stale memo instead of a result; then the same call goes through k_count_tiles, below.
+  const dctzhip_ctx::DecodeMemo& mm = c->memo;
+  const bool memo = c->dec_memo && mm.valid && sizeof(T) == 8 && mode == DCTZHIP_EC && box && !rem && takes_interleaved(p, geom) &&
+                    mm.bin == (const void*)d_bin && mm.dc == (const void*)d_dc && mm.ac == (const void*)d_ac && mm.n == n &&
+                    mm.dtype == (sizeof(T) == 8 ? DCTZHIP_F64 : DCTZHIP_F32) && mm.mode == mode && mm.cnt_total == ac_count && mm.stream == s;
+  if (memo) { p.tile_pre = c->memo_start; p.tile_cnt = c->ttot; }
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], s));
   // counts of "stored exactly" flags per tile and per workgroup of k_decompress: where every piece of AC_exact starts
-  if (ntiles) launch_count_tiles(d_bin, nfull, ntiles, p.nwg, c->tile_cnt, c->wg_cnt, s, mode == DCTZHIP_QT ? qtable_host : nullptr, sizeof(T) * 64, c->qtab,
+  if (ntiles && !memo) launch_count_tiles(d_bin, nfull, ntiles, p.nwg, c->tile_cnt, c->wg_cnt, s, mode == DCTZHIP_QT ? qtable_host : nullptr, sizeof(T) * 64, c->qtab,
                                  const_cast<unsigned*>(p.tile_pre));
   if (c->profiling) { HIPCHK(c, hipEventRecord(c->ev[1], s)); HIPCHK(c, hipEventRecord(c->ev[2], s)); }
   const unsigned long long seq = box ? ++c->seq : 0ull;
@@ -1857,8 +1905,9 @@ static int decompress_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_
   const bool early = box && ntiles && !rem;
   const FinArgs fin = {c->ctl, nullptr, 0, early ? c->box_dev : nullptr, seq, nullptr};
   if (ntiles) {
-    launch_decompress<T>(p, mode, grid, fin, geom, s);
-    if (takes_interleaved(p, geom)) SET_LAST(c, 1, "k_decompress_il<%s, %d, %d>", tname<T>(), mode, Phases<T>::D);
+    launch_decompress<T>(p, mode, grid, fin, geom, s, memo);
+    if (memo) { c->memo_decodes++; SET_LAST(c, 1, "k_decompress_il<%s, %d, %d, true>", tname<T>(), mode, Phases<T>::D); }
+    else if (takes_interleaved(p, geom)) SET_LAST(c, 1, "k_decompress_il<%s, %d, %d>", tname<T>(), mode, Phases<T>::D);
     else SET_LAST(c, 1, "k_decompress<%s, %d, %d, %d>", tname<T>(), mode, Phases<T>::D, geom);
   }
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[3], s));
@@ -1881,6 +1930,11 @@ static int decompress_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_
   // may be after the host has its answer --: the next call clears the block first.  Found by
   // test_under_run_is_refused_on_the_large_array_path: a good call behind a refused one was refused as well.)
   if (hc->error) c->ctl_dirty = 1;
+  if (memo && hc->error == DEC_ERR_MEMO_STALE) {    // the streams are not what the compress call left: the same call, counting first
+    c->memo.valid = false;
+    c->memo_redos++;
+    return decompress_impl<T>(c, d_bin, d_dc, d_ac, ac_count, qtable_host, n, eb, sf, mode, d_out, geom, nd);
+  }
   if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "bin_index flags more exact coefficients than ac_count provides");
   if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
   if (c->profiling) { int rc = read_timings(c, 2); if (rc) return rc; }

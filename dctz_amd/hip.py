@@ -90,6 +90,7 @@ _PROTOS = {
     "dctzhip_set_speculation": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t]),
     "dctzhip_set_one_launch": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_set_split": (C.c_int, [C.c_void_p, C.c_int]),
+    "dctzhip_set_decode_memo": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_debug_counter": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]),
     "dctzhip_debug_knob": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "dctzhip_debug_last_kernel": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
@@ -255,6 +256,10 @@ class Context:
     def set_split(self, on=True):
         """k_compress_eo (a block over two lanes) for flat fp64 arrays on the chain of kernels (include/dctz_hip.h)."""
         self._check(self.lib.dctzhip_set_split(self.h, int(on)), "set_split")
+
+    def set_decode_memo(self, on=True):
+        """A decode of the streams the last compress call wrote takes that call's tile counts, checked in the kernel (include/dctz_hip.h)."""
+        self._check(self.lib.dctzhip_set_decode_memo(self.h, int(on)), "set_decode_memo")
 
     def counter(self, which):
         """dctzhip_debug_counter (include/dctz_hip.h): 0 one-launch calls, 1 launches that gave up, 2 cooldown, 3 split calls, ..."""

@@ -128,12 +128,23 @@ int dctzhip_set_one_launch(dctzhip_ctx *ctx, int on);
  * gives up and the pass is run again through the lists (DCTZHIP_INFO_LB_FALLBACK).  Env DCTZHIP_EO=0/1 and
  * DCTZHIP_EO_DIRECT=0/1 set the defaults (off, off). */
 int dctzhip_set_split(dctzhip_ctx *ctx, int on);
+/* The decode memo.  A dctzhip_compress call on the chain of kernels (flat blocks, k_compress + k_compact_ac) leaves in the
+ * context, per tile of 64 blocks, the count of its exact coefficients and their first place in AC_exact[].  A
+ * dctzhip_decompress call on the same context and stream whose d_bin, d_dc, d_ac, n, dtype, mode are that call's and whose
+ * ac_count is its total (fp64 EC, n a multiple of 64, mailbox hand-off on) starts from those tables instead of counting the
+ * flags of bin_index in a pass of its own.  The tables are checked, not trusted: the decoder compares every tile's count
+ * with the flags it reads; if the buffers were rewritten in between so that any count differs, the same call decodes
+ * again the classic way and returns what that gives (its refusal of an under-run included).  With all counts equal the
+ * reconstruction is the classic decoder's bit for bit.  Any later compress call of the context (single, part, batch, N-D)
+ * and dctzhip_set_stream drop the memo.  Default: on (env DCTZHIP_DEC_MEMO=0 turns it off); counters 16 / 17 below. */
+int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
 /* (tests and tools)  Counters of the context -- which: 0 one-launch calls, 1 one-launch launches that gave up (run again
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr, 11 / 12 workgroups and
  * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran), 13 / 14 / 15 items
- * in the list of the last dctzhip_decompress_boxes call, workgroups of its decode launch and the list's bound -- and knobs that
+ * in the list of the last dctzhip_decompress_boxes call, workgroups of its decode launch and the list's bound, 16 / 17
+ * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
  * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
