@@ -654,6 +654,36 @@ struct NdBoxParams {
 template <typename T> int ndbox_occupancy(int mode, int geom);
 template <typename T> void launch_decompress_ndbox(const NdBoxParams<T>& p, int mode, int geom, int grid, hipStream_t s);
 
+// Coarse decode (dctz_kernels_coarse.hip: k_decompress_coarse, k_decompress_coarse_nd, k_decompress_coarse_rem,
+// k_decompress_coarse_dc): the whole array at 1 / factor of its resolution along every axis, from the K = edge / factor low
+// coefficients of every block.  The streams and the index describe the whole array as for RangeParams; a tiled array
+// (GEOM_2D | GEOM_3D) has n = 64 nblk, nfull = nblk and sits in the last axes of nb / od, the axes in front have extent 1.
+template <typename T>
+struct CoarseParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[0 .. ntiles] (and the short block's tile) are read
+  T* out;                          // dctzhip_coarse_len(n, factor) elements | prod od
+  const T* tab;                    // (unused: the low-band transforms carry their constants)
+  const T* rtab;                   // remainder-block tables (length n % 64)
+  const T* qtab;
+  Ctl* ctl;                        // error = 2: as RangeParams
+  unsigned n, nfull, ntiles, ac_count;   // ntiles: the stream tiles that hold a whole block, ceil(nfull / 64)
+  unsigned factor;
+  T sf, bin_width, range_min, range_max;
+  double eb;
+  unsigned nb[3];                  // tiled arrays: blocks per axis
+  unsigned od[3];                  // ... extents of the output, ceil(dims / factor)
+};
+constexpr bool coarse_k_ok(int geom, int k) {
+  return geom == GEOM_1D ? (k == 2 || k == 4 || k == 8 || k == 16 || k == 32) : geom == GEOM_2D ? (k == 2 || k == 4) : k == 2;
+}
+template <typename T> int coarse_occupancy(int mode, int geom, int k);
+template <typename T> void launch_decompress_coarse(const CoarseParams<T>& p, int mode, int geom, int k, int grid, hipStream_t s);
+template <typename T> void launch_decompress_coarse_rem(const CoarseParams<T>& p, int mode, hipStream_t s);
+template <typename T> void launch_decompress_coarse_dc(const float* dc, T* out, unsigned nblk, T sf, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

@@ -92,6 +92,7 @@ struct dctzhip_ctx {
   int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
   int box_occ[2][2] = {{0, 0}, {0, 0}};  // dctzhip_decompress_box: the same of k_decompress_box
   int ndbox_occ[2][2][2] = {};      // dctzhip_decompress_box_nd: the same of k_decompress_ndbox, [fp64][QT][3-D]
+  int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
   unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   // dctzhip_decompress_boxes: the box table (records, then the boxes of the short block) in pinned host memory and on the
   // device, the list of hit (box, tile) items, resident workgroups per CU of k_decompress_mbox [fp64][QT]
@@ -250,7 +251,7 @@ static int fail(dctzhip_ctx* c, int code, const char* fmt, ...) {
       return fail((c), DCTZHIP_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
-extern "C" const char* dctzhip_version(void) { return "0.3.0"; }
+extern "C" const char* dctzhip_version(void) { return "0.4.0"; }
 
 extern "C" const char* dctzhip_last_error(const dctzhip_ctx* ctx) { return ctx ? ctx->err : g_create_err; }
 
@@ -2566,6 +2567,130 @@ extern "C" int dctzhip_decompress_box_nd(dctzhip_ctx* c, const void* d_bin, cons
                                               (unsigned)t0, (unsigned)t1, (double*)d_out)
              : decompress_box_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode, lo, hi,
                                              (unsigned)t0, (unsigned)t1, (float*)d_out);
+}
+
+// ---- the whole array at reduced resolution (include/dctz_hip.h; dctz_kernels_coarse.hip) ------------------------
+// K = edge / factor coefficients kept per axis, or 0 for a factor the geometry does not have
+static int coarse_k(int geom, int factor) {
+  const int edge = geom == GEOM_1D ? 64 : geom == GEOM_2D ? 8 : 4;
+  if (factor < 2 || factor > edge || (factor & (factor - 1))) return 0;
+  return edge / factor;
+}
+extern "C" size_t dctzhip_coarse_len(size_t n, int factor) {
+  if (!coarse_k(GEOM_1D, factor)) return 0;
+  return (n + (size_t)factor - 1) / (size_t)factor;
+}
+
+// geom == GEOM_1D: sh is null, n elements in flat blocks; else the tiles of sh (n = 64 sh->nblk, no short block)
+template <typename T>
+static int decompress_coarse_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                  const uint32_t* d_index, const void* qtable_host, size_t n, const NdShape* sh, double eb, double sf,
+                                  int mode, int factor, T* d_out) {
+  hipStream_t s = c->stream;
+  const int geom = !sh ? GEOM_1D : sh->nd == 2 ? GEOM_2D : GEOM_3D;
+  const int k = coarse_k(geom, factor);
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+  CoarseParams<T> p;
+  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  p.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.n = (unsigned)n; p.nfull = nfull; p.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+  p.factor = (unsigned)factor;
+  for (int i = 0; i < 3; i++) { p.nb[i] = 1u; p.od[i] = 1u; }
+  if (sh)
+    for (int i = 0; i < sh->nd; i++) {
+      const int a = 3 - sh->nd + i;
+      p.nb[a] = (unsigned)sh->nb[i];
+      p.od[a] = (unsigned)((sh->d[i] + (size_t)factor - 1) / (size_t)factor);
+    }
+  if (k == 1) {
+    // the DC stream alone
+    if (nfull) launch_decompress_coarse_dc<T>(d_dc, d_out, nfull, (T)sf, s);
+    SET_LAST(c, 1, "k_decompress_coarse_dc<%s>", tname<T>());
+  } else {
+    // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
+    if (p.ntiles) {
+      int& occ = c->coarse_occ[sizeof(T) == 8][mode == DCTZHIP_QT][geom][k == 2 ? 0 : k == 4 ? 1 : k == 8 ? 2 : k == 16 ? 3 : 4];
+      if (occ == 0) occ = std::max(coarse_occupancy<T>(mode, geom, k), 1);
+      const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+      const int grid = (int)(p.ntiles < resident ? p.ntiles : resident);
+      launch_decompress_coarse<T>(p, mode, geom, k, grid, s);
+    }
+    if (geom == GEOM_1D) SET_LAST(c, 1, "k_decompress_coarse<%s, %d, %d>", tname<T>(), mode, k);
+    else SET_LAST(c, 1, "k_decompress_coarse_nd<%s, %d, %d, %d>", tname<T>(), mode, geom, k);
+  }
+  if (rem) launch_decompress_coarse_rem<T>(p, mode, s);
+  return ra_finish(c);
+}
+
+// the checks the two entry points share; n_out: elements of the output
+static int coarse_check(dctzhip_ctx* c, const char* what, int geom, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                        const uint32_t* d_index, const void* qtable_host, size_t n, size_t n_out, int dtype, int mode, int factor,
+                        const void* d_out) {
+  const int k = coarse_k(geom, factor);
+  if (!k)
+    return fail(c, DCTZHIP_E_ARG, "%s: factor %d is not one of %s", what, factor,
+                geom == GEOM_1D ? "2, 4, 8, 16, 32, 64" : geom == GEOM_2D ? "2, 4, 8" : "2, 4");
+  // factor == block edge reads the DC stream only -- but for the flat short block, which is decoded in full
+  const bool need_ac = k > 1 || (n % 64) != 0;
+  if (!d_dc || !d_out) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (need_ac && (!d_bin || !d_index || (ac_count && !d_ac))) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_out) || ((uintptr_t)d_dc & 3u)) return fail(c, DCTZHIP_E_ARG, "the output must be 16-byte aligned, DC 4-byte aligned");
+  if (need_ac && (!aligned16(d_bin) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u)))
+    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, AC_exact and the index 4-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  Span sp[5];
+  size_t m = 0;
+  add_span(sp, &m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, 0);
+  if (need_ac) {
+    add_span(sp, &m, d_bin, n, SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index, dctzhip_ac_index_len(n) * sizeof(uint32_t), SPAN_READ, 0);
+  }
+  add_span(sp, &m, d_out, n_out * elem_size(dtype), SPAN_OUT, 0);
+  return check_spans(c, sp, m, what, nullptr);
+}
+
+extern "C" int dctzhip_decompress_coarse(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                         const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf,
+                                         int mode, int factor, void* d_out) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  rc = coarse_check(c, "dctzhip_decompress_coarse", GEOM_1D, d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dctzhip_coarse_len(n, factor),
+                    dtype, mode, factor, d_out);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? decompress_coarse_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, nullptr, eb, sf, mode,
+                                              factor, (double*)d_out)
+             : decompress_coarse_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, nullptr, eb, sf, mode,
+                                             factor, (float*)d_out);
+}
+
+extern "C" int dctzhip_decompress_coarse_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                            const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype,
+                                            double eb, double sf, int mode, int factor, void* d_out) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64;
+  int rc = check_common(c, n_lin, dtype, mode);
+  if (rc) return rc;
+  const int geom = ndims == 2 ? GEOM_2D : GEOM_3D;
+  size_t n_out = 1;
+  if (coarse_k(geom, factor))
+    for (int i = 0; i < ndims; i++) n_out *= (dims[i] + (size_t)factor - 1) / (size_t)factor;
+  rc = coarse_check(c, "dctzhip_decompress_coarse_nd", geom, d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, n_out, dtype, mode, factor,
+                    d_out);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? decompress_coarse_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, &sh, eb, sf, mode,
+                                              factor, (double*)d_out)
+             : decompress_coarse_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, &sh, eb, sf, mode,
+                                             factor, (float*)d_out);
 }
 
 extern "C" int dctzhip_dct_blocks(dctzhip_ctx* c, const void* d_in, void* d_out, size_t n, int dtype, int inverse) {

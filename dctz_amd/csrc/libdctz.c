@@ -1907,6 +1907,80 @@ int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_v
   return decompress_part(var_z, 0, 0, PART_TILED, NULL, lo, hi, var_r, NULL);
 }
 
+/* ------------------------------------------------------------- dctz_decompress_coarse -- */
+/* The whole array at 1 / factor of its resolution (include/dctz_hip.h: dctzhip_decompress_coarse / _coarse_nd), flat and
+ * DZND containers alike: the trailer decides.  With factor == block edge (and no short block) the DC section alone is
+ * inflated and uploaded; otherwise the three sections, and the exception index is built once.  Only the coarse array is
+ * copied back.  Returns as dctz_decompress_box does: 1, or -1 for a bad factor or streams that disagree with each other. */
+int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r) {
+  const double t_begin = now_s();
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
+  const int tiled = v.nd != 0;
+  if (tiled && dzc_geometry(&v) != 0) return -1;                   /* extents that are no shape */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;               /* n: positions of the streams (flat: the elements) */
+  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const unsigned int cnt = v.cnt;
+  const int edge = !tiled ? BLK_SZ : v.nd == 2 ? 8 : 4;
+  if (n == 0 || !var_r || factor < 2 || factor > edge || (factor & (factor - 1))) return -1;
+  size_t out_elems = 1;
+  if (tiled) for (int i = 0; i < v.nd; i++) out_elems *= (v.dims[i] + (size_t)factor - 1) / (size_t)factor;
+  else out_elems = dctzhip_coarse_len(n, factor);
+  const int dc_only = factor == edge && (tiled || n % BLK_SZ == 0);
+
+  dctzhip_ctx *c = ctx();
+  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
+  size_t chunk = 0;
+  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
+  double qbuf[BLK_SZ];
+  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
+  int ret = -1;
+  size_t want[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
+  uint32_t ac_total = 0;
+  double t_zlib = 0.0, t_h2d = 0.0, t0;
+  for (int i = 0; i < 3; i++) {
+    if (dc_only && i != 1) continue;
+    if (i == 2) {                                            /* the index of the whole array, once */
+      t0 = now_s();
+      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(n) * sizeof(uint32_t));
+      if (dctzhip_ac_index(c, g_dev.bin, n, (uint32_t *)g_dev.idx, &ac_total) != DCTZHIP_OK) die("dctzhip_ac_index");
+      if (ac_total > cnt) goto out;                          /* the bin ids flag more than the header counts */
+      want[2] = (size_t)ac_total * sizeof(float);
+      t_h2d += now_s() - t0;
+    }
+    t0 = now_s();
+    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
+    unsigned char *hp = (unsigned char *)host_buf(i, room);
+    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
+    t_zlib += now_s() - t0;
+    t0 = now_s();
+    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
+    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
+    grow(dp, cp, want[i] ? want[i] : 4);
+    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp, want[i]) != DCTZHIP_OK) die("H2D section");
+    t_h2d += now_s() - t0;
+  }
+  t0 = now_s();
+  grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
+  const void *bin = dc_only ? NULL : g_dev.bin;
+  const float *ac = dc_only ? NULL : (const float *)g_dev.ac;
+  const uint32_t *idx = dc_only ? NULL : (const uint32_t *)g_dev.idx;
+  const int rc = tiled ? dctzhip_decompress_coarse_nd(c, bin, (const float *)g_dev.dc, ac, ac_total, idx, qtable, v.nd, v.dims, dtype,
+                                                      v.h.error_bound, v.sf, DCTZ_MODE, factor, g_dev.out)
+                       : dctzhip_decompress_coarse(c, bin, (const float *)g_dev.dc, ac, ac_total, idx, qtable, n, dtype, v.h.error_bound, v.sf,
+                                                   DCTZ_MODE, factor, g_dev.out);
+  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  if (rc != DCTZHIP_OK) die(tiled ? "dctzhip_decompress_coarse_nd" : "dctzhip_decompress_coarse");
+  const double t1s = now_s();
+  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
+  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
+  g_times.total_s = now_s() - t_begin;
+  ret = 1;
+out:
+  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  return ret;
+}
+
 /* ------------------------------------------------------ calc_data_stat ----- */
 /* util.c:12-44 on the GPU: max/min by tree reduction (order-independent),
  * the sum by the serial-order kernel so that mean is bit-identical. */

@@ -130,6 +130,12 @@ _PROTOS = {
     "dctzhip_decompress_box_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int,
                                             C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_coarse_len": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "dctzhip_decompress_coarse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "dctzhip_decompress_coarse_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                               C.c_void_p]),
     "dctzhip_dct_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dctzhip_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_serial_mean_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -580,6 +586,50 @@ class Context:
             index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, nd, arr(*shape), _dt(dtype),
             float(eb), float(sf), mode, arr(*lo), arr(*hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_box_nd")
+        return dst.view(ext)
+
+    # ---- coarse decode (include/dctz_hip.h: the whole array at 1 / factor of its resolution) ----
+    def _coarse_args(self, out, index, mode, qtable, dtype):
+        t = self.torch
+        q = None
+        if mode == QT:
+            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
+            assert q.size == 64
+        ptr = lambda v: v.data_ptr() if v is not None else None
+        return (ptr(out.get("bin_index")), ptr(out.get("dc")), ptr(out.get("ac_exact"))), ptr(index), q
+
+    def decompress_coarse(self, out, cnt, n, dtype, eb, sf, factor, index=None, mode=EC, qtable=None, dst=None):
+        """The n-element array of decompress() at 1 / factor of its resolution (factor 2 .. 64): ceil(n / factor) values, K =
+        64 / factor per block from its K lowest coefficients.  `index` from ac_index(); with factor 64 and n % 64 == 0 only
+        out["dc"] is read (bin_index, ac_exact and index may be missing / None).  Returns dst."""
+        t = self.torch
+        self._bind_stream()
+        if dst is None:
+            dst = t.empty(int(self.lib.dctzhip_coarse_len(n, int(factor))), dtype=dtype, device=self.device)
+        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        rc = self.lib.dctzhip_decompress_coarse(
+            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb),
+            float(sf), mode, int(factor), dst.data_ptr())
+        self._check(rc, "dctzhip_decompress_coarse")
+        return dst
+
+    def decompress_coarse_nd(self, out, cnt, shape, dtype, eb, sf, factor, index=None, mode=EC, qtable=None, dst=None):
+        """The array of decompress_nd() at 1 / factor of its resolution along every axis (2-D: factor 2, 4, 8; 3-D: 2, 4):
+        shape ceil(shape[i] / factor).  `index` from ac_index(out, 64 * nd_blocks(shape)); with factor == tile edge only
+        out["dc"] is read.  Returns dst."""
+        t = self.torch
+        self._bind_stream()
+        shape = [int(v) for v in shape]
+        f = max(int(factor), 1)
+        ext = [(v + f - 1) // f for v in shape]
+        if dst is None:
+            dst = t.empty(ext, dtype=dtype, device=self.device)
+        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        arr = C.c_size_t * max(len(shape), 1)
+        rc = self.lib.dctzhip_decompress_coarse_nd(
+            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, len(shape), arr(*shape),
+            _dt(dtype), float(eb), float(sf), mode, int(factor), dst.data_ptr())
+        self._check(rc, "dctzhip_decompress_coarse_nd")
         return dst.view(ext)
 
     def psnr_terms(self, x, r):

@@ -183,6 +183,16 @@ int dctz_decompress_boxes(t_var *var_z, int ndim, const size_t *dims, int k,
  * dctzhip_decompress_box_nd), and only the box is copied back.  dctz_decompress_range and dctz_decompress_box keep
  * refusing DZND containers. */
 int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_var *var_r);
+/* The whole array at reduced resolution (ADDITION, EC and QT builds): an overview at 1 / factor of the resolution along
+ * every axis, computed from the low coefficients of every block without decoding the array (include/dctz_hip.h:
+ * dctzhip_decompress_coarse / dctzhip_decompress_coarse_nd hold the definition).  var_z is a flat container (factor 2, 4,
+ * 8, 16, 32 or 64; var_r->buf receives ceil(n / factor) elements) or a DZND container (2-D: factor 2, 4 or 8; 3-D: 2 or 4;
+ * var_r->buf receives a dense C-order array of extents ceil(dims[i] / factor)); var_r->buf is allocated by the caller.  With
+ * factor equal to the block edge (64; 8 | 4) -- and, for a flat container, n a multiple of 64 -- only the DC section is
+ * inflated; otherwise the three sections are, and the exception index is built once.  Only the coarse array is copied back.
+ * Returns 1, or -1 for a bad factor, a null var_r and streams that disagree with each other -- dctz_decompress_box's
+ * conventions. */
+int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

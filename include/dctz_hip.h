@@ -469,6 +469,51 @@ int dctzhip_decompress_box_nd(dctzhip_ctx *ctx, const void *d_bin_index, const f
                               const size_t *dims, int dtype, double error_bound, double sf, int mode,
                               const size_t *lo, const size_t *hi, void *d_out);
 
+/* ---- coarse decode: the whole array at reduced resolution -------------------- */
+/* An overview of the whole array at 1 / factor of its resolution along every axis, from the low coefficients of every
+ * block -- without decoding the array.  For a block of length N (64; 8 or 4 per axis of a tile) with de-quantised
+ * coefficients c[0 .. N-1] -- (T)DC, a bin centre or (T)exact, with the QT de-normalisation in QT mode: exactly what
+ * every decoder's de-quantise step yields -- the full decoders write
+ *     x[m] = sf sum_k alpha_N(k) c[k] cos(pi k (2m + 1) / (2N)),   alpha_N(0) = sqrt(1/N), alpha_N(k > 0) = sqrt(2/N);
+ * with K = N / factor the coarse decode writes, for i = 0 .. K-1,
+ *     y[i] = sf sum_{k < K} alpha_N(k) c[k] cos(pi k (2i + 1) / (2K)):
+ * the part of the reconstruction below frequency K at the centres of the K cells of `factor` elements (the K-point
+ * orthonormal DCT-III of sqrt(K/N) c[0 .. K-1]).  The mean of y over a block is the block mean of the full reconstruction;
+ * K = 1 gives sf c[0] / sqrt(N).  Tiles use the formula separably along every axis, on the low corner k_a < K of the
+ * tile's row-major coefficients.  Whole arrays only: a part at full resolution is what the box calls are for.
+ *
+ * dctzhip_decompress_coarse   flat 64-element blocks (dctzhip_compress); factor in {2, 4, 8, 16, 32, 64}.
+ *   d_out       receives dctzhip_coarse_len(n, factor) = ceil(n / factor) elements of the data type; block b writes
+ *               d_out[b K, b K + K).  The short last block (l = n % 64, not a power-of-two transform) contributes
+ *               ceil(l / factor) values: each is the mean of one cell of the values dctzhip_decompress writes for that
+ *               block, summed left to right in the data type (starting from the cell's first value) and divided by the
+ *               cell's element count -- the last cell may be partial.  These are reproducible bit for bit from the full
+ *               decode.
+ * dctzhip_decompress_coarse_nd   the tiles of dctzhip_compress_nd; factor in {2, 4, 8} (2-D) or {2, 4} (3-D).
+ *   d_out       receives a dense C-order array of extents ceil(dims[i] / factor).  Edge tiles were padded on compress by
+ *               repeating the last sample: cells that begin inside the array are written, cells that begin past it are
+ *               not.  A cell that straddles the edge is evaluated from the padded tile, i.e. it sees the repeated
+ *               samples as well as the array's own.
+ * Both:
+ *   d_index     dctzhip_ac_index's, of n (flat) or 64 * dctzhip_nd_blocks(ndims, dims) positions.
+ *   factor == block edge (64; 8 | 4)   the call reads the DC stream only: d_bin_index, d_ac_exact and d_index may be NULL
+ *               -- except for a flat array with n % 64 != 0, whose short block is decoded in full (NULL is refused then).
+ *   refusals    before any launch, DCTZHIP_E_ARG for a factor outside the lists above, a null or misaligned pointer (the
+ *               rules of dctzhip_decompress_range), a d_out that overlaps an input, and a QT call without a table.  On
+ *               the device, for other factors (and the short block's tile): the flags of every tile t must number
+ *               idx[t + 1] - idx[t], and idx[t + 1] <= ac_count; a tile that fails reads no AC_exact and the call
+ *               returns DCTZHIP_E_ARG, the output is undefined and the context stays usable.
+ * Returns once that check is known, as dctzhip_decompress_box does (the call has synchronised the stream).
+ * dctzhip_debug_last_kernel(ctx, 1, ...) names the coarse kernel afterwards. */
+size_t dctzhip_coarse_len(size_t n, int factor);   /* 0 for a bad factor */
+int dctzhip_decompress_coarse(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                              uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
+                              double error_bound, double sf, int mode, int factor, void *d_out);
+int dctzhip_decompress_coarse_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                                 uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                                 const size_t *dims, int dtype, double error_bound, double sf, int mode, int factor,
+                                 void *d_out);
+
 /* ---- transform only ------------------------------------------------------ */
 /* Batched drop-in for dct_init + per-block dct_fftw / ifft_idct (+ the
  * remainder-length re-init), dct.h:17-27 as driven by dct-test.c:81-89, 144-152:
