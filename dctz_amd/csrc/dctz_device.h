@@ -684,6 +684,32 @@ template <typename T> void launch_decompress_coarse(const CoarseParams<T>& p, in
 template <typename T> void launch_decompress_coarse_rem(const CoarseParams<T>& p, int mode, hipStream_t s);
 template <typename T> void launch_decompress_coarse_dc(const float* dc, T* out, unsigned nblk, T sf, hipStream_t s);
 
+// Tile summaries (dctz_kernels_summary.hip: k_tile_summary, k_tile_summary_rem, k_tile_summary_final): one record per stream
+// tile of the reconstruction's extremes and sums, with `ref` also of its error against the original.  Flat blocks only; the
+// streams and the index describe the whole array as for RangeParams.
+template <typename T>
+struct SummaryParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[0 .. ceil(n / 4096)] are read
+  const T* tab;
+  const T* rtab;                   // remainder-block tables (length n % 64)
+  const T* qtab;
+  Ctl* ctl;                        // error = 2: as RangeParams
+  const T* ref;                    // the original, n elements (the REF instantiations only)
+  dctzhip_tile_summary_t* recs;      // ceil(n / 4096) records
+  unsigned n, nfull, ntiles, ac_count;   // ntiles: the stream tiles that hold a whole block, ceil(nfull / 64)
+  T sf, bin_width, range_min, range_max;
+  double eb;
+};
+constexpr int SUMMARY_FIN_WG = 256;          // records per workgroup of k_tile_summary_final
+template <typename T> int summary_occupancy(int mode, bool ref);
+template <typename T> void launch_tile_summary(const SummaryParams<T>& p, int mode, bool ref, int grid, bool with_rem, hipStream_t s);
+// m records -> one, level by level through `part` (summary_final_slots(m) records); returns where the last level left it
+size_t summary_final_slots(size_t m);
+const dctzhip_tile_summary_t* launch_tile_summary_final(const dctzhip_tile_summary_t* recs, size_t m, dctzhip_tile_summary_t* part, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

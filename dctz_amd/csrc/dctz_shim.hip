@@ -92,6 +92,9 @@ struct dctzhip_ctx {
   int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
   int box_occ[2][2] = {{0, 0}, {0, 0}};  // dctzhip_decompress_box: the same of k_decompress_box
   int ndbox_occ[2][2][2] = {};      // dctzhip_decompress_box_nd: the same of k_decompress_ndbox, [fp64][QT][3-D]
+  int sum_occ[2][2][2] = {};        // dctzhip_tile_summary: the same of k_tile_summary, [fp64][QT][with an original]
+  dctzhip_tile_summary_t* sum_buf = nullptr;   // ... the levels of k_tile_summary_final, then the records of a call without d_tiles
+  size_t sum_cap = 0;               // records
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
   unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   // dctzhip_decompress_boxes: the box table (records, then the boxes of the short block) in pinned host memory and on the
@@ -350,7 +353,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -2691,6 +2694,81 @@ extern "C" int dctzhip_decompress_coarse_nd(dctzhip_ctx* c, const void* d_bin, c
                                               factor, (double*)d_out)
              : decompress_coarse_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, &sh, eb, sf, mode,
                                              factor, (float*)d_out);
+}
+
+// ---- tile summaries (include/dctz_hip.h; dctz_kernels_summary.hip) ----------------------------------------------
+extern "C" size_t dctzhip_summary_tiles(size_t n) { return (n + (size_t)TILE_ELEMS - 1) / (size_t)TILE_ELEMS; }
+
+template <typename T>
+static int tile_summary_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                             const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode, const T* d_ref,
+                             dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+  hipStream_t s = c->stream;
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  const size_t m = dctzhip_summary_tiles(n);
+  const size_t fin = total ? summary_final_slots(m) : 0;
+  { int rc = regrow(c, &c->sum_buf, &c->sum_cap, fin + (d_tiles ? 0 : m), sizeof(dctzhip_tile_summary_t)); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+  SummaryParams<T> p;
+  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  p.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.ref = d_ref;
+  p.recs = d_tiles ? d_tiles : c->sum_buf + fin;
+  p.n = (unsigned)n; p.nfull = nfull; p.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+  const bool ref = d_ref != nullptr;
+  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
+  int grid = 0;
+  if (p.ntiles) {
+    int& occ = c->sum_occ[sizeof(T) == 8][mode == DCTZHIP_QT][ref];
+    if (occ == 0) occ = std::max(summary_occupancy<T>(mode, ref), 1);
+    const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+    grid = (int)(p.ntiles < resident ? p.ntiles : resident);
+  }
+  launch_tile_summary<T>(p, mode, ref, grid, rem != 0, s);
+  SET_LAST(c, 1, "%s<%s, %d, %s>", grid ? "k_tile_summary" : "k_tile_summary_rem", tname<T>(), mode, bname(ref));
+  dctzhip_tile_summary_t* ht = reinterpret_cast<dctzhip_tile_summary_t*>(c->h_pin + PIN_STATS);
+  static_assert(sizeof(dctzhip_tile_summary_t) == 64 && PIN_CTL - PIN_STATS >= sizeof(dctzhip_tile_summary_t), "the total fits the pinned statistics slot");
+  if (total) {
+    const dctzhip_tile_summary_t* dt = launch_tile_summary_final(p.recs, m, c->sum_buf, s);
+    HIPCHK(c, hipMemcpyAsync(ht, dt, sizeof(*ht), hipMemcpyDeviceToHost, s));
+  }
+  const int rc = ra_finish(c);
+  if (rc == DCTZHIP_OK && total) *total = *ht;
+  return rc;
+}
+
+extern "C" int dctzhip_tile_summary(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                    const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf, int mode,
+                                    const void* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  if (!d_tiles && !total) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary: at least one of d_tiles and total must be given");
+  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary: the original must be 16-byte aligned");
+  if ((uintptr_t)d_tiles & 7u) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary: the records must be 8-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    Span sp[6];
+    size_t m = 0;
+    add_span(sp, &m, d_bin, n, SPAN_READ, 0);
+    add_span(sp, &m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index, dctzhip_ac_index_len(n) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_ref, n * elem_size(dtype), SPAN_READ, 0);
+    add_span(sp, &m, d_tiles, dctzhip_summary_tiles(n) * sizeof(dctzhip_tile_summary_t), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_tile_summary", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? tile_summary_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const double*)d_ref,
+                                         d_tiles, total)
+             : tile_summary_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const float*)d_ref,
+                                        d_tiles, total);
 }
 
 extern "C" int dctzhip_dct_blocks(dctzhip_ctx* c, const void* d_in, void* d_out, size_t n, int dtype, int inverse) {

@@ -1981,6 +1981,79 @@ out:
   return ret;
 }
 
+/* ------------------------------------------------------------------ dctz_tile_summary -- */
+/* Per-tile records of the reconstruction, and with var_ref of its error (include/dctz_hip.h: dctzhip_tile_summary), of a
+ * flat container: the three sections inflated, the index built once, the original uploaded when given; records and total
+ * alone come back.  Returns as dctz_decompress_box does. */
+_Static_assert(sizeof(dctz_tile_summary_t) == sizeof(dctzhip_tile_summary_t), "one record layout");
+int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary_t *tiles, dctz_tile_summary_t *total) {
+  const double t_begin = now_s();
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
+  if (v.nd != 0) return -1;                                        /* tiled streams carry edge padding: out of scope */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
+  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const unsigned int cnt = v.cnt;
+  if (n == 0 || (!tiles && !total)) return -1;
+  if (var_ref && ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n || !var_bytes(var_ref))) return -1;
+  const size_t m = dctzhip_summary_tiles(n);
+
+  dctzhip_ctx *c = ctx();
+  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
+  size_t chunk = 0;
+  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
+  double qbuf[BLK_SZ];
+  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
+  int ret = -1;
+  size_t want[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
+  uint32_t ac_total = 0;
+  double t_zlib = 0.0, t_h2d = 0.0, t0;
+  for (int i = 0; i < 3; i++) {
+    if (i == 2) {                                            /* the index of the whole array, once */
+      t0 = now_s();
+      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(n) * sizeof(uint32_t));
+      if (dctzhip_ac_index(c, g_dev.bin, n, (uint32_t *)g_dev.idx, &ac_total) != DCTZHIP_OK) die("dctzhip_ac_index");
+      if (ac_total > cnt) goto out;                          /* the bin ids flag more than the header counts */
+      want[2] = (size_t)ac_total * sizeof(float);
+      t_h2d += now_s() - t0;
+    }
+    t0 = now_s();
+    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
+    unsigned char *hp = (unsigned char *)host_buf(i, room);
+    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
+    t_zlib += now_s() - t0;
+    t0 = now_s();
+    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
+    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
+    grow(dp, cp, want[i] ? want[i] : 4);
+    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp, want[i]) != DCTZHIP_OK) die("H2D section");
+    t_h2d += now_s() - t0;
+  }
+  t0 = now_s();
+  if (var_ref) {
+    grow(&g_dev.in, &g_dev.in_cap, n * ts);
+    if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n * ts) != DCTZHIP_OK) die("H2D original");
+  }
+  if (tiles) grow(&g_dev.out, &g_dev.out_cap, m * sizeof(dctzhip_tile_summary_t));
+  t_h2d += now_s() - t0;
+  t0 = now_s();
+  dctzhip_tile_summary_t tot;
+  const int rc = dctzhip_tile_summary(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable,
+                                      n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, var_ref ? g_dev.in : NULL,
+                                      tiles ? (dctzhip_tile_summary_t *)g_dev.out : NULL, total ? &tot : NULL);
+  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  if (rc != DCTZHIP_OK) die("dctzhip_tile_summary");
+  const double t1s = now_s();
+  if (tiles && dctzhip_memcpy_d2h(c, tiles, g_dev.out, m * sizeof(dctzhip_tile_summary_t)) != DCTZHIP_OK) die("D2H records");
+  if (total) memcpy(total, &tot, sizeof(tot));
+  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
+  g_times.total_s = now_s() - t_begin;
+  ret = 1;
+out:
+  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  return ret;
+}
+
 /* ------------------------------------------------------ calc_data_stat ----- */
 /* util.c:12-44 on the GPU: max/min by tree reduction (order-independent),
  * the sum by the serial-order kernel so that mean is bit-identical. */

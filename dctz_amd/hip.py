@@ -66,6 +66,15 @@ class BoxItem(C.Structure):          # dctzhip_box_item
     _fields_ = [("lo", C.c_size_t * BOX_MAXDIM), ("hi", C.c_size_t * BOX_MAXDIM), ("d_out", C.c_void_p)]
 
 
+class TileSummary(C.Structure):      # dctzhip_tile_summary_t: one record per 4096-element tile, or the records joined
+    _fields_ = [("rmin", C.c_double), ("rmax", C.c_double), ("rsum", C.c_double), ("rsq", C.c_double),
+                ("xmin", C.c_double), ("xmax", C.c_double), ("emax", C.c_double), ("esq", C.c_double)]
+
+    def psnr(self, n):
+        """calc_psnr (util.c:54-104) of a total taken with the original: 20 log10((xmax - xmin) / sqrt(esq / n))."""
+        return 20.0 * float(np.log10((self.xmax - self.xmin) / np.sqrt(self.esq / n)))
+
+
 RD_MAXK = 16                         # DCTZHIP_RD_MAXK: bounds per dctzhip_rd_probe call
 
 
@@ -136,6 +145,10 @@ _PROTOS = {
     "dctzhip_decompress_coarse_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                                C.c_void_p]),
+    "dctzhip_summary_tiles": (C.c_size_t, [C.c_size_t]),
+    "dctzhip_tile_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.POINTER(TileSummary)]),
     "dctzhip_dct_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dctzhip_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_serial_mean_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -631,6 +644,27 @@ class Context:
             _dt(dtype), float(eb), float(sf), mode, int(factor), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_coarse_nd")
         return dst.view(ext)
+
+    # ---- tile summaries (include/dctz_hip.h: verify and survey without writing the decode) ----
+    def tile_summary(self, out, cnt, n, dtype, eb, sf, index=None, mode=EC, qtable=None, ref=None):
+        """One record per 4096-element tile of what decompress() rebuilds from the same arguments -- min, max, sum and sum of
+        squares -- and, with `ref` (the original, a CUDA tensor of n elements), min and max of the original, max |x - r| and
+        sum (x - r)^2; the reconstruction is never written.  index=None builds the exception index.  Returns (records, total):
+        records a (tiles, 8) float64 CUDA tensor in TileSummary's field order, total a TileSummary of the records joined."""
+        t = self.torch
+        self._bind_stream()
+        if index is None:
+            index, _ = self.ac_index(out, n)
+        if ref is not None:
+            assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and ref.numel() == n
+        recs = t.empty((int(self.lib.dctzhip_summary_tiles(n)), 8), dtype=t.float64, device=self.device)
+        total = TileSummary()
+        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        rc = self.lib.dctzhip_tile_summary(
+            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb),
+            float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
+        self._check(rc, "dctzhip_tile_summary")
+        return recs, total
 
     def psnr_terms(self, x, r):
         """calc_psnr's reductions (util.c:54-104) on the GPU: (min x, max x, max |x - r|, sum (x - r)^2)."""

@@ -193,6 +193,22 @@ int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_v
  * Returns 1, or -1 for a bad factor, a null var_r and streams that disagree with each other -- dctz_decompress_box's
  * conventions. */
 int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r);
+/* Verify and survey without a reconstruction (ADDITION, EC and QT builds; include/dctz_hip.h: dctzhip_tile_summary holds the
+ * definition).  One record per 4096 elements of what dctz_decompress would rebuild from var_z -- its minimum, maximum, sum
+ * and sum of squares -- and, with var_ref, the minimum and maximum of the original, max |x - r| and sum (x - r)^2 of the
+ * tile: where the compression is worst.  var_ref->buf is the caller's UNSCALED original, N_ref elements (ignored when
+ * var_ref is NULL): dctz_compress has divided the array it was given by sf in place, so keep a copy (or multiply back)
+ * before asking.  tiles (or NULL) receives ceil(n / 4096) records, total (or NULL) the records joined; calc_psnr of the
+ * pair is 20 log10((total->xmax - total->xmin) / sqrt(total->esq / n)).  The three sections are inflated, the exception
+ * index is built once, the original is uploaded when given; records and total alone are copied back -- no reconstruction
+ * buffer exists on either side.  Returns 1, or -1 for a DZND container, a null total with null tiles, a reference of
+ * another type or length and streams that disagree with each other -- dctz_decompress_box's conventions. */
+typedef struct {             /* include/dctz_hip.h: dctzhip_tile_summary_t */
+  double rmin, rmax, rsum, rsq;
+  double xmin, xmax, emax, esq;
+} dctz_tile_summary_t;
+int dctz_tile_summary(t_var *var_z, t_var *var_ref /* or NULL */, int N_ref, dctz_tile_summary_t *tiles /* host, or NULL */,
+                      dctz_tile_summary_t *total);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

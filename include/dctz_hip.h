@@ -514,6 +514,46 @@ int dctzhip_decompress_coarse_nd(dctzhip_ctx *ctx, const void *d_bin_index, cons
                                  const size_t *dims, int dtype, double error_bound, double sf, int mode, int factor,
                                  void *d_out);
 
+/* ---- tile summaries: verify and survey without writing the decode ----------- */
+/* Two questions about a compressed array that need no reconstruction in memory: how far is it from the original, and where
+ * in it is anything worth decoding.  One record per stream tile (4096 elements, one index entry) of what dctzhip_decompress
+ * would write there, reduced in registers; with the original at hand (d_ref) also of the error, tile by tile: an error map.
+ * It reports the bound actually reached and promises none.  Flat 64-element blocks only (the streams of dctzhip_compress,
+ * fp32 and fp64, EC and QT, the short last block included): the streams of dctzhip_compress_nd carry edge padding that
+ * would have to be kept out of every reduction, which needs the geometry.
+ *   r           the elements dctzhip_decompress writes for the same arguments, bit for bit.
+ *   rmin, rmax, xmin, xmax, emax   exact.  Minima and maxima pass a NaN over (fmin / fmax, as dctzhip_psnr_terms does); a tile
+ *               of nothing but NaNs reports the starting pair rmin = +DBL_MAX, rmax = -DBL_MAX.
+ *   rsum, rsq, esq   summed in double, unfused; they carry a NaN.  The order of a tile's sum is fixed: the same call gives
+ *               the same bytes in every record every time, on every context, whatever grid is launched.  The r-fields with
+ *               and without d_ref may differ in their last digits (two orders).
+ *   d_ref       (or NULL) the ORIGINAL, n elements of dtype, 16-byte aligned -- what was handed to compress, not its
+ *               d_scaled output.  NULL: xmin, xmax, emax and esq are 0.
+ *   d_tiles     (or NULL) receives dctzhip_summary_tiles(n) records, 8-byte aligned; NULL: they live in scratch of the
+ *               context and only *total is reported.  At least one of d_tiles and total must be given.
+ *   total       (or NULL, HOST) the records joined: extremes over all records, sums added from the records in a fixed order
+ *               that depends on the tile count alone (a reduction kernel of its own, no atomics).  With d_ref, xmin, xmax
+ *               and emax equal dctzhip_psnr_terms' out[0], out[1], out[2] exactly, and
+ *               20 log10((xmax - xmin) / sqrt(esq / n)) is calc_psnr.
+ *   refusals    before any launch, DCTZHIP_E_ARG: the pointer and alignment rules of dctzhip_decompress_range, a d_ref that
+ *               is not 16-byte aligned, a d_tiles that is not 8-byte aligned or overlaps any input, both d_tiles and total
+ *               NULL, a QT call without a table, n == 0.  On the device: the flags of every tile t must number
+ *               idx[t + 1] - idx[t], and idx[t + 1] <= ac_count; a tile that fails reads no AC_exact and the call returns
+ *               DCTZHIP_E_ARG, the records are undefined and the context stays usable.
+ * Returns once that check is known, as dctzhip_decompress_box does (the call has synchronised the stream).
+ * dctzhip_debug_last_kernel(ctx, 1, ...) names the summary kernel afterwards. */
+typedef struct {             /* one per tile: elements [4096 t, min(4096 (t + 1), n)); 64 bytes */
+  double rmin, rmax;         /* min / max of r, the elements dctzhip_decompress writes (exact) */
+  double rsum, rsq;          /* sum (double)r, sum (double)r * (double)r */
+  double xmin, xmax;         /* min / max of the original        (d_ref only, else 0) */
+  double emax, esq;          /* max |x - r|, sum (double)(e * e), e = x - r and e * e taken in the data type, as k_psnr does (d_ref only, else 0) */
+} dctzhip_tile_summary_t;
+size_t dctzhip_summary_tiles(size_t n);     /* ceil(n / 4096) */
+int dctzhip_tile_summary(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                         uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
+                         double error_bound, double sf, int mode, const void *d_ref /* or NULL */,
+                         dctzhip_tile_summary_t *d_tiles /* or NULL */, dctzhip_tile_summary_t *total /* host, or NULL */);
+
 /* ---- transform only ------------------------------------------------------ */
 /* Batched drop-in for dct_init + per-block dct_fftw / ifft_idct (+ the
  * remainder-length re-init), dct.h:17-27 as driven by dct-test.c:81-89, 144-152:
