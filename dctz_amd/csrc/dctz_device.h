@@ -710,6 +710,46 @@ template <typename T> void launch_tile_summary(const SummaryParams<T>& p, int mo
 size_t summary_final_slots(size_t m);
 const dctzhip_tile_summary_t* launch_tile_summary_final(const dctzhip_tile_summary_t* recs, size_t m, dctzhip_tile_summary_t* part, hipStream_t s);
 
+// Correction list (dctz_kernels_fixup.hip: k_fixup_mark, k_fixup_mark_rem, k_fixup_scan, k_fixup_emit, k_fixup_apply): the
+// elements whose reconstruction misses the original by more than a bound, tile after tile (include/dctz_hip.h).  The streams
+// are a summary call's (`s`, with the original in s.ref; s.recs unused); mark leaves a 64-bit mask per block and a count per
+// tile, the scan their exclusive prefix, emit the entries.
+template <typename T>
+struct FixupParams {
+  SummaryParams<T> s;
+  T bound;                         // element i is listed iff !(fabs(ref[i] - r[i]) <= bound)
+  unsigned long long* mask;        // ceil(n / 64) words: bit j of word b = element 64 b + j is listed
+  unsigned* tile_cnt;              // ceil(n / 4096) counts
+};
+template <typename T>
+struct FixupEmitParams {
+  const unsigned long long* mask;
+  const unsigned* fix_start;       // ceil(n / 4096) + 1 entries, complete
+  const T* ref;
+  uint16_t* fix_off;
+  T* fix_val;
+  const Ctl* ctl;                  // a mark kernel's error: nothing is emitted
+  unsigned n, capacity;            // nothing is emitted either if fix_start[tiles] > capacity
+};
+template <typename T>
+struct FixupApplyParams {
+  const unsigned* fix_start;
+  const uint16_t* fix_off;
+  const T* fix_val;
+  T* out;                          // prod box.ext elements
+  Ctl* ctl;                        // error = 5: the list contradicts itself or the array; the tile stored nothing
+  unsigned n, count, t0, t1;       // tiles [t0, t1) are visited
+  BoxGeo box;
+};
+constexpr int FIXUP_SCAN_WG = 1024;          // counts per workgroup of k_fixup_scan
+template <typename T> int fixup_occupancy(int mode);
+template <typename T> void launch_fixup_mark(const FixupParams<T>& p, int mode, int grid, bool with_rem, hipStream_t s);
+// exclusive prefix of cnt[0 .. m) into start[0 .. m], start[m] = the total = ctl->cnt_total; `part`: fixup_scan_slots(m) words
+size_t fixup_scan_slots(size_t m);
+void launch_fixup_scan(const unsigned* cnt, size_t m, unsigned* start, unsigned* part, Ctl* ctl, hipStream_t s);
+template <typename T> void launch_fixup_emit(const FixupEmitParams<T>& p, int grid, hipStream_t s);
+template <typename T> void launch_fixup_apply(const FixupApplyParams<T>& p, int grid, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

@@ -5,7 +5,8 @@
 // dctzhip_decompress would write, and -- with the original x at hand (REF) -- min / max of x, max |x - r| and the sum of
 // (x - r)^2, difference and square taken in the data type as k_psnr takes them.
 //
-// k_tile_summary: one wave per stream tile, lane b = block b, grid-stride over the tiles.  The head of a tile is
+// k_tile_summary: one wave per stream tile, lane b = block b, grid-stride over the tiles.  The head of a tile
+// (summary_tile_values in dctz_summary_head.h, which the correction list's kernels call too) is
 // ra_tile_image's: sixteen dwords of bin ids, DC, the wave scan of the flag counts, the index check (a tile that fails
 // reads no AC_exact), the tile's exact coefficients staged in LDS; then dequantise_positional, block_inv and the de-scale
 // multiply -- the decoders' own functions in their order, so every r is bit for bit the element the decoders write.
@@ -25,7 +26,7 @@
 // written as that record when the tile holds no whole block.
 // k_tile_summary_final: SUMMARY_FIN_WG records -> one, a thread per record, butterfly, then the waves in order.  The host
 // launches it level by level until one record is left: the order of the total's sums depends on the tile count alone.
-#include "dctz_kernel_common.h"
+#include "dctz_summary_head.h"
 
 namespace dctz {
 
@@ -62,54 +63,6 @@ __device__ __forceinline__ double sum_field_of_lane(const SumRec& a, const int l
   return v;
 }
 
-// Tile t by one wave up to the lane's 64 reconstructed elements in registers: ra_tile_image without the image.  `stage`
-// holds a dense tile's exact coefficients (63 * 64 floats).  False: the index disagrees with the tile's own flags or leaves
-// the caller's AC_exact; nothing of AC_exact was read.  stage_free() runs once the staged coefficients are consumed, in front
-// of the transform: `stage` is the caller's again.
-template <typename T, int MODE, typename F>
-__device__ __forceinline__ bool summary_tile_values(const SummaryParams<T>& p, const unsigned t, const int lane, const CTab<T> tab,
-                                                    const QtLanes<T>& qtl, const bool scale, float* const stage, T (&x)[64], F&& stage_free) {
-  const unsigned rem = p.n - p.nfull * 64u;
-  const unsigned full_end = p.nfull * 64u;
-  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)lane;
-  unsigned w[16];
-  float dcv = 0.f;
-  unsigned cnt = 0;
-  if (blk < p.nfull) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const u32x4 v = src[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-    dcv = p.dc[blk];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 16; i++) w[i] = 0u;
-    // the short block's flags count for the tile (its elements are k_tile_summary_rem's)
-    if (blk == p.nfull && rem)
-      for (unsigned j = 1; j < rem; j++) cnt += p.bin[(size_t)full_end + j] == 255u ? 1u : 0u;
-  }
-  cnt += block_flag_count(w);
-  const unsigned incl = wave_incl_scan(cnt);
-  const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-  const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
-  if (s1 < s0 || s1 - s0 != tot || s1 > p.ac_count) return false;
-  for (unsigned i = (unsigned)lane; i < tot; i += 64u) stage[i] = p.ac[s0 + i];
-  __syncthreads();
-  unsigned ptr = incl - cnt;                                           // this block's first exact coefficient in the tile
-  dequantise_positional<T, MODE, false>(x, w, dcv, ptr, stage, (unsigned)(63 * 64 - 1), BinCentres<T, true>{p.bin_width, nullptr},
-                                        [&](int j) { return qtl.at(j); }, p.eb, p.range_min, p.range_max);
-  __syncthreads();                                                     // the staged coefficients are consumed
-  stage_free();
-  block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
-  if (scale) {
-#pragma unroll
-    for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                   // dctz-decomp-lib.c:494-511
-  }
-  return true;
-}
-
 // A lane's elements [J0, J1) of its block into its record: four running sums over j mod 4 (joined by the caller as
 // (0 + 1) + (2 + 3)); with REF against the same elements of the original in o[]
 template <typename T, bool REF, int J0, int J1>
@@ -129,12 +82,6 @@ __device__ __forceinline__ void summary_reduce(SumRec& a, double (&s)[4], double
     }
   }
 }
-
-// LDS of a wave: a dense tile's staged coefficients (63 * 64 floats), and behind them in time one phase of the original
-template <typename T> struct SummaryLds {
-  static constexpr int PH = 2;
-  static constexpr int BYTES = Geo<T, PH>::PHB > 63 * 64 * 4 ? Geo<T, PH>::PHB : 63 * 64 * 4;
-};
 
 template <typename T, int MODE, bool REF>
 __global__ __launch_bounds__(64) void k_tile_summary(SummaryParams<T> p) {
@@ -200,45 +147,11 @@ __global__ __launch_bounds__(64) void k_tile_summary_rem(SummaryParams<T> p) {
   const int l = (int)(p.n - p.nfull * 64u);
   const size_t base = (size_t)p.nfull * 64;
   const unsigned t = p.nfull / (unsigned)TILE_BLKS;                    // the tile that holds the short block
-  unsigned cfront = 0;                                                 // flags of the tile's whole blocks in front of it
-  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)k;
-  if (blk < p.nfull) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
-    unsigned w[16];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const u32x4 v = src[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-    cfront = block_flag_count(w);
-  }
-  const unsigned front = (unsigned)__builtin_amdgcn_readlane((int)wave_incl_scan(cfront), 63);
-  unsigned b = 0;
-  if (k < l) b = p.bin[base + k];
-  const bool exc = (k < l) && (k != 0) && (b == 255u);
-  const unsigned long long msk = __ballot(exc);
-  const unsigned rank = (unsigned)__popcll(msk & ((1ull << k) - 1ull));
-  const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
-  if (s1 < s0 || s1 - s0 != front + (unsigned)__popcll(msk) || s1 > p.ac_count) {      // (wave-uniform) refused, nothing of AC_exact read
-    if (k == 0) atomicExch(&p.ctl->error, 2u);
-    return;
-  }
-  const unsigned start = s0 + front;
-  short_inv_clear(cr, ci, k);
-  if (k < l) {
-    T e = T(0);
-    if (exc) e = (T)p.ac[start + rank];
-    a[k] = short_inv_value<T, MODE>(b, exc, k, k == 0 ? p.dc[p.nfull] : 0.f, e, p.bin_width, [&](int j) { return p.qtab[j]; }, p.eb, p.range_min,
-                                    p.range_max);
-  }
-  __syncthreads();
-  if (k < l) short_inv_spread(cr, ci, a, p.rtab, l, k);
-  __syncthreads();
+  T val;
+  if (!summary_rem_value<T, MODE>(p, k, a, cr, ci, val)) return;       // (wave-uniform) refused, nothing of AC_exact read
   SumRec s;
   s.init();
   if (k < l) {
-    T val = short_inv_sum(cr, ci, p.rtab, l, k);
-    if (p.sf != T(1)) val = val * p.sf;
     const double d = (double)val;
     s.v[0] = fmin(s.v[0], d); s.v[1] = fmax(s.v[1], d); s.v[2] = d; s.v[3] = d * d;
     if constexpr (REF) {

@@ -95,6 +95,11 @@ struct dctzhip_ctx {
   int sum_occ[2][2][2] = {};        // dctzhip_tile_summary: the same of k_tile_summary, [fp64][QT][with an original]
   dctzhip_tile_summary_t* sum_buf = nullptr;   // ... the levels of k_tile_summary_final, then the records of a call without d_tiles
   size_t sum_cap = 0;               // records
+  int fix_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_fixup_build: the same of k_fixup_mark [fp64][QT]
+  unsigned long long* fix_mask = nullptr;   // ... a mask per block of the array
+  size_t fix_mask_cap = 0;          // words
+  unsigned* fix_cnt = nullptr;      // ... a count per tile, then the levels of k_fixup_scan
+  size_t fix_cnt_cap = 0;           // entries
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
   unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   // dctzhip_decompress_boxes: the box table (records, then the boxes of the short block) in pinned host memory and on the
@@ -353,7 +358,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf, c->fix_mask, c->fix_cnt};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -2045,6 +2050,7 @@ static int ra_finish(dctzhip_ctx* c, unsigned* cnt_total = nullptr) {
   if (!hc->error && !cnt_total) c->ctl_dirty = 0;
   if (hc->error == 2) return fail(c, DCTZHIP_E_ARG, "the exception index disagrees with bin_index or exceeds ac_count");
   if (hc->error == 4) return fail(c, DCTZHIP_E_ARG, "the boxes hit more tiles than the bound of the work list");
+  if (hc->error == 5) return fail(c, DCTZHIP_E_ARG, "the correction list contradicts itself or the array (fix_start, count or an offset)");
   if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
   return DCTZHIP_OK;
 }
@@ -2769,6 +2775,148 @@ extern "C" int dctzhip_tile_summary(dctzhip_ctx* c, const void* d_bin, const flo
                                          d_tiles, total)
              : tile_summary_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const float*)d_ref,
                                         d_tiles, total);
+}
+
+// ---- correction list for a point-wise bound (include/dctz_hip.h; dctz_kernels_fixup.hip) -------------------------
+extern "C" size_t dctzhip_fixup_tiles(size_t n) { return (n + (size_t)TILE_ELEMS - 1) / (size_t)TILE_ELEMS; }
+
+template <typename T>
+static int fixup_build_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                            const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode, const T* d_ref,
+                            double bound, uint32_t* d_fix_start, uint16_t* d_fix_off, T* d_fix_val, uint32_t capacity, uint32_t* count) {
+  hipStream_t s = c->stream;
+  const unsigned nfull = (unsigned)(n / 64);
+  const int rem = (int)(n % 64);
+  const size_t m = dctzhip_fixup_tiles(n);
+  { int rc = regrow(c, &c->fix_mask, &c->fix_mask_cap, (n + 63) / 64, sizeof(unsigned long long)); if (rc) return rc; }
+  { int rc = regrow(c, &c->fix_cnt, &c->fix_cnt_cap, m + fixup_scan_slots(m), sizeof(unsigned)); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+  FixupParams<T> p;
+  ra_fill_streams<T>(c, p.s, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  p.s.rtab = reinterpret_cast<const T*>(c->rtab);
+  p.s.ref = d_ref;
+  p.s.recs = nullptr;
+  p.s.n = (unsigned)n; p.s.nfull = nfull; p.s.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+  p.bound = (T)bound;
+  p.mask = c->fix_mask;
+  p.tile_cnt = c->fix_cnt;
+  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
+  unsigned resident = (unsigned)c->num_cu;
+  int grid = 0;
+  if (p.s.ntiles) {
+    int& occ = c->fix_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
+    if (occ == 0) occ = std::max(fixup_occupancy<T>(mode), 1);
+    resident = (unsigned)c->num_cu * (unsigned)occ;
+    grid = (int)(p.s.ntiles < resident ? p.s.ntiles : resident);
+  }
+  launch_fixup_mark<T>(p, mode, grid, rem != 0, s);
+  SET_LAST(c, 1, "%s<%s, %d>", grid ? "k_fixup_mark" : "k_fixup_mark_rem", tname<T>(), mode);
+  launch_fixup_scan(c->fix_cnt, m, d_fix_start, c->fix_cnt + m, c->ctl, s);
+  if (d_fix_off) {
+    // behind the scan in stream order; the kernel itself stands back if the list does not fit or a tile was refused
+    FixupEmitParams<T> e;
+    e.mask = c->fix_mask; e.fix_start = d_fix_start; e.ref = d_ref; e.fix_off = d_fix_off; e.fix_val = d_fix_val; e.ctl = c->ctl;
+    e.n = (unsigned)n; e.capacity = capacity;
+    const unsigned g = (unsigned)std::min<size_t>(m, (size_t)c->num_cu * 32);      // (a few registers, no LDS: eight waves per SIMD)
+    launch_fixup_emit<T>(e, (int)g, s);
+  }
+  unsigned total = 0;
+  const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
+  if (rc) return rc;
+  *count = total;
+  if (d_fix_off && total > capacity)
+    return fail(c, DCTZHIP_E_SPACE, "dctzhip_fixup_build: %u entries do not fit the capacity of %u", total, capacity);
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_fixup_build(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                   const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf, int mode,
+                                   const void* d_ref, double bound, uint32_t* d_fix_start, uint16_t* d_fix_off, void* d_fix_val,
+                                   uint32_t capacity, uint32_t* count) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  if (!d_ref || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: the original and count must be given");
+  if (!(bound >= 0.0) || std::isinf(bound)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: the bound must be finite and >= 0");
+  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: the original must be 16-byte aligned");
+  if (!d_fix_start || ((uintptr_t)d_fix_start & 3u)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: fix_start must be given, 4-byte aligned");
+  if ((d_fix_off == nullptr) != (d_fix_val == nullptr))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: fix_off and fix_val must both be given or both be NULL");
+  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (elem_size(dtype) - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: fix_off must be 2-byte aligned, fix_val aligned to its elements");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    Span sp[8];
+    size_t m = 0;
+    add_span(sp, &m, d_bin, n, SPAN_READ, 0);
+    add_span(sp, &m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index, dctzhip_ac_index_len(n) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_ref, n * elem_size(dtype), SPAN_READ, 0);
+    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n) + 1) * sizeof(uint32_t), SPAN_OUT, 0);
+    add_span(sp, &m, d_fix_off, (size_t)capacity * sizeof(uint16_t), SPAN_OUT, 0);
+    add_span(sp, &m, d_fix_val, (size_t)capacity * elem_size(dtype), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_fixup_build", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? fixup_build_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const double*)d_ref,
+                                        bound, d_fix_start, d_fix_off, (double*)d_fix_val, capacity, count)
+             : fixup_build_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const float*)d_ref,
+                                       bound, d_fix_start, d_fix_off, (float*)d_fix_val, capacity, count);
+}
+
+template <typename T>
+static int fixup_apply_impl(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const T* d_fix_val, uint32_t count, size_t n,
+                            const BoxGeo& box, size_t first, size_t last, T* d_out) {
+  hipStream_t s = c->stream;
+  { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
+  FixupApplyParams<T> p;
+  p.fix_start = d_fix_start; p.fix_off = d_fix_off; p.fix_val = d_fix_val; p.out = d_out; p.ctl = c->ctl;
+  p.n = (unsigned)n; p.count = count;
+  p.t0 = (unsigned)(first / TILE_ELEMS); p.t1 = (unsigned)(last / TILE_ELEMS + 1);
+  p.box = box;
+  const unsigned tiles = p.t1 - p.t0, resident = (unsigned)c->num_cu * 32u;          // (a few registers, no LDS: eight waves per SIMD)
+  launch_fixup_apply<T>(p, (int)(tiles < resident ? tiles : resident), s);
+  SET_LAST(c, 1, "k_fixup_apply<%s>", tname<T>());
+  return ra_finish(c);
+}
+
+extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val, uint32_t count,
+                                   size_t n, int dtype, int ndim, const size_t* dims, const size_t* lo, const size_t* hi, void* d_out) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
+  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: null dims, lo or hi");
+  size_t cnt = 1, first = 0, last = 0;
+  rc = box_extents(c, "dctzhip_fixup_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  if (rc) return rc;
+  const size_t es = elem_size(dtype);
+  if (!d_fix_start || !d_out || ((uintptr_t)d_fix_start & 3u) || ((uintptr_t)d_out & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: fix_start and the output must be given, 4-byte / element aligned");
+  if (count > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: count %u exceeds n = %zu", count, n);
+  if (count && (!d_fix_off || !d_fix_val)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: null fix_off or fix_val");
+  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: fix_off must be 2-byte aligned, fix_val aligned to its elements");
+  {
+    Span sp[4];
+    size_t m = 0;
+    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n) + 1) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_fix_off, (size_t)count * sizeof(uint16_t), SPAN_READ, 0);
+    add_span(sp, &m, d_fix_val, (size_t)count * es, SPAN_READ, 0);
+    add_span(sp, &m, d_out, cnt * es, SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_fixup_apply", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const BoxGeo box = canonical_box(ndim, dims, lo, hi);
+  return (dtype == DCTZHIP_F64)
+             ? fixup_apply_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, n, box, first, last, (double*)d_out)
+             : fixup_apply_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, n, box, first, last, (float*)d_out);
 }
 
 extern "C" int dctzhip_dct_blocks(dctzhip_ctx* c, const void* d_in, void* d_out, size_t n, int dtype, int inverse) {

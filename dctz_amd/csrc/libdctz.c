@@ -37,6 +37,7 @@
 
 #include "dctz_hip.h"
 #include "dctz_container.h"
+#include "dctz_fixup_blob.h"
 
 #ifndef USE_TRUNCATE
 #error "build with -DUSE_TRUNCATE (every reference target does, Makefile:13-24)"
@@ -54,8 +55,8 @@
 /* ------------------------------------------------------------------ state -- */
 static dctzhip_ctx *g_ctx = NULL;
 static struct {
-  void *in, *bin, *dc, *ac, *out, *z[3], *idx;
-  size_t in_cap, bin_cap, dc_cap, ac_cap, out_cap, z_cap[3], idx_cap;
+  void *in, *bin, *dc, *ac, *out, *z[3], *idx, *fix;
+  size_t in_cap, bin_cap, dc_cap, ac_cap, out_cap, z_cap[3], idx_cap, fix_cap;
 } g_dev;
 /* Host copies of the raw streams (what the zlib tails read / the inflates write), kept between calls like the device
  * buffers above: a fresh 170 MB allocation per call costs its page faults on the way in and an munmap on the way out
@@ -1592,7 +1593,9 @@ static int decompress_pipelined(dctzhip_ctx *c, const dzc_view *v, size_t chunk,
   return ok;
 }
 
-int dctz_decompress(t_var *var_z, t_var *var_r) {
+/* fix (or NULL): a checked correction-list blob of this container (dctz_decompress_bounded), applied to the reconstruction on
+ * the device before it is copied back; -1 if the list contradicts itself. */
+static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix) {
   const double t_begin = now_s();
   dzc_view v;
   const int bad_nd = dzc_open(&v, var_z, DCTZ_QT); /* dctz-decomp-lib.c:84-94 */
@@ -1618,7 +1621,7 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
   grow(&g_dev.bin, &g_dev.bin_cap, npos);
   grow(&g_dev.dc, &g_dev.dc_cap, nblk * sizeof(float));
   grow(&g_dev.ac, &g_dev.ac_cap, (cnt ? cnt : 4) * sizeof(float));
-  if (indexed && !nd && !inflate_gpu() && pipeline_on()) {
+  if (indexed && !nd && !inflate_gpu() && pipeline_on() && !fix) {
     size_t got_p = 0;
     if (decompress_pipelined(c, &v, ix_chunk_bytes, ix_sizes, var_r, &got_p)) {
       for (int i = 0; i < 3; i++) free(ix_sizes[i]);
@@ -1689,6 +1692,19 @@ int dctz_decompress(t_var *var_z, t_var *var_r) {
                                    v.h.error_bound, v.sf, DCTZ_MODE, g_dev.out);
   if (rc != DCTZHIP_OK) die("dctzhip_decompress");
   if (dctzhip_sync(c) != DCTZHIP_OK) die("sync");   /* (stage timers: the call returns while the reconstruction is being written) */
+  if (fix) {
+    dzfx_header fh;
+    memcpy(&fh, fix, sizeof(fh));
+    const size_t payload = dzfx_payload_bytes((size_t)fh.tiles, (size_t)fh.count, ts);
+    grow(&g_dev.fix, &g_dev.fix_cap, payload);
+    if (dctzhip_memcpy_h2d(c, g_dev.fix, fix + DZFX_HEADER_BYTES, payload) != DCTZHIP_OK) die("H2D correction list");
+    const unsigned char *const d = (const unsigned char *)g_dev.fix;
+    const size_t whole[1] = {n}, zero[1] = {0};
+    rc = dctzhip_fixup_apply(c, (const uint32_t *)d, (const uint16_t *)(d + dzfx_off_at((size_t)fh.tiles)),
+                             d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, n, dtype, 1, whole, zero, whole, g_dev.out);
+    if (rc == DCTZHIP_E_ARG) return -1;                /* the list contradicts itself: nothing is handed out */
+    if (rc != DCTZHIP_OK) die("dctzhip_fixup_apply");
+  }
   double t3 = now_s();
   if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, n * ts) != DCTZHIP_OK) die("D2H output");
   double t4 = now_s();
@@ -2046,6 +2062,103 @@ int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary
   const double t1s = now_s();
   if (tiles && dctzhip_memcpy_d2h(c, tiles, g_dev.out, m * sizeof(dctzhip_tile_summary_t)) != DCTZHIP_OK) die("D2H records");
   if (total) memcpy(total, &tot, sizeof(tot));
+  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
+  g_times.total_s = now_s() - t_begin;
+  ret = 1;
+out:
+  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  return ret;
+}
+
+/* ------------------------------------------ dctz_fixup_build, dctz_decompress_bounded -- */
+int dctz_decompress(t_var *var_z, t_var *var_r) { return decompress_whole(var_z, var_r, NULL); }
+
+/* dctz_decompress with the correction list of `blob` applied (include/dctz.h).  The blob's header is held against the
+ * container's before anything else happens. */
+int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t_var *var_r) {
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype);
+  dzfx_header fh;
+  if (v.nd != 0 || v.n == 0 || !var_r) return -1;
+  if (dzfx_check(blob, blob_bytes, v.is_d, v.n, &fh) != 0) return -1;
+  return decompress_whole(var_z, var_r, (const unsigned char *)blob);
+}
+
+/* The correction list of a flat container against the caller's unscaled original, as one malloc'd blob
+ * (csrc/dctz_fixup_blob.h): dctz_tile_summary's way to the device, then a count-only call that sizes the list and the call
+ * that fills it. */
+int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void **blob, size_t *blob_bytes) {
+  const double t_begin = now_s();
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
+  if (v.nd != 0) return -1;                                        /* tiled streams carry edge padding: out of scope */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
+  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const unsigned int cnt = v.cnt;
+  if (n == 0 || !blob || !blob_bytes || !var_ref || !(bound >= 0.0) || isinf(bound)) return -1;
+  if ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n || !var_bytes(var_ref)) return -1;
+  const size_t m = dctzhip_fixup_tiles(n);
+
+  dctzhip_ctx *c = ctx();
+  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
+  size_t chunk = 0;
+  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
+  double qbuf[BLK_SZ];
+  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
+  int ret = -1;
+  size_t want[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
+  uint32_t ac_total = 0;
+  double t_zlib = 0.0, t_h2d = 0.0, t0;
+  for (int i = 0; i < 3; i++) {
+    if (i == 2) {                                            /* the index of the whole array, once */
+      t0 = now_s();
+      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(n) * sizeof(uint32_t));
+      if (dctzhip_ac_index(c, g_dev.bin, n, (uint32_t *)g_dev.idx, &ac_total) != DCTZHIP_OK) die("dctzhip_ac_index");
+      if (ac_total > cnt) goto out;                          /* the bin ids flag more than the header counts */
+      want[2] = (size_t)ac_total * sizeof(float);
+      t_h2d += now_s() - t0;
+    }
+    t0 = now_s();
+    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
+    unsigned char *hp = (unsigned char *)host_buf(i, room);
+    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
+    t_zlib += now_s() - t0;
+    t0 = now_s();
+    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
+    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
+    grow(dp, cp, want[i] ? want[i] : 4);
+    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp, want[i]) != DCTZHIP_OK) die("H2D section");
+    t_h2d += now_s() - t0;
+  }
+  t0 = now_s();
+  grow(&g_dev.in, &g_dev.in_cap, n * ts);
+  if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n * ts) != DCTZHIP_OK) die("H2D original");
+  grow(&g_dev.fix, &g_dev.fix_cap, dzfx_off_at(m));
+  t_h2d += now_s() - t0;
+  t0 = now_s();
+  uint32_t count = 0;
+  int rc = dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
+                               v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)g_dev.fix, NULL, NULL, 0, &count);
+  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  if (rc != DCTZHIP_OK) die("dctzhip_fixup_build");
+  const size_t payload = dzfx_payload_bytes(m, count, ts);
+  if (count) {
+    grow(&g_dev.fix, &g_dev.fix_cap, payload);
+    unsigned char *const d = (unsigned char *)g_dev.fix;
+    rc = dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
+                             v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)d, (uint16_t *)(d + dzfx_off_at(m)),
+                             d + dzfx_val_at(m, count), count, &count);
+    if (rc != DCTZHIP_OK) die("dctzhip_fixup_build");
+  }
+  const double t1s = now_s();
+  unsigned char *b = (unsigned char *)calloc(1, DZFX_HEADER_BYTES + payload);
+  if (!b) { fprintf(stderr, "Out of memory: correction list\n"); exit(1); }
+  dzfx_write_header(b, v.is_d, n, count, bound);
+  /* the three arrays sit on the device as they sit in the blob; the padding between them is cleared afterwards */
+  if (dctzhip_memcpy_d2h(c, b + DZFX_HEADER_BYTES, g_dev.fix, payload) != DCTZHIP_OK) die("D2H correction list");
+  memset(b + DZFX_HEADER_BYTES + (m + 1) * sizeof(uint32_t), 0, dzfx_off_at(m) - (m + 1) * sizeof(uint32_t));
+  memset(b + DZFX_HEADER_BYTES + dzfx_off_at(m) + (size_t)count * sizeof(uint16_t), 0, dzfx_val_at(m, count) - dzfx_off_at(m) - (size_t)count * sizeof(uint16_t));
+  *blob = b; *blob_bytes = DZFX_HEADER_BYTES + payload;
   g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
   g_times.total_s = now_s() - t_begin;
   ret = 1;

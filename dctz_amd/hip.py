@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 F32, F64 = 0, 1
 EC, QT = 0, 1
-OK, E_ARG, E_BOUND, E_HIP, E_INTERNAL = 0, -1, -2, -3, -4      # DCTZHIP_OK / DCTZHIP_E_*
+OK, E_ARG, E_BOUND, E_HIP, E_INTERNAL, E_SPACE = 0, -1, -2, -3, -4, -5      # DCTZHIP_OK / DCTZHIP_E_*
 
 
 class DctzHipError(RuntimeError):
@@ -149,6 +149,12 @@ _PROTOS = {
     "dctzhip_tile_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                        C.POINTER(TileSummary)]),
+    "dctzhip_fixup_tiles": (C.c_size_t, [C.c_size_t]),
+    "dctzhip_fixup_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_double, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "dctzhip_fixup_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_int, C.c_int,
+                                      C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "dctzhip_dct_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dctzhip_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_serial_mean_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -665,6 +671,66 @@ class Context:
             float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
         self._check(rc, "dctzhip_tile_summary")
         return recs, total
+
+    # ---- point-wise error bound (include/dctz_hip.h: a correction list beside the streams) ----
+    def fixup_build(self, out, cnt, n, dtype, eb, sf, ref, bound, index=None, mode=EC, qtable=None, capacity=None):
+        """The correction list of the streams against `ref` (the original, a CUDA tensor of n elements) for the absolute bound
+        `bound`: every element i with not |ref[i] - r[i]| <= bound, r what decompress() rebuilds from the same arguments.
+        Returns (fix_start, fix_off, fix_val, count): fix_start an int32 tensor of tiles + 1 entries, fix_off int16 offsets in
+        the tile (their bits are uint16), fix_val the originals of the listed elements.  capacity=None counts first and sizes
+        the list from the count; capacity=0 is the count-only call (fix_off and fix_val are None); a list that does not fit
+        the capacity raises DctzHipError, its .count says how many entries there are."""
+        t = self.torch
+        self._bind_stream()
+        if index is None:
+            index, _ = self.ac_index(out, n)
+        assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and ref.numel() == n
+        start = t.empty(int(self.lib.dctzhip_fixup_tiles(n)) + 1, dtype=t.int32, device=self.device)
+        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        qp = q.ctypes.data_as(C.c_void_p) if q is not None else None
+        count = C.c_uint32(0)
+
+        def call(off, val, cap):
+            return self.lib.dctzhip_fixup_build(
+                self.h, b, d, a, int(cnt), ix, qp, n, _dt(dtype), float(eb), float(sf), mode, ref.data_ptr(), float(bound),
+                start.data_ptr(), off.data_ptr() if off is not None else None, val.data_ptr() if val is not None else None,
+                int(cap), C.byref(count))
+
+        if capacity is None or capacity == 0:
+            self._check(call(None, None, 0), "dctzhip_fixup_build")
+            if capacity == 0:
+                return start, None, None, int(count.value)
+            capacity = int(count.value)
+        off = t.empty(max(int(capacity), 1), dtype=t.int16, device=self.device)
+        val = t.empty(max(int(capacity), 1), dtype=dtype, device=self.device)
+        rc = call(off, val, capacity)
+        if rc == E_SPACE:
+            err = DctzHipError(f"dctzhip_fixup_build failed ({rc}): {self.lib.dctzhip_last_error(self.h).decode()}")
+            err.count = int(count.value)
+            raise err
+        self._check(rc, "dctzhip_fixup_build")
+        k = int(count.value)
+        return start, off[:k], val[:k], k
+
+    def fixup_apply(self, fix, n, dtype, dst, dims=None, lo=None, hi=None):
+        """Applies the list `fix` (fixup_build's result) to dst: the dense box lo <= c < hi of the n-element array seen with
+        shape `dims` -- what decompress_box() wrote; dims=None: the range [lo, hi) of the flat array (what decompress_range()
+        wrote), by default all of it.  Returns dst."""
+        self._bind_stream()
+        start, off, val, count = fix
+        if dims is None:
+            dims, lo, hi = [n], [0 if lo is None else lo], [n if hi is None else hi]
+        dims, lo, hi = [int(v) for v in dims], [int(v) for v in lo], [int(v) for v in hi]
+        nd = len(dims)
+        assert len(lo) == nd and len(hi) == nd and dst.is_cuda and dst.is_contiguous() and dst.dtype == dtype
+        assert dst.numel() == int(np.prod([max(h - l, 0) for l, h in zip(lo, hi)], dtype=np.int64))
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_fixup_apply(
+            self.h, start.data_ptr(), off.data_ptr() if off is not None and count else None,
+            val.data_ptr() if val is not None and count else None, int(count), n, _dt(dtype), nd, arr(*dims), arr(*lo), arr(*hi),
+            dst.data_ptr())
+        self._check(rc, "dctzhip_fixup_apply")
+        return dst
 
     def psnr_terms(self, x, r):
         """calc_psnr's reductions (util.c:54-104) on the GPU: (min x, max x, max |x - r|, sum (x - r)^2)."""

@@ -209,6 +209,18 @@ typedef struct {             /* include/dctz_hip.h: dctzhip_tile_summary_t */
 } dctz_tile_summary_t;
 int dctz_tile_summary(t_var *var_z, t_var *var_ref /* or NULL */, int N_ref, dctz_tile_summary_t *tiles /* host, or NULL */,
                       dctz_tile_summary_t *total);
+/* Point-wise error bound (ADDITION, EC and QT builds, flat containers; include/dctz_hip.h, "point-wise error bound", holds the
+ * definition).  dctz_fixup_build lists every element that dctz_decompress would rebuild from var_z further than `bound`
+ * (absolute, in the data's units, >= 0) from the original, with the original's value, in one malloc'd self-describing block
+ * that the caller keeps beside the container and frees: "DZFX", version, dtype, n, tiles, count, bound, then fix_start,
+ * fix_off padded to 8 bytes, fix_val (csrc/dctz_fixup_blob.h).  var_ref->buf is the caller's UNSCALED original, N_ref elements,
+ * as for dctz_tile_summary.  dctz_decompress_bounded is dctz_decompress with that list applied: every element of var_r->buf
+ * then has the original's bits or lies within the bound of it.  The .z container does not change and dctz_decompress reads
+ * it as before.  Both return 1, or -1 for a DZND container, a reference of another type or length, a bound that is negative
+ * or not finite, a blob whose header does not fit the container (magic, version, dtype, n, sizes -- checked before anything
+ * else is done), a list that contradicts itself and streams that disagree with each other. */
+int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void **blob, size_t *blob_bytes);
+int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

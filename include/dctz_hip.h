@@ -34,8 +34,9 @@ enum {
   DCTZHIP_E_ARG = -1,        /* bad argument (null, misaligned, n == 0, n > INT_MAX) */
   DCTZHIP_E_BOUND = -2,      /* error_bound < 1e-6: dctz-comp-lib.c:135-138 */
   DCTZHIP_E_HIP = -3,        /* a HIP runtime call failed (no device, OOM, ...) */
-  DCTZHIP_E_INTERNAL = -4    /* the library caught itself out: a launch plan that does not fit its scratch tables, a
+  DCTZHIP_E_INTERNAL = -4,   /* the library caught itself out: a launch plan that does not fit its scratch tables, a
                                 hand-off that never arrived (10 s), an error flag set by a kernel */
+  DCTZHIP_E_SPACE = -5       /* dctzhip_fixup_build: the list has more entries than the caller's capacity (*count says how many) */
 };
 
 typedef struct dctzhip_ctx dctzhip_ctx;
@@ -553,6 +554,63 @@ int dctzhip_tile_summary(dctzhip_ctx *ctx, const void *d_bin_index, const float 
                          uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
                          double error_bound, double sf, int mode, const void *d_ref /* or NULL */,
                          dctzhip_tile_summary_t *d_tiles /* or NULL */, dctzhip_tile_summary_t *total /* host, or NULL */);
+
+/* ---- point-wise error bound: a correction list beside the streams ------------ */
+/* DCTZ bounds the error of every COEFFICIENT; an element's error can reach about twice error_bound * sf.  The correction list
+ * repairs that without touching the streams: it names every element whose reconstruction misses the original by more than a
+ * bound and keeps the original's value for it.  Applied to the output of any decode of the same streams -- whole array,
+ * range, box -- it makes that output bounded.  Flat 64-element blocks only (the streams of dctzhip_compress, fp32 and fp64,
+ * EC and QT, the short last block included), as for dctzhip_tile_summary.
+ *   x           the ORIGINAL, n elements of dtype: what was handed to compress, not its d_scaled output.
+ *   r           the elements dctzhip_decompress writes for the same arguments, bit for bit.
+ *   bound       an absolute bound b >= 0 in the data's units, taken as (T)b in the data type T (round to nearest).
+ *   listed      element i is listed iff !(fabs(x[i] - r[i]) <= (T)b), the difference taken in the data type.  A NaN on either
+ *               side therefore lists the element: the 63 finite neighbours a NaN drags down with its block are listed and
+ *               restored, the NaN itself is listed and stays a NaN.  The list stores x[i] itself, bit for bit.
+ *   layout      with m = dctzhip_fixup_tiles(n) tiles of 4096 elements (the tiles of the exception index):
+ *                 fix_start[0 .. m]   uint32: listed elements in the tiles in front of t; fix_start[m] == count
+ *                 fix_off[count]      uint16: offset in the tile (0 .. 4095), strictly ascending inside a tile
+ *                 fix_val[count]      elements of the data type
+ *               entries run tile after tile: a range or box apply touches only its own tiles' entries.
+ *   guarantee   after apply every element of the output either has the bits of x[i] or satisfies
+ *               fabs(x[i] - out[i]) <= (T)b.
+ *
+ * dctzhip_fixup_build: streams, alignment rules, overlap refusals and the in-kernel index check are dctzhip_tile_summary's (a
+ * tile whose flags disagree with the index reads no AC_exact; the call returns DCTZHIP_E_ARG, the outputs are undefined and
+ * the context stays usable).
+ *   d_ref       the original, 16-byte aligned.
+ *   d_fix_start m + 1 entries, 4-byte aligned; always complete on DCTZHIP_OK and DCTZHIP_E_SPACE.
+ *   d_fix_off, d_fix_val   `capacity` entries each (2-byte / element aligned), or both NULL: the count-only form ("what
+ *               would bound b cost?"), which returns DCTZHIP_OK.
+ *   count       (HOST) always reported on DCTZHIP_OK and DCTZHIP_E_SPACE.  If *count > capacity the call returns
+ *               DCTZHIP_E_SPACE and nothing is written to d_fix_off / d_fix_val.
+ *   refusals    before any launch, DCTZHIP_E_ARG: what dctzhip_tile_summary refuses; d_ref or count NULL; a bound that is
+ *               negative, NaN or infinite; d_fix_start NULL or misaligned; exactly one of d_fix_off / d_fix_val NULL, or one
+ *               misaligned; an output that overlaps an input or another output.
+ * The same call gives the same bytes every time, on every context, whatever grid is launched.  Host-synchronous like
+ * dctzhip_tile_summary; dctzhip_debug_last_kernel(ctx, 1, ...) names the mark kernel afterwards.
+ *
+ * dctzhip_fixup_apply: d_out is the dense C-order box lo[i] <= c[i] < hi[i] of the array seen as ndim-dimensional (1 ..
+ * DCTZHIP_BOX_MAXDIM, prod dims == n) -- exactly what dctzhip_decompress_box or dctzhip_decompress_boxes wrote; a range
+ * [lo, hi) is the 1-D case, the whole array ndim = 1, lo = 0, hi = n.  Only the tiles between the box's first and its last
+ * element are visited.
+ *   refusals    before any launch, DCTZHIP_E_ARG: the box rules of dctzhip_decompress_box; d_fix_start or d_out NULL or
+ *               misaligned (4 bytes / element size); count > n; with count > 0 a NULL or misaligned d_fix_off (2 bytes) /
+ *               d_fix_val (element size); d_out overlapping the list.  On the device the list is untrusted input: a visited
+ *               tile is refused, by plain comparisons made before any store of that tile, for fix_start[t + 1] <
+ *               fix_start[t], fix_start[t + 1] > count, an offset beyond the tile's elements, or offsets that are not
+ *               strictly ascending; every call is refused for fix_start[m] != count.  The call then returns DCTZHIP_E_ARG,
+ *               d_out is undefined inside its box, nothing outside it is ever written, and the context stays usable.
+ * Host-synchronous; dctzhip_debug_last_kernel(ctx, 1, ...) names the apply kernel afterwards. */
+size_t dctzhip_fixup_tiles(size_t n);       /* ceil(n / 4096) */
+int dctzhip_fixup_build(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                        uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
+                        double error_bound, double sf, int mode, const void *d_ref, double bound, uint32_t *d_fix_start,
+                        uint16_t *d_fix_off /* or NULL */, void *d_fix_val /* or NULL */, uint32_t capacity,
+                        uint32_t *count /* host */);
+int dctzhip_fixup_apply(dctzhip_ctx *ctx, const uint32_t *d_fix_start, const uint16_t *d_fix_off, const void *d_fix_val,
+                        uint32_t count, size_t n, int dtype, int ndim, const size_t *dims, const size_t *lo,
+                        const size_t *hi, void *d_out);
 
 /* ---- transform only ------------------------------------------------------ */
 /* Batched drop-in for dct_init + per-block dct_fftw / ifft_idct (+ the
