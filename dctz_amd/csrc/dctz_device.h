@@ -750,6 +750,30 @@ void launch_fixup_scan(const unsigned* cnt, size_t m, unsigned* start, unsigned*
 template <typename T> void launch_fixup_emit(const FixupEmitParams<T>& p, int grid, hipStream_t s);
 template <typename T> void launch_fixup_apply(const FixupApplyParams<T>& p, int grid, hipStream_t s);
 
+// Missing values (dctz_kernels_mask.hip: k_mask_fill, k_mask_apply): a bit per element beside the streams, the holes filled
+// by copies inside each 64-element block (include/dctz_hip.h).  The mask travels as 32-bit pieces, two per word.
+template <typename T>
+struct MaskFillParams {
+  const T* in;
+  T* out;                          // the filled copy: null (mask and count only), `in` itself, or disjoint from it
+  unsigned* mask32;                // 2 ceil(n / 64) pieces, all written
+  Ctl* ctl;                        // cnt_total += the missing elements
+  unsigned n, flags;               // DCTZHIP_MISS_*
+  T value, limit;
+};
+template <typename T>
+struct MaskApplyParams {
+  const unsigned* mask32;
+  T* out;                          // cnt elements: the dense box
+  T fill;
+  unsigned cnt, first, one_run;    // one_run: the box is one run of the flat array that starts at element `first`
+  BoxGeo box;
+};
+constexpr int MASK_WG = 256;
+constexpr int MASK_TRIPS = 4;                 // trips of k_mask_fill whose loads a wave has in flight together (1 KiB each)
+template <typename T> void launch_mask_fill(const MaskFillParams<T>& p, int grid, hipStream_t s);
+template <typename T> void launch_mask_apply(const MaskApplyParams<T>& p, int grid, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

@@ -100,6 +100,8 @@ struct dctzhip_ctx {
   size_t fix_mask_cap = 0;          // words
   unsigned* fix_cnt = nullptr;      // ... a count per tile, then the levels of k_fixup_scan
   size_t fix_cnt_cap = 0;           // entries
+  void* mask_filled = nullptr;      // dctzhip_compress_masked without d_filled: the filled copy
+  size_t mask_filled_cap = 0;       // bytes
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
   unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   // dctzhip_decompress_boxes: the box table (records, then the boxes of the short block) in pinned host memory and on the
@@ -358,7 +360,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf, c->fix_mask, c->fix_cnt};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf, c->fix_mask, c->fix_cnt, c->mask_filled};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -2917,6 +2919,136 @@ extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, 
   return (dtype == DCTZHIP_F64)
              ? fixup_apply_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, n, box, first, last, (double*)d_out)
              : fixup_apply_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, n, box, first, last, (float*)d_out);
+}
+
+// ---- missing values: a mask beside the streams (include/dctz_hip.h; dctz_kernels_mask.hip) ----------------------
+extern "C" size_t dctzhip_mask_words(size_t n) { return (n + 63) / 64; }
+
+static int check_missing(dctzhip_ctx* c, const char* what, const dctzhip_missing* miss) {
+  const unsigned all = DCTZHIP_MISS_NAN | DCTZHIP_MISS_INF | DCTZHIP_MISS_VALUE | DCTZHIP_MISS_ABS_GE;
+  if (!miss) return fail(c, DCTZHIP_E_ARG, "%s: the missing-value rule must be given", what);
+  if (miss->flags == 0 || (miss->flags & ~all)) return fail(c, DCTZHIP_E_ARG, "%s: flags 0x%x select no test or an unknown one", what, miss->flags);
+  if ((miss->flags & DCTZHIP_MISS_VALUE) && std::isnan(miss->value))
+    return fail(c, DCTZHIP_E_ARG, "%s: a NaN value matches nothing; use DCTZHIP_MISS_NAN", what);
+  if ((miss->flags & DCTZHIP_MISS_ABS_GE) && !(miss->limit > 0.0 && std::isfinite(miss->limit)))
+    return fail(c, DCTZHIP_E_ARG, "%s: the limit must be finite and > 0", what);
+  return DCTZHIP_OK;
+}
+
+// The arguments are checked.  The count is the control block's counter, read back with the error word.
+template <typename T>
+static int mask_build_impl(dctzhip_ctx* c, const T* d_in, size_t n, const dctzhip_missing* miss, uint64_t* d_mask, T* d_filled, uint64_t* count) {
+  c->ctl_dirty = 1;                                    // the kernel ADDS to the control block's counter: cleared in stream order, always
+  { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
+  MaskFillParams<T> p;
+  p.in = d_in; p.out = d_filled; p.mask32 = reinterpret_cast<unsigned*>(d_mask); p.ctl = c->ctl;
+  p.n = (unsigned)n; p.flags = miss->flags;
+  p.value = (T)miss->value; p.limit = (T)miss->limit;
+  // a wave trip is 1 KiB of the array, MASK_TRIPS of them at a time; eight waves per SIMD (a few registers, no LDS), persistent beyond that
+  const size_t trips = (n * sizeof(T) + 1023) / 1024, per_wg = (size_t)(MASK_WG / 64) * MASK_TRIPS, wgs = (trips + per_wg - 1) / per_wg;
+  launch_mask_fill<T>(p, (int)std::min<size_t>(wgs, (size_t)c->num_cu * 8), c->stream);
+  SET_LAST(c, 1, "k_mask_fill<%s>", tname<T>());
+  unsigned total = 0;
+  const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
+  if (rc) return rc;
+  *count = total;
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_mask_build(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, const dctzhip_missing* miss, uint64_t* d_mask,
+                                  void* d_filled, uint64_t* count) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (!d_in || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build: the array, the mask and count must be given");
+  rc = check_missing(c, "dctzhip_mask_build", miss);
+  if (rc) return rc;
+  if (!aligned16(d_in) || !aligned16(d_filled) || ((uintptr_t)d_mask & 7u))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build: the arrays must be 16-byte aligned, the mask 8-byte aligned");
+  {
+    Span sp[3];
+    size_t m = 0;
+    add_span(sp, &m, d_in, n * elem_size(dtype), d_filled == d_in ? SPAN_IN_PLACE : SPAN_READ, 0);
+    if (d_filled != d_in) add_span(sp, &m, d_filled, n * elem_size(dtype), SPAN_OUT, 0);
+    add_span(sp, &m, d_mask, dctzhip_mask_words(n) * sizeof(uint64_t), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_mask_build", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64) ? mask_build_impl<double>(c, (const double*)d_in, n, miss, d_mask, (double*)d_filled, count)
+                                : mask_build_impl<float>(c, (const float*)d_in, n, miss, d_mask, (float*)d_filled, count);
+}
+
+extern "C" int dctzhip_compress_masked(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, double eb, int mode, const dctzhip_missing* miss,
+                                       void* d_bin, float* d_dc, float* d_ac, uint64_t* d_mask, void* d_filled, dctzhip_cinfo* info,
+                                       uint64_t* count) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  if (!d_in || !d_bin || !d_dc || !d_ac || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_masked: null buffer or count");
+  rc = check_missing(c, "dctzhip_compress_masked", miss);
+  if (rc) return rc;
+  if (!aligned16(d_in) || !aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac) || !aligned16(d_filled) || ((uintptr_t)d_mask & 7u))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_masked: device buffers must be 16-byte aligned, the mask 8-byte aligned");
+  if (eb < 1E-6) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
+  {
+    Span sp[8];
+    size_t m = 0;
+    compress_spans(sp, &m, 0, d_in, n, dtype, d_bin, d_dc, d_ac, nullptr, nullptr);
+    add_span(sp, &m, d_filled, n * elem_size(dtype), SPAN_OUT, 0);      // (d_in itself included: d_in is not modified)
+    add_span(sp, &m, d_mask, dctzhip_mask_words(n) * sizeof(uint64_t), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_compress_masked", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!d_filled) {
+    rc = regrow(c, &c->mask_filled, &c->mask_filled_cap, n * elem_size(dtype), 1);
+    if (rc) return rc;
+    d_filled = c->mask_filled;
+  }
+  rc = (dtype == DCTZHIP_F64) ? mask_build_impl<double>(c, (const double*)d_in, n, miss, d_mask, (double*)d_filled, count)
+                              : mask_build_impl<float>(c, (const float*)d_in, n, miss, d_mask, (float*)d_filled, count);
+  if (rc) return rc;
+  return dctzhip_compress(c, d_filled, n, dtype, eb, mode, d_bin, d_dc, d_ac, nullptr, nullptr, info);
+}
+
+template <typename T>
+static int mask_apply_impl(dctzhip_ctx* c, const uint64_t* d_mask, double fill, const BoxGeo& box, size_t cnt, size_t first, T* d_out) {
+  MaskApplyParams<T> p;
+  p.mask32 = reinterpret_cast<const unsigned*>(d_mask); p.out = d_out; p.fill = (T)fill;
+  p.cnt = (unsigned)cnt; p.first = (unsigned)first;
+  p.one_run = box.ext[0] == 1u && box.ext[1] == 1u && box.ext[2] == 1u;
+  p.box = box;
+  const size_t wgs = (cnt + MASK_WG - 1) / MASK_WG;
+  launch_mask_apply<T>(p, (int)std::min<size_t>(wgs, (size_t)c->num_cu * 8), c->stream);
+  SET_LAST(c, 1, "k_mask_apply<%s>", tname<T>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_mask_apply(dctzhip_ctx* c, const uint64_t* d_mask, size_t n, int dtype, double fill, int ndim, const size_t* dims,
+                                  const size_t* lo, const size_t* hi, void* d_out) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_apply: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
+  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_apply: null dims, lo or hi");
+  size_t cnt = 1, first = 0, last = 0;
+  rc = box_extents(c, "dctzhip_mask_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  if (rc) return rc;
+  const size_t es = elem_size(dtype);
+  if (!d_mask || !d_out || ((uintptr_t)d_mask & 7u) || ((uintptr_t)d_out & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_apply: the mask and the output must be given, 8-byte / element aligned");
+  {
+    Span sp[2];
+    size_t m = 0;
+    add_span(sp, &m, d_mask + first / 64, (last / 64 - first / 64 + 1) * sizeof(uint64_t), SPAN_READ, 0);
+    add_span(sp, &m, d_out, cnt * es, SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_mask_apply", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const BoxGeo box = canonical_box(ndim, dims, lo, hi);
+  return (dtype == DCTZHIP_F64) ? mask_apply_impl<double>(c, d_mask, fill, box, cnt, first, (double*)d_out)
+                                : mask_apply_impl<float>(c, d_mask, fill, box, cnt, first, (float*)d_out);
 }
 
 extern "C" int dctzhip_dct_blocks(dctzhip_ctx* c, const void* d_in, void* d_out, size_t n, int dtype, int inverse) {

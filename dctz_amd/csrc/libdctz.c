@@ -38,6 +38,7 @@
 #include "dctz_hip.h"
 #include "dctz_container.h"
 #include "dctz_fixup_blob.h"
+#include "dctz_mask_blob.h"
 
 #ifndef USE_TRUNCATE
 #error "build with -DUSE_TRUNCATE (every reference target does, Makefile:13-24)"
@@ -1595,7 +1596,9 @@ static int decompress_pipelined(dctzhip_ctx *c, const dzc_view *v, size_t chunk,
 
 /* fix (or NULL): a checked correction-list blob of this container (dctz_decompress_bounded), applied to the reconstruction on
  * the device before it is copied back; -1 if the list contradicts itself. */
-static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix) {
+/* fix (or NULL): a checked correction-list blob, applied to the reconstruction; mask_words (or NULL): the words of a
+ * missing-value mask, whose set bits then receive `fill` -- in that order (include/dctz_hip.h, "composed guarantee") */
+static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix, const uint64_t *mask_words, double fill) {
   const double t_begin = now_s();
   dzc_view v;
   const int bad_nd = dzc_open(&v, var_z, DCTZ_QT); /* dctz-decomp-lib.c:84-94 */
@@ -1621,7 +1624,7 @@ static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix
   grow(&g_dev.bin, &g_dev.bin_cap, npos);
   grow(&g_dev.dc, &g_dev.dc_cap, nblk * sizeof(float));
   grow(&g_dev.ac, &g_dev.ac_cap, (cnt ? cnt : 4) * sizeof(float));
-  if (indexed && !nd && !inflate_gpu() && pipeline_on() && !fix) {
+  if (indexed && !nd && !inflate_gpu() && pipeline_on() && !fix && !mask_words) {
     size_t got_p = 0;
     if (decompress_pipelined(c, &v, ix_chunk_bytes, ix_sizes, var_r, &got_p)) {
       for (int i = 0; i < 3; i++) free(ix_sizes[i]);
@@ -1704,6 +1707,13 @@ static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix
                              d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, n, dtype, 1, whole, zero, whole, g_dev.out);
     if (rc == DCTZHIP_E_ARG) return -1;                /* the list contradicts itself: nothing is handed out */
     if (rc != DCTZHIP_OK) die("dctzhip_fixup_apply");
+  }
+  if (mask_words) {
+    const size_t whole[1] = {n}, zero[1] = {0};
+    const size_t mbytes = dctzhip_mask_words(n) * sizeof(uint64_t);
+    grow(&g_dev.fix, &g_dev.fix_cap, mbytes);
+    if (dctzhip_memcpy_h2d(c, g_dev.fix, mask_words, mbytes) != DCTZHIP_OK) die("H2D mask");
+    if (dctzhip_mask_apply(c, (const uint64_t *)g_dev.fix, n, dtype, fill, 1, whole, zero, whole, g_dev.out) != DCTZHIP_OK) die("dctzhip_mask_apply");
   }
   double t3 = now_s();
   if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, n * ts) != DCTZHIP_OK) die("D2H output");
@@ -2071,7 +2081,7 @@ out:
 }
 
 /* ------------------------------------------ dctz_fixup_build, dctz_decompress_bounded -- */
-int dctz_decompress(t_var *var_z, t_var *var_r) { return decompress_whole(var_z, var_r, NULL); }
+int dctz_decompress(t_var *var_z, t_var *var_r) { return decompress_whole(var_z, var_r, NULL, NULL, 0.0); }
 
 /* dctz_decompress with the correction list of `blob` applied (include/dctz.h).  The blob's header is held against the
  * container's before anything else happens. */
@@ -2081,7 +2091,7 @@ int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t
   dzfx_header fh;
   if (v.nd != 0 || v.n == 0 || !var_r) return -1;
   if (dzfx_check(blob, blob_bytes, v.is_d, v.n, &fh) != 0) return -1;
-  return decompress_whole(var_z, var_r, (const unsigned char *)blob);
+  return decompress_whole(var_z, var_r, (const unsigned char *)blob, NULL, 0.0);
 }
 
 /* The correction list of a flat container against the caller's unscaled original, as one malloc'd blob
@@ -2164,6 +2174,69 @@ int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void
   ret = 1;
 out:
   for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  return ret;
+}
+
+/* ------------------------------------------ dctz_compress_masked, dctz_decompress_masked -- */
+/* The array goes to the device, dctzhip_mask_build fills it in place and makes the mask, both come back, and the container
+ * is then simply dctz_compress of the filled array -- byte for byte that call's output, the in-place x /= sf of the caller's
+ * buffer included (as dctz_compress_psnr: the second H2D copy inside dctz_compress is the price of that identity).  The mask
+ * words leave as one zlib stream behind the blob's header (csrc/dctz_mask_blob.h). */
+int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, double error_bound, const dctz_missing *miss, double fill,
+                         void **mask_blob, size_t *mask_bytes) {
+  if (!var || !var_z || !outSize || !miss || !mask_blob || !mask_bytes || N <= 0) return -1;
+  if (g_nd || (getenv("DCTZ_BLOCK_DIMS") && *getenv("DCTZ_BLOCK_DIMS"))) return -1;   /* flat blocks only: the fill runs over them */
+  const int is_d = (var->datatype == DOUBLE);
+  if (!is_d && var->datatype != FLOAT) return -1;
+  void *host = var_bytes(var);
+  if (!host) return -1;
+  if (miss->flags == 0 || (miss->flags & ~DZMK_FLAGS_ALL)) return -1;
+  if ((miss->flags & DCTZHIP_MISS_VALUE) && isnan(miss->value)) return -1;
+  if ((miss->flags & DCTZHIP_MISS_ABS_GE) && !(miss->limit > 0.0 && !isinf(miss->limit))) return -1;
+  const size_t n = (size_t)N, ts = is_d ? sizeof(double) : sizeof(float), words = dctzhip_mask_words(n);
+  dctzhip_ctx *c = ctx();
+  grow(&g_dev.in, &g_dev.in_cap, n * ts);
+  grow(&g_dev.fix, &g_dev.fix_cap, words * sizeof(uint64_t));
+  if (dctzhip_memcpy_h2d(c, g_dev.in, host, n * ts) != DCTZHIP_OK) die("H2D");
+  dctzhip_missing m;
+  m.flags = miss->flags; m.value = miss->value; m.limit = miss->limit;
+  uint64_t count = 0;
+  if (dctzhip_mask_build(c, g_dev.in, n, is_d ? DCTZHIP_F64 : DCTZHIP_F32, &m, (uint64_t *)g_dev.fix, g_dev.in, &count) != DCTZHIP_OK)
+    die("dctzhip_mask_build");
+  uint64_t *w = (uint64_t *)malloc(words * sizeof(uint64_t));
+  uLongf zbytes = compressBound((uLong)(words * sizeof(uint64_t)));
+  unsigned char *b = (unsigned char *)malloc(DZMK_HEADER_BYTES + (size_t)zbytes);
+  if (!w || !b) { fprintf(stderr, "Out of memory: mask\n"); exit(1); }
+  if (dctzhip_memcpy_d2h(c, host, g_dev.in, n * ts) != DCTZHIP_OK) die("D2H filled array");
+  if (dctzhip_memcpy_d2h(c, w, g_dev.fix, words * sizeof(uint64_t)) != DCTZHIP_OK) die("D2H mask");
+  if (compress2(b + DZMK_HEADER_BYTES, &zbytes, (const Bytef *)w, (uLong)(words * sizeof(uint64_t)), DZMK_ZLIB_LEVEL) != Z_OK) die("compress2 (mask)");
+  free(w);
+  dzmk_write_header(b, is_d, miss->flags, n, (size_t)count, fill, (size_t)zbytes);
+  const int ret = dctz_compress(var, N, outSize, var_z, error_bound);
+  if (ret != 1) { free(b); return ret; }
+  *mask_blob = b; *mask_bytes = DZMK_HEADER_BYTES + (size_t)zbytes;
+  return 1;
+}
+
+/* dctz_decompress, then the correction list if one is given, then the mask.  Both blob headers are held against the
+ * container's before anything else happens, and the mask's payload must inflate to exactly its words. */
+int dctz_decompress_masked(t_var *var_z, const void *mask_blob, size_t mask_bytes, const void *fix_blob, size_t fix_bytes, t_var *var_r) {
+  dzc_view v;
+  if (!var_z || !var_bytes(var_z)) return -1;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype);
+  dzmk_header mh;
+  dzfx_header fh;
+  if (v.nd != 0 || v.n == 0 || !var_r) return -1;
+  if (dzmk_check(mask_blob, mask_bytes, v.is_d, v.n, &mh) != 0) return -1;
+  if (fix_blob && dzfx_check(fix_blob, fix_bytes, v.is_d, v.n, &fh) != 0) return -1;
+  const size_t wbytes = (size_t)mh.words * sizeof(uint64_t);
+  /* (one byte of room more: a payload that holds more than the words must not pass for one that holds them) */
+  unsigned char *w = (unsigned char *)malloc(wbytes + 8);
+  if (!w) { fprintf(stderr, "Out of memory: mask\n"); exit(1); }
+  uLongf got = (uLongf)(wbytes + 8);
+  if (uncompress(w, &got, (const Bytef *)mask_blob + DZMK_HEADER_BYTES, (uLong)mh.payload_bytes) != Z_OK || (size_t)got != wbytes) { free(w); return -1; }
+  const int ret = decompress_whole(var_z, var_r, (const unsigned char *)fix_blob, (const uint64_t *)w, mh.fill);
+  free(w);
   return ret;
 }
 

@@ -22,6 +22,13 @@ def lib_path():
     return os.environ.get("DCTZHIP_LIBRARY") or os.path.join(_HERE, "lib", "libdctzhip.so")   # override: A/B builds of the library
 
 
+MISS_NAN, MISS_INF, MISS_VALUE, MISS_ABS_GE = 1, 2, 4, 8      # DCTZHIP_MISS_*
+
+
+class Missing(C.Structure):          # dctzhip_missing
+    _fields_ = [("flags", C.c_uint), ("value", C.c_double), ("limit", C.c_double)]
+
+
 class CompressInfo(C.Structure):
     _fields_ = [("sf", C.c_double), ("mean", C.c_double), ("max_abs", C.c_double),
                 ("min_abs", C.c_double), ("cnt", C.c_uint32), ("nblk", C.c_uint32),
@@ -155,6 +162,14 @@ _PROTOS = {
                                       C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "dctzhip_fixup_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_int, C.c_int,
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_mask_words": (C.c_size_t, [C.c_size_t]),
+    "dctzhip_mask_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Missing), C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_uint64)]),
+    "dctzhip_mask_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_compress_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.POINTER(Missing),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CompressInfo),
+                                          C.POINTER(C.c_uint64)]),
     "dctzhip_dct_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dctzhip_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_serial_mean_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -731,6 +746,70 @@ class Context:
             dst.data_ptr())
         self._check(rc, "dctzhip_fixup_apply")
         return dst
+
+    # ---- missing values (include/dctz_hip.h: a mask beside the streams, the holes filled on compress) ----
+    @staticmethod
+    def _missing(flags, value=0.0, limit=0.0):
+        return flags if isinstance(flags, Missing) else Missing(int(flags), float(value), float(limit))
+
+    def mask_build(self, x, flags, value=0.0, limit=0.0, filled=None, mask=None):
+        """The mask of x (a 1-D CUDA tensor) under the tests `flags` (MISS_*), the count of missing elements, and the filled
+        copy: filled=None makes a new tensor, filled=x fills in place, filled=False asks for the mask and the count only.
+        Returns (mask, count, filled): mask an int64 tensor of ceil(n / 64) words (their bits are uint64)."""
+        t = self.torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 1
+        self._bind_stream()
+        n = x.numel()
+        if mask is None:
+            mask = t.empty(int(self.lib.dctzhip_mask_words(n)), dtype=t.int64, device=self.device)
+        if filled is None:
+            filled = t.empty_like(x)
+        elif filled is False:
+            filled = None
+        m = self._missing(flags, value, limit)
+        count = C.c_uint64(0)
+        rc = self.lib.dctzhip_mask_build(self.h, x.data_ptr(), n, _dt(x.dtype), C.byref(m), mask.data_ptr(),
+                                         filled.data_ptr() if filled is not None else None, C.byref(count))
+        self._check(rc, "dctzhip_mask_build")
+        return mask, int(count.value), filled
+
+    def mask_apply(self, mask, n, fill, dst, dims=None, lo=None, hi=None):
+        """Writes `fill` into every element of dst whose bit is set in `mask` (mask_build's); dst and its geometry are
+        fixup_apply's: the dense box lo <= c < hi of the n-element array seen with shape `dims`, or with dims=None the range
+        [lo, hi) of the flat array, by default all of it.  Returns dst."""
+        self._bind_stream()
+        if dims is None:
+            dims, lo, hi = [n], [0 if lo is None else lo], [n if hi is None else hi]
+        dims, lo, hi = [int(v) for v in dims], [int(v) for v in lo], [int(v) for v in hi]
+        nd = len(dims)
+        assert len(lo) == nd and len(hi) == nd and dst.is_cuda and dst.is_contiguous()
+        assert dst.numel() == int(np.prod([max(h - l, 0) for l, h in zip(lo, hi)], dtype=np.int64))
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_mask_apply(self.h, mask.data_ptr(), n, _dt(dst.dtype), float(fill), nd, arr(*dims), arr(*lo), arr(*hi),
+                                         dst.data_ptr())
+        self._check(rc, "dctzhip_mask_apply")
+        return dst
+
+    def compress_masked(self, x, eb, flags, value=0.0, limit=0.0, mode=EC, out=None, filled=None, mask=None):
+        """mask_build followed by compress of the filled array, in one call; x is not modified.  filled: a tensor like x that
+        receives the filled array (the reference for tile_summary and fixup_build), or None: the context keeps it.
+        Returns (out, info, mask, count)."""
+        t = self.torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 1
+        self._bind_stream()
+        n = x.numel()
+        if out is None:
+            out = self.alloc_outputs(n, x.dtype)
+        if mask is None:
+            mask = t.empty(int(self.lib.dctzhip_mask_words(n)), dtype=t.int64, device=self.device)
+        m = self._missing(flags, value, limit)
+        info, count = CompressInfo(), C.c_uint64(0)
+        rc = self.lib.dctzhip_compress_masked(
+            self.h, x.data_ptr(), n, _dt(x.dtype), float(eb), mode, C.byref(m), out["bin_index"].data_ptr(), out["dc"].data_ptr(),
+            out["ac_exact"].data_ptr(), mask.data_ptr(), filled.data_ptr() if filled is not None else None, C.byref(info),
+            C.byref(count))
+        self._check(rc, "dctzhip_compress_masked")
+        return out, info, mask, int(count.value)
 
     def psnr_terms(self, x, r):
         """calc_psnr's reductions (util.c:54-104) on the GPU: (min x, max x, max |x - r|, sum (x - r)^2)."""

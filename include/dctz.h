@@ -221,6 +221,22 @@ int dctz_tile_summary(t_var *var_z, t_var *var_ref /* or NULL */, int N_ref, dct
  * else is done), a list that contradicts itself and streams that disagree with each other. */
 int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void **blob, size_t *blob_bytes);
 int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t_var *var_r);
+/* Missing values (ADDITION, EC and QT builds, flat blocks; include/dctz_hip.h, "missing values", holds the definition: the
+ * tests, the fill rule, the mask).  dctz_compress_masked marks the elements of var->buf that `miss` selects, fills them with
+ * copies of their valid neighbours inside each 64-element block, and compresses the filled array: the container is byte for
+ * byte dctz_compress() of that array, and var->buf is left as that call leaves it (filled and divided by sf).  The mask comes
+ * back as one malloc'd self-describing block that the caller keeps beside the container and frees: "DZMK", version, dtype,
+ * flags, n, count, fill, words, payload bytes (48 bytes), then the mask words as one zlib stream (csrc/dctz_mask_blob.h).
+ * dctz_decompress_masked is dctz_decompress, then the correction list of fix_blob if one is given (dctz_fixup_build against
+ * the FILLED array), then `fill` written into every missing element.  Both return 1, or -1 for a DZND container or a pending
+ * dctz_set_block_dims, a rule that selects no test or an unknown one, a NaN value, a limit that is not finite and > 0, a blob
+ * whose header does not fit the container (magic, version, dtype, n, counts, length -- checked before anything else is done)
+ * and a payload that does not inflate to exactly the mask's words. */
+typedef struct { unsigned flags; double value; double limit; } dctz_missing;   /* flags: DCTZHIP_MISS_* of dctz_hip.h (1 NaN, 2 Inf, 4 == value, 8 |x| >= limit) */
+int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, double error_bound, const dctz_missing *miss,
+                         double fill, void **mask_blob, size_t *mask_bytes);
+int dctz_decompress_masked(t_var *var_z, const void *mask_blob, size_t mask_bytes,
+                           const void *fix_blob /* or NULL */, size_t fix_bytes, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

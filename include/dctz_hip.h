@@ -612,6 +612,68 @@ int dctzhip_fixup_apply(dctzhip_ctx *ctx, const uint32_t *d_fix_start, const uin
                         uint32_t count, size_t n, int dtype, int ndim, const size_t *dims, const size_t *lo,
                         const size_t *hi, void *d_out);
 
+/* ---- missing values: a mask beside the streams, the holes filled on compress ------------ */
+/* Fields with missing values (1e36 over land, NaN) ruin the codec as they are: sf is taken over every element, a NaN costs
+ * its 64-element block, an infinity the array.  The mask layer keeps one bit per element beside the streams, compresses a
+ * FILLED array whose holes hold copies of their valid neighbours, and writes the caller's fill value back after any decode.
+ * No compress or decode kernel and no stream byte changes.  Flat 64-element blocks only.
+ *   missing     element x (data type T) is missing iff a selected test holds, made in T:
+ *                 DCTZHIP_MISS_NAN      x != x (signalling NaNs too)
+ *                 DCTZHIP_MISS_INF      fabs(x) == inf
+ *                 DCTZHIP_MISS_VALUE    x == (T)value (-0.0 matches 0.0; a NaN value is refused: use MISS_NAN)
+ *                 DCTZHIP_MISS_ABS_GE   fabs(x) >= (T)limit (limit finite and > 0)
+ *               every other element is valid.
+ *   fill rule   blocks are the codec's: elements [64 b, 64 b + 64), the short last block has n % 64.  A missing element of
+ *               block B takes the value of the nearest valid element before it in B; else (a leading gap) the first valid
+ *               element of B; else (no valid element in B) +0.0.  Valid elements keep their bits; every filled value is a
+ *               copy of one, so the filled array has no missing element and its max|x| is the valid data's; so is its
+ *               min|x|, unless a block without a valid element brings in its +0.0.  (MISS_VALUE with value 0 calls that +0.0
+ *               missing again: the one case in which the fill is not idempotent.)
+ *   mask        dctzhip_mask_words(n) = ceil(n / 64) words of 64 bits: bit i & 63 of word i >> 6 is 1 iff element i is
+ *               missing.  Build writes the bits at positions >= n as 0; apply ignores them.
+ *
+ * dctzhip_mask_build: one pass over the array -- the mask, the count and (unless d_filled is NULL) the filled copy.
+ *   d_filled    NULL, exactly d_in (in place) or disjoint from it.
+ *   count       (HOST) the number of missing elements.
+ *   refusals    before any launch, DCTZHIP_E_ARG: ctx, d_in, miss, d_mask or count NULL; n == 0 or a bad dtype; flags of 0 or
+ *               with unknown bits; MISS_VALUE with a NaN value; MISS_ABS_GE with a limit that is not finite and > 0; d_in or
+ *               d_filled not 16-byte aligned, d_mask not 8-byte aligned; d_filled overlapping d_in partly; the mask
+ *               overlapping an array.
+ * The same call gives the same bytes every time, on every context, whatever grid is launched.  Host-synchronous like
+ * dctzhip_fixup_build; dctzhip_debug_last_kernel(ctx, 1, ...) names the kernel afterwards.
+ *
+ * dctzhip_compress_masked: dctzhip_mask_build followed by dctzhip_compress(ctx, filled, n, dtype, error_bound, mode,
+ * d_bin_index, d_dc, d_ac_exact, NULL, NULL, info): streams and *info are bit for bit that call's.  d_in is not modified.
+ *   d_filled    n elements that receive the filled array -- the reference to hand dctzhip_tile_summary and
+ *               dctzhip_fixup_build -- or NULL: the context keeps the copy in scratch of its own.
+ *   refusals    those of the two calls, all made before any launch.
+ *
+ * dctzhip_mask_apply: d_out is the dense C-order box of dctzhip_fixup_apply (a range is the 1-D case, the whole array ndim = 1,
+ * lo = 0, hi = n).  Every box element whose bit is set receives (T)fill (a NaN fill: a quiet NaN, its payload not pinned);
+ * nothing else is written, inside the box or outside it; only the mask words the box touches are read.  Any bit pattern is a
+ * valid mask.
+ *   refusals    before any launch, DCTZHIP_E_ARG: the box rules of dctzhip_decompress_box; d_mask or d_out NULL or misaligned
+ *               (8 bytes / element size); d_out overlapping the mask.
+ * Host-synchronous; dctzhip_debug_last_kernel(ctx, 1, ...) names the apply kernel afterwards.
+ *
+ * Composed guarantee: compress with dctzhip_compress_masked, build the correction list against d_filled, decode by any whole,
+ * range or box path, run dctzhip_fixup_apply, then dctzhip_mask_apply.  Every valid element then has the original's bits or
+ * lies within the list's bound of it, and every missing element has the fill's bits. */
+#define DCTZHIP_MISS_NAN     1u   /* x != x (signalling NaNs too) */
+#define DCTZHIP_MISS_INF     2u   /* fabs(x) == inf */
+#define DCTZHIP_MISS_VALUE   4u   /* x == (T)value: -0.0 matches 0.0; a NaN value is refused, use MISS_NAN */
+#define DCTZHIP_MISS_ABS_GE  8u   /* fabs(x) >= (T)limit; limit finite and > 0 */
+typedef struct { unsigned flags; double value; double limit; } dctzhip_missing;
+size_t dctzhip_mask_words(size_t n);
+int dctzhip_mask_build(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, const dctzhip_missing *miss,
+                       uint64_t *d_mask, void *d_filled /* NULL, == d_in, or disjoint */, uint64_t *count /* host */);
+int dctzhip_mask_apply(dctzhip_ctx *ctx, const uint64_t *d_mask, size_t n, int dtype, double fill, int ndim,
+                       const size_t *dims, const size_t *lo, const size_t *hi, void *d_out);
+int dctzhip_compress_masked(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, double error_bound, int mode,
+                            const dctzhip_missing *miss, void *d_bin_index, float *d_dc, float *d_ac_exact,
+                            uint64_t *d_mask, void *d_filled /* or NULL: context scratch, kept */, dctzhip_cinfo *info,
+                            uint64_t *count /* host */);
+
 /* ---- transform only ------------------------------------------------------ */
 /* Batched drop-in for dct_init + per-block dct_fftw / ifft_idct (+ the
  * remainder-length re-init), dct.h:17-27 as driven by dct-test.c:81-89, 144-152:
