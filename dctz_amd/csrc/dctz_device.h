@@ -750,6 +750,56 @@ void launch_fixup_scan(const unsigned* cnt, size_t m, unsigned* start, unsigned*
 template <typename T> void launch_fixup_emit(const FixupEmitParams<T>& p, int grid, hipStream_t s);
 template <typename T> void launch_fixup_apply(const FixupApplyParams<T>& p, int grid, hipStream_t s);
 
+// Correction list of an array compressed in 8 x 8 / 4 x 4 x 4 tiles (dctz_kernels_ndfix.hip: k_ndfix_mark, k_ndfix_emit,
+// k_ndfix_apply; the scan is k_fixup_scan).  The streams cover n = 64 nblk positions, nfull = nblk (no short block), as for
+// NdBoxParams; the original and the output are the array itself in C order.  A 2-D array sits in the last two axes of nb /
+// d, axis 0 has extent 1.  The fields ra_tile_image reads carry NdBoxParams' names.
+template <typename T>
+struct NdFixParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[0 .. ntiles]
+  const T* tab;
+  const T* qtab;
+  Ctl* ctl;                        // error = 2: as RangeParams
+  const T* ref;                    // the original, prod d elements
+  unsigned long long* mask;        // nblk words: bit j of word B = position 64 B + j is listed
+  unsigned* tile_cnt;              // ntiles counts
+  unsigned n, nfull, ntiles, ac_count;
+  T sf, bin_width, range_min, range_max;
+  T bound;                         // a real position is listed iff !(fabs(x - r) <= bound)
+  double eb;
+  unsigned nb[3];                  // blocks per axis
+  unsigned d[3];                   // extents of the array
+};
+template <typename T>
+struct NdFixEmitParams {
+  const unsigned long long* mask;
+  const unsigned* fix_start;       // ntiles + 1 entries, complete
+  const T* ref;
+  uint16_t* fix_off;
+  T* fix_val;
+  const Ctl* ctl;                  // the mark kernel's error: nothing is emitted
+  unsigned nblk, ntiles, capacity; // nothing is emitted either if fix_start[ntiles] > capacity
+  unsigned nb[3], d[3];
+};
+template <typename T>
+struct NdFixApplyParams {
+  const unsigned* fix_start;
+  const uint16_t* fix_off;
+  const T* fix_val;
+  T* out;                          // prod ext elements
+  Ctl* ctl;                        // error = 5: the list contradicts itself or the array; the tile stored nothing
+  unsigned nblk, ntiles, count, t0, t1;   // stream tiles [t0, t1) are visited
+  unsigned nb[3], d[3];
+  unsigned lo[3], ext[3];          // the box, in elements
+};
+template <typename T> int ndfix_occupancy(int mode, int geom);
+template <typename T> void launch_ndfix_mark(const NdFixParams<T>& p, int mode, int geom, int grid, hipStream_t s);
+template <typename T> void launch_ndfix_emit(const NdFixEmitParams<T>& p, int geom, int grid, hipStream_t s);
+template <typename T> void launch_ndfix_apply(const NdFixApplyParams<T>& p, int geom, int grid, hipStream_t s);
+
 // Missing values (dctz_kernels_mask.hip: k_mask_fill, k_mask_apply): a bit per element beside the streams, the holes filled
 // by copies inside each 64-element block (include/dctz_hip.h).  The mask travels as 32-bit pieces, two per word.
 template <typename T>

@@ -1,0 +1,26 @@
+// dctz_nd_image.h -- the LDS image of a stream tile of an array compressed in 8 x 8 / 4 x 4 x 4 tiles, as the kernels that
+// walk it in row strips lay it out (dctz_kernels_ndbox.hip: k_decompress_ndbox; dctz_kernels_ndfix.hip: k_ndfix_mark).
+#pragma once
+#include "dctz_kernel_common.h"
+
+namespace dctz {
+
+// Block b of the tile at elements [b * STRIDE, b * STRIDE + 64).  The read-back of step s, in-block row r has lane l at
+// (l / e + 64 / e * s) * STRIDE + e r + l % e; the image is written by lane b's 16-byte stores at b * STRIDE + 4 | 2 ch.
+//   fp32, 8 x 8 (ds_read_b32: 32 lanes per cycle, 32 banks): 4 blocks x 8 dwords -> STRIDE = 8 mod 32 is conflict-free
+//     (72); the 16-byte writes (8 lanes per cycle, 32 banks) then pair up lanes b and b + 4: 16 array cycles for the 13 the
+//     instruction takes anyway.  RaGeo's 68 would make every one of the 64 reads 2-way.
+//   fp32, 4 x 4 x 4: 8 blocks x 4 dwords -> STRIDE = 4 mod 32: RaGeo's 68, conflict-free both ways.
+//   fp64, 8 x 8 (ds_read_b64: 32 lanes, 64 banks): 4 blocks x 16 dwords -> conflict-free needs STRIDE = 8 mod 32, which
+//     puts the writes of 8 lanes on 2 x 16 banks (4-way, 32 writes a tile).  70: writes conflict-free (12 b mod 32 takes
+//     8 values 4 apart), reads 2-way.  RaGeo's 66 reads 4-way.
+//   fp64, 4 x 4 x 4: 8 blocks x 8 dwords -> STRIDE = 4 mod 32 (68) reads conflict-free, writes 2-way (16 cycles for 13).
+template <typename T, int GEOM> struct NdImage {
+  static constexpr int EPV = Traits<T>::EPV;
+  static constexpr int STRIDE = GEOM == GEOM_3D ? 68 : (sizeof(T) == 8 ? 70 : 72);
+  static constexpr int BYTES = TILE_BLKS * STRIDE * (int)sizeof(T);
+  static_assert(STRIDE % EPV == 0, "16-byte rows");
+  static_assert(BYTES >= 63 * 64 * 4, "a dense tile's exact coefficients fit the image");
+};
+
+}  // namespace dctz

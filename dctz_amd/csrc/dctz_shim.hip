@@ -100,6 +100,7 @@ struct dctzhip_ctx {
   size_t fix_mask_cap = 0;          // words
   unsigned* fix_cnt = nullptr;      // ... a count per tile, then the levels of k_fixup_scan
   size_t fix_cnt_cap = 0;           // entries
+  int ndfix_occ[2][2][2] = {};      // dctzhip_fixup_build_nd: the same of k_ndfix_mark, [fp64][QT][3-D]; scratch as above
   void* mask_filled = nullptr;      // dctzhip_compress_masked without d_filled: the filled copy
   size_t mask_filled_cap = 0;       // bytes
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
@@ -2919,6 +2920,162 @@ extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, 
   return (dtype == DCTZHIP_F64)
              ? fixup_apply_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, n, box, first, last, (double*)d_out)
              : fixup_apply_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, n, box, first, last, (float*)d_out);
+}
+
+// ---- correction list of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndfix.hip) ----------------
+// the array in the last sh.nd of three axes
+static void ndfix_axes(const NdShape& sh, unsigned (&nb)[3], unsigned (&d)[3]) {
+  for (int i = 0; i < 3; i++) { nb[i] = 1u; d[i] = 1u; }
+  for (int i = 0; i < sh.nd; i++) { nb[3 - sh.nd + i] = (unsigned)sh.nb[i]; d[3 - sh.nd + i] = (unsigned)sh.d[i]; }
+}
+
+template <typename T>
+static int fixup_build_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                               const uint32_t* d_index, const void* qtable_host, const NdShape& sh, double eb, double sf, int mode,
+                               const T* d_ref, double bound, uint32_t* d_fix_start, uint16_t* d_fix_off, T* d_fix_val, uint32_t capacity,
+                               uint32_t* count) {
+  hipStream_t s = c->stream;
+  const size_t n_lin = sh.nblk * 64;
+  const size_t m = dctzhip_fixup_tiles(n_lin);
+  { int rc = regrow(c, &c->fix_mask, &c->fix_mask_cap, sh.nblk, sizeof(unsigned long long)); if (rc) return rc; }
+  { int rc = regrow(c, &c->fix_cnt, &c->fix_cnt_cap, m + fixup_scan_slots(m), sizeof(unsigned)); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  NdFixParams<T> p;
+  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  p.ref = d_ref;
+  p.mask = c->fix_mask;
+  p.tile_cnt = c->fix_cnt;
+  p.n = (unsigned)n_lin; p.nfull = (unsigned)sh.nblk; p.ntiles = (unsigned)m;
+  p.bound = (T)bound;
+  ndfix_axes(sh, p.nb, p.d);
+  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
+  const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
+  int& occ = c->ndfix_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3];
+  if (occ == 0) occ = std::max(ndfix_occupancy<T>(mode, geom), 1);
+  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+  launch_ndfix_mark<T>(p, mode, geom, (int)(p.ntiles < resident ? p.ntiles : resident), s);
+  SET_LAST(c, 1, "k_ndfix_mark<%s, %d, %d>", tname<T>(), mode, geom);
+  launch_fixup_scan(c->fix_cnt, m, d_fix_start, c->fix_cnt + m, c->ctl, s);
+  if (d_fix_off) {
+    // behind the scan in stream order; the kernel itself stands back if the list does not fit or a tile was refused
+    NdFixEmitParams<T> e;
+    e.mask = c->fix_mask; e.fix_start = d_fix_start; e.ref = d_ref; e.fix_off = d_fix_off; e.fix_val = d_fix_val; e.ctl = c->ctl;
+    e.nblk = (unsigned)sh.nblk; e.ntiles = (unsigned)m; e.capacity = capacity;
+    ndfix_axes(sh, e.nb, e.d);
+    const unsigned g = (unsigned)std::min<size_t>(m, (size_t)c->num_cu * 32);      // (a few registers, no LDS: eight waves per SIMD)
+    launch_ndfix_emit<T>(e, geom, (int)g, s);
+  }
+  unsigned total = 0;
+  const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
+  if (rc) return rc;
+  *count = total;
+  if (d_fix_off && total > capacity)
+    return fail(c, DCTZHIP_E_SPACE, "dctzhip_fixup_build_nd: %u entries do not fit the capacity of %u", total, capacity);
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_fixup_build_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                      const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb,
+                                      double sf, int mode, const void* d_ref, double bound, uint32_t* d_fix_start, uint16_t* d_fix_off,
+                                      void* d_fix_val, uint32_t capacity, uint32_t* count) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
+  int rc = check_common(c, n_lin, dtype, mode);
+  if (rc) return rc;
+  if (!d_ref || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: the original and count must be given");
+  if (!(bound >= 0.0) || std::isinf(bound)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: the bound must be finite and >= 0");
+  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: the original must be 16-byte aligned");
+  if (!d_fix_start || ((uintptr_t)d_fix_start & 3u)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: fix_start must be given, 4-byte aligned");
+  if ((d_fix_off == nullptr) != (d_fix_val == nullptr))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: fix_off and fix_val must both be given or both be NULL");
+  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (elem_size(dtype) - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: fix_off must be 2-byte aligned, fix_val aligned to its elements");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    Span sp[8];
+    size_t m = 0;
+    add_span(sp, &m, d_bin, n_lin, SPAN_READ, 0);
+    add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index, dctzhip_ac_index_len(n_lin) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_ref, n_orig * elem_size(dtype), SPAN_READ, 0);
+    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n_lin) + 1) * sizeof(uint32_t), SPAN_OUT, 0);
+    add_span(sp, &m, d_fix_off, (size_t)capacity * sizeof(uint16_t), SPAN_OUT, 0);
+    add_span(sp, &m, d_fix_val, (size_t)capacity * elem_size(dtype), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_fixup_build_nd", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? fixup_build_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
+                                           (const double*)d_ref, bound, d_fix_start, d_fix_off, (double*)d_fix_val, capacity, count)
+             : fixup_build_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
+                                          (const float*)d_ref, bound, d_fix_start, d_fix_off, (float*)d_fix_val, capacity, count);
+}
+
+template <typename T>
+static int fixup_apply_nd_impl(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const T* d_fix_val, uint32_t count,
+                               const NdShape& sh, const size_t* lo, const size_t* hi, unsigned t0, unsigned t1, T* d_out) {
+  hipStream_t s = c->stream;
+  { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
+  NdFixApplyParams<T> p;
+  p.fix_start = d_fix_start; p.fix_off = d_fix_off; p.fix_val = d_fix_val; p.out = d_out; p.ctl = c->ctl;
+  p.nblk = (unsigned)sh.nblk; p.ntiles = (unsigned)dctzhip_fixup_tiles(sh.nblk * 64); p.count = count; p.t0 = t0; p.t1 = t1;
+  ndfix_axes(sh, p.nb, p.d);
+  for (int i = 0; i < 3; i++) { p.lo[i] = 0u; p.ext[i] = 1u; }
+  for (int i = 0; i < sh.nd; i++) { p.lo[3 - sh.nd + i] = (unsigned)lo[i]; p.ext[3 - sh.nd + i] = (unsigned)(hi[i] - lo[i]); }
+  const unsigned tiles = t1 - t0, resident = (unsigned)c->num_cu * 32u;              // (a few registers, no LDS: eight waves per SIMD)
+  launch_ndfix_apply<T>(p, sh.nd == 2 ? GEOM_2D : GEOM_3D, (int)(tiles < resident ? tiles : resident), s);
+  SET_LAST(c, 1, "k_ndfix_apply<%s, %d>", tname<T>(), sh.nd == 2 ? GEOM_2D : GEOM_3D);
+  return ra_finish(c);
+}
+
+extern "C" int dctzhip_fixup_apply_nd(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val,
+                                      uint32_t count, int ndims, const size_t* dims, int dtype, const size_t* lo, const size_t* hi,
+                                      void* d_out) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
+  int rc = check_common(c, n_lin, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (!lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: null lo or hi");
+  const size_t edge = ndims == 2 ? 8 : 4;
+  size_t cnt = 1, first = 0, last = 0;              // first / last intersecting block of the row-major block grid
+  for (int i = 0; i < ndims; i++) {
+    if (lo[i] >= hi[i] || hi[i] > dims[i])
+      return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: [%zu, %zu) is not inside dimension %d of %zu", lo[i], hi[i], i, dims[i]);
+    cnt *= hi[i] - lo[i];
+    first = first * sh.nb[i] + lo[i] / edge;
+    last = last * sh.nb[i] + (hi[i] - 1) / edge;
+  }
+  const size_t es = elem_size(dtype);
+  if (!d_fix_start || !d_out || ((uintptr_t)d_fix_start & 3u) || ((uintptr_t)d_out & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: fix_start and the output must be given, 4-byte / element aligned");
+  if (count > n_orig) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: count %u exceeds the array's %zu elements", count, n_orig);
+  if (count && (!d_fix_off || !d_fix_val)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: null fix_off or fix_val");
+  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: fix_off must be 2-byte aligned, fix_val aligned to its elements");
+  {
+    Span sp[4];
+    size_t m = 0;
+    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n_lin) + 1) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_fix_off, (size_t)count * sizeof(uint16_t), SPAN_READ, 0);
+    add_span(sp, &m, d_fix_val, (size_t)count * es, SPAN_READ, 0);
+    add_span(sp, &m, d_out, cnt * es, SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_fixup_apply_nd", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const unsigned t0 = (unsigned)(first / TILE_BLKS), t1 = (unsigned)(last / TILE_BLKS + 1);
+  return (dtype == DCTZHIP_F64)
+             ? fixup_apply_nd_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, sh, lo, hi, t0, t1, (double*)d_out)
+             : fixup_apply_nd_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, sh, lo, hi, t0, t1, (float*)d_out);
 }
 
 // ---- missing values: a mask beside the streams (include/dctz_hip.h; dctz_kernels_mask.hip) ----------------------

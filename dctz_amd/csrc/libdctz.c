@@ -1700,12 +1700,15 @@ static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix
     memcpy(&fh, fix, sizeof(fh));
     const size_t payload = dzfx_payload_bytes((size_t)fh.tiles, (size_t)fh.count, ts);
     grow(&g_dev.fix, &g_dev.fix_cap, payload);
-    if (dctzhip_memcpy_h2d(c, g_dev.fix, fix + DZFX_HEADER_BYTES, payload) != DCTZHIP_OK) die("H2D correction list");
+    if (dctzhip_memcpy_h2d(c, g_dev.fix, fix + dzfx_header_bytes(fh.version), payload) != DCTZHIP_OK) die("H2D correction list");
     const unsigned char *const d = (const unsigned char *)g_dev.fix;
-    const size_t whole[1] = {n}, zero[1] = {0};
-    rc = dctzhip_fixup_apply(c, (const uint32_t *)d, (const uint16_t *)(d + dzfx_off_at((size_t)fh.tiles)),
-                             d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, n, dtype, 1, whole, zero, whole, g_dev.out);
-    if (rc == DCTZHIP_E_ARG) return -1;                /* the list contradicts itself: nothing is handed out */
+    const size_t whole[1] = {n}, zero[3] = {0, 0, 0};
+    rc = nd ? dctzhip_fixup_apply_nd(c, (const uint32_t *)d, (const uint16_t *)(d + dzfx_off_at((size_t)fh.tiles)),
+                                     d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, nd, v.dims, dtype, zero, v.dims,
+                                     g_dev.out)
+            : dctzhip_fixup_apply(c, (const uint32_t *)d, (const uint16_t *)(d + dzfx_off_at((size_t)fh.tiles)),
+                                  d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, n, dtype, 1, whole, zero, whole, g_dev.out);
+    if (rc == DCTZHIP_E_ARG) return -1;                /* the list contradicts itself or the array: nothing is handed out */
     if (rc != DCTZHIP_OK) die("dctzhip_fixup_apply");
   }
   if (mask_words) {
@@ -2088,25 +2091,34 @@ int dctz_decompress(t_var *var_z, t_var *var_r) { return decompress_whole(var_z,
 int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t_var *var_r) {
   dzc_view v;
   dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype);
-  dzfx_header fh;
-  if (v.nd != 0 || v.n == 0 || !var_r) return -1;
-  if (dzfx_check(blob, blob_bytes, v.is_d, v.n, &fh) != 0) return -1;
+  if (v.n == 0 || !var_r) return -1;
+  if (v.nd == 0) {
+    dzfx_header fh;
+    if (dzfx_check(blob, blob_bytes, v.is_d, v.n, &fh) != 0) return -1;
+  } else {
+    /* a tiled container takes a tiled blob: the blob's version decides before the container's extents are looked at */
+    dzfx_header_nd nh;
+    if (dzfx_version(blob, blob_bytes) != DZFX_VERSION_ND || dzc_geometry(&v) != 0) return -1;
+    if (dzfx_check_nd(blob, blob_bytes, v.is_d, v.nd, v.dims, v.n, v.nblk, &nh) != 0) return -1;
+  }
   return decompress_whole(var_z, var_r, (const unsigned char *)blob, NULL, 0.0);
 }
 
-/* The correction list of a flat container against the caller's unscaled original, as one malloc'd blob
+/* The correction list of a container against the caller's unscaled original, as one malloc'd blob
  * (csrc/dctz_fixup_blob.h): dctz_tile_summary's way to the device, then a count-only call that sizes the list and the call
- * that fills it. */
+ * that fills it.  The container decides: a DZND container gives the list over its stream positions (a version-2 blob), the
+ * original being the array in C order. */
 int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void **blob, size_t *blob_bytes) {
   const double t_begin = now_s();
   dzc_view v;
   dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
-  if (v.nd != 0) return -1;                                        /* tiled streams carry edge padding: out of scope */
-  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
+  const int nd = v.nd;
+  if (nd != 0 && dzc_geometry(&v) != 0) return -1;                 /* a DZND container whose extents are none */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk, n_ref = v.n;  /* stream positions (tiled: edge padding included); elements */
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   const unsigned int cnt = v.cnt;
   if (n == 0 || !blob || !blob_bytes || !var_ref || !(bound >= 0.0) || isinf(bound)) return -1;
-  if ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n || !var_bytes(var_ref)) return -1;
+  if ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n_ref || !var_bytes(var_ref)) return -1;
   const size_t m = dctzhip_fixup_tiles(n);
 
   dctzhip_ctx *c = ctx();
@@ -2141,34 +2153,41 @@ int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void
     t_h2d += now_s() - t0;
   }
   t0 = now_s();
-  grow(&g_dev.in, &g_dev.in_cap, n * ts);
-  if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n * ts) != DCTZHIP_OK) die("H2D original");
+  grow(&g_dev.in, &g_dev.in_cap, n_ref * ts);
+  if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n_ref * ts) != DCTZHIP_OK) die("H2D original");
   grow(&g_dev.fix, &g_dev.fix_cap, dzfx_off_at(m));
   t_h2d += now_s() - t0;
   t0 = now_s();
   uint32_t count = 0;
-  int rc = dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
-                               v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)g_dev.fix, NULL, NULL, 0, &count);
+  int rc = nd ? dctzhip_fixup_build_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, nd,
+                                       v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)g_dev.fix, NULL, NULL, 0, &count)
+              : dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
+                                    v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)g_dev.fix, NULL, NULL, 0, &count);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
   if (rc != DCTZHIP_OK) die("dctzhip_fixup_build");
   const size_t payload = dzfx_payload_bytes(m, count, ts);
   if (count) {
     grow(&g_dev.fix, &g_dev.fix_cap, payload);
     unsigned char *const d = (unsigned char *)g_dev.fix;
-    rc = dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
-                             v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)d, (uint16_t *)(d + dzfx_off_at(m)),
-                             d + dzfx_val_at(m, count), count, &count);
+    rc = nd ? dctzhip_fixup_build_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, nd,
+                                     v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)d, (uint16_t *)(d + dzfx_off_at(m)),
+                                     d + dzfx_val_at(m, count), count, &count)
+            : dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
+                                  v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)d, (uint16_t *)(d + dzfx_off_at(m)),
+                                  d + dzfx_val_at(m, count), count, &count);
     if (rc != DCTZHIP_OK) die("dctzhip_fixup_build");
   }
   const double t1s = now_s();
-  unsigned char *b = (unsigned char *)calloc(1, DZFX_HEADER_BYTES + payload);
+  const size_t hb = dzfx_header_bytes(nd ? DZFX_VERSION_ND : DZFX_VERSION);
+  unsigned char *b = (unsigned char *)calloc(1, hb + payload);
   if (!b) { fprintf(stderr, "Out of memory: correction list\n"); exit(1); }
-  dzfx_write_header(b, v.is_d, n, count, bound);
+  if (nd) dzfx_write_header_nd(b, v.is_d, nd, v.dims, n_ref, nblk, count, bound);
+  else dzfx_write_header(b, v.is_d, n, count, bound);
   /* the three arrays sit on the device as they sit in the blob; the padding between them is cleared afterwards */
-  if (dctzhip_memcpy_d2h(c, b + DZFX_HEADER_BYTES, g_dev.fix, payload) != DCTZHIP_OK) die("D2H correction list");
-  memset(b + DZFX_HEADER_BYTES + (m + 1) * sizeof(uint32_t), 0, dzfx_off_at(m) - (m + 1) * sizeof(uint32_t));
-  memset(b + DZFX_HEADER_BYTES + dzfx_off_at(m) + (size_t)count * sizeof(uint16_t), 0, dzfx_val_at(m, count) - dzfx_off_at(m) - (size_t)count * sizeof(uint16_t));
-  *blob = b; *blob_bytes = DZFX_HEADER_BYTES + payload;
+  if (dctzhip_memcpy_d2h(c, b + hb, g_dev.fix, payload) != DCTZHIP_OK) die("D2H correction list");
+  memset(b + hb + (m + 1) * sizeof(uint32_t), 0, dzfx_off_at(m) - (m + 1) * sizeof(uint32_t));
+  memset(b + hb + dzfx_off_at(m) + (size_t)count * sizeof(uint16_t), 0, dzfx_val_at(m, count) - dzfx_off_at(m) - (size_t)count * sizeof(uint16_t));
+  *blob = b; *blob_bytes = hb + payload;
   g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
   g_times.total_s = now_s() - t_begin;
   ret = 1;

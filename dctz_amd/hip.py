@@ -162,6 +162,11 @@ _PROTOS = {
                                       C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "dctzhip_fixup_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_int, C.c_int,
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_fixup_build_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                         C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "dctzhip_fixup_apply_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                         C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "dctzhip_mask_words": (C.c_size_t, [C.c_size_t]),
     "dctzhip_mask_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(Missing), C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_uint64)]),
@@ -745,6 +750,64 @@ class Context:
             val.data_ptr() if val is not None and count else None, int(count), n, _dt(dtype), nd, arr(*dims), arr(*lo), arr(*hi),
             dst.data_ptr())
         self._check(rc, "dctzhip_fixup_apply")
+        return dst
+
+    def fixup_build_nd(self, out, cnt, shape, dtype, eb, sf, ref, bound, index=None, mode=EC, qtable=None, capacity=None):
+        """fixup_build() for the streams of compress_nd(): the correction list against `ref` (the original, a contiguous 2-D or
+        3-D CUDA tensor of `shape`) over the 64 * nd_blocks(shape) stream positions; r is what decompress_nd() rebuilds from
+        the same arguments, the edge padding is never listed.  Return value and capacity conventions are fixup_build's."""
+        t = self.torch
+        self._bind_stream()
+        shape = [int(v) for v in shape]
+        n_lin = self.nd_blocks(shape) * 64
+        if index is None:
+            index, _ = self.ac_index(out, n_lin)
+        assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and list(ref.shape) == shape
+        start = t.empty(int(self.lib.dctzhip_fixup_tiles(n_lin)) + 1, dtype=t.int32, device=self.device)
+        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        qp = q.ctypes.data_as(C.c_void_p) if q is not None else None
+        dims = (C.c_size_t * len(shape))(*shape)
+        count = C.c_uint32(0)
+
+        def call(off, val, cap):
+            return self.lib.dctzhip_fixup_build_nd(
+                self.h, b, d, a, int(cnt), ix, qp, len(shape), dims, _dt(dtype), float(eb), float(sf), mode, ref.data_ptr(),
+                float(bound), start.data_ptr(), off.data_ptr() if off is not None else None,
+                val.data_ptr() if val is not None else None, int(cap), C.byref(count))
+
+        if capacity is None or capacity == 0:
+            self._check(call(None, None, 0), "dctzhip_fixup_build_nd")
+            if capacity == 0:
+                return start, None, None, int(count.value)
+            capacity = int(count.value)
+        off = t.empty(max(int(capacity), 1), dtype=t.int16, device=self.device)
+        val = t.empty(max(int(capacity), 1), dtype=dtype, device=self.device)
+        rc = call(off, val, capacity)
+        if rc == E_SPACE:
+            err = DctzHipError(f"dctzhip_fixup_build_nd failed ({rc}): {self.lib.dctzhip_last_error(self.h).decode()}")
+            err.count = int(count.value)
+            raise err
+        self._check(rc, "dctzhip_fixup_build_nd")
+        k = int(count.value)
+        return start, off[:k], val[:k], k
+
+    def fixup_apply_nd(self, fix, shape, dtype, dst, lo=None, hi=None):
+        """Applies the list `fix` (fixup_build_nd's result) to dst: the dense box lo <= c < hi of the array of `shape` -- what
+        decompress_box_nd() wrote, by default the whole array (what decompress_nd() wrote).  Returns dst."""
+        self._bind_stream()
+        start, off, val, count = fix
+        shape = [int(v) for v in shape]
+        lo = [0] * len(shape) if lo is None else [int(v) for v in lo]
+        hi = list(shape) if hi is None else [int(v) for v in hi]
+        nd = len(shape)
+        assert len(lo) == nd and len(hi) == nd and dst.is_cuda and dst.is_contiguous() and dst.dtype == dtype
+        assert dst.numel() == int(np.prod([max(h - l, 0) for l, h in zip(lo, hi)], dtype=np.int64))
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_fixup_apply_nd(
+            self.h, start.data_ptr(), off.data_ptr() if off is not None and count else None,
+            val.data_ptr() if val is not None and count else None, int(count), nd, arr(*shape), _dt(dtype), arr(*lo), arr(*hi),
+            dst.data_ptr())
+        self._check(rc, "dctzhip_fixup_apply_nd")
         return dst
 
     # ---- missing values (include/dctz_hip.h: a mask beside the streams, the holes filled on compress) ----

@@ -209,16 +209,22 @@ typedef struct {             /* include/dctz_hip.h: dctzhip_tile_summary_t */
 } dctz_tile_summary_t;
 int dctz_tile_summary(t_var *var_z, t_var *var_ref /* or NULL */, int N_ref, dctz_tile_summary_t *tiles /* host, or NULL */,
                       dctz_tile_summary_t *total);
-/* Point-wise error bound (ADDITION, EC and QT builds, flat containers; include/dctz_hip.h, "point-wise error bound", holds the
+/* Point-wise error bound (ADDITION, EC and QT builds, flat and DZND containers; include/dctz_hip.h, "point-wise error bound", holds the
  * definition).  dctz_fixup_build lists every element that dctz_decompress would rebuild from var_z further than `bound`
  * (absolute, in the data's units, >= 0) from the original, with the original's value, in one malloc'd self-describing block
  * that the caller keeps beside the container and frees: "DZFX", version, dtype, n, tiles, count, bound, then fix_start,
  * fix_off padded to 8 bytes, fix_val (csrc/dctz_fixup_blob.h).  var_ref->buf is the caller's UNSCALED original, N_ref elements,
  * as for dctz_tile_summary.  dctz_decompress_bounded is dctz_decompress with that list applied: every element of var_r->buf
  * then has the original's bits or lies within the bound of it.  The .z container does not change and dctz_decompress reads
- * it as before.  Both return 1, or -1 for a DZND container, a reference of another type or length, a bound that is negative
- * or not finite, a blob whose header does not fit the container (magic, version, dtype, n, sizes -- checked before anything
- * else is done), a list that contradicts itself and streams that disagree with each other. */
+ * it as before.  The container decides the kind of list, as for dctz_decompress_coarse: for a DZND container (blocks of 8 x 8
+ * / 4 x 4 x 4 tiles) var_ref->buf is the array in C order, N_ref the product of its extents, the list runs over the stream
+ * positions (the edge padding is never listed) and the blob is version 2 -- the version-1 header with ndims in its zero
+ * field, n = the product of the extents and tiles over the 64 nblk stream positions, then the three extents as 64-bit words
+ * (unused ones 0), 72 bytes in all; a flat blob stays version 1, byte for byte.  Both return 1, or -1 for a reference of
+ * another type or length, a bound that is negative or not finite, a blob whose header does not fit the container (magic,
+ * version -- a flat blob with a DZND container and a tiled blob with a flat one --, dtype, ndims, extents, n, sizes, a
+ * count above the array's elements -- checked before anything else is done), a list that contradicts itself or the array
+ * and streams that disagree with each other. */
 int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void **blob, size_t *blob_bytes);
 int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t_var *var_r);
 /* Missing values (ADDITION, EC and QT builds, flat blocks; include/dctz_hip.h, "missing values", holds the definition: the

@@ -559,8 +559,9 @@ int dctzhip_tile_summary(dctzhip_ctx *ctx, const void *d_bin_index, const float 
 /* DCTZ bounds the error of every COEFFICIENT; an element's error can reach about twice error_bound * sf.  The correction list
  * repairs that without touching the streams: it names every element whose reconstruction misses the original by more than a
  * bound and keeps the original's value for it.  Applied to the output of any decode of the same streams -- whole array,
- * range, box -- it makes that output bounded.  Flat 64-element blocks only (the streams of dctzhip_compress, fp32 and fp64,
- * EC and QT, the short last block included), as for dctzhip_tile_summary.
+ * range, box -- it makes that output bounded.  Flat 64-element blocks (the streams of dctzhip_compress, fp32 and fp64, EC
+ * and QT, the short last block included), as for dctzhip_tile_summary; the streams of dctzhip_compress_nd have the _nd pair
+ * further down.
  *   x           the ORIGINAL, n elements of dtype: what was handed to compress, not its d_scaled output.
  *   r           the elements dctzhip_decompress writes for the same arguments, bit for bit.
  *   bound       an absolute bound b >= 0 in the data's units, taken as (T)b in the data type T (round to nearest).
@@ -611,6 +612,55 @@ int dctzhip_fixup_build(dctzhip_ctx *ctx, const void *d_bin_index, const float *
 int dctzhip_fixup_apply(dctzhip_ctx *ctx, const uint32_t *d_fix_start, const uint16_t *d_fix_off, const void *d_fix_val,
                         uint32_t count, size_t n, int dtype, int ndim, const size_t *dims, const size_t *lo,
                         const size_t *hi, void *d_out);
+
+/* The correction list of an array compressed in 8 x 8 / 4 x 4 x 4 tiles: the streams of dctzhip_compress_nd, fp32 and fp64,
+ * EC and QT, 2-D and 3-D, aligned and ragged extents alike.  The flat list's contract with stream positions in place of
+ * elements:
+ *   positions   the streams cover 64 nblk positions, nblk = dctzhip_nd_blocks(ndims, dims).  Position q belongs to block
+ *               B = q >> 6, numbered row-major over the tile grid; its in-block place is j = q & 63, row-major inside the
+ *               tile: j = 8 r + c in 2-D, j = 16 z + 4 y + x in 3-D.  Its coordinate along axis a is e B_a + j_a with e = 8 in
+ *               2-D and 4 in 3-D.  A position is REAL iff every coordinate is below dims[a]; the others are the edge padding.
+ *   x           the ORIGINAL array, not d_scaled.
+ *   r           what dctzhip_decompress_nd writes at the same coordinates, bit for bit.
+ *   bound       b >= 0, taken as (T)b.
+ *   listed      a real position is listed iff !(fabs(x - r) <= (T)b), the difference taken in T.  A padded position is never
+ *               listed, and the original is never read there.  A NaN on either side lists the position: a NaN in the original
+ *               lists every real position of its tile and stays a NaN.
+ *   layout      with m = dctzhip_fixup_tiles(64 nblk) stream tiles of 4096 positions (the tiles of the exception index and of
+ *               dctzhip_decompress_box_nd's hit test):
+ *                 fix_start[0 .. m]   uint32; fix_start[m] == count
+ *                 fix_off[count]      uint16: q & 4095, strictly ascending inside a tile
+ *                 fix_val[count]      T: x itself, bit for bit
+ *               The bytes depend on the streams, the original and b alone, never on the grid.
+ *   guarantee   after apply every element of the output has the original's bits or lies within (T)b of it.
+ *
+ * dctzhip_fixup_build_nd: d_ref is the original in its own C-order layout, prod dims elements, 16-byte aligned; it is read in
+ * place, for ragged extents too.  The count-only form (d_fix_off and d_fix_val NULL), DCTZHIP_E_SPACE, "count always
+ * reported" and the host-synchronous return are dctzhip_fixup_build's, and so are its refusals, with the shape rules of
+ * dctzhip_decompress_nd in place of the rules for n and the span and overlap checks made over the sizes above.  The in-kernel
+ * index check is the box decoder's: a tile whose flags disagree with the index reads no AC_exact, and the call returns
+ * DCTZHIP_E_ARG.  dctzhip_debug_last_kernel(ctx, 1, ...) names the mark kernel afterwards.
+ *
+ * dctzhip_fixup_apply_nd: d_out is the dense C-order box lo <= c < hi of the array -- exactly what dctzhip_decompress_box_nd
+ * wrote, or dctzhip_decompress_nd for lo = 0, hi = dims.  Only the candidate stream tiles are visited, from the first to the
+ * last block that meets the box; an entry whose coordinates lie outside the box is passed over.
+ *   refusals    before any launch, DCTZHIP_E_ARG: the shape and box rules of dctzhip_decompress_box_nd; d_fix_start or d_out
+ *               NULL or misaligned (4 bytes / element size); count > prod dims; with count > 0 a NULL or misaligned d_fix_off
+ *               / d_fix_val; d_out overlapping the list.  On the device the list is untrusted input: a visited tile is refused,
+ *               by plain comparisons made before any store of that tile, for dctzhip_fixup_apply's reasons (table not
+ *               monotone, more entries than count, more entries than the tile holds, offsets not strictly ascending), for an
+ *               entry in a block >= nblk and for an entry at a padded position; every call is refused for fix_start[m] !=
+ *               count.  The call then returns DCTZHIP_E_ARG, d_out is undefined inside its box, nothing outside it is ever
+ *               written, and the context stays usable.
+ * Host-synchronous; dctzhip_debug_last_kernel(ctx, 1, ...) names the apply kernel afterwards. */
+int dctzhip_fixup_build_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                           uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                           const size_t *dims, int dtype, double error_bound, double sf, int mode, const void *d_ref,
+                           double bound, uint32_t *d_fix_start, uint16_t *d_fix_off /* or NULL */,
+                           void *d_fix_val /* or NULL */, uint32_t capacity, uint32_t *count /* host */);
+int dctzhip_fixup_apply_nd(dctzhip_ctx *ctx, const uint32_t *d_fix_start, const uint16_t *d_fix_off,
+                           const void *d_fix_val, uint32_t count, int ndims, const size_t *dims, int dtype,
+                           const size_t *lo, const size_t *hi, void *d_out);
 
 /* ---- missing values: a mask beside the streams, the holes filled on compress ------------ */
 /* Fields with missing values (1e36 over land, NaN) ruin the codec as they are: sf is taken over every element, a NaN costs
