@@ -49,6 +49,13 @@ static inline size_t dzfx_pad8(size_t v) { return (v + 7) & ~(size_t)7; }
 static inline size_t dzfx_off_at(size_t tiles) { return dzfx_pad8((tiles + 1) * sizeof(uint32_t)); }
 static inline size_t dzfx_val_at(size_t tiles, size_t count) { return dzfx_off_at(tiles) + dzfx_pad8(count * sizeof(uint16_t)); }
 static inline size_t dzfx_payload_bytes(size_t tiles, size_t count, size_t ts) { return dzfx_val_at(tiles, count) + count * ts; }
+/* the three arrays of a payload that starts at p, in host or device memory alike */
+typedef struct { uint32_t *start; uint16_t *off; void *val; } dzfx_arrays;
+static inline dzfx_arrays dzfx_arrays_at(void *p, size_t tiles, size_t count) {
+  unsigned char *const d = (unsigned char *)p;
+  const dzfx_arrays a = {(uint32_t *)d, (uint16_t *)(d + dzfx_off_at(tiles)), d + dzfx_val_at(tiles, count)};
+  return a;
+}
 
 static inline void dzfx_write_header(void *blob, int is_d, size_t n, size_t count, double bound) {
   dzfx_header h;

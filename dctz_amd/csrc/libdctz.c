@@ -1594,6 +1594,14 @@ static int decompress_pipelined(dctzhip_ctx *c, const dzc_view *v, size_t chunk,
   return ok;
 }
 
+/* dctzhip_fixup_apply or dctzhip_fixup_apply_nd, as the container says: the list `a` over the whole array in g_dev.out */
+static int fixup_apply_dev(dctzhip_ctx *c, const dzc_view *v, dzfx_arrays a, uint32_t count) {
+  const int dtype = v->is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const size_t whole[1] = {v->n}, zero[3] = {0, 0, 0};
+  return v->nd ? dctzhip_fixup_apply_nd(c, a.start, a.off, a.val, count, v->nd, v->dims, dtype, zero, v->dims, g_dev.out)
+               : dctzhip_fixup_apply(c, a.start, a.off, a.val, count, v->n, dtype, 1, whole, zero, whole, g_dev.out);
+}
+
 /* fix (or NULL): a checked correction-list blob of this container (dctz_decompress_bounded), applied to the reconstruction on
  * the device before it is copied back; -1 if the list contradicts itself. */
 /* fix (or NULL): a checked correction-list blob, applied to the reconstruction; mask_words (or NULL): the words of a
@@ -1701,13 +1709,7 @@ static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix
     const size_t payload = dzfx_payload_bytes((size_t)fh.tiles, (size_t)fh.count, ts);
     grow(&g_dev.fix, &g_dev.fix_cap, payload);
     if (dctzhip_memcpy_h2d(c, g_dev.fix, fix + dzfx_header_bytes(fh.version), payload) != DCTZHIP_OK) die("H2D correction list");
-    const unsigned char *const d = (const unsigned char *)g_dev.fix;
-    const size_t whole[1] = {n}, zero[3] = {0, 0, 0};
-    rc = nd ? dctzhip_fixup_apply_nd(c, (const uint32_t *)d, (const uint16_t *)(d + dzfx_off_at((size_t)fh.tiles)),
-                                     d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, nd, v.dims, dtype, zero, v.dims,
-                                     g_dev.out)
-            : dctzhip_fixup_apply(c, (const uint32_t *)d, (const uint16_t *)(d + dzfx_off_at((size_t)fh.tiles)),
-                                  d + dzfx_val_at((size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count, n, dtype, 1, whole, zero, whole, g_dev.out);
+    rc = fixup_apply_dev(c, &v, dzfx_arrays_at(g_dev.fix, (size_t)fh.tiles, (size_t)fh.count), (uint32_t)fh.count);
     if (rc == DCTZHIP_E_ARG) return -1;                /* the list contradicts itself or the array: nothing is handed out */
     if (rc != DCTZHIP_OK) die("dctzhip_fixup_apply");
   }
@@ -1771,6 +1773,70 @@ static size_t inflate_prefix(const unsigned char *sec, unsigned int zlen, size_t
   return done;
 }
 
+/* The way from a container's sections to the device, for every reader that does not decode the whole array: the first
+ * bin_bytes of bin_index and the first dc_bytes of DC inflated and uploaded (DC into room for dc_room >= dc_bytes bytes), the
+ * exception index built over those bin ids, and as many AC_exact words as it counts -- idx[t] of a prefix's index is idx[t]
+ * of the whole array's.  dc_only: the DC section alone; bin, ac and idx stay NULL and ac_count 0.  Returns 1, or -1 for a
+ * section that does not hold its prefix or bin ids that flag more than the header counts, with nothing left to free.  It is
+ * the first thing in a reader that asks for the device: every refusal of the arguments comes before it. */
+typedef struct {
+  dctzhip_ctx *c;
+  const void *bin;
+  const float *dc, *ac;
+  const uint32_t *idx;
+  uint32_t ac_count;
+  const void *qtable;                                        /* NULL, or qbuf */
+  double qbuf[BLK_SZ];
+  double t_zlib, t_h2d;                                      /* seconds inflating; seconds copying and indexing */
+} dev_streams;
+#define DEV_STREAMS(s) (s).c, (s).bin, (s).dc, (s).ac, (s).ac_count, (s).idx, (s).qtable   /* as every dctzhip_ reader takes them */
+static int sections_to_device(const dzc_view *v, size_t bin_bytes, size_t dc_bytes, size_t dc_room, int dc_only, dev_streams *s) {
+  memset(s, 0, sizeof(*s));
+  dctzhip_ctx *c = s->c = ctx();
+  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
+  size_t chunk = 0;
+  const int indexed = dzc_read_index(v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
+  s->qtable = dzc_qtable(v, s->qbuf);                        /* :193-199 */
+  void **const dp[3] = {&g_dev.bin, &g_dev.dc, &g_dev.ac};
+  size_t *const cp[3] = {&g_dev.bin_cap, &g_dev.dc_cap, &g_dev.ac_cap};
+  size_t want[3] = {bin_bytes, dc_bytes, 0};                 /* AC_exact: known once the index is built */
+  int ret = -1;
+  double t0;
+  for (int i = 0; i < 3; i++) {
+    if (dc_only && i != 1) continue;
+    if (i == 2) {
+      t0 = now_s();
+      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(bin_bytes) * sizeof(uint32_t));
+      if (dctzhip_ac_index(c, g_dev.bin, bin_bytes, (uint32_t *)g_dev.idx, &s->ac_count) != DCTZHIP_OK) die("dctzhip_ac_index");
+      if (s->ac_count > v->cnt) goto out;                    /* the bin ids flag more than the header counts */
+      want[2] = (size_t)s->ac_count * sizeof(float);
+      s->t_h2d += now_s() - t0;
+    }
+    t0 = now_s();
+    const size_t room = indexed ? MIN(v->raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
+    unsigned char *hp = (unsigned char *)host_buf(i, room);
+    if (inflate_prefix(v->sec[i], v->zlen[i], v->raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
+    s->t_zlib += now_s() - t0;
+    t0 = now_s();
+    const size_t dev = i == 1 ? dc_room : want[i];
+    grow(dp[i], cp[i], dev ? dev : 4);
+    if (want[i] && dctzhip_memcpy_h2d(c, *dp[i], hp, want[i]) != DCTZHIP_OK) die("H2D section");
+    s->t_h2d += now_s() - t0;
+  }
+  s->dc = (const float *)g_dev.dc;
+  if (!dc_only) { s->bin = g_dev.bin; s->ac = (const float *)g_dev.ac; s->idx = (const uint32_t *)g_dev.idx; }
+  ret = 1;
+out:
+  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
+  return ret;
+}
+/* The stage times of such a reader: the loader's (with what the reader added of its own), the device calls from t_gpu to
+ * t_d2h, the copy back from there to now. */
+static void part_times(const dev_streams *s, double t_begin, double t_gpu, double t_d2h) {
+  g_times.zlib_s = s->t_zlib; g_times.h2d_s = s->t_h2d; g_times.gpu_s = t_d2h - t_gpu; g_times.d2h_s = now_s() - t_d2h;
+  g_times.total_s = now_s() - t_begin;
+}
+
 /* dctz_decompress_range (ndim == 0: elements [lo, hi)), dctz_decompress_box (ndim >= 1: the box; [lo, hi) becomes
  * [first box element, last box element + 1)) and dctz_decompress_box_nd (ndim == PART_TILED: a DZND container, geometry and
  * extents from the container; [lo, hi) becomes the stream positions [64 * first intersecting block, 64 * (last + 1))): the
@@ -1804,7 +1870,6 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   if (!tiled && v.nd != 0) return -1;                              /* DZND: element order is not block order */
   const size_t ts = v.ts, n = v.npos, nblk = v.nblk;               /* n: positions of the streams (flat: the elements) */
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const unsigned int cnt = v.cnt;
   size_t out_elems;
   dctzhip_box_item *items = NULL;
   if (tiled) {
@@ -1847,58 +1912,19 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   if (n == 0 || lo >= hi || hi > n) { free(items); return -1; }
   const size_t S = DCTZHIP_INDEX_STRIDE;
   const size_t t1 = (hi + S - 1) / S;                        /* the range's tiles end here */
-  const size_t need[3] = {MIN(n, S * t1),                    /* bin ids: the flags in front give AC_exact's position */
-                          (hi + BLK_SZ - 1) / BLK_SZ * sizeof(float),   /* DC up to the range's last block */
-                          0};                                /* AC_exact up to idx[t1]: known once the index is built */
   const size_t dc_dev = MIN(nblk, t1 * (S / BLK_SZ));        /* DC words the range's tiles cover on the device */
-
-  dctzhip_ctx *c = ctx();
-  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
-  size_t chunk = 0;
-  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
-  double qbuf[BLK_SZ];
-  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
+  dev_streams s;
+  /* bin ids up to the end of the range's tiles (the flags in front give AC_exact's position), DC up to the range's last block */
+  if (sections_to_device(&v, MIN(n, S * t1), (hi + BLK_SZ - 1) / BLK_SZ * sizeof(float), dc_dev * sizeof(float), 0, &s) != 1) { free(items); return -1; }
+  dctzhip_ctx *c = s.c;
   int ret = -1;
-  unsigned char *hp[3];
-  size_t want[3] = {need[0], need[1], need[2]};
-  uint32_t ac_need = 0;
-  double t_zlib = 0.0, t_h2d = 0.0, t0;
-  for (int i = 0; i < 3; i++) {
-    if (i == 2) {                                            /* idx[t1] of the prefix's index = idx[t1] of the whole array's */
-      t0 = now_s();
-      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(need[0]) * sizeof(uint32_t));
-      if (dctzhip_ac_index(c, g_dev.bin, need[0], (uint32_t *)g_dev.idx, &ac_need) != DCTZHIP_OK) die("dctzhip_ac_index");
-      if (ac_need > cnt) goto out;                           /* the bin ids flag more than the header counts */
-      want[2] = (size_t)ac_need * sizeof(float);
-      t_h2d += now_s() - t0;
-    }
-    t0 = now_s();
-    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
-    hp[i] = (unsigned char *)host_buf(i, room);
-    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp[i], chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
-    t_zlib += now_s() - t0;
-    t0 = now_s();
-    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
-    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
-    grow(dp, cp, i == 1 ? dc_dev * sizeof(float) : (want[i] ? want[i] : 4));
-    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp[i], want[i]) != DCTZHIP_OK) die("H2D section prefix");
-    t_h2d += now_s() - t0;
-  }
-  t0 = now_s();
+  const double t0 = now_s();
   grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
   if (list) for (int j = 0; j < list->k; j++) items[j].d_out = (unsigned char *)g_dev.out + (uintptr_t)items[j].d_out;
-  const int rc = list      ? dctzhip_decompress_boxes(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
-                                                      (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims,
-                                                      list->k, items)
-                 : tiled   ? dctzhip_decompress_box_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
-                                                       (const uint32_t *)g_dev.idx, qtable, v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE,
-                                                       blo, bhi, g_dev.out)
-                 : ndim == 0 ? dctzhip_decompress_range(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
-                                                      (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi,
-                                                      g_dev.out)
-                           : dctzhip_decompress_box(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_need,
-                                                    (const uint32_t *)g_dev.idx, qtable, n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims,
-                                                    blo, bhi, g_dev.out);
+  const int rc = list      ? dctzhip_decompress_boxes(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims, list->k, items)
+                 : tiled   ? dctzhip_decompress_box_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, blo, bhi, g_dev.out)
+                 : ndim == 0 ? dctzhip_decompress_range(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi, g_dev.out)
+                           : dctzhip_decompress_box(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims, blo, bhi, g_dev.out);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
   if (rc != DCTZHIP_OK)
     die(list ? "dctzhip_decompress_boxes" : tiled ? "dctzhip_decompress_box_nd" : ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
@@ -1910,11 +1936,9 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
       if (dctzhip_memcpy_d2h(c, var_bytes(list->var_r[j]), items[j].d_out, elems * ts) != DCTZHIP_OK) die("D2H output");
     }
   } else if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
-  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
-  g_times.total_s = now_s() - t_begin;
+  part_times(&s, t_begin, t0, t1s);
   ret = 1;
 out:
-  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
   free(items);
   return ret;
 }
@@ -1949,7 +1973,6 @@ int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r) {
   if (tiled && dzc_geometry(&v) != 0) return -1;                   /* extents that are no shape */
   const size_t ts = v.ts, n = v.npos, nblk = v.nblk;               /* n: positions of the streams (flat: the elements) */
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const unsigned int cnt = v.cnt;
   const int edge = !tiled ? BLK_SZ : v.nd == 2 ? 8 : 4;
   if (n == 0 || !var_r || factor < 2 || factor > edge || (factor & (factor - 1))) return -1;
   size_t out_elems = 1;
@@ -1957,57 +1980,18 @@ int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r) {
   else out_elems = dctzhip_coarse_len(n, factor);
   const int dc_only = factor == edge && (tiled || n % BLK_SZ == 0);
 
-  dctzhip_ctx *c = ctx();
-  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
-  size_t chunk = 0;
-  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
-  double qbuf[BLK_SZ];
-  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
-  int ret = -1;
-  size_t want[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
-  uint32_t ac_total = 0;
-  double t_zlib = 0.0, t_h2d = 0.0, t0;
-  for (int i = 0; i < 3; i++) {
-    if (dc_only && i != 1) continue;
-    if (i == 2) {                                            /* the index of the whole array, once */
-      t0 = now_s();
-      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(n) * sizeof(uint32_t));
-      if (dctzhip_ac_index(c, g_dev.bin, n, (uint32_t *)g_dev.idx, &ac_total) != DCTZHIP_OK) die("dctzhip_ac_index");
-      if (ac_total > cnt) goto out;                          /* the bin ids flag more than the header counts */
-      want[2] = (size_t)ac_total * sizeof(float);
-      t_h2d += now_s() - t0;
-    }
-    t0 = now_s();
-    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
-    unsigned char *hp = (unsigned char *)host_buf(i, room);
-    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
-    t_zlib += now_s() - t0;
-    t0 = now_s();
-    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
-    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
-    grow(dp, cp, want[i] ? want[i] : 4);
-    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp, want[i]) != DCTZHIP_OK) die("H2D section");
-    t_h2d += now_s() - t0;
-  }
-  t0 = now_s();
+  dev_streams s;
+  if (sections_to_device(&v, n, nblk * sizeof(float), nblk * sizeof(float), dc_only, &s) != 1) return -1;
+  const double t0 = now_s();
   grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
-  const void *bin = dc_only ? NULL : g_dev.bin;
-  const float *ac = dc_only ? NULL : (const float *)g_dev.ac;
-  const uint32_t *idx = dc_only ? NULL : (const uint32_t *)g_dev.idx;
-  const int rc = tiled ? dctzhip_decompress_coarse_nd(c, bin, (const float *)g_dev.dc, ac, ac_total, idx, qtable, v.nd, v.dims, dtype,
-                                                      v.h.error_bound, v.sf, DCTZ_MODE, factor, g_dev.out)
-                       : dctzhip_decompress_coarse(c, bin, (const float *)g_dev.dc, ac, ac_total, idx, qtable, n, dtype, v.h.error_bound, v.sf,
-                                                   DCTZ_MODE, factor, g_dev.out);
-  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  const int rc = tiled ? dctzhip_decompress_coarse_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, factor, g_dev.out)
+                       : dctzhip_decompress_coarse(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, factor, g_dev.out);
+  if (rc == DCTZHIP_E_ARG) return -1;                        /* the streams disagree with each other */
   if (rc != DCTZHIP_OK) die(tiled ? "dctzhip_decompress_coarse_nd" : "dctzhip_decompress_coarse");
   const double t1s = now_s();
-  if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
-  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
-  g_times.total_s = now_s() - t_begin;
-  ret = 1;
-out:
-  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
-  return ret;
+  if (dctzhip_memcpy_d2h(s.c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
+  part_times(&s, t_begin, t0, t1s);
+  return 1;
 }
 
 /* ------------------------------------------------------------------ dctz_tile_summary -- */
@@ -2022,65 +2006,31 @@ int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary
   if (v.nd != 0) return -1;                                        /* tiled streams carry edge padding: out of scope */
   const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const unsigned int cnt = v.cnt;
   if (n == 0 || (!tiles && !total)) return -1;
   if (var_ref && ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n || !var_bytes(var_ref))) return -1;
   const size_t m = dctzhip_summary_tiles(n);
 
-  dctzhip_ctx *c = ctx();
-  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
-  size_t chunk = 0;
-  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
-  double qbuf[BLK_SZ];
-  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
-  int ret = -1;
-  size_t want[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
-  uint32_t ac_total = 0;
-  double t_zlib = 0.0, t_h2d = 0.0, t0;
-  for (int i = 0; i < 3; i++) {
-    if (i == 2) {                                            /* the index of the whole array, once */
-      t0 = now_s();
-      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(n) * sizeof(uint32_t));
-      if (dctzhip_ac_index(c, g_dev.bin, n, (uint32_t *)g_dev.idx, &ac_total) != DCTZHIP_OK) die("dctzhip_ac_index");
-      if (ac_total > cnt) goto out;                          /* the bin ids flag more than the header counts */
-      want[2] = (size_t)ac_total * sizeof(float);
-      t_h2d += now_s() - t0;
-    }
-    t0 = now_s();
-    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
-    unsigned char *hp = (unsigned char *)host_buf(i, room);
-    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
-    t_zlib += now_s() - t0;
-    t0 = now_s();
-    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
-    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
-    grow(dp, cp, want[i] ? want[i] : 4);
-    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp, want[i]) != DCTZHIP_OK) die("H2D section");
-    t_h2d += now_s() - t0;
-  }
-  t0 = now_s();
+  dev_streams s;
+  if (sections_to_device(&v, n, nblk * sizeof(float), nblk * sizeof(float), 0, &s) != 1) return -1;
+  dctzhip_ctx *c = s.c;
+  double t0 = now_s();
   if (var_ref) {
     grow(&g_dev.in, &g_dev.in_cap, n * ts);
     if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n * ts) != DCTZHIP_OK) die("H2D original");
   }
   if (tiles) grow(&g_dev.out, &g_dev.out_cap, m * sizeof(dctzhip_tile_summary_t));
-  t_h2d += now_s() - t0;
+  s.t_h2d += now_s() - t0;
   t0 = now_s();
   dctzhip_tile_summary_t tot;
-  const int rc = dctzhip_tile_summary(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable,
-                                      n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, var_ref ? g_dev.in : NULL,
+  const int rc = dctzhip_tile_summary(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, var_ref ? g_dev.in : NULL,
                                       tiles ? (dctzhip_tile_summary_t *)g_dev.out : NULL, total ? &tot : NULL);
-  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  if (rc == DCTZHIP_E_ARG) return -1;                        /* the streams disagree with each other */
   if (rc != DCTZHIP_OK) die("dctzhip_tile_summary");
   const double t1s = now_s();
   if (tiles && dctzhip_memcpy_d2h(c, tiles, g_dev.out, m * sizeof(dctzhip_tile_summary_t)) != DCTZHIP_OK) die("D2H records");
   if (total) memcpy(total, &tot, sizeof(tot));
-  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
-  g_times.total_s = now_s() - t_begin;
-  ret = 1;
-out:
-  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
-  return ret;
+  part_times(&s, t_begin, t0, t1s);
+  return 1;
 }
 
 /* ------------------------------------------ dctz_fixup_build, dctz_decompress_bounded -- */
@@ -2104,8 +2054,18 @@ int dctz_decompress_bounded(t_var *var_z, const void *blob, size_t blob_bytes, t
   return decompress_whole(var_z, var_r, (const unsigned char *)blob, NULL, 0.0);
 }
 
+/* dctzhip_fixup_build or dctzhip_fixup_build_nd, as the container says: the list of the streams `s` against the original in
+ * g_dev.in, into `a` with room for `capacity` entries (a.off and a.val NULL: the tile starts and the count alone) */
+static int fixup_build_dev(const dzc_view *v, const dev_streams *s, double bound, dzfx_arrays a, uint32_t capacity, uint32_t *count) {
+  const int dtype = v->is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  return v->nd ? dctzhip_fixup_build_nd(DEV_STREAMS(*s), v->nd, v->dims, dtype, v->h.error_bound, v->sf, DCTZ_MODE, g_dev.in, bound, a.start, a.off,
+                                        a.val, capacity, count)
+               : dctzhip_fixup_build(DEV_STREAMS(*s), v->npos, dtype, v->h.error_bound, v->sf, DCTZ_MODE, g_dev.in, bound, a.start, a.off, a.val,
+                                     capacity, count);
+}
+
 /* The correction list of a container against the caller's unscaled original, as one malloc'd blob
- * (csrc/dctz_fixup_blob.h): dctz_tile_summary's way to the device, then a count-only call that sizes the list and the call
+ * (csrc/dctz_fixup_blob.h): the whole streams to the device (sections_to_device), then a count-only call that sizes the list and the call
  * that fills it.  The container decides: a DZND container gives the list over its stream positions (a version-2 blob), the
  * original being the array in C order. */
 int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void **blob, size_t *blob_bytes) {
@@ -2115,66 +2075,28 @@ int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void
   const int nd = v.nd;
   if (nd != 0 && dzc_geometry(&v) != 0) return -1;                 /* a DZND container whose extents are none */
   const size_t ts = v.ts, n = v.npos, nblk = v.nblk, n_ref = v.n;  /* stream positions (tiled: edge padding included); elements */
-  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
-  const unsigned int cnt = v.cnt;
   if (n == 0 || !blob || !blob_bytes || !var_ref || !(bound >= 0.0) || isinf(bound)) return -1;
   if ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n_ref || !var_bytes(var_ref)) return -1;
   const size_t m = dctzhip_fixup_tiles(n);
 
-  dctzhip_ctx *c = ctx();
-  uint32_t *ix_sizes[3] = {NULL, NULL, NULL};
-  size_t chunk = 0;
-  const int indexed = dzc_read_index(&v, DZC_UNKNOWN, &chunk, ix_sizes) == DZC_IX_OK;
-  double qbuf[BLK_SZ];
-  const void *qtable = dzc_qtable(&v, qbuf);                 /* :193-199 */
-  int ret = -1;
-  size_t want[3] = {n, nblk * sizeof(float), (size_t)cnt * sizeof(float)};
-  uint32_t ac_total = 0;
-  double t_zlib = 0.0, t_h2d = 0.0, t0;
-  for (int i = 0; i < 3; i++) {
-    if (i == 2) {                                            /* the index of the whole array, once */
-      t0 = now_s();
-      grow(&g_dev.idx, &g_dev.idx_cap, dctzhip_ac_index_len(n) * sizeof(uint32_t));
-      if (dctzhip_ac_index(c, g_dev.bin, n, (uint32_t *)g_dev.idx, &ac_total) != DCTZHIP_OK) die("dctzhip_ac_index");
-      if (ac_total > cnt) goto out;                          /* the bin ids flag more than the header counts */
-      want[2] = (size_t)ac_total * sizeof(float);
-      t_h2d += now_s() - t0;
-    }
-    t0 = now_s();
-    const size_t room = indexed ? MIN(v.raw[i], (want[i] + chunk - 1) / chunk * chunk) : want[i];
-    unsigned char *hp = (unsigned char *)host_buf(i, room);
-    if (inflate_prefix(v.sec[i], v.zlen[i], v.raw[i], want[i], hp, chunk, indexed ? ix_sizes[i] : NULL) < want[i]) goto out;
-    t_zlib += now_s() - t0;
-    t0 = now_s();
-    void **dp = i == 0 ? &g_dev.bin : i == 1 ? &g_dev.dc : &g_dev.ac;
-    size_t *cp = i == 0 ? &g_dev.bin_cap : i == 1 ? &g_dev.dc_cap : &g_dev.ac_cap;
-    grow(dp, cp, want[i] ? want[i] : 4);
-    if (want[i] && dctzhip_memcpy_h2d(c, *dp, hp, want[i]) != DCTZHIP_OK) die("H2D section");
-    t_h2d += now_s() - t0;
-  }
-  t0 = now_s();
+  dev_streams s;
+  if (sections_to_device(&v, n, nblk * sizeof(float), nblk * sizeof(float), 0, &s) != 1) return -1;
+  dctzhip_ctx *c = s.c;
+  double t0 = now_s();
   grow(&g_dev.in, &g_dev.in_cap, n_ref * ts);
   if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n_ref * ts) != DCTZHIP_OK) die("H2D original");
   grow(&g_dev.fix, &g_dev.fix_cap, dzfx_off_at(m));
-  t_h2d += now_s() - t0;
+  s.t_h2d += now_s() - t0;
   t0 = now_s();
   uint32_t count = 0;
-  int rc = nd ? dctzhip_fixup_build_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, nd,
-                                       v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)g_dev.fix, NULL, NULL, 0, &count)
-              : dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
-                                    v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)g_dev.fix, NULL, NULL, 0, &count);
-  if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
+  const dzfx_arrays starts = {(uint32_t *)g_dev.fix, NULL, NULL};
+  int rc = fixup_build_dev(&v, &s, bound, starts, 0, &count);
+  if (rc == DCTZHIP_E_ARG) return -1;                        /* the streams disagree with each other */
   if (rc != DCTZHIP_OK) die("dctzhip_fixup_build");
   const size_t payload = dzfx_payload_bytes(m, count, ts);
   if (count) {
     grow(&g_dev.fix, &g_dev.fix_cap, payload);
-    unsigned char *const d = (unsigned char *)g_dev.fix;
-    rc = nd ? dctzhip_fixup_build_nd(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, nd,
-                                     v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)d, (uint16_t *)(d + dzfx_off_at(m)),
-                                     d + dzfx_val_at(m, count), count, &count)
-            : dctzhip_fixup_build(c, g_dev.bin, (const float *)g_dev.dc, (const float *)g_dev.ac, ac_total, (const uint32_t *)g_dev.idx, qtable, n, dtype,
-                                  v.h.error_bound, v.sf, DCTZ_MODE, g_dev.in, bound, (uint32_t *)d, (uint16_t *)(d + dzfx_off_at(m)),
-                                  d + dzfx_val_at(m, count), count, &count);
+    rc = fixup_build_dev(&v, &s, bound, dzfx_arrays_at(g_dev.fix, m, count), count, &count);
     if (rc != DCTZHIP_OK) die("dctzhip_fixup_build");
   }
   const double t1s = now_s();
@@ -2188,12 +2110,8 @@ int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void
   memset(b + hb + (m + 1) * sizeof(uint32_t), 0, dzfx_off_at(m) - (m + 1) * sizeof(uint32_t));
   memset(b + hb + dzfx_off_at(m) + (size_t)count * sizeof(uint16_t), 0, dzfx_val_at(m, count) - dzfx_off_at(m) - (size_t)count * sizeof(uint16_t));
   *blob = b; *blob_bytes = hb + payload;
-  g_times.zlib_s = t_zlib; g_times.h2d_s = t_h2d; g_times.gpu_s = t1s - t0; g_times.d2h_s = now_s() - t1s;
-  g_times.total_s = now_s() - t_begin;
-  ret = 1;
-out:
-  for (int i = 0; i < 3; i++) free(ix_sizes[i]);
-  return ret;
+  part_times(&s, t_begin, t0, t1s);
+  return 1;
 }
 
 /* ------------------------------------------ dctz_compress_masked, dctz_decompress_masked -- */

@@ -1,7 +1,7 @@
-"""Containers and checks of the drop-in tests for lists of boxes (tests/test_gpu_boxes_dropin.py): t_var, the two builds of
-the library, a container with the zlib tail or the DZIX chunk index, one dctz_decompress_box call, the sections of a
-container.  The definitions are those of tests/test_gpu_box_dropin.py; they live here so that the list tests do not depend
-on another test file."""
+"""Containers and checks shared by the drop-in tests (tests/test_gpu_*_dropin.py): t_var, the two builds of the library, a
+container with the zlib tail or the DZIX chunk index, flat or in tiles, one dctz_decompress_box call, the sections of a
+container.  They live here so that no test file depends on another test file; each test file sets the argtypes of the
+calls it tests on top of _lib."""
 import ctypes as C
 import os
 import struct
@@ -48,8 +48,8 @@ def _tvar(arr):
     return v
 
 
-def _container(lib, x, eb, gpu_tail):
-    """(container bytes as a uint8 array, the full dctz_decompress result)."""
+def _container(lib, x, eb, gpu_tail, shape=None):
+    """(container bytes as a uint8 array, the full dctz_decompress result); shape: a DZND container in tiles of that shape."""
     if gpu_tail:
         os.environ["DCTZ_ZLIB_GPU"] = "1"
     try:
@@ -57,9 +57,13 @@ def _container(lib, x, eb, gpu_tail):
         z = np.zeros(x.size * x.itemsize + (1 << 16), np.uint8)
         zv = _tvar(z.view(x.dtype)[: z.size // x.itemsize])
         sz = C.c_size_t(0)
+        if shape is not None:
+            assert lib.dctz_set_block_dims(len(shape), (C.c_size_t * len(shape))(*shape)) == 0
         assert lib.dctz_compress(C.byref(_tvar(xin)), x.size, C.byref(sz), C.byref(zv), eb) == 1
     finally:
         os.environ.pop("DCTZ_ZLIB_GPU", None)
+    if shape is not None:
+        assert (struct.unpack_from("<I", z, 0)[0] >> 8) & 0xFF == len(shape)      # a DZND container
     full = np.empty_like(x)
     assert lib.dctz_decompress(C.byref(zv), C.byref(_tvar(full))) == 1
     return z, full
@@ -83,10 +87,11 @@ def _sl(full, dims, lo, hi):
     return full.reshape(dims)[tuple(slice(l, h) for l, h in zip(lo, hi))]
 
 
-
 def _sections(z, dtype, qt):
     dt, n, eb, cnt = struct.unpack_from("<IIdI", z, 0)
     sizes = struct.unpack_from("<III", z, 40)
     offs = [56, 56 + sizes[0], 56 + sizes[0] + sizes[1]]
     end = offs[2] + sizes[2] + (64 * np.dtype(dtype).itemsize if qt else 0)
+    if (dt >> 8) & 0xFF:
+        end += 16                                        # "DZND" and its three extents
     return n, cnt, sizes, offs, end

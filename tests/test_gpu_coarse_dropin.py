@@ -3,65 +3,31 @@ container with the reference's zlib tail and from one with the DZIX chunk index 
 byte, what the C-ABI call (dctzhip_decompress_coarse / dctzhip_decompress_coarse_nd) gives for the container's inflated
 streams.  A bad factor returns -1, and a good call follows."""
 import ctypes as C
-import os
 import struct
 import zlib
 
 import numpy as np
 import pytest
 
+from tests import dropin_cases as D
 from tests import workloads as W
+from tests.dropin_cases import TVar, _tvar
 from dctz_amd import hip as H
 
 pytestmark = pytest.mark.gpu
-LIBDIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dctz_amd", "lib")
 EB = 1e-3
 
 
-class TVarBuf(C.Union):
-    _fields_ = [("f", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_double))]
-
-
-class TVar(C.Structure):   # dctz.h:49-59
-    _fields_ = [("datatype", C.c_int), ("err_bound", C.c_double), ("var_name", C.c_char_p), ("buf", TVarBuf)]
-
-
 def _lib(mode):
-    os.environ["DCTZ_QUIET"] = "1"
-    lib = C.CDLL(os.path.join(LIBDIR, f"libdctz-{mode}.so"))
-    lib.dctz_compress.restype = C.c_int
-    lib.dctz_compress.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(TVar), C.c_double]
+    lib = D._lib(mode)
     lib.dctz_decompress_coarse.restype = C.c_int
     lib.dctz_decompress_coarse.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(TVar)]
-    lib.dctz_set_block_dims.restype = C.c_int
-    lib.dctz_set_block_dims.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
     return lib
-
-
-def _tvar(arr):
-    v = TVar()
-    v.datatype = 1 if arr.dtype == np.float64 else 0
-    if arr.dtype == np.float64:
-        v.buf.d = arr.ctypes.data_as(C.POINTER(C.c_double))
-    else:
-        v.buf.f = arr.ctypes.data_as(C.POINTER(C.c_float))
-    return v
 
 
 def _container(lib, x, shape, gpu_tail):
     """Container bytes as a uint8 array; shape None: flat blocks."""
-    if gpu_tail:
-        os.environ["DCTZ_ZLIB_GPU"] = "1"
-    try:
-        xin = x.copy()                                  # (dctz_compress scales its input in place)
-        z = np.zeros(x.size * x.itemsize + (1 << 16), np.uint8)
-        zv = _tvar(z.view(x.dtype)[: z.size // x.itemsize])
-        sz = C.c_size_t(0)
-        if shape is not None:
-            assert lib.dctz_set_block_dims(len(shape), (C.c_size_t * len(shape))(*shape)) == 0
-        assert lib.dctz_compress(C.byref(_tvar(xin)), x.size, C.byref(sz), C.byref(zv), EB) == 1
-    finally:
-        os.environ.pop("DCTZ_ZLIB_GPU", None)
+    z, _ = D._container(lib, x, EB, gpu_tail, shape)
     assert (struct.unpack_from("<I", z, 0)[0] >> 8) & 0xFF == (len(shape) if shape is not None else 0)
     assert (z[56 + 1] == 0x5E) == bool(gpu_tail)         # the GPU entropy stage's mark
     return z

@@ -4,73 +4,25 @@ reference's zlib tail and from one with the DZIX chunk index (DCTZ_ZLIB_GPU=1). 
 compressed chunk that lies wholly beyond the prefix the box needs is zeroed first: the result does not change.  A flat
 container and bad boxes are refused with -1, and a good call follows."""
 import ctypes as C
-import os
 import struct
 import zlib
 
 import numpy as np
 import pytest
 
+from tests import dropin_cases as D
 from tests import workloads as W
+from tests.dropin_cases import IX_MAGIC, TILE, TVar, _container, _same, _sections, _sl, _tvar
 
 pytestmark = pytest.mark.gpu
-LIBDIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dctz_amd", "lib")
-TILE = 4096
-IX_MAGIC = 0x58495A44                                  # "DZIX"
 EDGE = {2: 8, 3: 4}
 
 
-class TVarBuf(C.Union):
-    _fields_ = [("f", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_double))]
-
-
-class TVar(C.Structure):   # dctz.h:49-59
-    _fields_ = [("datatype", C.c_int), ("err_bound", C.c_double), ("var_name", C.c_char_p), ("buf", TVarBuf)]
-
-
 def _lib(mode):
-    os.environ["DCTZ_QUIET"] = "1"
-    lib = C.CDLL(os.path.join(LIBDIR, f"libdctz-{mode}.so"))
-    lib.dctz_compress.restype = C.c_int
-    lib.dctz_compress.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(TVar), C.c_double]
-    lib.dctz_decompress.restype = C.c_int
-    lib.dctz_decompress.argtypes = [C.POINTER(TVar), C.POINTER(TVar)]
+    lib = D._lib(mode)
     lib.dctz_decompress_box_nd.restype = C.c_int
     lib.dctz_decompress_box_nd.argtypes = [C.POINTER(TVar), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(TVar)]
-    lib.dctz_set_block_dims.restype = C.c_int
-    lib.dctz_set_block_dims.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
     return lib
-
-
-def _tvar(arr):
-    v = TVar()
-    v.datatype = 1 if arr.dtype == np.float64 else 0
-    if arr.dtype == np.float64:
-        v.buf.d = arr.ctypes.data_as(C.POINTER(C.c_double))
-    else:
-        v.buf.f = arr.ctypes.data_as(C.POINTER(C.c_float))
-    return v
-
-
-def _container(lib, x, shape, eb, gpu_tail):
-    """(container bytes as a uint8 array, the full dctz_decompress result); shape None: flat blocks."""
-    if gpu_tail:
-        os.environ["DCTZ_ZLIB_GPU"] = "1"
-    try:
-        xin = x.copy()                                  # (dctz_compress scales its input in place)
-        z = np.zeros(x.size * x.itemsize + (1 << 16), np.uint8)
-        zv = _tvar(z.view(x.dtype)[: z.size // x.itemsize])
-        sz = C.c_size_t(0)
-        if shape is not None:
-            assert lib.dctz_set_block_dims(len(shape), (C.c_size_t * len(shape))(*shape)) == 0
-        assert lib.dctz_compress(C.byref(_tvar(xin)), x.size, C.byref(sz), C.byref(zv), eb) == 1
-    finally:
-        os.environ.pop("DCTZ_ZLIB_GPU", None)
-    if shape is not None:
-        assert (struct.unpack_from("<I", z, 0)[0] >> 8) & 0xFF == len(shape)      # a DZND container
-    full = np.empty_like(x)
-    assert lib.dctz_decompress(C.byref(zv), C.byref(_tvar(full))) == 1
-    return z, full
 
 
 def _box(lib, z, dtype, lo, hi):
@@ -79,15 +31,6 @@ def _box(lib, z, dtype, lo, hi):
     arr = lambda v: None if v is None else (C.c_size_t * len(v))(*v)
     rc = lib.dctz_decompress_box_nd(C.byref(_tvar(z.view(dtype)[: z.size // np.dtype(dtype).itemsize])), arr(lo), arr(hi), C.byref(_tvar(out)))
     return rc, out[: int(np.prod(ext))].reshape(ext) if rc == 1 else out
-
-
-def _same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _sl(full, dims, lo, hi):
-    return full.reshape(dims)[tuple(slice(l, h) for l, h in zip(lo, hi))]
 
 
 # (shape, element type, ten boxes): the whole array, corners, an interior box, boxes on and off block edges, one that
@@ -109,19 +52,11 @@ def test_box_is_the_slice_of_dctz_decompress(mode, work, gpu_tail):
     dims, dtype, boxes = work
     lib = _lib(mode)
     x = W.ragged(int(np.prod(dims)), dtype, scale=37.0)
-    z, full = _container(lib, x, dims, 1e-3, gpu_tail)
+    z, full = _container(lib, x, 1e-3, gpu_tail, dims)
     assert len(boxes) == 10
     for lo, hi in boxes:
         rc, r = _box(lib, z, dtype, lo, hi)
         assert rc == 1 and _same(r, _sl(full, dims, lo, hi)), (lo, hi)
-
-
-def _sections(z, dtype, qt):
-    dt, n, eb, cnt = struct.unpack_from("<IIdI", z, 0)
-    sizes = struct.unpack_from("<III", z, 40)
-    offs = [56, 56 + sizes[0], 56 + sizes[0] + sizes[1]]
-    end = offs[2] + sizes[2] + (64 * np.dtype(dtype).itemsize if qt else 0) + 16      # (+ "DZND" and its three extents)
-    return n, cnt, sizes, offs, end
 
 
 # a larger array so that whole 16 KiB chunks of every section lie behind what an early box needs
@@ -138,7 +73,7 @@ def test_dzix_chunks_beyond_the_box_are_not_inflated(mode, work):
     dims, dtype, boxes = work
     lib = _lib(mode)
     x = W.ragged(int(np.prod(dims)), dtype, scale=37.0)
-    z, full = _container(lib, x, dims, 1e-3, True)
+    z, full = _container(lib, x, 1e-3, True, dims)
     n, cnt, sizes, offs, end = _sections(z, dtype, mode == "qt")
     assert all(z[o + 1] == 0x5E for o in offs)          # the GPU entropy stage's mark
     magic, chunk, c0, c1, c2 = struct.unpack_from("<5I", z, end)
@@ -173,7 +108,7 @@ def test_flat_containers_and_bad_boxes_are_refused(mode):
     lib = _lib(mode)
     dims = (13, 22, 35)
     x = W.ragged(int(np.prod(dims)), np.float64, scale=37.0)
-    z, full = _container(lib, x, dims, 1e-3, False)
+    z, full = _container(lib, x, 1e-3, False, dims)
     bad = [((0, 0, 0), (14, 22, 35)), ((0, 0, 35), (13, 22, 36)), ((5, 5, 5), (5, 6, 6)), ((6, 5, 5), (5, 6, 6))]
     for lo, hi in bad:
         assert _box(lib, z, np.float64, lo, hi)[0] == -1, (lo, hi)
@@ -182,7 +117,7 @@ def test_flat_containers_and_bad_boxes_are_refused(mode):
     zv = _tvar(z.view(np.float64)[: z.size // 8])
     assert lib.dctz_decompress_box_nd(C.byref(zv), None, arr((1, 1, 1)), C.byref(_tvar(out))) == -1
     assert lib.dctz_decompress_box_nd(C.byref(zv), arr((0, 0, 0)), None, C.byref(_tvar(out))) == -1
-    zf, _ = _container(lib, x, None, 1e-3, False)        # flat blocks
+    zf, _ = _container(lib, x, 1e-3, False)        # flat blocks
     assert (struct.unpack_from("<I", zf, 0)[0] >> 8) & 0xFF == 0
     assert _box(lib, zf, np.float64, (0, 0, 0), (1, 1, 1))[0] == -1
     # and the library still decodes a box of the tiled container afterwards

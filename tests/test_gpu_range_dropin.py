@@ -4,68 +4,24 @@ chunk index (DCTZ_ZLIB_GPU=1).  On the indexed container, every compressed chunk
 needs is zeroed first: the result does not change, so those chunks are not inflated.  A DZND container and bad ranges
 are refused with -1."""
 import ctypes as C
-import os
 import struct
 import zlib
 
 import numpy as np
 import pytest
 
+from tests import dropin_cases as D
 from tests import workloads as W
+from tests.dropin_cases import IX_MAGIC, TILE, TVar, _container, _sections, _tvar
 
 pytestmark = pytest.mark.gpu
-LIBDIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dctz_amd", "lib")
-TILE = 4096
-IX_MAGIC = 0x58495A44                                  # "DZIX"
-
-
-class TVarBuf(C.Union):
-    _fields_ = [("f", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_double))]
-
-
-class TVar(C.Structure):   # dctz.h:49-59
-    _fields_ = [("datatype", C.c_int), ("err_bound", C.c_double), ("var_name", C.c_char_p), ("buf", TVarBuf)]
 
 
 def _lib(mode):
-    os.environ["DCTZ_QUIET"] = "1"
-    lib = C.CDLL(os.path.join(LIBDIR, f"libdctz-{mode}.so"))
-    lib.dctz_compress.restype = C.c_int
-    lib.dctz_compress.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(TVar), C.c_double]
-    lib.dctz_decompress.restype = C.c_int
-    lib.dctz_decompress.argtypes = [C.POINTER(TVar), C.POINTER(TVar)]
+    lib = D._lib(mode)
     lib.dctz_decompress_range.restype = C.c_int
     lib.dctz_decompress_range.argtypes = [C.POINTER(TVar), C.c_size_t, C.c_size_t, C.POINTER(TVar)]
-    lib.dctz_set_block_dims.restype = C.c_int
-    lib.dctz_set_block_dims.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
     return lib
-
-
-def _tvar(arr):
-    v = TVar()
-    v.datatype = 1 if arr.dtype == np.float64 else 0
-    if arr.dtype == np.float64:
-        v.buf.d = arr.ctypes.data_as(C.POINTER(C.c_double))
-    else:
-        v.buf.f = arr.ctypes.data_as(C.POINTER(C.c_float))
-    return v
-
-
-def _container(lib, x, eb, gpu_tail):
-    """(container bytes as a uint8 array, the full dctz_decompress result)."""
-    if gpu_tail:
-        os.environ["DCTZ_ZLIB_GPU"] = "1"
-    try:
-        xin = x.copy()                                  # (dctz_compress scales its input in place)
-        z = np.zeros(x.size * x.itemsize + (1 << 16), np.uint8)
-        zv = _tvar(z.view(x.dtype)[: z.size // x.itemsize])
-        sz = C.c_size_t(0)
-        assert lib.dctz_compress(C.byref(_tvar(xin)), x.size, C.byref(sz), C.byref(zv), eb) == 1
-    finally:
-        os.environ.pop("DCTZ_ZLIB_GPU", None)
-    full = np.empty_like(x)
-    assert lib.dctz_decompress(C.byref(zv), C.byref(_tvar(full))) == 1
-    return z, full
 
 
 def _range(lib, z, dtype, lo, hi):
@@ -93,14 +49,6 @@ def test_range_is_the_slice_of_dctz_decompress(mode, dtype, gpu_tail):
     for lo, hi in RANGES:
         rc, r = _range(lib, z, dtype, lo, hi)
         assert rc == 1 and _same(r, full[lo:hi]), (lo, hi)
-
-
-def _sections(z, dtype, qt):
-    dt, n, eb, cnt = struct.unpack_from("<IIdI", z, 0)
-    sizes = struct.unpack_from("<III", z, 40)
-    offs = [56, 56 + sizes[0], 56 + sizes[0] + sizes[1]]
-    end = offs[2] + sizes[2] + (64 * np.dtype(dtype).itemsize if qt else 0)
-    return n, cnt, sizes, offs, end
 
 
 @pytest.mark.parametrize("mode", ["ec", "qt"])
