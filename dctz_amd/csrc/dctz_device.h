@@ -824,6 +824,26 @@ constexpr int MASK_TRIPS = 4;                 // trips of k_mask_fill whose load
 template <typename T> void launch_mask_fill(const MaskFillParams<T>& p, int grid, hipStream_t s);
 template <typename T> void launch_mask_apply(const MaskApplyParams<T>& p, int grid, hipStream_t s);
 
+// Missing values of an array compressed in tiles (dctz_kernels_ndmask.hip: k_ndmask_fill): the same mask, in C element
+// order, and the holes filled by copies inside each 8 x 8 / 4 x 4 x 4 tile.  A wave trip is E = 16 / sizeof(T) tiles that are
+// neighbours along the fastest axis; trips are numbered with that axis fastest.
+template <typename T>
+struct NdMaskFillParams {
+  const T* in;
+  T* out;                          // the filled copy: null (mask and count only), `in` itself, or disjoint from it
+  unsigned* mask32;                // 2 ceil(n / 64) pieces of the mask over the n = dz dy dx elements in C order
+  Ctl* ctl;                        // cnt_total += the missing elements
+  unsigned dz, dy, dx;             // extents, dx fastest; a 2-D array has dz = 1
+  unsigned nby, ntx;               // tiles along y; trips along x = ceil(tiles along x / E)
+  unsigned trips;                  // tile planes x nby x ntx
+  unsigned pitch16;                // dx * sizeof(T) is a multiple of 16: a trip inside the array moves as 16-byte pieces
+  unsigned plain;                  // dx is a multiple of a trip's width: a trip row is whole aligned bytes of the mask, stored
+                                   // plainly; else the mask was cleared in stream order and the rows are ORed in
+  unsigned flags;                  // DCTZHIP_MISS_*
+  T value, limit;
+};
+template <typename T> void launch_ndmask_fill(const NdMaskFillParams<T>& p, int geom, int grid, hipStream_t s);
+
 // GPU entropy stage (dctz_deflate.hip): one section -> one zlib stream, everything in device memory
 size_t deflate_chunk_bytes();
 size_t deflate_scratch_bytes(size_t n);

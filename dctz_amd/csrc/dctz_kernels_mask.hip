@@ -10,18 +10,9 @@
 // an OR butterfly over the 32 / E lanes of a piece.  The count is an integer sum (a wave reduction and one atomic per wave);
 // nothing else depends on the grid.
 // k_mask_apply: a lane per element of the dense box; the element's flat position gives its bit; set bits store the fill.
-#include "dctz_kernel_common.h"
+#include "dctz_mask_fill.h"          // the fill inside one block, shared with k_ndmask_fill
 
 namespace dctz {
-
-template <typename T> struct MaskBits { using U = unsigned long long; };
-template <> struct MaskBits<float> { using U = unsigned; };
-
-template <typename T>
-__device__ __forceinline__ bool mask_is_missing(const T v, const unsigned flags, const T value, const T limit) {
-  return ((flags & DCTZHIP_MISS_NAN) && v != v) || ((flags & DCTZHIP_MISS_INF) && fabs(v) == (T)INFINITY) ||
-         ((flags & DCTZHIP_MISS_VALUE) && v == value) || ((flags & DCTZHIP_MISS_ABS_GE) && fabs(v) >= limit);
-}
 
 // One trip of a wave: the 64 E elements from element ch * 64 E on.  x holds this lane's E elements as bit patterns (zeros
 // where `present` has no bit: beyond the array's end); the lane's count of missing elements is returned.
@@ -30,13 +21,9 @@ __device__ __forceinline__ unsigned mask_fill_trip(const MaskFillParams<T>& p, c
                                                    const unsigned present) {
   using U = typename MaskBits<T>::U;
   constexpr int E = 16 / (int)sizeof(T);             // elements of a lane
-  constexpr int L = 64 / E;                          // lanes of a block
   constexpr int PL = 32 / E;                         // lanes of a 32-bit piece of the mask
   const unsigned e0 = ch * (64u * E) + (unsigned)lane * E;
-  unsigned miss = 0;
-#pragma unroll
-  for (int k = 0; k < E; k++) miss |= mask_is_missing<T>(__builtin_bit_cast(T, x[k]), p.flags, p.value, p.limit) ? 1u << k : 0u;
-  miss &= present;
+  const unsigned miss = mask_settle<T>(x, present, p.flags, p.value, p.limit);
   const unsigned valid = present & ~miss;
   // the mask: this lane's bits at their place in the piece, joined across the piece's lanes
   unsigned w = miss << (E * (lane & (PL - 1)));
@@ -46,31 +33,8 @@ __device__ __forceinline__ unsigned mask_fill_trip(const MaskFillParams<T>& p, c
   if ((lane & (PL - 1)) == 0 && piece < (p.n + 63u) / 64u * 2u) p.mask32[piece] = w;     // two pieces per word of the mask
   U* const out = reinterpret_cast<U*>(p.out);
   if (!out) return (unsigned)__popc(miss);           // (wave-uniform) mask and count only
-  // the nearest lane in front that holds a valid element of this block hands over its last one; with none in front, the
-  // block's first lane that holds one -- this lane itself or one behind it -- hands over its first one
-  const unsigned long long has = __ballot(valid != 0u) & (((1ull << L) - 1ull) << (lane & ~(L - 1)));
-  U lastv = U(0), firstv = U(0);
-#pragma unroll
-  for (int k = 0; k < E; k++) lastv = (valid >> k) & 1u ? x[k] : lastv;
-#pragma unroll
-  for (int k = E - 1; k >= 0; k--) firstv = (valid >> k) & 1u ? x[k] : firstv;
-  const unsigned long long front = has & ((1ull << lane) - 1ull);
-  const U from_front = __shfl(lastv, front ? 63 - __clzll((long long)front) : lane);
-  const U from_first = __shfl(firstv, has ? __ffsll((unsigned long long)has) - 1 : lane);
-  U run = front ? from_front : has ? from_first : U(0);   // (no valid element in the block: +0.0)
-#pragma unroll
-  for (int k = 0; k < E; k++) {
-    if ((valid >> k) & 1u) run = x[k];
-    else x[k] = run;
-  }
-  if (present == (1u << E) - 1u) {
-    u32x4 v;
-    __builtin_memcpy(&v, x, 16);
-    *reinterpret_cast<u32x4*>(out + e0) = v;
-  } else {
-#pragma unroll
-    for (int k = 0; k < E; k++) if ((present >> k) & 1u) out[e0 + k] = x[k];
-  }
+  mask_fill_block<T>(x, valid, lane);
+  mask_store_lane<T>(out, e0, x, present, present == (1u << E) - 1u);
   return (unsigned)__popc(miss);
 }
 

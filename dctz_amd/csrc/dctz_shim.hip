@@ -3167,6 +3167,106 @@ extern "C" int dctzhip_compress_masked(dctzhip_ctx* c, const void* d_in, size_t 
   return dctzhip_compress(c, d_filled, n, dtype, eb, mode, d_bin, d_dc, d_ac, nullptr, nullptr, info);
 }
 
+// The tiled twin (dctz_kernels_ndmask.hip).  The arguments are checked; n = prod dims <= 64 nblk <= INT_MAX (nd_shape).
+template <typename T>
+static int mask_build_nd_impl(dctzhip_ctx* c, const T* d_in, const NdShape& sh, const dctzhip_missing* miss, uint64_t* d_mask, T* d_filled,
+                              uint64_t* count) {
+  constexpr size_t E = 16 / sizeof(T);
+  const size_t n = sh.d[0] * sh.d[1] * sh.d[2], width = (sh.nd == 2 ? 8 : 4) * E;      // elements of a trip row
+  c->ctl_dirty = 1;                                    // the kernel ADDS to the control block's counter: cleared in stream order, always
+  { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
+  NdMaskFillParams<T> p;
+  p.in = d_in; p.out = d_filled; p.mask32 = reinterpret_cast<unsigned*>(d_mask); p.ctl = c->ctl;
+  p.dz = sh.nd == 3 ? (unsigned)sh.d[0] : 1u; p.dy = (unsigned)sh.d[sh.nd - 2]; p.dx = (unsigned)sh.d[sh.nd - 1];
+  p.nby = (unsigned)sh.nb[sh.nd - 2];
+  p.ntx = (unsigned)((sh.nb[sh.nd - 1] + E - 1) / E);
+  const size_t trips = (sh.nd == 3 ? sh.nb[0] : 1) * p.nby * (size_t)p.ntx;           // <= nblk
+  p.trips = (unsigned)trips;
+  p.pitch16 = sh.d[sh.nd - 1] * sizeof(T) % 16 == 0;
+  p.plain = sh.d[sh.nd - 1] % width == 0;
+  p.flags = miss->flags;
+  p.value = (T)miss->value; p.limit = (T)miss->limit;
+  // plain: the trip rows are the bytes of the bits below n, all stored; what the last word has beyond n is cleared here.
+  // Else every row is ORed into a cleared mask.
+  const size_t words = dctzhip_mask_words(n);
+  if (!p.plain) HIPCHK(c, hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), c->stream));
+  else if (n % 64) HIPCHK(c, hipMemsetAsync(d_mask + words - 1, 0, sizeof(uint64_t), c->stream));
+  // a wave trip is 1 KiB of the array, MASK_TRIPS of them at a time; the flat build's grid
+  const size_t per_wg = (size_t)(MASK_WG / 64) * MASK_TRIPS, wgs = (trips + per_wg - 1) / per_wg;
+  launch_ndmask_fill<T>(p, sh.nd == 2 ? GEOM_2D : GEOM_3D, (int)std::min<size_t>(wgs, (size_t)c->num_cu * 8), c->stream);
+  SET_LAST(c, 1, "k_ndmask_fill<%s, %d>", tname<T>(), sh.nd == 2 ? GEOM_2D : GEOM_3D);
+  unsigned total = 0;
+  const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
+  if (rc) return rc;
+  *count = total;
+  return DCTZHIP_OK;
+}
+
+// The refusals a tiled build shares with the masked tiled compress, behind the shape, dtype and NULL checks of either: the rule,
+// alignment, and the buffers against each other.  d_filled: NULL, d_in itself (where in_place_ok) or disjoint; sp[0 .. m) holds
+// the spans of the caller's other buffers and has room for three more.
+static int check_mask_nd(dctzhip_ctx* c, const char* what, const void* d_in, const NdShape& sh, int dtype, const dctzhip_missing* miss,
+                         const uint64_t* d_mask, const void* d_filled, bool in_place_ok, Span* sp, size_t m) {
+  int rc = check_missing(c, what, miss);
+  if (rc) return rc;
+  if (!aligned16(d_in) || !aligned16(d_filled) || ((uintptr_t)d_mask & 7u))
+    return fail(c, DCTZHIP_E_ARG, "%s: the arrays must be 16-byte aligned, the mask 8-byte aligned", what);
+  const size_t n = sh.d[0] * sh.d[1] * sh.d[2], es = elem_size(dtype);
+  const bool in_place = in_place_ok && d_filled == d_in;
+  add_span(sp, &m, d_in, n * es, in_place ? SPAN_IN_PLACE : SPAN_READ, 0);
+  if (!in_place) add_span(sp, &m, d_filled, n * es, SPAN_OUT, 0);
+  add_span(sp, &m, d_mask, dctzhip_mask_words(n) * sizeof(uint64_t), SPAN_OUT, 0);
+  return check_spans(c, sp, m, what, nullptr);
+}
+
+extern "C" int dctzhip_mask_build_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, const dctzhip_missing* miss,
+                                     uint64_t* d_mask, void* d_filled, uint64_t* count) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  int rc = check_common(c, sh.nblk * 64, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (!d_in || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build_nd: the array, the mask and count must be given");
+  Span sp[3];
+  rc = check_mask_nd(c, "dctzhip_mask_build_nd", d_in, sh, dtype, miss, d_mask, d_filled, true, sp, 0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64) ? mask_build_nd_impl<double>(c, (const double*)d_in, sh, miss, d_mask, (double*)d_filled, count)
+                                : mask_build_nd_impl<float>(c, (const float*)d_in, sh, miss, d_mask, (float*)d_filled, count);
+}
+
+extern "C" int dctzhip_compress_masked_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, double eb, int mode,
+                                          const dctzhip_missing* miss, void* d_bin, float* d_dc, float* d_ac, uint64_t* d_mask,
+                                          void* d_filled, dctzhip_cinfo* info, uint64_t* count) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64, n = sh.d[0] * sh.d[1] * sh.d[2];
+  int rc = check_common(c, n_lin, dtype, mode);
+  if (rc) return rc;
+  if (!d_in || !d_bin || !d_dc || !d_ac || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_masked_nd: null buffer or count");
+  if (!aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac))
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_masked_nd: device buffers must be 16-byte aligned");
+  if (eb < 1E-6) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
+  Span sp[6];
+  size_t m = 0;
+  add_span(sp, &m, d_bin, n_lin, SPAN_OUT, 0);
+  add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_OUT, 0);
+  add_span(sp, &m, d_ac, n_lin * sizeof(float), SPAN_OUT, 0);
+  rc = check_mask_nd(c, "dctzhip_compress_masked_nd", d_in, sh, dtype, miss, d_mask, d_filled, false, sp, m);   // (d_in is not modified)
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!d_filled) {
+    rc = regrow(c, &c->mask_filled, &c->mask_filled_cap, n * elem_size(dtype), 1);
+    if (rc) return rc;
+    d_filled = c->mask_filled;
+  }
+  rc = (dtype == DCTZHIP_F64) ? mask_build_nd_impl<double>(c, (const double*)d_in, sh, miss, d_mask, (double*)d_filled, count)
+                              : mask_build_nd_impl<float>(c, (const float*)d_in, sh, miss, d_mask, (float*)d_filled, count);
+  if (rc) return rc;
+  return dctzhip_compress_nd(c, d_filled, ndims, dims, dtype, eb, mode, d_bin, d_dc, d_ac, nullptr, info);
+}
+
 template <typename T>
 static int mask_apply_impl(dctzhip_ctx* c, const uint64_t* d_mask, double fill, const BoxGeo& box, size_t cnt, size_t first, T* d_out) {
   MaskApplyParams<T> p;

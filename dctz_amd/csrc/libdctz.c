@@ -2119,17 +2119,23 @@ int dctz_fixup_build(t_var *var_z, t_var *var_ref, int N_ref, double bound, void
  * is then simply dctz_compress of the filled array -- byte for byte that call's output, the in-place x /= sf of the caller's
  * buffer included (as dctz_compress_psnr: the second H2D copy inside dctz_compress is the price of that identity).  The mask
  * words leave as one zlib stream behind the blob's header (csrc/dctz_mask_blob.h). */
-int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, double error_bound, const dctz_missing *miss, double fill,
-                         void **mask_blob, size_t *mask_bytes) {
-  if (!var || !var_z || !outSize || !miss || !mask_blob || !mask_bytes || N <= 0) return -1;
-  if (g_nd || (getenv("DCTZ_BLOCK_DIMS") && *getenv("DCTZ_BLOCK_DIMS"))) return -1;   /* flat blocks only: the fill runs over them */
-  const int is_d = (var->datatype == DOUBLE);
-  if (!is_d && var->datatype != FLOAT) return -1;
+static int masked_args_ok(const t_var *var, const t_var *var_z, const size_t *outSize, const dctz_missing *miss, void **mask_blob,
+                          const size_t *mask_bytes) {
+  if (!var || !var_z || !outSize || !miss || !mask_blob || !mask_bytes) return 0;
+  if (var->datatype != DOUBLE && var->datatype != FLOAT) return 0;
+  if (!var_bytes((t_var *)var)) return 0;
+  if (miss->flags == 0 || (miss->flags & ~DZMK_FLAGS_ALL)) return 0;
+  if ((miss->flags & DCTZHIP_MISS_VALUE) && isnan(miss->value)) return 0;
+  if ((miss->flags & DCTZHIP_MISS_ABS_GE) && !(miss->limit > 0.0 && !isinf(miss->limit))) return 0;
+  return 1;
+}
+
+/* The checked call: nd = 0 fills inside flat blocks, nd = 2 / 3 inside the tiles of the array dims, which dctz_compress is
+ * then asked to compress in tiles. */
+static int compress_masked_checked(t_var *var, int nd, const size_t *dims, int N, size_t *outSize, t_var *var_z, double error_bound,
+                                   const dctz_missing *miss, double fill, void **mask_blob, size_t *mask_bytes) {
+  const int is_d = (var->datatype == DOUBLE), dtype = is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   void *host = var_bytes(var);
-  if (!host) return -1;
-  if (miss->flags == 0 || (miss->flags & ~DZMK_FLAGS_ALL)) return -1;
-  if ((miss->flags & DCTZHIP_MISS_VALUE) && isnan(miss->value)) return -1;
-  if ((miss->flags & DCTZHIP_MISS_ABS_GE) && !(miss->limit > 0.0 && !isinf(miss->limit))) return -1;
   const size_t n = (size_t)N, ts = is_d ? sizeof(double) : sizeof(float), words = dctzhip_mask_words(n);
   dctzhip_ctx *c = ctx();
   grow(&g_dev.in, &g_dev.in_cap, n * ts);
@@ -2138,8 +2144,11 @@ int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, doubl
   dctzhip_missing m;
   m.flags = miss->flags; m.value = miss->value; m.limit = miss->limit;
   uint64_t count = 0;
-  if (dctzhip_mask_build(c, g_dev.in, n, is_d ? DCTZHIP_F64 : DCTZHIP_F32, &m, (uint64_t *)g_dev.fix, g_dev.in, &count) != DCTZHIP_OK)
+  if (nd) {
+    if (dctzhip_mask_build_nd(c, g_dev.in, nd, dims, dtype, &m, (uint64_t *)g_dev.fix, g_dev.in, &count) != DCTZHIP_OK) die("dctzhip_mask_build_nd");
+  } else if (dctzhip_mask_build(c, g_dev.in, n, dtype, &m, (uint64_t *)g_dev.fix, g_dev.in, &count) != DCTZHIP_OK) {
     die("dctzhip_mask_build");
+  }
   uint64_t *w = (uint64_t *)malloc(words * sizeof(uint64_t));
   uLongf zbytes = compressBound((uLong)(words * sizeof(uint64_t)));
   unsigned char *b = (unsigned char *)malloc(DZMK_HEADER_BYTES + (size_t)zbytes);
@@ -2149,10 +2158,46 @@ int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, doubl
   if (compress2(b + DZMK_HEADER_BYTES, &zbytes, (const Bytef *)w, (uLong)(words * sizeof(uint64_t)), DZMK_ZLIB_LEVEL) != Z_OK) die("compress2 (mask)");
   free(w);
   dzmk_write_header(b, is_d, miss->flags, n, (size_t)count, fill, (size_t)zbytes);
+  if (nd && dctz_set_block_dims(nd, dims) != 0) { free(b); return -1; }
   const int ret = dctz_compress(var, N, outSize, var_z, error_bound);
   if (ret != 1) { free(b); return ret; }
   *mask_blob = b; *mask_bytes = DZMK_HEADER_BYTES + (size_t)zbytes;
   return 1;
+}
+
+int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, double error_bound, const dctz_missing *miss, double fill,
+                         void **mask_blob, size_t *mask_bytes) {
+  if (N <= 0 || !masked_args_ok(var, var_z, outSize, miss, mask_blob, mask_bytes)) return -1;
+  if (g_nd || (getenv("DCTZ_BLOCK_DIMS") && *getenv("DCTZ_BLOCK_DIMS"))) return -1;   /* flat blocks only: the fill runs over them */
+  return compress_masked_checked(var, 0, NULL, N, outSize, var_z, error_bound, miss, fill, mask_blob, mask_bytes);
+}
+
+/* The same for an array compressed in tiles: dctzhip_mask_build_nd fills inside the tiles, and the container is byte for byte
+ * dctz_set_block_dims(ndims, dims) + dctz_compress of the filled array.  A request of the caller's that is still pending is
+ * not consumed: the call is refused. */
+int dctz_compress_masked_nd(t_var *var, int ndims, const size_t *dims, size_t *outSize, t_var *var_z, double error_bound,
+                            const dctz_missing *miss, double fill, void **mask_blob, size_t *mask_bytes) {
+  if (mask_blob) *mask_blob = NULL;
+  if (!masked_args_ok(var, var_z, outSize, miss, mask_blob, mask_bytes)) return -1;
+  if ((ndims != 2 && ndims != 3) || !dims || g_nd) return -1;
+  size_t n = 1;
+  for (int i = 0; i < ndims; i++) {
+    if (dims[i] == 0 || dims[i] > 0x7FFFFFFFu || n > (size_t)0x7FFFFFFF / dims[i]) return -1;
+    n *= dims[i];
+  }
+  if (dctzhip_nd_blocks(ndims, dims) == 0) return -1;      /* (more tiles than the streams can number) */
+  return compress_masked_checked(var, ndims, dims, (int)n, outSize, var_z, error_bound, miss, fill, mask_blob, mask_bytes);
+}
+
+/* The mask words of a checked blob, inflated (malloc'd), or NULL if the payload is not exactly those words */
+static unsigned char *mask_words_of(const void *mask_blob, const dzmk_header *mh) {
+  const size_t wbytes = (size_t)mh->words * sizeof(uint64_t);
+  /* (one byte of room more: a payload that holds more than the words must not pass for one that holds them) */
+  unsigned char *w = (unsigned char *)malloc(wbytes + 8);
+  if (!w) { fprintf(stderr, "Out of memory: mask\n"); exit(1); }
+  uLongf got = (uLongf)(wbytes + 8);
+  if (uncompress(w, &got, (const Bytef *)mask_blob + DZMK_HEADER_BYTES, (uLong)mh->payload_bytes) != Z_OK || (size_t)got != wbytes) { free(w); return NULL; }
+  return w;
 }
 
 /* dctz_decompress, then the correction list if one is given, then the mask.  Both blob headers are held against the
@@ -2166,12 +2211,26 @@ int dctz_decompress_masked(t_var *var_z, const void *mask_blob, size_t mask_byte
   if (v.nd != 0 || v.n == 0 || !var_r) return -1;
   if (dzmk_check(mask_blob, mask_bytes, v.is_d, v.n, &mh) != 0) return -1;
   if (fix_blob && dzfx_check(fix_blob, fix_bytes, v.is_d, v.n, &fh) != 0) return -1;
-  const size_t wbytes = (size_t)mh.words * sizeof(uint64_t);
-  /* (one byte of room more: a payload that holds more than the words must not pass for one that holds them) */
-  unsigned char *w = (unsigned char *)malloc(wbytes + 8);
-  if (!w) { fprintf(stderr, "Out of memory: mask\n"); exit(1); }
-  uLongf got = (uLongf)(wbytes + 8);
-  if (uncompress(w, &got, (const Bytef *)mask_blob + DZMK_HEADER_BYTES, (uLong)mh.payload_bytes) != Z_OK || (size_t)got != wbytes) { free(w); return -1; }
+  unsigned char *w = mask_words_of(mask_blob, &mh);
+  if (!w) return -1;
+  const int ret = decompress_whole(var_z, var_r, (const unsigned char *)fix_blob, (const uint64_t *)w, mh.fill);
+  free(w);
+  return ret;
+}
+
+/* The same for a DZND container: the mask covers the array's prod dims elements in C order, as the reconstruction lies on the
+ * device, and a correction blob is the tiled kind (dctz_decompress_bounded's checks). */
+int dctz_decompress_masked_nd(t_var *var_z, const void *mask_blob, size_t mask_bytes, const void *fix_blob, size_t fix_bytes, t_var *var_r) {
+  dzc_view v;
+  if (!var_z || !var_bytes(var_z)) return -1;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype);
+  dzmk_header mh;
+  dzfx_header_nd nh;
+  if (v.nd == 0 || v.n == 0 || !var_r || dzc_geometry(&v) != 0) return -1;
+  if (dzmk_check(mask_blob, mask_bytes, v.is_d, v.n, &mh) != 0) return -1;
+  if (fix_blob && dzfx_check_nd(fix_blob, fix_bytes, v.is_d, v.nd, v.dims, v.n, v.nblk, &nh) != 0) return -1;   /* (a flat blob: its version) */
+  unsigned char *w = mask_words_of(mask_blob, &mh);
+  if (!w) return -1;
   const int ret = decompress_whole(var_z, var_r, (const unsigned char *)fix_blob, (const uint64_t *)w, mh.fill);
   free(w);
   return ret;

@@ -175,6 +175,11 @@ _PROTOS = {
     "dctzhip_compress_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int, C.POINTER(Missing),
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CompressInfo),
                                           C.POINTER(C.c_uint64)]),
+    "dctzhip_mask_build_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.POINTER(Missing),
+                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "dctzhip_compress_masked_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_int,
+                                             C.POINTER(Missing), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(CompressInfo), C.POINTER(C.c_uint64)]),
     "dctzhip_dct_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]),
     "dctzhip_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(CompressInfo)]),
     "dctzhip_serial_mean_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -872,6 +877,48 @@ class Context:
             out["ac_exact"].data_ptr(), mask.data_ptr(), filled.data_ptr() if filled is not None else None, C.byref(info),
             C.byref(count))
         self._check(rc, "dctzhip_compress_masked")
+        return out, info, mask, int(count.value)
+
+    def mask_build_nd(self, x, flags, value=0.0, limit=0.0, filled=None, mask=None):
+        """mask_build for a contiguous 2-D or 3-D CUDA tensor that compress_nd() will take: the same mask, over x in C element
+        order, and the holes filled inside each 8 x 8 / 4 x 4 x 4 tile.  Returns (mask, count, filled), filled shaped like x."""
+        t = self.torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() in (2, 3)
+        self._bind_stream()
+        shape = tuple(x.shape)
+        if mask is None:
+            mask = t.empty(int(self.lib.dctzhip_mask_words(x.numel())), dtype=t.int64, device=self.device)
+        if filled is None:
+            filled = t.empty_like(x)
+        elif filled is False:
+            filled = None
+        m = self._missing(flags, value, limit)
+        count = C.c_uint64(0)
+        rc = self.lib.dctzhip_mask_build_nd(self.h, x.data_ptr(), len(shape), (C.c_size_t * len(shape))(*shape), _dt(x.dtype),
+                                            C.byref(m), mask.data_ptr(), filled.data_ptr() if filled is not None else None,
+                                            C.byref(count))
+        self._check(rc, "dctzhip_mask_build_nd")
+        return mask, int(count.value), filled
+
+    def compress_masked_nd(self, x, eb, flags, value=0.0, limit=0.0, mode=EC, out=None, filled=None, mask=None):
+        """mask_build_nd followed by compress_nd of the filled array, in one call; x is not modified.  filled: a tensor like x
+        that receives the filled array (the reference for fixup_build_nd), or None: the context keeps it.
+        Returns (out, info, mask, count)."""
+        t = self.torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() in (2, 3)
+        self._bind_stream()
+        shape = tuple(x.shape)
+        if out is None:
+            out = self.alloc_outputs(self.nd_blocks(shape) * 64, x.dtype)
+        if mask is None:
+            mask = t.empty(int(self.lib.dctzhip_mask_words(x.numel())), dtype=t.int64, device=self.device)
+        m = self._missing(flags, value, limit)
+        info, count = CompressInfo(), C.c_uint64(0)
+        rc = self.lib.dctzhip_compress_masked_nd(
+            self.h, x.data_ptr(), len(shape), (C.c_size_t * len(shape))(*shape), _dt(x.dtype), float(eb), mode, C.byref(m),
+            out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), mask.data_ptr(),
+            filled.data_ptr() if filled is not None else None, C.byref(info), C.byref(count))
+        self._check(rc, "dctzhip_compress_masked_nd")
         return out, info, mask, int(count.value)
 
     def psnr_terms(self, x, r):

@@ -243,6 +243,22 @@ int dctz_compress_masked(t_var *var, int N, size_t *outSize, t_var *var_z, doubl
                          double fill, void **mask_blob, size_t *mask_bytes);
 int dctz_decompress_masked(t_var *var_z, const void *mask_blob, size_t mask_bytes,
                            const void *fix_blob /* or NULL */, size_t fix_bytes, t_var *var_r);
+/* Missing values of an array compressed in tiles (ADDITION, EC and QT builds; include/dctz_hip.h, "missing values of an array
+ * compressed in 8 x 8 / 4 x 4 x 4 tiles").  The two calls above keep refusing tiled input; these are their twins.
+ * dctz_compress_masked_nd treats var->buf as a row-major array of ndims = 2 or 3 extents, fills the missing elements inside
+ * each tile, and compresses the filled array in tiles: the container is byte for byte dctz_set_block_dims(ndims, dims) +
+ * dctz_compress() of that array, var->buf is left as that call leaves it, and the blob is the one above with n = prod dims,
+ * the mask over the array in C order.  dctz_decompress_masked_nd is dctz_decompress of a DZND container, then the correction
+ * list of fix_blob if one is given (the tiled kind: dctz_fixup_build of that container against the FILLED array), then `fill`
+ * written into every missing element.  Both return 1, or -1: compress for the argument errors of dctz_compress_masked, for
+ * ndims other than 2 or 3, an extent of 0, a product or a tile count beyond an int, and while a dctz_set_block_dims request of
+ * the caller's is pending (it stays pending) -- all before a device is asked for, *mask_blob left NULL; decompress for a flat
+ * container, a mask blob whose n is not the product of the container's extents, a correction blob that is flat or has other
+ * extents (all checked before anything else is done), and a payload that does not inflate to exactly the mask's words. */
+int dctz_compress_masked_nd(t_var *var, int ndims, const size_t *dims, size_t *outSize, t_var *var_z, double error_bound,
+                            const dctz_missing *miss, double fill, void **mask_blob, size_t *mask_bytes);
+int dctz_decompress_masked_nd(t_var *var_z, const void *mask_blob, size_t mask_bytes,
+                              const void *fix_blob /* or NULL */, size_t fix_bytes, t_var *var_r);
 /* Multi-dimensional blocks (optional; SURVEY section 8 f4 -- NOT in the reference, whose library flattens every
  * array, dctz-test.c:77-91; the hint is its FFTW r2r experiment dct-fftw-test.c:74-97).  The NEXT dctz_compress call
  * treats var->buf as a row-major ndims-dimensional array (ndims = 2: 8 x 8 tiles, ndims = 3: 4 x 4 x 4 tiles, last

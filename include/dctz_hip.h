@@ -666,7 +666,8 @@ int dctzhip_fixup_apply_nd(dctzhip_ctx *ctx, const uint32_t *d_fix_start, const 
 /* Fields with missing values (1e36 over land, NaN) ruin the codec as they are: sf is taken over every element, a NaN costs
  * its 64-element block, an infinity the array.  The mask layer keeps one bit per element beside the streams, compresses a
  * FILLED array whose holes hold copies of their valid neighbours, and writes the caller's fill value back after any decode.
- * No compress or decode kernel and no stream byte changes.  Flat 64-element blocks only.
+ * No compress or decode kernel and no stream byte changes.  These three calls fill inside flat 64-element blocks; arrays
+ * compressed in tiles have dctzhip_mask_build_nd / dctzhip_compress_masked_nd below, and share dctzhip_mask_apply.
  *   missing     element x (data type T) is missing iff a selected test holds, made in T:
  *                 DCTZHIP_MISS_NAN      x != x (signalling NaNs too)
  *                 DCTZHIP_MISS_INF      fabs(x) == inf
@@ -723,6 +724,44 @@ int dctzhip_compress_masked(dctzhip_ctx *ctx, const void *d_in, size_t n, int dt
                             const dctzhip_missing *miss, void *d_bin_index, float *d_dc, float *d_ac_exact,
                             uint64_t *d_mask, void *d_filled /* or NULL: context scratch, kept */, dctzhip_cinfo *info,
                             uint64_t *count /* host */);
+
+/* Missing values of an array compressed in 8 x 8 / 4 x 4 x 4 tiles (dctzhip_compress_nd), fp32 and fp64, 2-D and 3-D, aligned
+ * and ragged extents alike.  The tests for "missing" are the ones above.
+ *   positions   those of dctzhip_fixup_build_nd: block B numbered row-major over the tile grid, the in-block place j = 8 r + c
+ *               in 2-D and j = 16 z + 4 y + x in 3-D; a position is REAL iff every coordinate is below dims[a].
+ *   fill rule   a real missing position of tile B takes the value of the nearest real valid position before it in B, in
+ *               ascending j; else the tile's first real valid position; else +0.0.  Padded positions are neither valid nor
+ *               missing and are never read or written.  Valid elements keep their bits; every filled value is a copy, moved
+ *               as a bit pattern (a signalling NaN among valid data keeps its bits).  The edge padding of dctzhip_compress_nd
+ *               (repeat the last sample) then acts on the filled array as on any array.
+ *   mask        exactly the flat layer's mask of the array seen as n = prod dims elements in C order -- byte for byte what
+ *               dctzhip_mask_build(d_in, n, ..., d_filled = NULL) writes -- so dctzhip_mask_apply serves tiled arrays as it is.
+ *
+ * dctzhip_mask_build_nd: one pass over the array -- the mask, the count and (unless d_filled is NULL) the filled copy, in the
+ * array's own C-order layout.  d_filled: NULL, exactly d_in (in place) or disjoint from it.
+ *   refusals    before any launch, DCTZHIP_E_ARG: the shape rules of dctzhip_compress_nd (which keep prod dims below 2^31);
+ *               the rules of dctzhip_mask_build for NULL pointers, dtype, flags, a NaN value and a bad limit; d_in or d_filled
+ *               not 16-byte aligned, d_mask not 8-byte aligned; d_filled overlapping d_in partly; the mask overlapping an
+ *               array.  The context stays usable.
+ * The same call gives the same bytes every time, on every context, whatever grid is launched.  Host-synchronous;
+ * dctzhip_debug_last_kernel(ctx, 1, ...) names the kernel afterwards.
+ *
+ * dctzhip_compress_masked_nd: dctzhip_mask_build_nd followed by dctzhip_compress_nd(ctx, filled, ndims, dims, dtype,
+ * error_bound, mode, d_bin_index, d_dc, d_ac_exact, NULL, info): streams and *info are bit for bit that call's.  d_in is not
+ * modified.  d_filled: prod dims elements that receive the filled array -- the reference to hand dctzhip_fixup_build_nd -- or
+ * NULL: the context keeps the copy in scratch of its own.  Refusals: those of the two calls, all made before any launch.
+ *
+ * Composed guarantee: dctzhip_compress_masked_nd; dctzhip_fixup_build_nd against d_filled; dctzhip_decompress_nd or
+ * dctzhip_decompress_box_nd; dctzhip_fixup_apply_nd; dctzhip_mask_apply(d_mask, prod dims, dtype, fill, ndims, dims, lo, hi,
+ * d_out).  Every valid element then has the original's bits or lies within the list's bound of it, and every missing element
+ * has the fill's bits. */
+int dctzhip_mask_build_nd(dctzhip_ctx *ctx, const void *d_in, int ndims, const size_t *dims, int dtype,
+                          const dctzhip_missing *miss, uint64_t *d_mask,
+                          void *d_filled /* NULL, == d_in, or disjoint */, uint64_t *count /* host */);
+int dctzhip_compress_masked_nd(dctzhip_ctx *ctx, const void *d_in, int ndims, const size_t *dims, int dtype,
+                               double error_bound, int mode, const dctzhip_missing *miss, void *d_bin_index, float *d_dc,
+                               float *d_ac_exact, uint64_t *d_mask, void *d_filled /* or NULL: context scratch, kept */,
+                               dctzhip_cinfo *info, uint64_t *count /* host */);
 
 /* ---- transform only ------------------------------------------------------ */
 /* Batched drop-in for dct_init + per-block dct_fftw / ifft_idct (+ the
