@@ -143,7 +143,8 @@ template <typename F> auto with_mode_bool(int mode, bool b, F&& f) {
 }
 
 // Per-call control block in device memory; zeroed by the first kernel of every compress call (k_stats_final) --
-// a decode call only ever sets `error`, and the host clears the block after a failed call.
+// a decode call only ever sets `error`, and the host clears the block after a failed call.  The context has two: a
+// compress call with no statistics kernel in front moves to the one the last call's k_compact_ac zeroed (FinArgs::zero_words).
 struct Ctl {
   unsigned pad_ticket;
   unsigned cnt_total;              // exceptions emitted / consumed so far
@@ -199,7 +200,7 @@ struct FinArgs {
   HostBox* box;
   unsigned long long seq;
   const SfGuess* guess;            // device-chosen scaling factor of this call, reported with the results (NULL: the host chose it)
-  unsigned* zero_words;            // k_finish only: words to clear for the next call (the ticket counters of k_compress_eo), or NULL
+  unsigned* zero_words;            // k_finish / k_compact_ac: words to clear for the next call (the ticket counters of k_compress_eo / the context's other control block), or NULL
   unsigned nzero;
 };
 

@@ -826,6 +826,9 @@ template <typename T, int MODE>
 __global__ __launch_bounds__(SWG) void k_compact_ac(FwdParams<T> p, double eb, unsigned nlists, FinArgs fin, unsigned* memo) {
   __shared__ unsigned sh[SWG / 64];
   if (fin.box != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
+    // (the context's OTHER control block, for the next call: nothing in flight touches it, and the end of the kernel
+    // publishes the zeros -- a call that guesses sf from the statistics it remembers has no kernel in front to clear one)
+    if (fin.zero_words != nullptr) for (unsigned i = threadIdx.x; i < fin.nzero; i += SWG) fin.zero_words[i] = 0u;
     unsigned all = 0;
     for (unsigned i = threadIdx.x; i < nlists; i += SWG) all += p.tile_cnt[i] & LIST_LEN;
     FinBody f;

@@ -24,6 +24,7 @@
 
 #include "dctz_device.h"
 #include "dctz_tables.h"
+#include "dctz_spec_memory.h"
 
 // RCCL is loaded with dlopen (single-GPU users need none), so its header is not needed -- but where it is installed at build
 // time, the things this file restates from it are checked against it by the compiler (the header declares, it defines
@@ -59,7 +60,9 @@ struct dctzhip_ctx {
   int rtab_l = -1, rtab_dtype = -1;
   void* qtab = nullptr;             // 64 doubles
   // per-call state
-  Ctl* ctl = nullptr;
+  Ctl* ctl = nullptr;               // the control block of the current call: one of ctl_pair's two
+  Ctl* ctl_pair = nullptr;          // a compress call that guesses sf from spec_mem moves to the other block, which the hand-off workgroup of the last k_compact_ac has zeroed: no launch in front of k_compress
+  int ctl_other_clean = 0;          // the block c->ctl is NOT is all zeros (the hand-off of the call that zeroed it has been seen, nothing has used it since)
   double* part = nullptr;           // stats partials
   double* stats_out = nullptr;      // 4 doubles
   float* ac_tmp = nullptr;          // workgroup-local AC_exact lists (list of workgroup b at the slot of its first tile)
@@ -174,6 +177,9 @@ struct dctzhip_ctx {
   int b_spec_now = 0;               // this batch call may speculate (no cooldown pending when it started)
   unsigned long long b_spec_items = 0, b_spec_misses = 0;   // speculative batch items / those done again on their own
   unsigned long long spec_hits = 0, spec_misses = 0;
+  SpecMemory spec_mem;              // the last verified statistics per (input, length, element type): a guess that needs no sample (dctz_spec_memory.h)
+  int spec_memory = 1;              // 0: every speculative call samples (DCTZHIP_SPEC_MEMORY, dctzhip_set_spec_memory)
+  unsigned long long hist_hits = 0, hist_misses = 0;   // guesses taken from spec_mem that verified / that did not (dctzhip_debug_counter 18 / 19)
   int profiling = 0;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   dctzhip_timings last = {0, 0, 0, 0};
@@ -292,6 +298,7 @@ extern "C" int dctzhip_ctx_create(dctzhip_ctx** out, int device) {
   if (const char* e = getenv("DCTZHIP_SPECULATE")) c->speculate = atoi(e) != 0;
   if (const char* e = getenv("DCTZHIP_BATCH_SPECULATE")) c->batch_speculate = atoi(e) != 0;
   if (const char* e = getenv("DCTZHIP_SPEC_MIN")) { long long v = atoll(e); if (v >= 0) c->spec_min = (size_t)v; }
+  if (const char* e = getenv("DCTZHIP_SPEC_MEMORY")) c->spec_memory = atoi(e) != 0;
   if (const char* e = getenv("DCTZHIP_SPEC_GROUP")) { int v = atoi(e); if (v >= 1 && v <= 4096) c->spec_group = (unsigned)v; }
   HIPCHK(nullptr, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
@@ -301,7 +308,8 @@ extern "C" int dctzhip_ctx_create(dctzhip_ctx** out, int device) {
   HIPCHK(nullptr, hipMalloc(&c->tab_f32, sizeof(float) * TBP_TOTAL));
   HIPCHK(nullptr, hipMalloc(&c->rtab, sizeof(double) * RTAB_SIZE));
   HIPCHK(nullptr, hipMalloc(&c->qtab, sizeof(double) * 64));
-  HIPCHK(nullptr, hipMalloc(&c->ctl, sizeof(Ctl)));
+  HIPCHK(nullptr, hipMalloc(&c->ctl_pair, sizeof(Ctl) * 2));
+  c->ctl = c->ctl_pair;
   HIPCHK(nullptr, hipMalloc(&c->part, sizeof(double) * 3 * PART_SLOTS * 2));      // (second half: the second chain of a mixed batch)
   HIPCHK(nullptr, hipMalloc(&c->stats_out, sizeof(double) * 4));
   HIPCHK(nullptr, hipHostMalloc(&c->h_pin, PIN_BYTES, hipHostMallocDefault));
@@ -361,7 +369,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   (void)dctzhip_comm_destroy(c);
   (void)hipStreamSynchronize(c->stream);
   if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf, c->fix_mask, c->fix_cnt, c->mask_filled};
+  void* bufs[] = {c->tile_pre, c->ix_part, c->one_qt, c->one_bqt, c->one_bctl, c->one_dbg, c->one_ga, c->one_gb, c->one_rec, c->one_ctl, c->qcnt, c->ttot, c->memo_start, c->ac_tmp, c->tile_cnt, c->wg_cnt, c->serial_out, c->tab_f64, c->tab_f32, c->rtab, c->qtab, c->ctl_pair, c->part, c->stats_out, c->qt_item, c->qt_j, c->nd_buf, c->dfl_buf, c->sf_thr[0], c->sf_thr[1], c->sf_pw[0], c->sf_pw[1], c->sf_guess, c->rd_slab, c->rd_rec, c->mb_dev, c->mb_items, c->sum_buf, c->fix_mask, c->fix_cnt, c->mask_filled};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->h_pin) (void)hipHostFree(c->h_pin);
   if (c->box) (void)hipHostFree(c->box);
@@ -422,7 +430,14 @@ extern "C" int dctzhip_set_speculation(dctzhip_ctx* c, int on, size_t min_elemen
   if (!c) return DCTZHIP_E_ARG;
   c->speculate = on != 0;
   c->spec_cooldown = 0;
+  if (!on) c->spec_mem.clear();
   if (min_elements) c->spec_min = min_elements;
+  return DCTZHIP_OK;
+}
+extern "C" int dctzhip_set_spec_memory(dctzhip_ctx* c, int on) {
+  if (!c) return DCTZHIP_E_ARG;
+  c->spec_memory = on != 0;
+  c->spec_mem.clear();
   return DCTZHIP_OK;
 }
 // (tools) the name rocprofv3 lists the big kernel of the last call under -- every template argument -- so that bench.py can ask
@@ -457,6 +472,8 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 15: *value = c->mbox_bound; break;          // ... the host's bound B of the items, the list's capacity
     case 16: *value = c->memo_decodes; break;        // dctzhip_decompress calls launched on the last compress call's tile counts (the decode memo)
     case 17: *value = c->memo_redos; break;          // ... of them, found stale by the decoder and done again behind k_count_tiles
+    case 18: *value = c->hist_hits; break;           // speculative compress calls that took their guess from the remembered statistics of the same input, verified
+    case 19: *value = c->hist_misses; break;         // ... refused by the true statistics (done again, like a sampled miss)
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
   return DCTZHIP_OK;
@@ -1339,12 +1356,13 @@ template <typename T>
 static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int mode, uint8_t* d_bin, float* d_dc,
                          float* d_ac, T* d_coef, const HostStats& st, bool fused, double* sf_out, T* sf_t_out,
                          unsigned* fast_sf_out, unsigned long long seq, int geom, bool device_sf = false,
-                         const NdDirect* nd = nullptr, T* d_scaled = nullptr) {
+                         const NdDirect* nd = nullptr, T* d_scaled = nullptr, bool* zeroed_other = nullptr) {
   const int dtype = sizeof(T) == 8 ? DCTZHIP_F64 : DCTZHIP_F32;
   hipStream_t s = c->stream;
   const unsigned nfull = (unsigned)(n / 64);
   const int rem = (int)(n % 64);
   const unsigned ntiles = (nfull + TILE_BLKS - 1) / TILE_BLKS;
+  if (zeroed_other) *zeroed_other = false;           // (set where this pass's k_compact_ac zeroes the context's other control block)
   const double sf = device_sf ? 1.0 : scaling_factor(dtype, st.max_abs);   // (device_sf: k_stats_final_sf has chosen it; read back after the call)
   *sf_out = sf;
   c->memo.valid = false; c->memo_pass = false;       // (ttot / memo_start are about to be rewritten)
@@ -1442,7 +1460,12 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   // (k_compact_ac finds the place of every list itself: no scan kernel.)  With the mailbox its first workgroup hands
   // the call's results to the host as soon as the kernel starts -- all of them are in by then -- so the host is back in
   // the caller, queueing the next call's launches, while the lists are still being moved
-  const FinArgs fin = {c->ctl, c->part, fused ? (int)nlists : 0, seq ? c->box_dev : nullptr, seq, p.guess};
+  // (... and zeroes the context's other control block for a next call that has no statistics kernel in front)
+  const bool zeroing = seq != 0 && !direct;
+  if (zeroed_other) *zeroed_other = zeroing;
+  Ctl* const other = c->ctl == c->ctl_pair ? c->ctl_pair + 1 : c->ctl_pair;
+  const FinArgs fin = {c->ctl, c->part, fused ? (int)nlists : 0, seq ? c->box_dev : nullptr, seq, p.guess,
+                       zeroing ? reinterpret_cast<unsigned*>(other) : nullptr, (unsigned)(sizeof(Ctl) / 4)};
   if (direct) {
     // every exact coefficient is at its place and Ctl::cnt_total is final: only the hand-off is left
     if (seq) launch_finish(c->ctl, c->part, fused ? (int)nlists : 0, c->box_dev, seq, s, p.guess, c->lb_ticket, 128u);
@@ -1510,13 +1533,35 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
     c->ctl_dirty = 1;                               // until this call's hand-off has been seen
     return DCTZHIP_OK;
   };
-  { int rc = reset(); if (rc) return rc; }
+  // A speculative call on an input whose last calls all verified with one scaling factor guesses from THEIR true
+  // statistics (dctz_spec_memory.h): no sample, no launch in front of k_compress.  The control block, which a statistics
+  // kernel would have zeroed, is then the context's other one -- zeroed by the last call's k_compact_ac -- or, where that
+  // one is not known to be clean (first call, a failed call, a call that went another way), memset like any other.
+  SpecMemory::Entry hist_e;
+  bool hist = false;
+  // (not for an input the library owns -- the filled copy of dctzhip_compress_masked: every masked array of one size would
+  // share its key, a rotation of unrelated fields the caller cannot see; such calls sample and leave the table alone)
+  const bool remember = c->spec_memory && (const void*)d_in != c->mask_filled;
+  if (spec && remember) {
+    if (const SpecMemory::Entry* e = c->spec_mem.predict(d_in, n, dtype)) { hist_e = *e; hist = true; }
+  }
+  if (hist && box && c->ctl_other_clean) {
+    c->ctl = c->ctl == c->ctl_pair ? c->ctl_pair + 1 : c->ctl_pair;
+    c->ctl_other_clean = 0;                         // (the block that is left: until this call's k_compact_ac has zeroed it)
+    c->ctl_dirty = 1;
+  } else {
+    if (hist) c->ctl_dirty = 1;                     // (no k_stats_final in front)
+    int rc = reset();
+    if (rc) return rc;
+  }
 
   // ---- calc_data_stat (util.c:12-44): the full pass, or the sample -------------
   unsigned long long seq = box ? ++c->seq : 0ull;
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[0], s));
   const SfTable tab = {c->sf_thr[dtype], c->sf_pw[dtype], c->sf_nk[dtype], c->fastdiv, dtype};
-  if (pre) {
+  if (hist) {
+    // nothing to launch
+  } else if (pre) {
     launch_stats_final(c->part, pre_parts, c->stats_out, s, box ? c->box_dev : nullptr, seq, box ? c->ctl : nullptr,
                        dsf ? &tab : nullptr, c->sf_guess);
   } else if (spec) {
@@ -1537,7 +1582,9 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   }
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[1], s));
   HostStats st = {0.0, 0.0, 0.0};
-  if (dsf) {
+  if (hist) {
+    st = {hist_e.max_abs, hist_e.min_abs, 0.0};      // the host's guess: sf and the FastDiv level follow from it in compress_pass
+  } else if (dsf) {
     // nothing to wait for: the scaling factor is chosen on the device (k_stats_final_sf) and the main launch follows at
     // once; the choice comes back with the call's results and is verified below
   } else if (box) {
@@ -1564,8 +1611,9 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   // one pass of the kernels + the hand-off of its results into *hc / hs[4..6]
   bool lb_retry = false;
   auto run = [&](const HostStats& stats, bool fused) -> int {
-    const bool dev = dsf && !respin;
-    int rc = compress_pass<T>(c, d_in, n, eb, mode, d_bin, d_dc, d_ac, d_coef, stats, fused, &sf, &sf_t, &fast_sf, seq, geom, dev, nd, scaled_by_kernel);
+    const bool dev = dsf && !respin && !hist;
+    bool zeroed_other = false;                        // the pass that stands had its k_compact_ac zero the context's other control block
+    int rc = compress_pass<T>(c, d_in, n, eb, mode, d_bin, d_dc, d_ac, d_coef, stats, fused, &sf, &sf_t, &fast_sf, seq, geom, dev, nd, scaled_by_kernel, &zeroed_other);
     if (rc) return rc;
     if (box) {
       rc = wait_seq(c, &hb->seq_done, seq, "compress");
@@ -1588,7 +1636,7 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
       rc = reset();
       if (rc) return rc;
       if (box) seq = ++c->seq;
-      rc = compress_pass<T>(c, d_in, n, eb, mode, d_bin, d_dc, d_ac, d_coef, stats, fused, &sf, &sf_t, &fast_sf, seq, geom, dev, nd, scaled_by_kernel);
+      rc = compress_pass<T>(c, d_in, n, eb, mode, d_bin, d_dc, d_ac, d_coef, stats, fused, &sf, &sf_t, &fast_sf, seq, geom, dev, nd, scaled_by_kernel, &zeroed_other);
       if (rc) return rc;
       if (box) {
         rc = wait_seq(c, &hb->seq_done, seq, "compress");
@@ -1606,6 +1654,7 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
       }
     }
     if (hc->error) { c->ctl_dirty = 1; return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error); }
+    if (box) c->ctl_other_clean = zeroed_other;       // (the zeros were fenced before the hand-off that has just been seen)
     if (c->profiling) { rc = read_timings(c, 2); if (rc) return rc; }
     return DCTZHIP_OK;
   };
@@ -1620,11 +1669,19 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
     st = truth;
     if ((T)true_sf == sf_t && window_ok) {
       sf = true_sf;
-      if (spec) { flags |= DCTZHIP_INFO_STATS_FUSED; c->spec_hits++; }
+      if (spec) {
+        flags |= DCTZHIP_INFO_STATS_FUSED; c->spec_hits++;
+        if (hist) c->hist_hits++;
+        if (remember) c->spec_mem.verified(d_in, n, dtype, truth.max_abs, truth.min_abs, true_sf);
+      }
     } else {                                        // wrong guess: everything again with the true statistics
       if (scale_in_place)                           // (cannot happen: the device chose sf from the full statistics by the host's own tables)
         return fail(c, DCTZHIP_E_INTERNAL, "scaling factor %g chosen on the device differs from the host's %g after an in-place pass", (double)sf_t, true_sf);
-      if (spec) { c->spec_misses++; c->spec_cooldown = SPEC_COOLDOWN; }
+      if (spec) {
+        c->spec_misses++; c->spec_cooldown = SPEC_COOLDOWN;
+        if (hist) c->hist_misses++;
+        if (remember) c->spec_mem.missed(d_in, n, dtype, hist);
+      }
       respin = true;
       flags |= DCTZHIP_INFO_RESPUN;
       c->ctl_dirty = 1;                             // the first pass left its QT maxima behind

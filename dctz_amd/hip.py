@@ -104,6 +104,7 @@ _PROTOS = {
     "dctzhip_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_last_timings": (C.c_int, [C.c_void_p, C.POINTER(Timings)]),
     "dctzhip_set_speculation": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t]),
+    "dctzhip_set_spec_memory": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_set_one_launch": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_set_split": (C.c_int, [C.c_void_p, C.c_int]),
     "dctzhip_set_decode_memo": (C.c_int, [C.c_void_p, C.c_int]),
@@ -298,6 +299,10 @@ class Context:
     def set_speculation(self, on=True, min_elements=0):
         """Fused statistics behind a sampled guess of sf (include/dctz_hip.h, DCTZHIP_INFO_*)."""
         self._check(self.lib.dctzhip_set_speculation(self.h, int(on), int(min_elements)), "set_speculation")
+
+    def set_spec_memory(self, on=True):
+        """The sf guess from the last verified statistics of the same input instead of a sample (include/dctz_hip.h); counters 18 / 19."""
+        self._check(self.lib.dctzhip_set_spec_memory(self.h, int(on)), "set_spec_memory")
 
     def set_one_launch(self, on=True):
         """One kernel per call for arrays whose tiles are all resident at once (include/dctz_hip.h); off: the chain of kernels."""

@@ -108,6 +108,18 @@ int dctzhip_set_profiling(dctzhip_ctx *ctx, int on);
  * guess) and takes the full statistics pass first.  DCTZHIP_FUSE_SCALED=0: a pass of its
  * own behind the kernels, as before round 3. */
 int dctzhip_set_speculation(dctzhip_ctx *ctx, int on, size_t min_elements);
+/* The guess without a sample.  A speculative call (above) whose input -- the same d_in, n and dtype -- was compressed by
+ * the last two or more speculative calls with one and the same verified scaling factor guesses from the TRUE statistics of
+ * the last of them instead of sampling: the two statistics launches in front of the compress kernel fall away (a field of a
+ * time-stepping code, a snapshot slot).  The guess is verified exactly as a sampled one is and the streams never depend on
+ * it; a wrong one costs what a wrong sample costs (one re-run, then 8 calls on the full statistics pass) and doubles the
+ * number of verified sampled calls the input needs before it is trusted again (2, 4, ... at most 64).  The context
+ * remembers 8 inputs, the least recently used one replaced.  info->flags does not tell the two kinds of guess apart
+ * (DCTZHIP_INFO_STATS_FUSED / _RESPUN); dctzhip_debug_counter 18 / 19 do.  on == 0: every speculative call samples; either
+ * value clears what is remembered, and so does dctzhip_set_speculation(ctx, 0, ..).  An input the library owns (the filled
+ * copy of dctzhip_compress_masked without d_filled) is never remembered: such calls sample.  Turn it off for a caller that rotates
+ * unrelated fields through one buffer.  Default: on (env DCTZHIP_SPEC_MEMORY=0 turns it off). */
+int dctzhip_set_spec_memory(dctzhip_ctx *ctx, int on);
 int dctzhip_last_timings(dctzhip_ctx *ctx, dctzhip_timings *t);
 /* One launch per call.  An array whose tiles are all resident on the chip at once (up to about 8 M fp32 / 4 M fp64 elements:
  * 2048 / 1024 tiles of 64 blocks) is compressed -- and decompressed -- by ONE kernel: calc_data_stat, scaling, transform,
@@ -145,7 +157,8 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr, 11 / 12 workgroups and
  * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran), 13 / 14 / 15 items
  * in the list of the last dctzhip_decompress_boxes call, workgroups of its decode launch and the list's bound, 16 / 17
- * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again -- and knobs that
+ * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again, 18 / 19 guesses of the
+ * scaling factor taken from the remembered statistics of the same input that verified / that did not -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
  * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
