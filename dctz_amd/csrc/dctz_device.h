@@ -141,6 +141,10 @@ template <typename F> auto with_bool(bool b, F&& f) { return b ? f(std::true_typ
 template <typename F> auto with_mode_bool(int mode, bool b, F&& f) {
   return with_mode(mode, [&](auto M) { return with_bool(b, [&](auto B) { return f(decltype(M){}, B); }); });
 }
+// ... and with two flags: f(M, A, B)
+template <typename F> auto with_mode_bool2(int mode, bool a, bool b, F&& f) {
+  return with_mode_bool(mode, a, [&](auto M, auto A) { return with_bool(b, [&](auto B) { return f(decltype(M){}, decltype(A){}, B); }); });
+}
 
 // Per-call control block in device memory; zeroed by the first kernel of every compress call (k_stats_final) --
 // a decode call only ever sets `error`, and the host clears the block after a failed call.  The context has two: a
@@ -800,6 +804,29 @@ template <typename T> int ndfix_occupancy(int mode, int geom);
 template <typename T> void launch_ndfix_mark(const NdFixParams<T>& p, int mode, int geom, int grid, hipStream_t s);
 template <typename T> void launch_ndfix_emit(const NdFixEmitParams<T>& p, int geom, int grid, hipStream_t s);
 template <typename T> void launch_ndfix_apply(const NdFixApplyParams<T>& p, int geom, int grid, hipStream_t s);
+
+// Tile summaries of an array compressed in 8 x 8 / 4 x 4 x 4 tiles (dctz_kernels_ndsummary.hip: k_ndsummary; the total is
+// k_tile_summary_final's): SummaryParams' record per stream tile over the tile's real positions.  Streams and geometry as for
+// NdFixParams; the fields ra_tile_image reads carry NdBoxParams' names.
+template <typename T>
+struct NdSummaryParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[0 .. ntiles]
+  const T* tab;
+  const T* qtab;
+  Ctl* ctl;                        // error = 2: as RangeParams
+  const T* ref;                    // the original, prod d elements in C order (the REF instantiations only)
+  dctzhip_tile_summary_t* recs;    // ntiles records
+  unsigned n, nfull, ntiles, ac_count;   // n = 64 nfull
+  T sf, bin_width, range_min, range_max;
+  double eb;
+  unsigned nb[3];                  // blocks per axis
+  unsigned d[3];                   // extents of the array
+};
+template <typename T> int ndsummary_occupancy(int mode, int geom, bool ref);
+template <typename T> void launch_tile_summary_nd(const NdSummaryParams<T>& p, int mode, int geom, bool ref, int grid, hipStream_t s);
 
 // Missing values (dctz_kernels_mask.hip: k_mask_fill, k_mask_apply): a bit per element beside the streams, the holes filled
 // by copies inside each 64-element block (include/dctz_hip.h).  The mask travels as 32-bit pieces, two per word.

@@ -21,22 +21,6 @@
 
 namespace dctz {
 
-// The grid coordinates of block B (2-D: z = 0)
-template <int GEOM>
-__device__ __forceinline__ void ndfix_block(const unsigned B, const unsigned nbx, const unsigned nby, unsigned& bz, unsigned& by, unsigned& bx) {
-  const unsigned q = B / nbx;
-  bx = B - q * nbx;
-  bz = GEOM == GEOM_3D ? q / nby : 0u;
-  by = q - bz * nby;
-}
-// ... and the array coordinates of its in-block place j
-template <int GEOM>
-__device__ __forceinline__ void ndfix_place(const unsigned bz, const unsigned by, const unsigned bx, const unsigned j, unsigned& z, unsigned& y,
-                                            unsigned& x) {
-  if (GEOM == GEOM_3D) { z = bz * 4u + (j >> 4); y = by * 4u + ((j >> 2) & 3u); x = bx * 4u + (j & 3u); }
-  else { z = 0u; y = by * 8u + (j >> 3); x = bx * 8u + (j & 7u); }
-}
-
 template <typename T, int MODE, int GEOM>
 __global__ __launch_bounds__(64) void k_ndfix_mark(NdFixParams<T> p) {
   using G = NdImage<T, GEOM>;

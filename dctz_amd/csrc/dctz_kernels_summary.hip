@@ -30,39 +30,6 @@
 
 namespace dctz {
 
-constexpr double SUM_HUGE = 1.79769313486231570815e308;                // k_psnr's starting pair: min = +SUM_HUGE, max = -SUM_HUGE
-
-// The eight fields of a record in a lane's registers
-struct SumRec {
-  double v[8];                                                         // rmin, rmax, rsum, rsq, xmin, xmax, emax, esq
-  __device__ __forceinline__ void init() {
-    v[0] = SUM_HUGE; v[1] = -SUM_HUGE; v[2] = 0.0; v[3] = 0.0; v[4] = SUM_HUGE; v[5] = -SUM_HUGE; v[6] = 0.0; v[7] = 0.0;
-  }
-};
-// field f joins as a minimum (0, 4), a maximum (1, 5, 6) or a sum (2, 3, 7); a NaN is passed over by the first two
-__device__ __forceinline__ double sum_join(const int f, const double a, const double b) {
-  return (f == 0 || f == 4) ? fmin(a, b) : (f == 1 || f == 5 || f == 6) ? fmax(a, b) : a + b;
-}
-// ... over the wave: every lane ends with the same eight values (a butterfly; the partners' operands commute)
-template <int NF>
-__device__ __forceinline__ void sum_wave(SumRec& a) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-    for (int f = 0; f < NF; f++) a.v[f] = sum_join(f, a.v[f], __shfl_xor(a.v[f], d));
-  }
-}
-// lanes 0-7 hold field `lane` of the wave's record
-__device__ __forceinline__ double sum_field_of_lane(const SumRec& a, const int lane) {
-  double v = a.v[0];
-#pragma unroll
-  for (int f = 1; f < 8; f++) {
-    v = lane == f ? a.v[f] : v;
-    asm volatile("" : "+v"(v));                                        // seven selects, not a table in scratch memory indexed by the lane
-  }
-  return v;
-}
-
 // A lane's elements [J0, J1) of its block into its record: four running sums over j mod 4 (joined by the caller as
 // (0 + 1) + (2 + 3)); with REF against the same elements of the original in o[]
 template <typename T, bool REF, int J0, int J1>

@@ -1,5 +1,6 @@
 // dctz_nd_image.h -- the LDS image of a stream tile of an array compressed in 8 x 8 / 4 x 4 x 4 tiles, as the kernels that
-// walk it in row strips lay it out (dctz_kernels_ndbox.hip: k_decompress_ndbox; dctz_kernels_ndfix.hip: k_ndfix_mark).
+// walk it in row strips lay it out (dctz_kernels_ndbox.hip: k_decompress_ndbox; dctz_kernels_ndfix.hip: k_ndfix_mark;
+// dctz_kernels_ndsummary.hip: k_ndsummary), and the array coordinates of a stream position.
 #pragma once
 #include "dctz_kernel_common.h"
 
@@ -22,5 +23,21 @@ template <typename T, int GEOM> struct NdImage {
   static_assert(STRIDE % EPV == 0, "16-byte rows");
   static_assert(BYTES >= 63 * 64 * 4, "a dense tile's exact coefficients fit the image");
 };
+
+// The grid coordinates of block B (2-D: z = 0)
+template <int GEOM>
+__device__ __forceinline__ void ndfix_block(const unsigned B, const unsigned nbx, const unsigned nby, unsigned& bz, unsigned& by, unsigned& bx) {
+  const unsigned q = B / nbx;
+  bx = B - q * nbx;
+  bz = GEOM == GEOM_3D ? q / nby : 0u;
+  by = q - bz * nby;
+}
+// ... and the array coordinates of its in-block place j
+template <int GEOM>
+__device__ __forceinline__ void ndfix_place(const unsigned bz, const unsigned by, const unsigned bx, const unsigned j, unsigned& z, unsigned& y,
+                                            unsigned& x) {
+  if (GEOM == GEOM_3D) { z = bz * 4u + (j >> 4); y = by * 4u + ((j >> 2) & 3u); x = bx * 4u + (j & 3u); }
+  else { z = 0u; y = by * 8u + (j >> 3); x = bx * 8u + (j & 7u); }
+}
 
 }  // namespace dctz

@@ -104,6 +104,7 @@ struct dctzhip_ctx {
   unsigned* fix_cnt = nullptr;      // ... a count per tile, then the levels of k_fixup_scan
   size_t fix_cnt_cap = 0;           // entries
   int ndfix_occ[2][2][2] = {};      // dctzhip_fixup_build_nd: the same of k_ndfix_mark, [fp64][QT][3-D]; scratch as above
+  int ndsum_occ[2][2][2][2] = {};   // dctzhip_tile_summary_nd: the same of k_ndsummary, [fp64][QT][3-D][with an original]; scratch: sum_buf
   void* mask_filled = nullptr;      // dctzhip_compress_masked without d_filled: the filled copy
   size_t mask_filled_cap = 0;       // bytes
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
@@ -3133,6 +3134,78 @@ extern "C" int dctzhip_fixup_apply_nd(dctzhip_ctx* c, const uint32_t* d_fix_star
   return (dtype == DCTZHIP_F64)
              ? fixup_apply_nd_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, sh, lo, hi, t0, t1, (double*)d_out)
              : fixup_apply_nd_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, sh, lo, hi, t0, t1, (float*)d_out);
+}
+
+// ---- tile summaries of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndsummary.hip) ------------
+template <typename T>
+static int tile_summary_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                const uint32_t* d_index, const void* qtable_host, const NdShape& sh, double eb, double sf, int mode,
+                                const T* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+  hipStream_t s = c->stream;
+  const size_t n_lin = sh.nblk * 64;
+  const size_t m = dctzhip_summary_tiles(n_lin);
+  const size_t fin = total ? summary_final_slots(m) : 0;
+  { int rc = regrow(c, &c->sum_buf, &c->sum_cap, fin + (d_tiles ? 0 : m), sizeof(dctzhip_tile_summary_t)); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  NdSummaryParams<T> p;
+  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  p.ref = d_ref;
+  p.recs = d_tiles ? d_tiles : c->sum_buf + fin;
+  p.n = (unsigned)n_lin; p.nfull = (unsigned)sh.nblk; p.ntiles = (unsigned)m;
+  ndfix_axes(sh, p.nb, p.d);
+  const bool ref = d_ref != nullptr;
+  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
+  const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
+  int& occ = c->ndsum_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3][ref];
+  if (occ == 0) occ = std::max(ndsummary_occupancy<T>(mode, geom, ref), 1);
+  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+  launch_tile_summary_nd<T>(p, mode, geom, ref, (int)(p.ntiles < resident ? p.ntiles : resident), s);
+  SET_LAST(c, 1, "k_ndsummary<%s, %d, %d, %s>", tname<T>(), mode, geom, bname(ref));
+  dctzhip_tile_summary_t* ht = reinterpret_cast<dctzhip_tile_summary_t*>(c->h_pin + PIN_STATS);
+  if (total) {
+    const dctzhip_tile_summary_t* dt = launch_tile_summary_final(p.recs, m, c->sum_buf, s);
+    HIPCHK(c, hipMemcpyAsync(ht, dt, sizeof(*ht), hipMemcpyDeviceToHost, s));
+  }
+  const int rc = ra_finish(c);
+  if (rc == DCTZHIP_OK && total) *total = *ht;
+  return rc;
+}
+
+extern "C" int dctzhip_tile_summary_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                       const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb,
+                                       double sf, int mode, const void* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
+  int rc = check_common(c, n_lin, dtype, mode);
+  if (rc) return rc;
+  if (!d_tiles && !total) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: at least one of d_tiles and total must be given");
+  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  // (the original is read element by element at its own coordinates: the rows of a ragged array are not 16-byte aligned anyway)
+  if ((uintptr_t)d_ref & (elem_size(dtype) - 1)) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: the original must be aligned to its elements");
+  if ((uintptr_t)d_tiles & 7u) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: the records must be 8-byte aligned");
+  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  {
+    Span sp[6];
+    size_t m = 0;
+    add_span(sp, &m, d_bin, n_lin, SPAN_READ, 0);
+    add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_index, dctzhip_ac_index_len(n_lin) * sizeof(uint32_t), SPAN_READ, 0);
+    add_span(sp, &m, d_ref, n_orig * elem_size(dtype), SPAN_READ, 0);
+    add_span(sp, &m, d_tiles, dctzhip_summary_tiles(n_lin) * sizeof(dctzhip_tile_summary_t), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_tile_summary_nd", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? tile_summary_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
+                                            (const double*)d_ref, d_tiles, total)
+             : tile_summary_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
+                                           (const float*)d_ref, d_tiles, total);
 }
 
 // ---- missing values: a mask beside the streams (include/dctz_hip.h; dctz_kernels_mask.hip) ----------------------

@@ -1,11 +1,46 @@
 // dctz_summary_head.h -- the head of a stream tile that the tile summaries (dctz_kernels_summary.hip) and the correction
 // list (dctz_kernels_fixup.hip) share: one wave up to the 64 elements per lane that the decoders would write, and the LDS
-// such a wave needs when the original's tile follows the staged coefficients through the same buffer.
+// such a wave needs when the original's tile follows the staged coefficients through the same buffer.  The record of eight
+// doubles in a lane's registers and its join over the wave are here as well: the flat summaries and those of a tiled array
+// (dctz_kernels_ndsummary.hip) write the same record.
 #pragma once
 
 #include "dctz_kernel_common.h"
 
 namespace dctz {
+
+constexpr double SUM_HUGE = 1.79769313486231570815e308;                // k_psnr's starting pair: min = +SUM_HUGE, max = -SUM_HUGE
+
+// The eight fields of a record in a lane's registers
+struct SumRec {
+  double v[8];                                                         // rmin, rmax, rsum, rsq, xmin, xmax, emax, esq
+  __device__ __forceinline__ void init() {
+    v[0] = SUM_HUGE; v[1] = -SUM_HUGE; v[2] = 0.0; v[3] = 0.0; v[4] = SUM_HUGE; v[5] = -SUM_HUGE; v[6] = 0.0; v[7] = 0.0;
+  }
+};
+// field f joins as a minimum (0, 4), a maximum (1, 5, 6) or a sum (2, 3, 7); a NaN is passed over by the first two
+__device__ __forceinline__ double sum_join(const int f, const double a, const double b) {
+  return (f == 0 || f == 4) ? fmin(a, b) : (f == 1 || f == 5 || f == 6) ? fmax(a, b) : a + b;
+}
+// ... over the wave: every lane ends with the same eight values (a butterfly; the partners' operands commute)
+template <int NF>
+__device__ __forceinline__ void sum_wave(SumRec& a) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+    for (int f = 0; f < NF; f++) a.v[f] = sum_join(f, a.v[f], __shfl_xor(a.v[f], d));
+  }
+}
+// lanes 0-7 hold field `lane` of the wave's record
+__device__ __forceinline__ double sum_field_of_lane(const SumRec& a, const int lane) {
+  double v = a.v[0];
+#pragma unroll
+  for (int f = 1; f < 8; f++) {
+    v = lane == f ? a.v[f] : v;
+    asm volatile("" : "+v"(v));                                        // seven selects, not a table in scratch memory indexed by the lane
+  }
+  return v;
+}
 
 // Tile t by one wave up to the lane's 64 reconstructed elements in registers: ra_tile_image without the image.  `stage`
 // holds a dense tile's exact coefficients (63 * 64 floats).  False: the index disagrees with the tile's own flags or leaves
@@ -48,6 +83,46 @@ __device__ __forceinline__ bool summary_tile_values(const SummaryParams<T>& p, c
   __syncthreads();                                                     // the staged coefficients are consumed
   stage_free();
   block_inv<T, CTab<T>, GEOM_1D, (sizeof(T) == 4)>(x, tab);
+  if (scale) {
+#pragma unroll
+    for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                   // dctz-decomp-lib.c:494-511
+  }
+  return true;
+}
+
+// summary_tile_values for a stream tile of an array compressed in 8 x 8 / 4 x 4 x 4 tiles (GEOM): the lane's block comes out of
+// block_inv<GEOM>, x[j] is in-block place j (row-major in the brick).  Such streams hold whole blocks only (n = 64 nfull), so
+// the short block's branch is gone; a lane beyond the last block decodes zeros that its caller masks out.  P: NdSummaryParams<T>.
+template <typename T, int MODE, int GEOM, typename P>
+__device__ __forceinline__ bool summary_tile_values_nd(const P& p, const unsigned t, const int lane, const CTab<T> tab, const QtLanes<T>& qtl,
+                                                       const bool scale, float* const stage, T (&x)[64]) {
+  const unsigned blk = t * (unsigned)TILE_BLKS + (unsigned)lane;
+  unsigned w[16];
+  float dcv = 0.f;
+  if (blk < p.nfull) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(p.bin + (size_t)blk * 64);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u32x4 v = src[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    dcv = p.dc[blk];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] = 0u;
+  }
+  const unsigned cnt = block_flag_count(w);
+  const unsigned incl = wave_incl_scan(cnt);
+  const unsigned tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+  const unsigned s0 = p.idx[t], s1 = p.idx[t + 1];
+  if (s1 < s0 || s1 - s0 != tot || s1 > p.ac_count) return false;
+  for (unsigned i = (unsigned)lane; i < tot; i += 64u) stage[i] = p.ac[s0 + i];
+  __syncthreads();
+  unsigned ptr = incl - cnt;                                           // this block's first exact coefficient in the tile
+  dequantise_positional<T, MODE, false>(x, w, dcv, ptr, stage, (unsigned)(63 * 64 - 1), BinCentres<T, true>{p.bin_width, nullptr},
+                                        [&](int j) { return qtl.at(j); }, p.eb, p.range_min, p.range_max);
+  __syncthreads();                                                     // the staged coefficients are consumed
+  block_inv<T, CTab<T>, GEOM, (sizeof(T) == 4)>(x, tab);
   if (scale) {
 #pragma unroll
     for (int j = 0; j < 64; j++) x[j] = x[j] * p.sf;                   // dctz-decomp-lib.c:494-511

@@ -1995,19 +1995,21 @@ int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r) {
 }
 
 /* ------------------------------------------------------------------ dctz_tile_summary -- */
-/* Per-tile records of the reconstruction, and with var_ref of its error (include/dctz_hip.h: dctzhip_tile_summary), of a
- * flat container: the three sections inflated, the index built once, the original uploaded when given; records and total
- * alone come back.  Returns as dctz_decompress_box does. */
+/* Per-tile records of the reconstruction, and with var_ref of its error (include/dctz_hip.h: dctzhip_tile_summary,
+ * dctzhip_tile_summary_nd): the three sections inflated, the index built once, the original uploaded when given; records and
+ * total alone come back.  `tiled`: the container must be a DZND one (geometry and extents from the container, the original
+ * is the array in C order), else a flat one -- each entry point refuses the other kind.  Returns as dctz_decompress_box does. */
 _Static_assert(sizeof(dctz_tile_summary_t) == sizeof(dctzhip_tile_summary_t), "one record layout");
-int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary_t *tiles, dctz_tile_summary_t *total) {
+static int tile_summary_part(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary_t *tiles, dctz_tile_summary_t *total, int tiled) {
   const double t_begin = now_s();
   dzc_view v;
   dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
-  if (v.nd != 0) return -1;                                        /* tiled streams carry edge padding: out of scope */
-  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
+  if ((v.nd != 0) != (tiled != 0)) return -1;                      /* tiled streams carry edge padding: they need the geometry */
+  if (tiled && dzc_geometry(&v) != 0) return -1;                   /* a DZND container whose extents are none */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk, n_ref = v.n;  /* stream positions (tiled: edge padding included); elements */
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   if (n == 0 || (!tiles && !total)) return -1;
-  if (var_ref && ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n || !var_bytes(var_ref))) return -1;
+  if (var_ref && ((var_ref->datatype == DOUBLE) != (v.is_d != 0) || N_ref < 0 || (size_t)N_ref != n_ref || !var_bytes(var_ref))) return -1;
   const size_t m = dctzhip_summary_tiles(n);
 
   dev_streams s;
@@ -2015,15 +2017,17 @@ int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary
   dctzhip_ctx *c = s.c;
   double t0 = now_s();
   if (var_ref) {
-    grow(&g_dev.in, &g_dev.in_cap, n * ts);
-    if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n * ts) != DCTZHIP_OK) die("H2D original");
+    grow(&g_dev.in, &g_dev.in_cap, n_ref * ts);
+    if (dctzhip_memcpy_h2d(c, g_dev.in, var_bytes(var_ref), n_ref * ts) != DCTZHIP_OK) die("H2D original");
   }
   if (tiles) grow(&g_dev.out, &g_dev.out_cap, m * sizeof(dctzhip_tile_summary_t));
   s.t_h2d += now_s() - t0;
   t0 = now_s();
   dctzhip_tile_summary_t tot;
-  const int rc = dctzhip_tile_summary(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, var_ref ? g_dev.in : NULL,
-                                      tiles ? (dctzhip_tile_summary_t *)g_dev.out : NULL, total ? &tot : NULL);
+  const void *ref = var_ref ? g_dev.in : NULL;
+  dctzhip_tile_summary_t *recs = tiles ? (dctzhip_tile_summary_t *)g_dev.out : NULL;
+  const int rc = tiled ? dctzhip_tile_summary_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ref, recs, total ? &tot : NULL)
+                       : dctzhip_tile_summary(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ref, recs, total ? &tot : NULL);
   if (rc == DCTZHIP_E_ARG) return -1;                        /* the streams disagree with each other */
   if (rc != DCTZHIP_OK) die("dctzhip_tile_summary");
   const double t1s = now_s();
@@ -2031,6 +2035,12 @@ int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary
   if (total) memcpy(total, &tot, sizeof(tot));
   part_times(&s, t_begin, t0, t1s);
   return 1;
+}
+int dctz_tile_summary(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary_t *tiles, dctz_tile_summary_t *total) {
+  return tile_summary_part(var_z, var_ref, N_ref, tiles, total, 0);
+}
+int dctz_tile_summary_nd(t_var *var_z, t_var *var_ref, int N_ref, dctz_tile_summary_t *tiles, dctz_tile_summary_t *total) {
+  return tile_summary_part(var_z, var_ref, N_ref, tiles, total, 1);
 }
 
 /* ------------------------------------------ dctz_fixup_build, dctz_decompress_bounded -- */

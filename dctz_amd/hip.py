@@ -157,6 +157,9 @@ _PROTOS = {
     "dctzhip_tile_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                        C.POINTER(TileSummary)]),
+    "dctzhip_tile_summary_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.POINTER(TileSummary)]),
     "dctzhip_fixup_tiles": (C.c_size_t, [C.c_size_t]),
     "dctzhip_fixup_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_double, C.c_void_p,
@@ -700,6 +703,30 @@ class Context:
             self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb),
             float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
         self._check(rc, "dctzhip_tile_summary")
+        return recs, total
+
+    def tile_summary_nd(self, out, cnt, shape, dtype, eb, sf, index=None, mode=EC, qtable=None, ref=None):
+        """tile_summary() for the streams of compress_nd(): one record per stream tile (64 blocks of 8 x 8 / 4 x 4 x 4) of what
+        decompress_nd() rebuilds from the same arguments, over the array's own elements -- the edge padding of the streams
+        enters no field.  `ref`: the original, a contiguous 2-D or 3-D CUDA tensor of `shape` (it may be a slice of a larger
+        buffer; only element alignment is asked).  index=None builds the index over 64 * nd_blocks(shape).  Returns
+        (records, total) as tile_summary() does."""
+        t = self.torch
+        self._bind_stream()
+        shape = [int(v) for v in shape]
+        n_lin = self.nd_blocks(shape) * 64
+        if index is None:
+            index, _ = self.ac_index(out, n_lin)
+        if ref is not None:
+            assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and list(ref.shape) == shape
+        recs = t.empty((int(self.lib.dctzhip_summary_tiles(n_lin)), 8), dtype=t.float64, device=self.device)
+        total = TileSummary()
+        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        dims = (C.c_size_t * len(shape))(*shape)
+        rc = self.lib.dctzhip_tile_summary_nd(
+            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, len(shape), dims, _dt(dtype),
+            float(eb), float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
+        self._check(rc, "dctzhip_tile_summary_nd")
         return recs, total
 
     # ---- point-wise error bound (include/dctz_hip.h: a correction list beside the streams) ----

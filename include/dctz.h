@@ -209,6 +209,15 @@ typedef struct {             /* include/dctz_hip.h: dctzhip_tile_summary_t */
 } dctz_tile_summary_t;
 int dctz_tile_summary(t_var *var_z, t_var *var_ref /* or NULL */, int N_ref, dctz_tile_summary_t *tiles /* host, or NULL */,
                       dctz_tile_summary_t *total);
+/* dctz_tile_summary for a DZND container (ADDITION, EC and QT builds; include/dctz_hip.h: dctzhip_tile_summary_nd holds the
+ * definition and the order of the sums).  Geometry and extents come from the container; the records are per stream tile (64
+ * blocks of 8 x 8 / 4 x 4 x 4, row-major over the block grid) over the array's own elements -- the edge padding of the
+ * streams enters nothing.  var_ref->buf is the UNSCALED original in C order, N_ref = prod dims.  tiles (or NULL) receives
+ * ceil(64 nblk / 4096) records.  It goes through the same loader as the other partial readers; records and total alone are
+ * copied back.  Returns 1, or -1 for a flat container, a null total with null tiles, a reference of another type or length
+ * and streams that disagree with each other.  dctz_tile_summary keeps refusing DZND containers. */
+int dctz_tile_summary_nd(t_var *var_z, t_var *var_ref /* or NULL */, int N_ref, dctz_tile_summary_t *tiles /* host, or NULL */,
+                         dctz_tile_summary_t *total);
 /* Point-wise error bound (ADDITION, EC and QT builds, flat and DZND containers; include/dctz_hip.h, "point-wise error bound", holds the
  * definition).  dctz_fixup_build lists every element that dctz_decompress would rebuild from var_z further than `bound`
  * (absolute, in the data's units, >= 0) from the original, with the original's value, in one malloc'd self-describing block

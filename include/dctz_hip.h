@@ -532,9 +532,9 @@ int dctzhip_decompress_coarse_nd(dctzhip_ctx *ctx, const void *d_bin_index, cons
 /* Two questions about a compressed array that need no reconstruction in memory: how far is it from the original, and where
  * in it is anything worth decoding.  One record per stream tile (4096 elements, one index entry) of what dctzhip_decompress
  * would write there, reduced in registers; with the original at hand (d_ref) also of the error, tile by tile: an error map.
- * It reports the bound actually reached and promises none.  Flat 64-element blocks only (the streams of dctzhip_compress,
- * fp32 and fp64, EC and QT, the short last block included): the streams of dctzhip_compress_nd carry edge padding that
- * would have to be kept out of every reduction, which needs the geometry.
+ * It reports the bound actually reached and promises none.  Flat 64-element blocks (the streams of dctzhip_compress, fp32
+ * and fp64, EC and QT, the short last block included); the streams of dctzhip_compress_nd carry edge padding that has to be
+ * kept out of every reduction, which needs the geometry: they have dctzhip_tile_summary_nd below.
  *   r           the elements dctzhip_decompress writes for the same arguments, bit for bit.
  *   rmin, rmax, xmin, xmax, emax   exact.  Minima and maxima pass a NaN over (fmin / fmax, as dctzhip_psnr_terms does); a tile
  *               of nothing but NaNs reports the starting pair rmin = +DBL_MAX, rmax = -DBL_MAX.
@@ -567,6 +567,45 @@ int dctzhip_tile_summary(dctzhip_ctx *ctx, const void *d_bin_index, const float 
                          uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, size_t n, int dtype,
                          double error_bound, double sf, int mode, const void *d_ref /* or NULL */,
                          dctzhip_tile_summary_t *d_tiles /* or NULL */, dctzhip_tile_summary_t *total /* host, or NULL */);
+
+/* dctzhip_tile_summary for the streams of dctzhip_compress_nd (8 x 8 / 4 x 4 x 4 tiles): the same record, per stream tile, over
+ * the array's own elements.  Streams, ac_count, qtable_host, ndims, dims, dtype, error_bound, sf and mode are
+ * dctzhip_decompress_nd's; d_index is dctzhip_ac_index's over the 64 * dctzhip_nd_blocks(ndims, dims) stream positions, as
+ * for dctzhip_fixup_build_nd.
+ *   positions   as in dctzhip_fixup_build_nd: position q belongs to block q >> 6 (row-major over the block grid) at in-block
+ *               place q & 63 (row-major in the tile); it is REAL iff every coordinate is below its extent.  Record t covers
+ *               the real positions among [4096 t, min(4096 (t + 1), 64 nblk)); every block holds a real position, so no
+ *               record is empty.  There are dctzhip_summary_tiles(64 * nblk) records.  A padded position enters no field,
+ *               and the original is never read there, nor outside d_ref[0, prod dims).
+ *   r           the element dctzhip_decompress_nd writes at the same coordinates, bit for bit.
+ *   fields      as above: extremes exact and NaN-passing (a tile of nothing but NaNs: +DBL_MAX / -DBL_MAX), rsum, rsq and esq
+ *               summed in double, unfused, NaN-carrying; e = x - r and e * e in the data type; without d_ref the last four
+ *               fields are +0.0.
+ *   order       of a record's sums: fixed by dims and the geometry (e = 8 | 4 the tile edge), independent of the grid
+ *               launched, the context and the call count -- the same call gives the same bytes every time.
+ *               Without d_ref: lane b of a wave takes block b of the stream tile, places j = 0 .. 63 in order, into four
+ *               running sums by j mod 4, joined (0 + 1) + (2 + 3).  With d_ref: lane l takes, for s = 0 .. e - 1 and in-block
+ *               row i = 0 .. 64 / e - 1, in-row offset l mod e of the tile's block l / e + (64 / e) s, into two running sums
+ *               by i mod 2, joined 0 + 1.  Either way a position that is not real adds nothing, and the 64 lanes join in a
+ *               butterfly: partners 32, 16, 8, 4, 2, 1 lanes apart.  The r-fields with and without d_ref may differ in
+ *               their last digits (two orders).
+ *   d_ref       (or NULL) the ORIGINAL in C order, prod dims elements of dtype, aligned to its elements (the rows of a
+ *               ragged array are not 16-byte aligned, so nothing more is asked).
+ *   d_tiles, total   as above; total joins the records with the same reduction kernel, in an order that depends on the tile
+ *               count alone.  With d_ref, total's xmin, xmax and emax equal out[0 .. 2] of dctzhip_psnr_terms over the
+ *               original and dctzhip_decompress_nd's output exactly, and 20 log10((xmax - xmin) / sqrt(esq / prod dims)) is
+ *               calc_psnr.
+ *   refusals    before any launch, DCTZHIP_E_ARG: what dctzhip_fixup_build_nd refuses for the same arguments (ndims not 2
+ *               or 3, a zero extent, null or misaligned stream pointers, QT without a table), both d_tiles and total NULL, a
+ *               d_ref that is not aligned to its elements, a d_tiles that is not 8-byte aligned or overlaps an input.  On the
+ *               device: the index check above; a tile that fails reads no AC_exact, the call returns DCTZHIP_E_ARG and the
+ *               context stays usable.
+ * Host-synchronous on return; dctzhip_debug_last_kernel(ctx, 1, ...) names the summary kernel afterwards. */
+int dctzhip_tile_summary_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                            uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                            const size_t *dims, int dtype, double error_bound, double sf, int mode,
+                            const void *d_ref /* or NULL */, dctzhip_tile_summary_t *d_tiles /* or NULL */,
+                            dctzhip_tile_summary_t *total /* host, or NULL */);
 
 /* ---- point-wise error bound: a correction list beside the streams ------------ */
 /* DCTZ bounds the error of every COEFFICIENT; an element's error can reach about twice error_bound * sf.  The correction list
