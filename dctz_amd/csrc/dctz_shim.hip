@@ -95,16 +95,14 @@ struct dctzhip_ctx {
   int ra_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_decompress_range: resident workgroups per CU of k_decompress_range [fp64][QT] on this device (0: not asked yet)
   int box_occ[2][2] = {{0, 0}, {0, 0}};  // dctzhip_decompress_box: the same of k_decompress_box
   int ndbox_occ[2][2][2] = {};      // dctzhip_decompress_box_nd: the same of k_decompress_ndbox, [fp64][QT][3-D]
-  int sum_occ[2][2][2] = {};        // dctzhip_tile_summary: the same of k_tile_summary, [fp64][QT][with an original]
+  int sum_occ[2][2][3][2] = {};     // dctzhip_tile_summary / _nd: the same of k_tile_summary / k_ndsummary, [fp64][QT][geometry][with an original]
   dctzhip_tile_summary_t* sum_buf = nullptr;   // ... the levels of k_tile_summary_final, then the records of a call without d_tiles
   size_t sum_cap = 0;               // records
-  int fix_occ[2][2] = {{0, 0}, {0, 0}};   // dctzhip_fixup_build: the same of k_fixup_mark [fp64][QT]
+  int fix_occ[2][2][3] = {};        // dctzhip_fixup_build / _nd: the same of k_fixup_mark / k_ndfix_mark, [fp64][QT][geometry]
   unsigned long long* fix_mask = nullptr;   // ... a mask per block of the array
   size_t fix_mask_cap = 0;          // words
   unsigned* fix_cnt = nullptr;      // ... a count per tile, then the levels of k_fixup_scan
   size_t fix_cnt_cap = 0;           // entries
-  int ndfix_occ[2][2][2] = {};      // dctzhip_fixup_build_nd: the same of k_ndfix_mark, [fp64][QT][3-D]; scratch as above
-  int ndsum_occ[2][2][2][2] = {};   // dctzhip_tile_summary_nd: the same of k_ndsummary, [fp64][QT][3-D][with an original]; scratch: sum_buf
   void* mask_filled = nullptr;      // dctzhip_compress_masked without d_filled: the filled copy
   size_t mask_filled_cap = 0;       // bytes
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
@@ -2115,6 +2113,15 @@ static int ra_finish(dctzhip_ctx* c, unsigned* cnt_total = nullptr) {
   if (hc->error) return fail(c, DCTZHIP_E_INTERNAL, "in-kernel error flag set (code %u)", hc->error);
   return DCTZHIP_OK;
 }
+// The grid of a launch with one single-wave workgroup per unit of work, persistent only beyond what is resident at once.
+// What a unit is -- a candidate tile, a stream tile, a list item -- is said at the call.  slot: the context's (so its
+// device's) cache of the kernel's resident workgroups per CU, 0 = not asked yet; occupancy() asks.
+template <typename F>
+static unsigned resident_grid(dctzhip_ctx* c, int& slot, size_t units, F occupancy) {
+  if (slot == 0) slot = std::max(occupancy(), 1);
+  const size_t resident = (size_t)c->num_cu * (size_t)slot;
+  return (unsigned)(units < resident ? units : resident);
+}
 
 template <typename T>
 static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -2131,12 +2138,8 @@ static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const flo
   ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.n = (unsigned)n; p.nfull = nfull; p.lo = (unsigned)lo; p.hi = (unsigned)hi; p.t0 = t0; p.t1 = t1;
-  // one single-wave workgroup per tile of the range, persistent only beyond what is resident at once
-  int& occ = c->ra_occ[sizeof(T) == 8][mode == DCTZHIP_QT];    // (per context: the context's device)
-  if (occ == 0) occ = std::max(range_occupancy<T>(mode), 1);
-  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
-  const unsigned tiles = t1 - t0;
-  const int grid = (int)(tiles < resident ? tiles : resident);
+  // a workgroup per tile of the range
+  const int grid = (int)resident_grid(c, c->ra_occ[sizeof(T) == 8][mode == DCTZHIP_QT], t1 - t0, [&] { return range_occupancy<T>(mode); });
   // (no stage timings: dctzhip_last_timings keeps reporting the last compress / decompress call)
   launch_decompress_range<T>(p, mode, grid, with_rem, s);
   SET_LAST(c, 1, "k_decompress_range<%s, %d>", tname<T>(), mode);
@@ -2253,12 +2256,9 @@ static int decompress_box_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.n = (unsigned)n; p.nfull = nfull; p.t0 = t0; p.t1 = t1;
   p.box = box;
-  // one single-wave workgroup per candidate tile, persistent only beyond what is resident at once
-  int& occ = c->box_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
-  if (occ == 0) occ = std::max(box_occupancy<T>(mode), 1);
-  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
+  // a workgroup per candidate tile
   const unsigned tiles = t1 - t0;
-  const int grid = (int)(tiles < resident ? tiles : resident);
+  const int grid = (int)resident_grid(c, c->box_occ[sizeof(T) == 8][mode == DCTZHIP_QT], tiles, [&] { return box_occupancy<T>(mode); });
   c->box_grid = (unsigned)grid; c->box_tiles = tiles;
   launch_decompress_box<T>(p, mode, grid, with_rem, s);
   SET_LAST(c, 1, "k_decompress_box<%s, %d>", tname<T>(), mode);
@@ -2341,11 +2341,8 @@ static int decompress_boxes_impl(dctzhip_ctx* c, const uint8_t* d_bin, const flo
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.recs = lp.recs; p.items = c->mb_items; p.rem_boxes = reinterpret_cast<const unsigned*>(c->mb_dev + rec_bytes);
   p.cap = (unsigned)B; p.n = (unsigned)n; p.nfull = nfull;
-  // single-wave workgroups that take items: as many as are resident at once, at most one per item the list can hold
-  int& occ = c->mbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
-  if (occ == 0) occ = std::max(mbox_occupancy<T>(mode), 1);
-  const size_t resident = (size_t)c->num_cu * (size_t)occ;
-  const int grid = (int)std::min(resident, B);
+  // workgroups that take items off the list: at most one per item the list can hold
+  const int grid = (int)resident_grid(c, c->mbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT], B, [&] { return mbox_occupancy<T>(mode); });
   c->mbox_grid = (unsigned)grid; c->mbox_bound = (unsigned)B; c->mbox_items = 0;
   launch_boxlist_build(lp, s);
   launch_decompress_mbox<T>(p, mode, grid, nrem, s);
@@ -2573,20 +2570,17 @@ static int decompress_box_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const fl
     const unsigned bl = (unsigned)lo[i] / edge, bh = (unsigned)(hi[i] - 1) / edge;
     p.blocks.dim[a + 1] = (unsigned)sh.nb[i]; p.blocks.lo[a + 1] = bl; p.blocks.ext[a + 1] = bh - bl + 1u;
   }
-  // one single-wave workgroup per candidate tile, persistent only beyond what is resident at once
+  // a workgroup per candidate tile
   const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
-  int& occ = c->ndbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3];
-  if (occ == 0) occ = std::max(ndbox_occupancy<T>(mode, geom), 1);
-  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
   const unsigned tiles = t1 - t0;
+  int grid = (int)resident_grid(c, c->ndbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3], tiles, [&] { return ndbox_occupancy<T>(mode, geom); });
   // A heuristic, measured on two boxes of one volume only: the stride of the loop over tiles is kept ODD.  The hit tiles
   // of a box repeat with the tiles per block row and per block plane, even numbers for most shapes; with the even stride
   // 1024 the x-plane of a 512^3 volume (every other tile is hit) left half of the workgroups without a single hit tile:
   // 254 -> 142 us.  It does not balance the 64^3 brick (a workgroup still meets four hit tiles) and costs the full box
   // 3.5 % (369 -> 382 us).  An assignment that follows the hit tiles instead of the candidates is the real fix (EXPERIMENTS
   // section 22).
-  int grid = (int)(tiles < resident ? tiles : resident);
-  if (tiles > resident && grid > 1 && !(grid & 1)) grid--;
+  if (tiles > (unsigned)grid && grid > 1 && !(grid & 1)) grid--;       // (more tiles than the grid: the workgroups are persistent)
   c->box_grid = (unsigned)grid; c->box_tiles = tiles;
   launch_decompress_ndbox<T>(p, mode, geom, grid, s);
   SET_LAST(c, 1, "k_decompress_ndbox<%s, %d, %d>", tname<T>(), mode, geom);
@@ -2680,13 +2674,10 @@ static int decompress_coarse_impl(dctzhip_ctx* c, const uint8_t* d_bin, const fl
     if (nfull) launch_decompress_coarse_dc<T>(d_dc, d_out, nfull, (T)sf, s);
     SET_LAST(c, 1, "k_decompress_coarse_dc<%s>", tname<T>());
   } else {
-    // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
+    // a workgroup per stream tile
     if (p.ntiles) {
       int& occ = c->coarse_occ[sizeof(T) == 8][mode == DCTZHIP_QT][geom][k == 2 ? 0 : k == 4 ? 1 : k == 8 ? 2 : k == 16 ? 3 : 4];
-      if (occ == 0) occ = std::max(coarse_occupancy<T>(mode, geom, k), 1);
-      const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
-      const int grid = (int)(p.ntiles < resident ? p.ntiles : resident);
-      launch_decompress_coarse<T>(p, mode, geom, k, grid, s);
+      launch_decompress_coarse<T>(p, mode, geom, k, (int)resident_grid(c, occ, p.ntiles, [&] { return coarse_occupancy<T>(mode, geom, k); }), s);
     }
     if (geom == GEOM_1D) SET_LAST(c, 1, "k_decompress_coarse<%s, %d, %d>", tname<T>(), mode, k);
     else SET_LAST(c, 1, "k_decompress_coarse_nd<%s, %d, %d, %d>", tname<T>(), mode, geom, k);
@@ -2763,42 +2754,99 @@ extern "C" int dctzhip_decompress_coarse_nd(dctzhip_ctx* c, const void* d_bin, c
                                              factor, (float*)d_out);
 }
 
-// ---- tile summaries (include/dctz_hip.h; dctz_kernels_summary.hip) ----------------------------------------------
+// ---- what the summary and correction-list calls share: a whole stream set with its index, flat or tiled ----------
+namespace {
+// the arguments that describe the streams, as an entry point gets them (host only)
+struct StreamSet {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  uint32_t ac_count;
+  const uint32_t* index;
+  const void* qtable;             // on the host, 64 entries of the data type (QT mode)
+  size_t n;                       // positions the streams cover: the elements of a flat array, 64 per block of a tiled one
+  int dtype;
+  double eb, sf;
+  int mode;
+};
+}
+// The streams are given and aligned and QT mode has its table (none of these messages names the entry point); what the
+// call reads of them -- all of it -- goes in front of the caller's own ranges in sp.
+static int streams_check(dctzhip_ctx* c, const StreamSet& st, Span* sp, size_t* m) {
+  if (!st.bin || !st.dc || !st.index || (st.ac_count && !st.ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(st.bin) || ((uintptr_t)st.dc & 3u) || ((uintptr_t)st.ac & 3u) || ((uintptr_t)st.index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
+  if (st.mode == DCTZHIP_QT && !st.qtable) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  add_span(sp, m, st.bin, st.n, SPAN_READ, 0);
+  add_span(sp, m, st.dc, (st.n + 63) / 64 * sizeof(float), SPAN_READ, 0);
+  add_span(sp, m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, 0);
+  add_span(sp, m, st.index, dctzhip_ac_index_len(st.n) * sizeof(uint32_t), SPAN_READ, 0);
+  return DCTZHIP_OK;
+}
+// The entries of a correction list over n stream positions, written (SPAN_OUT, `entries` the capacity) or read (SPAN_READ,
+// `entries` the count): aligned, and their ranges behind the caller's in sp.  Whether the arrays must be given is the caller's.
+static int fixlist_check(dctzhip_ctx* c, const char* what, size_t n, int dtype, const uint32_t* d_fix_start, const uint16_t* d_fix_off,
+                         const void* d_fix_val, uint32_t entries, int kind, Span* sp, size_t* m) {
+  const size_t es = elem_size(dtype);
+  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "%s: fix_off must be 2-byte aligned, fix_val aligned to its elements", what);
+  add_span(sp, m, d_fix_start, (dctzhip_fixup_tiles(n) + 1) * sizeof(uint32_t), kind, 0);
+  add_span(sp, m, d_fix_off, (size_t)entries * sizeof(uint16_t), kind, 0);
+  add_span(sp, m, d_fix_val, (size_t)entries * es, kind, 0);
+  return DCTZHIP_OK;
+}
+// a tiled array in the last sh.nd of three axes
+static void ndfix_axes(const NdShape& sh, unsigned (&nb)[3], unsigned (&d)[3]) {
+  for (int i = 0; i < 3; i++) { nb[i] = 1u; d[i] = 1u; }
+  for (int i = 0; i < sh.nd; i++) { nb[3 - sh.nd + i] = (unsigned)sh.nb[i]; d[3 - sh.nd + i] = (unsigned)sh.d[i]; }
+}
+
+// ---- tile summaries (include/dctz_hip.h; dctz_kernels_summary.hip, tiled: dctz_kernels_ndsummary.hip) -----------
 extern "C" size_t dctzhip_summary_tiles(size_t n) { return (n + (size_t)TILE_ELEMS - 1) / (size_t)TILE_ELEMS; }
 
+// sh null: st.n elements in flat blocks; else the tiles of sh (st.n = 64 sh->nblk, no short block)
 template <typename T>
-static int tile_summary_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                             const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode, const T* d_ref,
-                             dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+static int tile_summary_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape* sh, const T* d_ref, dctzhip_tile_summary_t* d_tiles,
+                             dctzhip_tile_summary_t* total) {
   hipStream_t s = c->stream;
-  const unsigned nfull = (unsigned)(n / 64);
-  const int rem = (int)(n % 64);
-  const size_t m = dctzhip_summary_tiles(n);
+  const int mode = st.mode, geom = !sh ? GEOM_1D : sh->nd == 2 ? GEOM_2D : GEOM_3D;
+  const unsigned nfull = (unsigned)(st.n / 64);
+  const int rem = (int)(st.n % 64);
+  const size_t m = dctzhip_summary_tiles(st.n);
   const size_t fin = total ? summary_final_slots(m) : 0;
   { int rc = regrow(c, &c->sum_buf, &c->sum_cap, fin + (d_tiles ? 0 : m), sizeof(dctzhip_tile_summary_t)); if (rc) return rc; }
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
-  if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
-  SummaryParams<T> p;
-  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
-  p.rtab = reinterpret_cast<const T*>(c->rtab);
-  p.ref = d_ref;
-  p.recs = d_tiles ? d_tiles : c->sum_buf + fin;
-  p.n = (unsigned)n; p.nfull = nfull; p.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
+  dctzhip_tile_summary_t* recs = d_tiles ? d_tiles : c->sum_buf + fin;
   const bool ref = d_ref != nullptr;
-  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
-  int grid = 0;
-  if (p.ntiles) {
-    int& occ = c->sum_occ[sizeof(T) == 8][mode == DCTZHIP_QT][ref];
-    if (occ == 0) occ = std::max(summary_occupancy<T>(mode, ref), 1);
-    const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
-    grid = (int)(p.ntiles < resident ? p.ntiles : resident);
+  // what the two parameter blocks share; ntiles: the stream tiles that hold a whole block (of a tiled array all m)
+  auto fill = [&](auto& p) {
+    ra_fill_streams<T>(c, p, st.bin, st.dc, st.ac, st.index, st.ac_count, st.eb, st.sf);
+    p.ref = d_ref;
+    p.recs = recs;
+    p.n = (unsigned)st.n; p.nfull = nfull; p.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+  };
+  // a workgroup per stream tile
+  int& occ = c->sum_occ[sizeof(T) == 8][mode == DCTZHIP_QT][geom][ref];
+  if (!sh) {
+    if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+    SummaryParams<T> p;
+    fill(p);
+    p.rtab = reinterpret_cast<const T*>(c->rtab);
+    const int grid = p.ntiles ? (int)resident_grid(c, occ, p.ntiles, [&] { return summary_occupancy<T>(mode, ref); }) : 0;
+    launch_tile_summary<T>(p, mode, ref, grid, rem != 0, s);
+    SET_LAST(c, 1, "%s<%s, %d, %s>", grid ? "k_tile_summary" : "k_tile_summary_rem", tname<T>(), mode, bname(ref));
+  } else {
+    NdSummaryParams<T> p;
+    fill(p);
+    ndfix_axes(*sh, p.nb, p.d);
+    const int grid = (int)resident_grid(c, occ, p.ntiles, [&] { return ndsummary_occupancy<T>(mode, geom, ref); });
+    launch_tile_summary_nd<T>(p, mode, geom, ref, grid, s);
+    SET_LAST(c, 1, "k_ndsummary<%s, %d, %d, %s>", tname<T>(), mode, geom, bname(ref));
   }
-  launch_tile_summary<T>(p, mode, ref, grid, rem != 0, s);
-  SET_LAST(c, 1, "%s<%s, %d, %s>", grid ? "k_tile_summary" : "k_tile_summary_rem", tname<T>(), mode, bname(ref));
   dctzhip_tile_summary_t* ht = reinterpret_cast<dctzhip_tile_summary_t*>(c->h_pin + PIN_STATS);
   static_assert(sizeof(dctzhip_tile_summary_t) == 64 && PIN_CTL - PIN_STATS >= sizeof(dctzhip_tile_summary_t), "the total fits the pinned statistics slot");
   if (total) {
-    const dctzhip_tile_summary_t* dt = launch_tile_summary_final(p.recs, m, c->sum_buf, s);
+    const dctzhip_tile_summary_t* dt = launch_tile_summary_final(recs, m, c->sum_buf, s);
     HIPCHK(c, hipMemcpyAsync(ht, dt, sizeof(*ht), hipMemcpyDeviceToHost, s));
   }
   const int rc = ra_finish(c);
@@ -2806,89 +2854,142 @@ static int tile_summary_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* 
   return rc;
 }
 
+// what the two entry points share once the geometry is known; n_ref: the elements of the original
+static int tile_summary_call(dctzhip_ctx* c, const char* what, const StreamSet& st, const NdShape* sh, size_t n_ref, const void* d_ref,
+                             dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+  if (!d_tiles && !total) return fail(c, DCTZHIP_E_ARG, "%s: at least one of d_tiles and total must be given", what);
+  if ((uintptr_t)d_tiles & 7u) return fail(c, DCTZHIP_E_ARG, "%s: the records must be 8-byte aligned", what);
+  Span sp[6];
+  size_t m = 0;
+  int rc = streams_check(c, st, sp, &m);
+  if (rc) return rc;
+  add_span(sp, &m, d_ref, n_ref * elem_size(st.dtype), SPAN_READ, 0);
+  add_span(sp, &m, d_tiles, dctzhip_summary_tiles(st.n) * sizeof(dctzhip_tile_summary_t), SPAN_OUT, 0);
+  rc = check_spans(c, sp, m, what, nullptr);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return (st.dtype == DCTZHIP_F64) ? tile_summary_impl<double>(c, st, sh, (const double*)d_ref, d_tiles, total)
+                                   : tile_summary_impl<float>(c, st, sh, (const float*)d_ref, d_tiles, total);
+}
+
 extern "C" int dctzhip_tile_summary(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                     const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf, int mode,
                                     const void* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
   int rc = check_common(c, n, dtype, mode);
   if (rc) return rc;
-  if (!d_tiles && !total) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary: at least one of d_tiles and total must be given");
-  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
   if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary: the original must be 16-byte aligned");
-  if ((uintptr_t)d_tiles & 7u) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary: the records must be 8-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
-  {
-    Span sp[6];
-    size_t m = 0;
-    add_span(sp, &m, d_bin, n, SPAN_READ, 0);
-    add_span(sp, &m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index, dctzhip_ac_index_len(n) * sizeof(uint32_t), SPAN_READ, 0);
-    add_span(sp, &m, d_ref, n * elem_size(dtype), SPAN_READ, 0);
-    add_span(sp, &m, d_tiles, dctzhip_summary_tiles(n) * sizeof(dctzhip_tile_summary_t), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_tile_summary", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? tile_summary_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const double*)d_ref,
-                                         d_tiles, total)
-             : tile_summary_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const float*)d_ref,
-                                        d_tiles, total);
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  return tile_summary_call(c, "dctzhip_tile_summary", st, nullptr, n, d_ref, d_tiles, total);
 }
 
-// ---- correction list for a point-wise bound (include/dctz_hip.h; dctz_kernels_fixup.hip) -------------------------
+extern "C" int dctzhip_tile_summary_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                       const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb,
+                                       double sf, int mode, const void* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
+  if (!c) return DCTZHIP_E_ARG;
+  NdShape sh;
+  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
+  int rc = check_common(c, n_lin, dtype, mode);
+  if (rc) return rc;
+  // (the original is read element by element at its own coordinates: the rows of a ragged array are not 16-byte aligned anyway)
+  if ((uintptr_t)d_ref & (elem_size(dtype) - 1)) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: the original must be aligned to its elements");
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, dtype, eb, sf, mode};
+  return tile_summary_call(c, "dctzhip_tile_summary_nd", st, &sh, n_orig, d_ref, d_tiles, total);
+}
+
+// ---- correction list for a point-wise bound (include/dctz_hip.h; dctz_kernels_fixup.hip, tiled: dctz_kernels_ndfix.hip) ----
 extern "C" size_t dctzhip_fixup_tiles(size_t n) { return (n + (size_t)TILE_ELEMS - 1) / (size_t)TILE_ELEMS; }
 
+// sh as for tile_summary_impl; what: the entry point, for the report of a list that does not fit
 template <typename T>
-static int fixup_build_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                            const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode, const T* d_ref,
-                            double bound, uint32_t* d_fix_start, uint16_t* d_fix_off, T* d_fix_val, uint32_t capacity, uint32_t* count) {
+static int fixup_build_impl(dctzhip_ctx* c, const char* what, const StreamSet& st, const NdShape* sh, const T* d_ref, double bound,
+                            uint32_t* d_fix_start, uint16_t* d_fix_off, T* d_fix_val, uint32_t capacity, uint32_t* count) {
   hipStream_t s = c->stream;
-  const unsigned nfull = (unsigned)(n / 64);
-  const int rem = (int)(n % 64);
-  const size_t m = dctzhip_fixup_tiles(n);
-  { int rc = regrow(c, &c->fix_mask, &c->fix_mask_cap, (n + 63) / 64, sizeof(unsigned long long)); if (rc) return rc; }
+  const int mode = st.mode, geom = !sh ? GEOM_1D : sh->nd == 2 ? GEOM_2D : GEOM_3D;
+  const unsigned nfull = (unsigned)(st.n / 64);
+  const int rem = (int)(st.n % 64);
+  const size_t m = dctzhip_fixup_tiles(st.n);
+  { int rc = regrow(c, &c->fix_mask, &c->fix_mask_cap, (st.n + 63) / 64, sizeof(unsigned long long)); if (rc) return rc; }
   { int rc = regrow(c, &c->fix_cnt, &c->fix_cnt_cap, m + fixup_scan_slots(m), sizeof(unsigned)); if (rc) return rc; }
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
-  if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
-  FixupParams<T> p;
-  ra_fill_streams<T>(c, p.s, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
-  p.s.rtab = reinterpret_cast<const T*>(c->rtab);
-  p.s.ref = d_ref;
-  p.s.recs = nullptr;
-  p.s.n = (unsigned)n; p.s.nfull = nfull; p.s.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
-  p.bound = (T)bound;
-  p.mask = c->fix_mask;
-  p.tile_cnt = c->fix_cnt;
-  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
-  unsigned resident = (unsigned)c->num_cu;
-  int grid = 0;
-  if (p.s.ntiles) {
-    int& occ = c->fix_occ[sizeof(T) == 8][mode == DCTZHIP_QT];
-    if (occ == 0) occ = std::max(fixup_occupancy<T>(mode), 1);
-    resident = (unsigned)c->num_cu * (unsigned)occ;
-    grid = (int)(p.s.ntiles < resident ? p.s.ntiles : resident);
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
+  // what the two parameter blocks share; q: where a block keeps the streams.  ntiles as for tile_summary_impl
+  auto fill = [&](auto& p, auto& q) {
+    ra_fill_streams<T>(c, q, st.bin, st.dc, st.ac, st.index, st.ac_count, st.eb, st.sf);
+    q.ref = d_ref;
+    q.n = (unsigned)st.n; q.nfull = nfull; q.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+    p.bound = (T)bound;
+    p.mask = c->fix_mask;
+    p.tile_cnt = c->fix_cnt;
+  };
+  // a workgroup per stream tile
+  int& occ = c->fix_occ[sizeof(T) == 8][mode == DCTZHIP_QT][geom];
+  if (!sh) {
+    if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
+    FixupParams<T> p;
+    fill(p, p.s);
+    p.s.rtab = reinterpret_cast<const T*>(c->rtab);
+    p.s.recs = nullptr;
+    const int grid = p.s.ntiles ? (int)resident_grid(c, occ, p.s.ntiles, [&] { return fixup_occupancy<T>(mode); }) : 0;
+    launch_fixup_mark<T>(p, mode, grid, rem != 0, s);
+    SET_LAST(c, 1, "%s<%s, %d>", grid ? "k_fixup_mark" : "k_fixup_mark_rem", tname<T>(), mode);
+  } else {
+    NdFixParams<T> p;
+    fill(p, p);
+    ndfix_axes(*sh, p.nb, p.d);
+    const int grid = (int)resident_grid(c, occ, p.ntiles, [&] { return ndfix_occupancy<T>(mode, geom); });
+    launch_ndfix_mark<T>(p, mode, geom, grid, s);
+    SET_LAST(c, 1, "k_ndfix_mark<%s, %d, %d>", tname<T>(), mode, geom);
   }
-  launch_fixup_mark<T>(p, mode, grid, rem != 0, s);
-  SET_LAST(c, 1, "%s<%s, %d>", grid ? "k_fixup_mark" : "k_fixup_mark_rem", tname<T>(), mode);
   launch_fixup_scan(c->fix_cnt, m, d_fix_start, c->fix_cnt + m, c->ctl, s);
   if (d_fix_off) {
     // behind the scan in stream order; the kernel itself stands back if the list does not fit or a tile was refused
-    FixupEmitParams<T> e;
-    e.mask = c->fix_mask; e.fix_start = d_fix_start; e.ref = d_ref; e.fix_off = d_fix_off; e.fix_val = d_fix_val; e.ctl = c->ctl;
-    e.n = (unsigned)n; e.capacity = capacity;
-    const unsigned g = (unsigned)std::min<size_t>(m, (size_t)c->num_cu * 32);      // (a few registers, no LDS: eight waves per SIMD)
-    launch_fixup_emit<T>(e, (int)g, s);
+    auto fill_emit = [&](auto& e) {
+      e.mask = c->fix_mask; e.fix_start = d_fix_start; e.ref = d_ref; e.fix_off = d_fix_off; e.fix_val = d_fix_val; e.ctl = c->ctl;
+      e.capacity = capacity;
+    };
+    const int g = (int)std::min<size_t>(m, (size_t)c->num_cu * 32);                 // (a few registers, no LDS: eight waves per SIMD)
+    if (!sh) {
+      FixupEmitParams<T> e;
+      fill_emit(e);
+      e.n = (unsigned)st.n;
+      launch_fixup_emit<T>(e, g, s);
+    } else {
+      NdFixEmitParams<T> e;
+      fill_emit(e);
+      e.nblk = nfull; e.ntiles = (unsigned)m;
+      ndfix_axes(*sh, e.nb, e.d);
+      launch_ndfix_emit<T>(e, geom, g, s);
+    }
   }
   unsigned total = 0;
   const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
   if (rc) return rc;
   *count = total;
-  if (d_fix_off && total > capacity)
-    return fail(c, DCTZHIP_E_SPACE, "dctzhip_fixup_build: %u entries do not fit the capacity of %u", total, capacity);
+  if (d_fix_off && total > capacity) return fail(c, DCTZHIP_E_SPACE, "%s: %u entries do not fit the capacity of %u", what, total, capacity);
   return DCTZHIP_OK;
+}
+
+// what the two entry points share once the geometry is known; n_ref: the elements of the original
+static int fixup_build_call(dctzhip_ctx* c, const char* what, const StreamSet& st, const NdShape* sh, size_t n_ref, const void* d_ref,
+                            double bound, uint32_t* d_fix_start, uint16_t* d_fix_off, void* d_fix_val, uint32_t capacity, uint32_t* count) {
+  if (!d_ref || !count) return fail(c, DCTZHIP_E_ARG, "%s: the original and count must be given", what);
+  if (!(bound >= 0.0) || std::isinf(bound)) return fail(c, DCTZHIP_E_ARG, "%s: the bound must be finite and >= 0", what);
+  if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "%s: the original must be 16-byte aligned", what);
+  if (!d_fix_start || ((uintptr_t)d_fix_start & 3u)) return fail(c, DCTZHIP_E_ARG, "%s: fix_start must be given, 4-byte aligned", what);
+  if ((d_fix_off == nullptr) != (d_fix_val == nullptr)) return fail(c, DCTZHIP_E_ARG, "%s: fix_off and fix_val must both be given or both be NULL", what);
+  Span sp[8];
+  size_t m = 0;
+  int rc = streams_check(c, st, sp, &m);
+  if (rc) return rc;
+  add_span(sp, &m, d_ref, n_ref * elem_size(st.dtype), SPAN_READ, 0);
+  rc = fixlist_check(c, what, st.n, st.dtype, d_fix_start, d_fix_off, d_fix_val, capacity, SPAN_OUT, sp, &m);
+  if (rc) return rc;
+  rc = check_spans(c, sp, m, what, nullptr);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return (st.dtype == DCTZHIP_F64)
+             ? fixup_build_impl<double>(c, what, st, sh, (const double*)d_ref, bound, d_fix_start, d_fix_off, (double*)d_fix_val, capacity, count)
+             : fixup_build_impl<float>(c, what, st, sh, (const float*)d_ref, bound, d_fix_start, d_fix_off, (float*)d_fix_val, capacity, count);
 }
 
 extern "C" int dctzhip_fixup_build(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -2897,139 +2998,8 @@ extern "C" int dctzhip_fixup_build(dctzhip_ctx* c, const void* d_bin, const floa
                                    uint32_t capacity, uint32_t* count) {
   int rc = check_common(c, n, dtype, mode);
   if (rc) return rc;
-  if (!d_ref || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: the original and count must be given");
-  if (!(bound >= 0.0) || std::isinf(bound)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: the bound must be finite and >= 0");
-  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: the original must be 16-byte aligned");
-  if (!d_fix_start || ((uintptr_t)d_fix_start & 3u)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: fix_start must be given, 4-byte aligned");
-  if ((d_fix_off == nullptr) != (d_fix_val == nullptr))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: fix_off and fix_val must both be given or both be NULL");
-  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (elem_size(dtype) - 1)))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build: fix_off must be 2-byte aligned, fix_val aligned to its elements");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
-  {
-    Span sp[8];
-    size_t m = 0;
-    add_span(sp, &m, d_bin, n, SPAN_READ, 0);
-    add_span(sp, &m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index, dctzhip_ac_index_len(n) * sizeof(uint32_t), SPAN_READ, 0);
-    add_span(sp, &m, d_ref, n * elem_size(dtype), SPAN_READ, 0);
-    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n) + 1) * sizeof(uint32_t), SPAN_OUT, 0);
-    add_span(sp, &m, d_fix_off, (size_t)capacity * sizeof(uint16_t), SPAN_OUT, 0);
-    add_span(sp, &m, d_fix_val, (size_t)capacity * elem_size(dtype), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_fixup_build", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? fixup_build_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const double*)d_ref,
-                                        bound, d_fix_start, d_fix_off, (double*)d_fix_val, capacity, count)
-             : fixup_build_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, (const float*)d_ref,
-                                       bound, d_fix_start, d_fix_off, (float*)d_fix_val, capacity, count);
-}
-
-template <typename T>
-static int fixup_apply_impl(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const T* d_fix_val, uint32_t count, size_t n,
-                            const BoxGeo& box, size_t first, size_t last, T* d_out) {
-  hipStream_t s = c->stream;
-  { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
-  FixupApplyParams<T> p;
-  p.fix_start = d_fix_start; p.fix_off = d_fix_off; p.fix_val = d_fix_val; p.out = d_out; p.ctl = c->ctl;
-  p.n = (unsigned)n; p.count = count;
-  p.t0 = (unsigned)(first / TILE_ELEMS); p.t1 = (unsigned)(last / TILE_ELEMS + 1);
-  p.box = box;
-  const unsigned tiles = p.t1 - p.t0, resident = (unsigned)c->num_cu * 32u;          // (a few registers, no LDS: eight waves per SIMD)
-  launch_fixup_apply<T>(p, (int)(tiles < resident ? tiles : resident), s);
-  SET_LAST(c, 1, "k_fixup_apply<%s>", tname<T>());
-  return ra_finish(c);
-}
-
-extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val, uint32_t count,
-                                   size_t n, int dtype, int ndim, const size_t* dims, const size_t* lo, const size_t* hi, void* d_out) {
-  int rc = check_common(c, n, dtype, DCTZHIP_EC);
-  if (rc) return rc;
-  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
-  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: null dims, lo or hi");
-  size_t cnt = 1, first = 0, last = 0;
-  rc = box_extents(c, "dctzhip_fixup_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
-  if (rc) return rc;
-  const size_t es = elem_size(dtype);
-  if (!d_fix_start || !d_out || ((uintptr_t)d_fix_start & 3u) || ((uintptr_t)d_out & (es - 1)))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: fix_start and the output must be given, 4-byte / element aligned");
-  if (count > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: count %u exceeds n = %zu", count, n);
-  if (count && (!d_fix_off || !d_fix_val)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: null fix_off or fix_val");
-  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (es - 1)))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: fix_off must be 2-byte aligned, fix_val aligned to its elements");
-  {
-    Span sp[4];
-    size_t m = 0;
-    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n) + 1) * sizeof(uint32_t), SPAN_READ, 0);
-    add_span(sp, &m, d_fix_off, (size_t)count * sizeof(uint16_t), SPAN_READ, 0);
-    add_span(sp, &m, d_fix_val, (size_t)count * es, SPAN_READ, 0);
-    add_span(sp, &m, d_out, cnt * es, SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_fixup_apply", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const BoxGeo box = canonical_box(ndim, dims, lo, hi);
-  return (dtype == DCTZHIP_F64)
-             ? fixup_apply_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, n, box, first, last, (double*)d_out)
-             : fixup_apply_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, n, box, first, last, (float*)d_out);
-}
-
-// ---- correction list of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndfix.hip) ----------------
-// the array in the last sh.nd of three axes
-static void ndfix_axes(const NdShape& sh, unsigned (&nb)[3], unsigned (&d)[3]) {
-  for (int i = 0; i < 3; i++) { nb[i] = 1u; d[i] = 1u; }
-  for (int i = 0; i < sh.nd; i++) { nb[3 - sh.nd + i] = (unsigned)sh.nb[i]; d[3 - sh.nd + i] = (unsigned)sh.d[i]; }
-}
-
-template <typename T>
-static int fixup_build_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                               const uint32_t* d_index, const void* qtable_host, const NdShape& sh, double eb, double sf, int mode,
-                               const T* d_ref, double bound, uint32_t* d_fix_start, uint16_t* d_fix_off, T* d_fix_val, uint32_t capacity,
-                               uint32_t* count) {
-  hipStream_t s = c->stream;
-  const size_t n_lin = sh.nblk * 64;
-  const size_t m = dctzhip_fixup_tiles(n_lin);
-  { int rc = regrow(c, &c->fix_mask, &c->fix_mask_cap, sh.nblk, sizeof(unsigned long long)); if (rc) return rc; }
-  { int rc = regrow(c, &c->fix_cnt, &c->fix_cnt_cap, m + fixup_scan_slots(m), sizeof(unsigned)); if (rc) return rc; }
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
-  NdFixParams<T> p;
-  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
-  p.ref = d_ref;
-  p.mask = c->fix_mask;
-  p.tile_cnt = c->fix_cnt;
-  p.n = (unsigned)n_lin; p.nfull = (unsigned)sh.nblk; p.ntiles = (unsigned)m;
-  p.bound = (T)bound;
-  ndfix_axes(sh, p.nb, p.d);
-  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
-  const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
-  int& occ = c->ndfix_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3];
-  if (occ == 0) occ = std::max(ndfix_occupancy<T>(mode, geom), 1);
-  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
-  launch_ndfix_mark<T>(p, mode, geom, (int)(p.ntiles < resident ? p.ntiles : resident), s);
-  SET_LAST(c, 1, "k_ndfix_mark<%s, %d, %d>", tname<T>(), mode, geom);
-  launch_fixup_scan(c->fix_cnt, m, d_fix_start, c->fix_cnt + m, c->ctl, s);
-  if (d_fix_off) {
-    // behind the scan in stream order; the kernel itself stands back if the list does not fit or a tile was refused
-    NdFixEmitParams<T> e;
-    e.mask = c->fix_mask; e.fix_start = d_fix_start; e.ref = d_ref; e.fix_off = d_fix_off; e.fix_val = d_fix_val; e.ctl = c->ctl;
-    e.nblk = (unsigned)sh.nblk; e.ntiles = (unsigned)m; e.capacity = capacity;
-    ndfix_axes(sh, e.nb, e.d);
-    const unsigned g = (unsigned)std::min<size_t>(m, (size_t)c->num_cu * 32);      // (a few registers, no LDS: eight waves per SIMD)
-    launch_ndfix_emit<T>(e, geom, (int)g, s);
-  }
-  unsigned total = 0;
-  const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
-  if (rc) return rc;
-  *count = total;
-  if (d_fix_off && total > capacity)
-    return fail(c, DCTZHIP_E_SPACE, "dctzhip_fixup_build_nd: %u entries do not fit the capacity of %u", total, capacity);
-  return DCTZHIP_OK;
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  return fixup_build_call(c, "dctzhip_fixup_build", st, nullptr, n, d_ref, bound, d_fix_start, d_fix_off, d_fix_val, capacity, count);
 }
 
 extern "C" int dctzhip_fixup_build_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -3042,55 +3012,78 @@ extern "C" int dctzhip_fixup_build_nd(dctzhip_ctx* c, const void* d_bin, const f
   const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
   int rc = check_common(c, n_lin, dtype, mode);
   if (rc) return rc;
-  if (!d_ref || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: the original and count must be given");
-  if (!(bound >= 0.0) || std::isinf(bound)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: the bound must be finite and >= 0");
-  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (!aligned16(d_ref)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: the original must be 16-byte aligned");
-  if (!d_fix_start || ((uintptr_t)d_fix_start & 3u)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: fix_start must be given, 4-byte aligned");
-  if ((d_fix_off == nullptr) != (d_fix_val == nullptr))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: fix_off and fix_val must both be given or both be NULL");
-  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (elem_size(dtype) - 1)))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_build_nd: fix_off must be 2-byte aligned, fix_val aligned to its elements");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
-  {
-    Span sp[8];
-    size_t m = 0;
-    add_span(sp, &m, d_bin, n_lin, SPAN_READ, 0);
-    add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index, dctzhip_ac_index_len(n_lin) * sizeof(uint32_t), SPAN_READ, 0);
-    add_span(sp, &m, d_ref, n_orig * elem_size(dtype), SPAN_READ, 0);
-    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n_lin) + 1) * sizeof(uint32_t), SPAN_OUT, 0);
-    add_span(sp, &m, d_fix_off, (size_t)capacity * sizeof(uint16_t), SPAN_OUT, 0);
-    add_span(sp, &m, d_fix_val, (size_t)capacity * elem_size(dtype), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_fixup_build_nd", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? fixup_build_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
-                                           (const double*)d_ref, bound, d_fix_start, d_fix_off, (double*)d_fix_val, capacity, count)
-             : fixup_build_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
-                                          (const float*)d_ref, bound, d_fix_start, d_fix_off, (float*)d_fix_val, capacity, count);
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, dtype, eb, sf, mode};
+  return fixup_build_call(c, "dctzhip_fixup_build_nd", st, &sh, n_orig, d_ref, bound, d_fix_start, d_fix_off, d_fix_val, capacity, count);
 }
 
+// sh null: the box of the flat n-element array, its stream tiles [t0, t1) of 4096 elements; else the box [lo, hi) of the
+// tiled array, the stream tiles [t0, t1) of 64 blocks (n = 64 sh->nblk)
 template <typename T>
-static int fixup_apply_nd_impl(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const T* d_fix_val, uint32_t count,
-                               const NdShape& sh, const size_t* lo, const size_t* hi, unsigned t0, unsigned t1, T* d_out) {
+static int fixup_apply_impl(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const T* d_fix_val, uint32_t count, size_t n,
+                            const NdShape* sh, const BoxGeo* box, const size_t* lo, const size_t* hi, unsigned t0, unsigned t1, T* d_out) {
   hipStream_t s = c->stream;
   { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
-  NdFixApplyParams<T> p;
-  p.fix_start = d_fix_start; p.fix_off = d_fix_off; p.fix_val = d_fix_val; p.out = d_out; p.ctl = c->ctl;
-  p.nblk = (unsigned)sh.nblk; p.ntiles = (unsigned)dctzhip_fixup_tiles(sh.nblk * 64); p.count = count; p.t0 = t0; p.t1 = t1;
-  ndfix_axes(sh, p.nb, p.d);
-  for (int i = 0; i < 3; i++) { p.lo[i] = 0u; p.ext[i] = 1u; }
-  for (int i = 0; i < sh.nd; i++) { p.lo[3 - sh.nd + i] = (unsigned)lo[i]; p.ext[3 - sh.nd + i] = (unsigned)(hi[i] - lo[i]); }
+  auto fill = [&](auto& p) {
+    p.fix_start = d_fix_start; p.fix_off = d_fix_off; p.fix_val = d_fix_val; p.out = d_out; p.ctl = c->ctl;
+    p.count = count; p.t0 = t0; p.t1 = t1;
+  };
   const unsigned tiles = t1 - t0, resident = (unsigned)c->num_cu * 32u;              // (a few registers, no LDS: eight waves per SIMD)
-  launch_ndfix_apply<T>(p, sh.nd == 2 ? GEOM_2D : GEOM_3D, (int)(tiles < resident ? tiles : resident), s);
-  SET_LAST(c, 1, "k_ndfix_apply<%s, %d>", tname<T>(), sh.nd == 2 ? GEOM_2D : GEOM_3D);
+  const int grid = (int)(tiles < resident ? tiles : resident);
+  if (!sh) {
+    FixupApplyParams<T> p;
+    fill(p);
+    p.n = (unsigned)n;
+    p.box = *box;
+    launch_fixup_apply<T>(p, grid, s);
+    SET_LAST(c, 1, "k_fixup_apply<%s>", tname<T>());
+  } else {
+    const int geom = sh->nd == 2 ? GEOM_2D : GEOM_3D;
+    NdFixApplyParams<T> p;
+    fill(p);
+    p.nblk = (unsigned)sh->nblk; p.ntiles = (unsigned)dctzhip_fixup_tiles(n);
+    ndfix_axes(*sh, p.nb, p.d);
+    for (int i = 0; i < 3; i++) { p.lo[i] = 0u; p.ext[i] = 1u; }
+    for (int i = 0; i < sh->nd; i++) { p.lo[3 - sh->nd + i] = (unsigned)lo[i]; p.ext[3 - sh->nd + i] = (unsigned)(hi[i] - lo[i]); }
+    launch_ndfix_apply<T>(p, geom, grid, s);
+    SET_LAST(c, 1, "k_ndfix_apply<%s, %d>", tname<T>(), geom);
+  }
   return ra_finish(c);
+}
+
+// what the two entry points share once the box is known to lie in the array; n: the stream positions, cnt: the elements of the box
+static int fixup_apply_call(dctzhip_ctx* c, const char* what, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val,
+                            uint32_t count, size_t n, int dtype, const NdShape* sh, const BoxGeo* box, const size_t* lo, const size_t* hi,
+                            unsigned t0, unsigned t1, size_t cnt, void* d_out) {
+  const size_t es = elem_size(dtype);
+  if (!d_fix_start || !d_out || ((uintptr_t)d_fix_start & 3u) || ((uintptr_t)d_out & (es - 1)))
+    return fail(c, DCTZHIP_E_ARG, "%s: fix_start and the output must be given, 4-byte / element aligned", what);
+  if (count && (!d_fix_off || !d_fix_val)) return fail(c, DCTZHIP_E_ARG, "%s: null fix_off or fix_val", what);
+  Span sp[4];
+  size_t m = 0;
+  int rc = fixlist_check(c, what, n, dtype, d_fix_start, d_fix_off, d_fix_val, count, SPAN_READ, sp, &m);
+  if (rc) return rc;
+  add_span(sp, &m, d_out, cnt * es, SPAN_OUT, 0);
+  rc = check_spans(c, sp, m, what, nullptr);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64)
+             ? fixup_apply_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, n, sh, box, lo, hi, t0, t1, (double*)d_out)
+             : fixup_apply_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, n, sh, box, lo, hi, t0, t1, (float*)d_out);
+}
+
+extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val, uint32_t count,
+                                   size_t n, int dtype, int ndim, const size_t* dims, const size_t* lo, const size_t* hi, void* d_out) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
+  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: null dims, lo or hi");
+  size_t cnt = 1, first = 0, last = 0;
+  rc = box_extents(c, "dctzhip_fixup_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  if (rc) return rc;
+  if (count > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: count %u exceeds n = %zu", count, n);
+  const BoxGeo box = canonical_box(ndim, dims, lo, hi);
+  return fixup_apply_call(c, "dctzhip_fixup_apply", d_fix_start, d_fix_off, d_fix_val, count, n, dtype, nullptr, &box, nullptr, nullptr,
+                          (unsigned)(first / TILE_ELEMS), (unsigned)(last / TILE_ELEMS + 1), cnt, d_out);
 }
 
 extern "C" int dctzhip_fixup_apply_nd(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val,
@@ -3112,100 +3105,9 @@ extern "C" int dctzhip_fixup_apply_nd(dctzhip_ctx* c, const uint32_t* d_fix_star
     first = first * sh.nb[i] + lo[i] / edge;
     last = last * sh.nb[i] + (hi[i] - 1) / edge;
   }
-  const size_t es = elem_size(dtype);
-  if (!d_fix_start || !d_out || ((uintptr_t)d_fix_start & 3u) || ((uintptr_t)d_out & (es - 1)))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: fix_start and the output must be given, 4-byte / element aligned");
   if (count > n_orig) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: count %u exceeds the array's %zu elements", count, n_orig);
-  if (count && (!d_fix_off || !d_fix_val)) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: null fix_off or fix_val");
-  if (((uintptr_t)d_fix_off & 1u) || ((uintptr_t)d_fix_val & (es - 1)))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: fix_off must be 2-byte aligned, fix_val aligned to its elements");
-  {
-    Span sp[4];
-    size_t m = 0;
-    add_span(sp, &m, d_fix_start, (dctzhip_fixup_tiles(n_lin) + 1) * sizeof(uint32_t), SPAN_READ, 0);
-    add_span(sp, &m, d_fix_off, (size_t)count * sizeof(uint16_t), SPAN_READ, 0);
-    add_span(sp, &m, d_fix_val, (size_t)count * es, SPAN_READ, 0);
-    add_span(sp, &m, d_out, cnt * es, SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_fixup_apply_nd", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const unsigned t0 = (unsigned)(first / TILE_BLKS), t1 = (unsigned)(last / TILE_BLKS + 1);
-  return (dtype == DCTZHIP_F64)
-             ? fixup_apply_nd_impl<double>(c, d_fix_start, d_fix_off, (const double*)d_fix_val, count, sh, lo, hi, t0, t1, (double*)d_out)
-             : fixup_apply_nd_impl<float>(c, d_fix_start, d_fix_off, (const float*)d_fix_val, count, sh, lo, hi, t0, t1, (float*)d_out);
-}
-
-// ---- tile summaries of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndsummary.hip) ------------
-template <typename T>
-static int tile_summary_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                const uint32_t* d_index, const void* qtable_host, const NdShape& sh, double eb, double sf, int mode,
-                                const T* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
-  hipStream_t s = c->stream;
-  const size_t n_lin = sh.nblk * 64;
-  const size_t m = dctzhip_summary_tiles(n_lin);
-  const size_t fin = total ? summary_final_slots(m) : 0;
-  { int rc = regrow(c, &c->sum_buf, &c->sum_cap, fin + (d_tiles ? 0 : m), sizeof(dctzhip_tile_summary_t)); if (rc) return rc; }
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
-  NdSummaryParams<T> p;
-  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
-  p.ref = d_ref;
-  p.recs = d_tiles ? d_tiles : c->sum_buf + fin;
-  p.n = (unsigned)n_lin; p.nfull = (unsigned)sh.nblk; p.ntiles = (unsigned)m;
-  ndfix_axes(sh, p.nb, p.d);
-  const bool ref = d_ref != nullptr;
-  // one single-wave workgroup per stream tile, persistent only beyond what is resident at once
-  const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
-  int& occ = c->ndsum_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3][ref];
-  if (occ == 0) occ = std::max(ndsummary_occupancy<T>(mode, geom, ref), 1);
-  const unsigned resident = (unsigned)c->num_cu * (unsigned)occ;
-  launch_tile_summary_nd<T>(p, mode, geom, ref, (int)(p.ntiles < resident ? p.ntiles : resident), s);
-  SET_LAST(c, 1, "k_ndsummary<%s, %d, %d, %s>", tname<T>(), mode, geom, bname(ref));
-  dctzhip_tile_summary_t* ht = reinterpret_cast<dctzhip_tile_summary_t*>(c->h_pin + PIN_STATS);
-  if (total) {
-    const dctzhip_tile_summary_t* dt = launch_tile_summary_final(p.recs, m, c->sum_buf, s);
-    HIPCHK(c, hipMemcpyAsync(ht, dt, sizeof(*ht), hipMemcpyDeviceToHost, s));
-  }
-  const int rc = ra_finish(c);
-  if (rc == DCTZHIP_OK && total) *total = *ht;
-  return rc;
-}
-
-extern "C" int dctzhip_tile_summary_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                       const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb,
-                                       double sf, int mode, const void* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
-  if (!c) return DCTZHIP_E_ARG;
-  NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
-  int rc = check_common(c, n_lin, dtype, mode);
-  if (rc) return rc;
-  if (!d_tiles && !total) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: at least one of d_tiles and total must be given");
-  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  // (the original is read element by element at its own coordinates: the rows of a ragged array are not 16-byte aligned anyway)
-  if ((uintptr_t)d_ref & (elem_size(dtype) - 1)) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: the original must be aligned to its elements");
-  if ((uintptr_t)d_tiles & 7u) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: the records must be 8-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
-  {
-    Span sp[6];
-    size_t m = 0;
-    add_span(sp, &m, d_bin, n_lin, SPAN_READ, 0);
-    add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index, dctzhip_ac_index_len(n_lin) * sizeof(uint32_t), SPAN_READ, 0);
-    add_span(sp, &m, d_ref, n_orig * elem_size(dtype), SPAN_READ, 0);
-    add_span(sp, &m, d_tiles, dctzhip_summary_tiles(n_lin) * sizeof(dctzhip_tile_summary_t), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_tile_summary_nd", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? tile_summary_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
-                                            (const double*)d_ref, d_tiles, total)
-             : tile_summary_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode,
-                                           (const float*)d_ref, d_tiles, total);
+  return fixup_apply_call(c, "dctzhip_fixup_apply_nd", d_fix_start, d_fix_off, d_fix_val, count, n_lin, dtype, &sh, nullptr, lo, hi,
+                          (unsigned)(first / TILE_BLKS), (unsigned)(last / TILE_BLKS + 1), cnt, d_out);
 }
 
 // ---- missing values: a mask beside the streams (include/dctz_hip.h; dctz_kernels_mask.hip) ----------------------

@@ -640,8 +640,8 @@ class Context:
         self._check(rc, "dctzhip_decompress_box_nd")
         return dst.view(ext)
 
-    # ---- coarse decode (include/dctz_hip.h: the whole array at 1 / factor of its resolution) ----
-    def _coarse_args(self, out, index, mode, qtable, dtype):
+    def _stream_args(self, out, index, mode, qtable, dtype):
+        """The streams, the index and the QT table as the coarse, summary and correction-list calls pass them."""
         t = self.torch
         q = None
         if mode == QT:
@@ -650,6 +650,7 @@ class Context:
         ptr = lambda v: v.data_ptr() if v is not None else None
         return (ptr(out.get("bin_index")), ptr(out.get("dc")), ptr(out.get("ac_exact"))), ptr(index), q
 
+    # ---- coarse decode (include/dctz_hip.h: the whole array at 1 / factor of its resolution) ----
     def decompress_coarse(self, out, cnt, n, dtype, eb, sf, factor, index=None, mode=EC, qtable=None, dst=None):
         """The n-element array of decompress() at 1 / factor of its resolution (factor 2 .. 64): ceil(n / factor) values, K =
         64 / factor per block from its K lowest coefficients.  `index` from ac_index(); with factor 64 and n % 64 == 0 only
@@ -658,7 +659,7 @@ class Context:
         self._bind_stream()
         if dst is None:
             dst = t.empty(int(self.lib.dctzhip_coarse_len(n, int(factor))), dtype=dtype, device=self.device)
-        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
         rc = self.lib.dctzhip_decompress_coarse(
             self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb),
             float(sf), mode, int(factor), dst.data_ptr())
@@ -676,7 +677,7 @@ class Context:
         ext = [(v + f - 1) // f for v in shape]
         if dst is None:
             dst = t.empty(ext, dtype=dtype, device=self.device)
-        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
+        (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
         arr = C.c_size_t * max(len(shape), 1)
         rc = self.lib.dctzhip_decompress_coarse_nd(
             self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, len(shape), arr(*shape),
@@ -684,26 +685,42 @@ class Context:
         self._check(rc, "dctzhip_decompress_coarse_nd")
         return dst.view(ext)
 
+    # ---- flat and tiled streams through one body per operation ----
+    # What a public method makes of its geometry argument: the geometry arguments of the C call (in the flat call's place of n),
+    # the positions the streams cover, and whether a tensor is the array's original.
+    @staticmethod
+    def _geo_flat(n):
+        return (n,), n, lambda v: v.numel() == n
+
+    def _geo_nd(self, shape):
+        shape = [int(v) for v in shape]
+        dims = (C.c_size_t * len(shape))(*shape)
+        return (len(shape), dims), self.nd_blocks(shape) * 64, lambda v: list(v.shape) == shape
+
     # ---- tile summaries (include/dctz_hip.h: verify and survey without writing the decode) ----
+    def _tile_summary(self, name, geo, out, cnt, dtype, eb, sf, index, mode, qtable, ref):
+        t = self.torch
+        self._bind_stream()
+        gargs, n_lin, is_original = geo
+        if index is None:
+            index, _ = self.ac_index(out, n_lin)
+        if ref is not None:
+            assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and is_original(ref)
+        recs = t.empty((int(self.lib.dctzhip_summary_tiles(n_lin)), 8), dtype=t.float64, device=self.device)
+        total = TileSummary()
+        (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
+        rc = getattr(self.lib, name)(
+            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, *gargs, _dt(dtype), float(eb),
+            float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
+        self._check(rc, name)
+        return recs, total
+
     def tile_summary(self, out, cnt, n, dtype, eb, sf, index=None, mode=EC, qtable=None, ref=None):
         """One record per 4096-element tile of what decompress() rebuilds from the same arguments -- min, max, sum and sum of
         squares -- and, with `ref` (the original, a CUDA tensor of n elements), min and max of the original, max |x - r| and
         sum (x - r)^2; the reconstruction is never written.  index=None builds the exception index.  Returns (records, total):
         records a (tiles, 8) float64 CUDA tensor in TileSummary's field order, total a TileSummary of the records joined."""
-        t = self.torch
-        self._bind_stream()
-        if index is None:
-            index, _ = self.ac_index(out, n)
-        if ref is not None:
-            assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and ref.numel() == n
-        recs = t.empty((int(self.lib.dctzhip_summary_tiles(n)), 8), dtype=t.float64, device=self.device)
-        total = TileSummary()
-        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
-        rc = self.lib.dctzhip_tile_summary(
-            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb),
-            float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
-        self._check(rc, "dctzhip_tile_summary")
-        return recs, total
+        return self._tile_summary("dctzhip_tile_summary", self._geo_flat(n), out, cnt, dtype, eb, sf, index, mode, qtable, ref)
 
     def tile_summary_nd(self, out, cnt, shape, dtype, eb, sf, index=None, mode=EC, qtable=None, ref=None):
         """tile_summary() for the streams of compress_nd(): one record per stream tile (64 blocks of 8 x 8 / 4 x 4 x 4) of what
@@ -711,25 +728,43 @@ class Context:
         enters no field.  `ref`: the original, a contiguous 2-D or 3-D CUDA tensor of `shape` (it may be a slice of a larger
         buffer; only element alignment is asked).  index=None builds the index over 64 * nd_blocks(shape).  Returns
         (records, total) as tile_summary() does."""
-        t = self.torch
-        self._bind_stream()
-        shape = [int(v) for v in shape]
-        n_lin = self.nd_blocks(shape) * 64
-        if index is None:
-            index, _ = self.ac_index(out, n_lin)
-        if ref is not None:
-            assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and list(ref.shape) == shape
-        recs = t.empty((int(self.lib.dctzhip_summary_tiles(n_lin)), 8), dtype=t.float64, device=self.device)
-        total = TileSummary()
-        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
-        dims = (C.c_size_t * len(shape))(*shape)
-        rc = self.lib.dctzhip_tile_summary_nd(
-            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, len(shape), dims, _dt(dtype),
-            float(eb), float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
-        self._check(rc, "dctzhip_tile_summary_nd")
-        return recs, total
+        return self._tile_summary("dctzhip_tile_summary_nd", self._geo_nd(shape), out, cnt, dtype, eb, sf, index, mode, qtable, ref)
 
     # ---- point-wise error bound (include/dctz_hip.h: a correction list beside the streams) ----
+    def _fixup_build(self, name, geo, out, cnt, dtype, eb, sf, ref, bound, index, mode, qtable, capacity):
+        t = self.torch
+        self._bind_stream()
+        gargs, n_lin, is_original = geo
+        if index is None:
+            index, _ = self.ac_index(out, n_lin)
+        assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and is_original(ref)
+        start = t.empty(int(self.lib.dctzhip_fixup_tiles(n_lin)) + 1, dtype=t.int32, device=self.device)
+        (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
+        qp = q.ctypes.data_as(C.c_void_p) if q is not None else None
+        count = C.c_uint32(0)
+
+        def call(off, val, cap):
+            return getattr(self.lib, name)(
+                self.h, b, d, a, int(cnt), ix, qp, *gargs, _dt(dtype), float(eb), float(sf), mode, ref.data_ptr(), float(bound),
+                start.data_ptr(), off.data_ptr() if off is not None else None, val.data_ptr() if val is not None else None,
+                int(cap), C.byref(count))
+
+        if capacity is None or capacity == 0:
+            self._check(call(None, None, 0), name)
+            if capacity == 0:
+                return start, None, None, int(count.value)
+            capacity = int(count.value)
+        off = t.empty(max(int(capacity), 1), dtype=t.int16, device=self.device)
+        val = t.empty(max(int(capacity), 1), dtype=dtype, device=self.device)
+        rc = call(off, val, capacity)
+        if rc == E_SPACE:
+            err = DctzHipError(f"{name} failed ({rc}): {self.lib.dctzhip_last_error(self.h).decode()}")
+            err.count = int(count.value)
+            raise err
+        self._check(rc, name)
+        k = int(count.value)
+        return start, off[:k], val[:k], k
+
     def fixup_build(self, out, cnt, n, dtype, eb, sf, ref, bound, index=None, mode=EC, qtable=None, capacity=None):
         """The correction list of the streams against `ref` (the original, a CUDA tensor of n elements) for the absolute bound
         `bound`: every element i with not |ref[i] - r[i]| <= bound, r what decompress() rebuilds from the same arguments.
@@ -737,115 +772,51 @@ class Context:
         the tile (their bits are uint16), fix_val the originals of the listed elements.  capacity=None counts first and sizes
         the list from the count; capacity=0 is the count-only call (fix_off and fix_val are None); a list that does not fit
         the capacity raises DctzHipError, its .count says how many entries there are."""
-        t = self.torch
-        self._bind_stream()
-        if index is None:
-            index, _ = self.ac_index(out, n)
-        assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and ref.numel() == n
-        start = t.empty(int(self.lib.dctzhip_fixup_tiles(n)) + 1, dtype=t.int32, device=self.device)
-        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
-        qp = q.ctypes.data_as(C.c_void_p) if q is not None else None
-        count = C.c_uint32(0)
-
-        def call(off, val, cap):
-            return self.lib.dctzhip_fixup_build(
-                self.h, b, d, a, int(cnt), ix, qp, n, _dt(dtype), float(eb), float(sf), mode, ref.data_ptr(), float(bound),
-                start.data_ptr(), off.data_ptr() if off is not None else None, val.data_ptr() if val is not None else None,
-                int(cap), C.byref(count))
-
-        if capacity is None or capacity == 0:
-            self._check(call(None, None, 0), "dctzhip_fixup_build")
-            if capacity == 0:
-                return start, None, None, int(count.value)
-            capacity = int(count.value)
-        off = t.empty(max(int(capacity), 1), dtype=t.int16, device=self.device)
-        val = t.empty(max(int(capacity), 1), dtype=dtype, device=self.device)
-        rc = call(off, val, capacity)
-        if rc == E_SPACE:
-            err = DctzHipError(f"dctzhip_fixup_build failed ({rc}): {self.lib.dctzhip_last_error(self.h).decode()}")
-            err.count = int(count.value)
-            raise err
-        self._check(rc, "dctzhip_fixup_build")
-        k = int(count.value)
-        return start, off[:k], val[:k], k
-
-    def fixup_apply(self, fix, n, dtype, dst, dims=None, lo=None, hi=None):
-        """Applies the list `fix` (fixup_build's result) to dst: the dense box lo <= c < hi of the n-element array seen with
-        shape `dims` -- what decompress_box() wrote; dims=None: the range [lo, hi) of the flat array (what decompress_range()
-        wrote), by default all of it.  Returns dst."""
-        self._bind_stream()
-        start, off, val, count = fix
-        if dims is None:
-            dims, lo, hi = [n], [0 if lo is None else lo], [n if hi is None else hi]
-        dims, lo, hi = [int(v) for v in dims], [int(v) for v in lo], [int(v) for v in hi]
-        nd = len(dims)
-        assert len(lo) == nd and len(hi) == nd and dst.is_cuda and dst.is_contiguous() and dst.dtype == dtype
-        assert dst.numel() == int(np.prod([max(h - l, 0) for l, h in zip(lo, hi)], dtype=np.int64))
-        arr = C.c_size_t * max(nd, 1)
-        rc = self.lib.dctzhip_fixup_apply(
-            self.h, start.data_ptr(), off.data_ptr() if off is not None and count else None,
-            val.data_ptr() if val is not None and count else None, int(count), n, _dt(dtype), nd, arr(*dims), arr(*lo), arr(*hi),
-            dst.data_ptr())
-        self._check(rc, "dctzhip_fixup_apply")
-        return dst
+        return self._fixup_build("dctzhip_fixup_build", self._geo_flat(n), out, cnt, dtype, eb, sf, ref, bound, index, mode, qtable,
+                                 capacity)
 
     def fixup_build_nd(self, out, cnt, shape, dtype, eb, sf, ref, bound, index=None, mode=EC, qtable=None, capacity=None):
         """fixup_build() for the streams of compress_nd(): the correction list against `ref` (the original, a contiguous 2-D or
         3-D CUDA tensor of `shape`) over the 64 * nd_blocks(shape) stream positions; r is what decompress_nd() rebuilds from
         the same arguments, the edge padding is never listed.  Return value and capacity conventions are fixup_build's."""
-        t = self.torch
+        return self._fixup_build("dctzhip_fixup_build_nd", self._geo_nd(shape), out, cnt, dtype, eb, sf, ref, bound, index, mode,
+                                 qtable, capacity)
+
+    def _fixup_apply(self, name, fix, dtype, dst, lo, hi, before_dtype, after_dtype):
+        """before_dtype / after_dtype: the C call's geometry arguments on either side of its dtype."""
         self._bind_stream()
-        shape = [int(v) for v in shape]
-        n_lin = self.nd_blocks(shape) * 64
-        if index is None:
-            index, _ = self.ac_index(out, n_lin)
-        assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and list(ref.shape) == shape
-        start = t.empty(int(self.lib.dctzhip_fixup_tiles(n_lin)) + 1, dtype=t.int32, device=self.device)
-        (b, d, a), ix, q = self._coarse_args(out, index, mode, qtable, dtype)
-        qp = q.ctypes.data_as(C.c_void_p) if q is not None else None
-        dims = (C.c_size_t * len(shape))(*shape)
-        count = C.c_uint32(0)
+        start, off, val, count = fix
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        nd = len(lo)
+        assert len(hi) == nd and dst.is_cuda and dst.is_contiguous() and dst.dtype == dtype
+        assert dst.numel() == int(np.prod([max(h - l, 0) for l, h in zip(lo, hi)], dtype=np.int64))
+        arr = C.c_size_t * max(nd, 1)
+        rc = getattr(self.lib, name)(
+            self.h, start.data_ptr(), off.data_ptr() if off is not None and count else None,
+            val.data_ptr() if val is not None and count else None, int(count), *before_dtype, _dt(dtype), *after_dtype,
+            arr(*lo), arr(*hi), dst.data_ptr())
+        self._check(rc, name)
+        return dst
 
-        def call(off, val, cap):
-            return self.lib.dctzhip_fixup_build_nd(
-                self.h, b, d, a, int(cnt), ix, qp, len(shape), dims, _dt(dtype), float(eb), float(sf), mode, ref.data_ptr(),
-                float(bound), start.data_ptr(), off.data_ptr() if off is not None else None,
-                val.data_ptr() if val is not None else None, int(cap), C.byref(count))
-
-        if capacity is None or capacity == 0:
-            self._check(call(None, None, 0), "dctzhip_fixup_build_nd")
-            if capacity == 0:
-                return start, None, None, int(count.value)
-            capacity = int(count.value)
-        off = t.empty(max(int(capacity), 1), dtype=t.int16, device=self.device)
-        val = t.empty(max(int(capacity), 1), dtype=dtype, device=self.device)
-        rc = call(off, val, capacity)
-        if rc == E_SPACE:
-            err = DctzHipError(f"dctzhip_fixup_build_nd failed ({rc}): {self.lib.dctzhip_last_error(self.h).decode()}")
-            err.count = int(count.value)
-            raise err
-        self._check(rc, "dctzhip_fixup_build_nd")
-        k = int(count.value)
-        return start, off[:k], val[:k], k
+    def fixup_apply(self, fix, n, dtype, dst, dims=None, lo=None, hi=None):
+        """Applies the list `fix` (fixup_build's result) to dst: the dense box lo <= c < hi of the n-element array seen with
+        shape `dims` -- what decompress_box() wrote; dims=None: the range [lo, hi) of the flat array (what decompress_range()
+        wrote), by default all of it.  Returns dst."""
+        if dims is None:
+            dims, lo, hi = [n], [0 if lo is None else lo], [n if hi is None else hi]
+        dims = [int(v) for v in dims]
+        assert len(lo) == len(dims)
+        return self._fixup_apply("dctzhip_fixup_apply", fix, dtype, dst, lo, hi, (n,),
+                                 (len(dims), (C.c_size_t * max(len(dims), 1))(*dims)))
 
     def fixup_apply_nd(self, fix, shape, dtype, dst, lo=None, hi=None):
         """Applies the list `fix` (fixup_build_nd's result) to dst: the dense box lo <= c < hi of the array of `shape` -- what
         decompress_box_nd() wrote, by default the whole array (what decompress_nd() wrote).  Returns dst."""
-        self._bind_stream()
-        start, off, val, count = fix
         shape = [int(v) for v in shape]
-        lo = [0] * len(shape) if lo is None else [int(v) for v in lo]
-        hi = list(shape) if hi is None else [int(v) for v in hi]
-        nd = len(shape)
-        assert len(lo) == nd and len(hi) == nd and dst.is_cuda and dst.is_contiguous() and dst.dtype == dtype
-        assert dst.numel() == int(np.prod([max(h - l, 0) for l, h in zip(lo, hi)], dtype=np.int64))
-        arr = C.c_size_t * max(nd, 1)
-        rc = self.lib.dctzhip_fixup_apply_nd(
-            self.h, start.data_ptr(), off.data_ptr() if off is not None and count else None,
-            val.data_ptr() if val is not None and count else None, int(count), nd, arr(*shape), _dt(dtype), arr(*lo), arr(*hi),
-            dst.data_ptr())
-        self._check(rc, "dctzhip_fixup_apply_nd")
-        return dst
+        lo, hi = [0] * len(shape) if lo is None else lo, list(shape) if hi is None else hi
+        assert len(lo) == len(shape)
+        return self._fixup_apply("dctzhip_fixup_apply_nd", fix, dtype, dst, lo, hi,
+                                 (len(shape), (C.c_size_t * max(len(shape), 1))(*shape)), ())
 
     # ---- missing values (include/dctz_hip.h: a mask beside the streams, the holes filled on compress) ----
     @staticmethod
