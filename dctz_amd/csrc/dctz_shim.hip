@@ -2063,9 +2063,47 @@ extern "C" int dctzhip_ac_index(dctzhip_ctx* c, const void* d_bin, size_t n, uin
   return DCTZHIP_OK;
 }
 
-// What the three random-access calls (range, box, box of a tiled array) share around their launch.  ra_begin: the control
-// block is clean and the QT table staged; ra_fill: the fields every parameter block has; ra_finish: the error word read
-// back -- the call returns once the index check is known, and has synchronised the stream.
+namespace {
+// the arguments that describe the streams, as an entry point gets them (host only)
+struct StreamSet {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  uint32_t ac_count;
+  const uint32_t* index;
+  const void* qtable;             // on the host, 64 entries of the data type (QT mode)
+  size_t n;                       // positions the streams cover: the elements of a flat array, 64 per block of a tiled one
+  int dtype;
+  double eb, sf;
+  int mode;
+};
+}
+// The streams are given and aligned and QT mode has its table (none of these messages names the entry point).  and_out: what
+// the alignment message says beside bin_index -- "", or the call's output(s); has_out: d_out is the call's one output, to be
+// given and 16-byte aligned like bin_index.
+static int streams_given(dctzhip_ctx* c, const StreamSet& st, const char* and_out, bool has_out = false, const void* d_out = nullptr) {
+  if (!st.bin || !st.dc || !st.index || (has_out && !d_out) || (st.ac_count && !st.ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(st.bin) || !aligned16(d_out) || ((uintptr_t)st.dc & 3u) || ((uintptr_t)st.ac & 3u) || ((uintptr_t)st.index & 3u))
+    return fail(c, DCTZHIP_E_ARG, "bin_index%s must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned", and_out);
+  if (st.mode == DCTZHIP_QT && !st.qtable) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  return DCTZHIP_OK;
+}
+// What the stream tiles [t0, t1) read of bin_index, DC and the index: the tiles' positions [b0, b1), the DC of every block
+// that has one of them, the index entries t0 .. t1.  (AC_exact is the caller's line, all of it: where a tile's part starts is
+// only known on the device.)  The whole array is [0, ceil(n / TILE_ELEMS)): b0 = 0, b1 = n -- n bytes of bin_index,
+// (n + 63) / 64 DC values, dctzhip_ac_index_len(n) index entries.  Of a tiled array n, so b1, is a multiple of 64 and the DC
+// count is b1 / 64 - b0 / 64.
+static void tile_read_spans(Span* sp, size_t* m, const StreamSet& st, size_t t0, size_t t1, int item) {
+  const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(st.n, t1 * (size_t)TILE_ELEMS);
+  add_span(sp, m, st.bin + b0, b1 - b0, SPAN_READ, item);
+  add_span(sp, m, st.dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, item);
+  add_span(sp, m, st.index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, item);
+}
+static_assert(DCTZHIP_INDEX_STRIDE == TILE_ELEMS && TILE_ELEMS % 64 == 0, "index entries are per stream tile, tiles hold whole blocks");
+
+// What the random-access calls share around their launch.  ra_begin: the control block is clean and the QT table staged;
+// ra_fill: the fields every parameter block has; ra_finish: the error word read back -- the call returns once the index
+// check is known, and has synchronised the stream.
 template <typename T>
 static int ra_begin(dctzhip_ctx* c, int mode, const void* qtable_host) {
   hipStream_t s = c->stream;
@@ -2080,22 +2118,20 @@ static int ra_begin(dctzhip_ctx* c, int mode, const void* qtable_host) {
   return DCTZHIP_OK;
 }
 template <typename T, typename P>
-static void ra_fill_streams(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_dc, const float* d_ac, const uint32_t* d_index,
-                            uint32_t ac_count, double eb, double sf) {
-  p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.idx = d_index;
+static void ra_fill_streams(dctzhip_ctx* c, P& p, const StreamSet& st) {
+  p.bin = st.bin; p.dc = st.dc; p.ac = st.ac; p.idx = st.index;
   p.tab = tab_of<T>(c); p.qtab = reinterpret_cast<const T*>(c->qtab);
   p.ctl = c->ctl;
-  p.ac_count = ac_count;
-  p.sf = (T)sf;
-  p.bin_width = (T)((T)eb * 2 * 1.0);               // as decompress_impl (binning.c:17 / :37)
-  p.range_max = (T)(eb * DCTZHIP_NBINS);
-  p.range_min = (T)(-eb * DCTZHIP_NBINS);
-  p.eb = eb;
+  p.ac_count = st.ac_count;
+  p.sf = (T)st.sf;
+  p.bin_width = (T)((T)st.eb * 2 * 1.0);            // as decompress_impl (binning.c:17 / :37)
+  p.range_max = (T)(st.eb * DCTZHIP_NBINS);
+  p.range_min = (T)(-st.eb * DCTZHIP_NBINS);
+  p.eb = st.eb;
 }
 template <typename T, typename P>
-static void ra_fill(dctzhip_ctx* c, P& p, const uint8_t* d_bin, const float* d_dc, const float* d_ac, const uint32_t* d_index, T* d_out,
-                    uint32_t ac_count, double eb, double sf) {
-  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+static void ra_fill(dctzhip_ctx* c, P& p, const StreamSet& st, T* d_out) {
+  ra_fill_streams<T>(c, p, st);
   p.out = d_out;
 }
 // cnt_total (or null): the control block's counter of the same read-back; a call that used it leaves the block to be cleared
@@ -2124,18 +2160,18 @@ static unsigned resident_grid(dctzhip_ctx* c, int& slot, size_t units, F occupan
 }
 
 template <typename T>
-static int decompress_range_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                 const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
-                                 size_t lo, size_t hi, T* d_out) {
+static int decompress_range_impl(dctzhip_ctx* c, const StreamSet& st, size_t lo, size_t hi, T* d_out) {
   hipStream_t s = c->stream;
+  const size_t n = st.n;
+  const int mode = st.mode;
   const unsigned nfull = (unsigned)(n / 64);
   const int rem = (int)(n % 64);
   const unsigned t0 = (unsigned)(lo / TILE_ELEMS), t1 = (unsigned)((hi + TILE_ELEMS - 1) / TILE_ELEMS);
   const bool with_rem = rem && hi > (size_t)nfull * 64;
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
   if (with_rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   RangeParams<T> p;
-  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  ra_fill<T>(c, p, st, d_out);
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.n = (unsigned)n; p.nfull = nfull; p.lo = (unsigned)lo; p.hi = (unsigned)hi; p.t0 = t0; p.t1 = t1;
   // a workgroup per tile of the range
@@ -2152,31 +2188,21 @@ extern "C" int dctzhip_decompress_range(dctzhip_ctx* c, const void* d_bin, const
   int rc = check_common(c, n, dtype, mode);
   if (rc) return rc;
   if (lo >= hi || hi > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_range: the range [%zu, %zu) is not inside [0, %zu)", lo, hi, n);
-  if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
   {
-    // what the call reads: the bin ids and DC of the range's tiles, their index entries, AC_exact (all of it: where the
-    // range's part starts is only known on the device)
-    const size_t t0 = lo / TILE_ELEMS, t1 = (hi + TILE_ELEMS - 1) / TILE_ELEMS;
-    const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n, t1 * (size_t)TILE_ELEMS);
+    // what the call reads: the range's tiles and AC_exact
     Span sp[5];
     size_t m = 0;
-    add_span(sp, &m, (const uint8_t*)d_bin + b0, b1 - b0, SPAN_READ, 0);
-    add_span(sp, &m, d_dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, 0);
+    tile_read_spans(sp, &m, st, lo / TILE_ELEMS, (hi + TILE_ELEMS - 1) / TILE_ELEMS, 0);
     add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, 0);
     add_span(sp, &m, d_out, (hi - lo) * elem_size(dtype), SPAN_OUT, 0);
     rc = check_spans(c, sp, m, "dctzhip_decompress_range", nullptr);
     if (rc) return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? decompress_range_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, lo, hi,
-                                             (double*)d_out)
-             : decompress_range_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, lo, hi,
-                                            (float*)d_out);
+  return (dtype == DCTZHIP_F64) ? decompress_range_impl<double>(c, st, lo, hi, (double*)d_out)
+                                : decompress_range_impl<float>(c, st, lo, hi, (float*)d_out);
 }
 
 // ---- a box of an N-D array (include/dctz_hip.h; dctz_kernels_box.hip) -------------------------------------------
@@ -2229,30 +2255,28 @@ static int box_extents(dctzhip_ctx* c, const char* what, size_t n, int ndim, con
   if (prod != n) return fail(c, DCTZHIP_E_ARG, "%s: the product of dims is not n = %zu", what, n);
   return DCTZHIP_OK;
 }
-// what a box call may read of bin_index, DC and the index: what dctzhip_decompress_range reads for [first box element, last box
-// element + 1)
-static void box_read_spans(Span* sp, size_t* m, const uint8_t* d_bin, const float* d_dc, const uint32_t* d_index, size_t n, size_t first,
-                           size_t last, int item) {
-  const size_t t0 = first / TILE_ELEMS, t1 = last / TILE_ELEMS + 1;
-  const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n, t1 * (size_t)TILE_ELEMS);
-  add_span(sp, m, d_bin + b0, b1 - b0, SPAN_READ, item);
-  add_span(sp, m, d_dc + b0 / 64, ((b1 + 63) / 64 - b0 / 64) * sizeof(float), SPAN_READ, item);
-  add_span(sp, m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, item);
+// The box arguments of a call with one box of a flat array: the rank, the arrays, then the extents.
+static int box_front(dctzhip_ctx* c, const char* what, size_t n, int ndim, const size_t* dims, const size_t* lo, const size_t* hi,
+                     size_t* cnt, size_t* first, size_t* last) {
+  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "%s: ndim must be in [1, %d]", what, DCTZHIP_BOX_MAXDIM);
+  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "%s: null dims, lo or hi", what);
+  return box_extents(c, what, n, ndim, dims, lo, hi, cnt, first, last);
 }
 
+// [first, last]: the box's first and last flat element -- the candidate tiles are those of the range [first, last + 1)
 template <typename T>
-static int decompress_box_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                               const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
-                               const BoxGeo& box, size_t first, size_t last, T* d_out) {
+static int decompress_box_impl(dctzhip_ctx* c, const StreamSet& st, const BoxGeo& box, size_t first, size_t last, T* d_out) {
   hipStream_t s = c->stream;
+  const size_t n = st.n;
+  const int mode = st.mode;
   const unsigned nfull = (unsigned)(n / 64);
   const int rem = (int)(n % 64);
   const unsigned t0 = (unsigned)(first / TILE_ELEMS), t1 = (unsigned)(last / TILE_ELEMS + 1);
   const bool with_rem = rem && box.rank((unsigned)n) != box.rank(nfull * 64u);    // an element of the short block lies in the box
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
   if (with_rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   BoxParams<T> p;
-  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  ra_fill<T>(c, p, st, d_out);
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.n = (unsigned)n; p.nfull = nfull; p.t0 = t0; p.t1 = t1;
   p.box = box;
@@ -2270,20 +2294,16 @@ extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const f
                                       int mode, int ndim, const size_t* dims, const size_t* lo, const size_t* hi, void* d_out) {
   int rc = check_common(c, n, dtype, mode);
   if (rc) return rc;
-  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
-  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box: null dims, lo or hi");
   size_t cnt = 1, first = 0, last = 0;
-  rc = box_extents(c, "dctzhip_decompress_box", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  rc = box_front(c, "dctzhip_decompress_box", n, ndim, dims, lo, hi, &cnt, &first, &last);
   if (rc) return rc;
-  if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
   {
     // what the call may read: what dctzhip_decompress_range reads for [first box element, last box element + 1)
     Span sp[5];
     size_t m = 0;
-    box_read_spans(sp, &m, (const uint8_t*)d_bin, d_dc, d_index, n, first, last, 0);
+    tile_read_spans(sp, &m, st, first / TILE_ELEMS, last / TILE_ELEMS + 1, 0);
     add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
     add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
     rc = check_spans(c, sp, m, "dctzhip_decompress_box", nullptr);
@@ -2291,11 +2311,8 @@ extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const f
   }
   HIPCHK(c, hipSetDevice(c->device));
   const BoxGeo box = canonical_box(ndim, dims, lo, hi);
-  return (dtype == DCTZHIP_F64)
-             ? decompress_box_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, box, first,
-                                           last, (double*)d_out)
-             : decompress_box_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, box, first,
-                                          last, (float*)d_out);
+  return (dtype == DCTZHIP_F64) ? decompress_box_impl<double>(c, st, box, first, last, (double*)d_out)
+                                : decompress_box_impl<float>(c, st, box, first, last, (float*)d_out);
 }
 
 // ---- a list of boxes in one call (include/dctz_hip.h; dctz_kernels_mbox.hip) ------------------------------------
@@ -2304,10 +2321,11 @@ static constexpr size_t MBOX_TABLE_BYTES = (size_t)DCTZHIP_BOXES_MAX * (sizeof(B
 
 // recs[0, k) are complete but for the device side of the table; rem_boxes[0, nrem) reach into the short block; B bounds the hits.
 template <typename T>
-static int decompress_boxes_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                 const uint32_t* d_index, const void* qtable_host, size_t n, double eb, double sf, int mode,
-                                 int k, const BoxRec* recs, const unsigned* rem_boxes, int nrem, unsigned total, size_t B) {
+static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, int k, const BoxRec* recs, const unsigned* rem_boxes, int nrem,
+                                 unsigned total, size_t B) {
   hipStream_t s = c->stream;
+  const size_t n = st.n;
+  const int mode = st.mode;
   const unsigned nfull = (unsigned)(n / 64);
   const int rem = (int)(n % 64);
   int rc;
@@ -2317,7 +2335,7 @@ static int decompress_boxes_impl(dctzhip_ctx* c, const uint8_t* d_bin, const flo
   }
   if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
   c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
-  if ((rc = ra_begin<T>(c, mode, qtable_host))) return rc;
+  if ((rc = ra_begin<T>(c, mode, st.qtable))) return rc;
   if (nrem) { if ((rc = upload_rtab<T>(c, rem))) return rc; }
   // the table in one transfer, on the call's stream, behind everything of the prologue that can fail: from here on the call
   // reaches its synchronisation (ra_finish), or the stream is synchronised before the error is returned, so the pinned
@@ -2337,7 +2355,7 @@ static int decompress_boxes_impl(dctzhip_ctx* c, const uint8_t* d_bin, const flo
   lp.nbox = (unsigned)k; lp.total = total; lp.unit = (unsigned)TILE_ELEMS; lp.end = (unsigned)n;
   lp.items = c->mb_items; lp.cap = (unsigned)B; lp.ctl = c->ctl;
   MBoxParams<T> p;
-  ra_fill_streams<T>(c, p, d_bin, d_dc, d_ac, d_index, ac_count, eb, sf);
+  ra_fill_streams<T>(c, p, st);
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.recs = lp.recs; p.items = c->mb_items; p.rem_boxes = reinterpret_cast<const unsigned*>(c->mb_dev + rec_bytes);
   p.cap = (unsigned)B; p.n = (unsigned)n; p.nfull = nfull;
@@ -2361,10 +2379,8 @@ extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const
   if (!boxes) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: null boxes");
   if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
   if (!dims) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: null dims");
-  if (!d_bin || !d_dc || !d_index || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index and the outputs must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  if ((rc = streams_given(c, st, " and the outputs"))) return rc;           // (the outputs themselves: box by box, below)
   const unsigned nfull = (unsigned)(n / 64);
   const bool rem = n % 64 != 0;
   std::vector<BoxRec> recs((size_t)k);
@@ -2380,7 +2396,7 @@ extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const
     if ((rc = box_extents(c, what, n, ndim, dims, boxes[i].lo, boxes[i].hi, &cnt, &first, &last))) return rc;
     if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", what);
     if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", what);
-    box_read_spans(sp.data(), &m, (const uint8_t*)d_bin, d_dc, d_index, n, first, last, i);
+    tile_read_spans(sp.data(), &m, st, first / TILE_ELEMS, last / TILE_ELEMS + 1, i);
     add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(dtype), SPAN_OUT, i);
     BoxRec& r = recs[(size_t)i];
     r.g = canonical_box(ndim, dims, boxes[i].lo, boxes[i].hi);
@@ -2401,10 +2417,8 @@ extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const
     return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: the boxes may hit %zu tiles, more than the %zu a call lists", B, MBOX_LIST_MAX);
   HIPCHK(c, hipSetDevice(c->device));
   return (dtype == DCTZHIP_F64)
-             ? decompress_boxes_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, k,
-                                             recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B)
-             : decompress_boxes_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, eb, sf, mode, k,
-                                            recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B);
+             ? decompress_boxes_impl<double>(c, st, k, recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B)
+             : decompress_boxes_impl<float>(c, st, k, recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B);
 }
 
 // ---- multi-dimensional blocks (include/dctz_hip.h) -------------------------------------------------
@@ -2427,6 +2441,35 @@ static bool nd_shape(int ndims, const size_t* dims, NdShape* sh) {
 extern "C" size_t dctzhip_nd_blocks(int ndims, const size_t* dims) {
   NdShape sh;
   return nd_shape(ndims, dims, &sh) ? sh.nblk : 0;
+}
+// How every entry point for a tiled array opens: the context, the shape, then dtype, mode and the 64 sh->nblk stream positions.
+static int nd_front(dctzhip_ctx* c, int ndims, const size_t* dims, int dtype, int mode, NdShape* sh) {
+  if (!c) return DCTZHIP_E_ARG;
+  if (!nd_shape(ndims, dims, sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
+  return check_common(c, sh->nblk * 64, dtype, mode);
+}
+// The box [lo, hi) of a tiled array: inside the array, cnt its elements, [t0, t1) the stream tiles from the one of its first
+// intersecting block to the one of its last (blocks in the row-major order of the block grid).
+static int nd_box_front(dctzhip_ctx* c, const char* what, const NdShape& sh, const size_t* lo, const size_t* hi, size_t* cnt, unsigned* t0,
+                        unsigned* t1) {
+  if (!lo || !hi) return fail(c, DCTZHIP_E_ARG, "%s: null lo or hi", what);
+  const size_t edge = sh.nd == 2 ? 8 : 4;
+  size_t first = 0, last = 0;
+  *cnt = 1;
+  for (int i = 0; i < sh.nd; i++) {
+    if (lo[i] >= hi[i] || hi[i] > sh.d[i])
+      return fail(c, DCTZHIP_E_ARG, "%s: [%zu, %zu) is not inside dimension %d of %zu", what, lo[i], hi[i], i, sh.d[i]);
+    *cnt *= hi[i] - lo[i];
+    first = first * sh.nb[i] + lo[i] / edge;
+    last = last * sh.nb[i] + (hi[i] - 1) / edge;
+  }
+  *t0 = (unsigned)(first / TILE_BLKS); *t1 = (unsigned)(last / TILE_BLKS + 1);
+  return DCTZHIP_OK;
+}
+// value(0 .. nd - 1) in the last nd of three axes, `front` in the axes before them: how the kernels take a tiled array or a box of one
+template <typename F>
+static void last_axes(int nd, unsigned (&a)[3], unsigned front, F value) {
+  for (int i = 0; i < 3; i++) a[i] = i < 3 - nd ? front : (unsigned)value(i - (3 - nd));
 }
 
 // The kernels can read / write the array in place (NdDirect) when no tile is padded and one 32-bit buffer descriptor
@@ -2489,10 +2532,8 @@ static int compress_nd_impl(dctzhip_ctx* c, const T* d_in, const NdShape& sh, do
 
 extern "C" int dctzhip_compress_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, double eb,
                                    int mode, void* d_bin, float* d_dc, float* d_ac, void* d_scaled, dctzhip_cinfo* info) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  int rc = check_common(c, sh.nblk * 64, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
   if (!d_in || !d_bin || !d_dc || !d_ac) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   if (!aligned16(d_in) || !aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac) || (d_scaled && !aligned16(d_scaled)))
@@ -2508,57 +2549,54 @@ extern "C" int dctzhip_compress_nd(dctzhip_ctx* c, const void* d_in, int ndims, 
   return rc;
 }
 
+template <typename T>
+static int decompress_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                              const void* qtable_host, const NdShape& sh, double eb, double sf, int mode, T* d_out) {
+  const size_t n_lin = sh.nblk * 64;
+  const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
+  NdDirect direct;
+  if (nd_direct(c, sh, sizeof(T), &direct))         // no padding, below 4 GiB: the flat pipeline with other addresses
+    return decompress_impl<T>(c, d_bin, d_dc, d_ac, ac_count, qtable_host, n_lin, eb, sf, mode, d_out, geom, &direct);
+  int rc = ensure_nd(c, n_lin * sizeof(T));
+  if (rc) return rc;
+  T* lin = reinterpret_cast<T*>(c->nd_buf);
+  rc = decompress_impl<T>(c, d_bin, d_dc, d_ac, ac_count, qtable_host, n_lin, eb, sf, mode, lin, geom);
+  if (rc) return rc;
+  // block after block -> tiles
+  launch_scatter_nd<T>(lin, d_out, sh, c->num_cu * 8, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return DCTZHIP_OK;
+}
+
 extern "C" int dctzhip_decompress_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                      const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb, double sf,
                                      int mode, void* d_out) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64;
-  int rc = check_common(c, n_lin, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
   if (!d_bin || !d_dc || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   if (!aligned16(d_bin) || !aligned16(d_out)) return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
   if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
   HIPCHK(c, hipSetDevice(c->device));
-  rc = ensure_scratch(c, n_lin, dtype, DCTZHIP_EC, false);
+  rc = ensure_scratch(c, sh.nblk * 64, dtype, DCTZHIP_EC, false);
   if (rc) return rc;
-  const int geom = ndims == 2 ? GEOM_2D : GEOM_3D;
-  NdDirect direct;
-  if (nd_direct(c, sh, elem_size(dtype), &direct)) {
-    rc = (dtype == DCTZHIP_F64)
-             ? decompress_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, n_lin, eb, sf, mode, (double*)d_out, geom, &direct)
-             : decompress_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, n_lin, eb, sf, mode, (float*)d_out, geom, &direct);
-    if (rc == DCTZHIP_OK && c->blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return rc;
-  }
-  rc = ensure_nd(c, n_lin * elem_size(dtype));
-  if (rc) return rc;
-  const int grid = c->num_cu * 8;
-  if (dtype == DCTZHIP_F64) {
-    rc = decompress_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, n_lin, eb, sf, mode, (double*)c->nd_buf, geom);
-    if (rc) return rc;
-    launch_scatter_nd<double>((const double*)c->nd_buf, (double*)d_out, sh, grid, c->stream);
-  } else {
-    rc = decompress_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, n_lin, eb, sf, mode, (float*)c->nd_buf, geom);
-    if (rc) return rc;
-    launch_scatter_nd<float>((const float*)c->nd_buf, (float*)d_out, sh, grid, c->stream);
-  }
-  HIPCHK(c, hipGetLastError());
-  if (c->blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
-  return DCTZHIP_OK;
+  rc = (dtype == DCTZHIP_F64)
+           ? decompress_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, sh, eb, sf, mode, (double*)d_out)
+           : decompress_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, qtable_host, sh, eb, sf, mode, (float*)d_out);
+  if (rc == DCTZHIP_OK && c->blocking) HIPCHK(c, hipStreamSynchronize(c->stream));
+  return rc;
 }
 
 // ---- a box of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndbox.hip) -------------------------
 template <typename T>
-static int decompress_box_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                  const uint32_t* d_index, const void* qtable_host, const NdShape& sh, double eb, double sf, int mode,
-                                  const size_t* lo, const size_t* hi, unsigned t0, unsigned t1, T* d_out) {
+static int decompress_box_nd_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape& sh, const size_t* lo, const size_t* hi, unsigned t0,
+                                  unsigned t1, T* d_out) {
   hipStream_t s = c->stream;
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  const int mode = st.mode;
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
   const unsigned edge = sh.nd == 2 ? 8u : 4u;
   NdBoxParams<T> p;
-  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  ra_fill<T>(c, p, st, d_out);
   p.n = (unsigned)(sh.nblk * 64); p.nfull = (unsigned)sh.nblk; p.t0 = t0; p.t1 = t1;
   // the array in the last sh.nd of three axes; the intersecting blocks as a box of the block grid
   memset(&p.blocks, 0, sizeof(p.blocks));
@@ -2590,47 +2628,27 @@ static int decompress_box_nd_impl(dctzhip_ctx* c, const uint8_t* d_bin, const fl
 extern "C" int dctzhip_decompress_box_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                          const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype,
                                          double eb, double sf, int mode, const size_t* lo, const size_t* hi, void* d_out) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64;
-  int rc = check_common(c, n_lin, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
-  if (!lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box_nd: null lo or hi");
-  const size_t edge = ndims == 2 ? 8 : 4;
-  size_t cnt = 1, first = 0, last = 0;              // first / last intersecting block of the row-major block grid
-  for (int i = 0; i < ndims; i++) {
-    if (lo[i] >= hi[i] || hi[i] > dims[i])
-      return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_box_nd: [%zu, %zu) is not inside dimension %d of %zu", lo[i], hi[i], i, dims[i]);
-    cnt *= hi[i] - lo[i];
-    first = first * sh.nb[i] + lo[i] / edge;
-    last = last * sh.nb[i] + (hi[i] - 1) / edge;
-  }
-  if (!d_bin || !d_dc || !d_index || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_bin) || !aligned16(d_out) || ((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index and the output must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
-  const size_t t0 = first / TILE_BLKS, t1 = last / TILE_BLKS + 1;
+  size_t cnt = 1;
+  unsigned t0 = 0, t1 = 0;
+  if ((rc = nd_box_front(c, "dctzhip_decompress_box_nd", sh, lo, hi, &cnt, &t0, &t1))) return rc;
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
+  if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
   {
-    // what the call may read: bin ids, DC and index entries of the candidate tiles, AC_exact (all of it: where a tile's
-    // part starts is only known on the device)
-    const size_t b0 = t0 * TILE_ELEMS, b1 = std::min(n_lin, t1 * (size_t)TILE_ELEMS);
+    // what the call may read: the candidate tiles and AC_exact
     Span sp[5];
     size_t m = 0;
-    add_span(sp, &m, (const uint8_t*)d_bin + b0, b1 - b0, SPAN_READ, 0);
-    add_span(sp, &m, d_dc + b0 / 64, (b1 / 64 - b0 / 64) * sizeof(float), SPAN_READ, 0);
+    tile_read_spans(sp, &m, st, t0, t1, 0);
     add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, 0);
     add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
     rc = check_spans(c, sp, m, "dctzhip_decompress_box_nd", nullptr);
     if (rc) return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? decompress_box_nd_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode, lo, hi,
-                                              (unsigned)t0, (unsigned)t1, (double*)d_out)
-             : decompress_box_nd_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh, eb, sf, mode, lo, hi,
-                                             (unsigned)t0, (unsigned)t1, (float*)d_out);
+  return (dtype == DCTZHIP_F64) ? decompress_box_nd_impl<double>(c, st, sh, lo, hi, t0, t1, (double*)d_out)
+                                : decompress_box_nd_impl<float>(c, st, sh, lo, hi, t0, t1, (float*)d_out);
 }
 
 // ---- the whole array at reduced resolution (include/dctz_hip.h; dctz_kernels_coarse.hip) ------------------------
@@ -2647,31 +2665,25 @@ extern "C" size_t dctzhip_coarse_len(size_t n, int factor) {
 
 // geom == GEOM_1D: sh is null, n elements in flat blocks; else the tiles of sh (n = 64 sh->nblk, no short block)
 template <typename T>
-static int decompress_coarse_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                  const uint32_t* d_index, const void* qtable_host, size_t n, const NdShape* sh, double eb, double sf,
-                                  int mode, int factor, T* d_out) {
+static int decompress_coarse_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape* sh, int factor, T* d_out) {
   hipStream_t s = c->stream;
-  const int geom = !sh ? GEOM_1D : sh->nd == 2 ? GEOM_2D : GEOM_3D;
+  const size_t n = st.n;
+  const int mode = st.mode, geom = !sh ? GEOM_1D : sh->nd == 2 ? GEOM_2D : GEOM_3D;
   const int k = coarse_k(geom, factor);
   const unsigned nfull = (unsigned)(n / 64);
   const int rem = (int)(n % 64);
-  { int rc = ra_begin<T>(c, mode, qtable_host); if (rc) return rc; }
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
   if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   CoarseParams<T> p;
-  ra_fill<T>(c, p, d_bin, d_dc, d_ac, d_index, d_out, ac_count, eb, sf);
+  ra_fill<T>(c, p, st, d_out);
   p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.n = (unsigned)n; p.nfull = nfull; p.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
   p.factor = (unsigned)factor;
-  for (int i = 0; i < 3; i++) { p.nb[i] = 1u; p.od[i] = 1u; }
-  if (sh)
-    for (int i = 0; i < sh->nd; i++) {
-      const int a = 3 - sh->nd + i;
-      p.nb[a] = (unsigned)sh->nb[i];
-      p.od[a] = (unsigned)((sh->d[i] + (size_t)factor - 1) / (size_t)factor);
-    }
+  last_axes(sh ? sh->nd : 0, p.nb, 1u, [&](int i) { return sh->nb[i]; });
+  last_axes(sh ? sh->nd : 0, p.od, 1u, [&](int i) { return (sh->d[i] + (size_t)factor - 1) / (size_t)factor; });
   if (k == 1) {
     // the DC stream alone
-    if (nfull) launch_decompress_coarse_dc<T>(d_dc, d_out, nfull, (T)sf, s);
+    if (nfull) launch_decompress_coarse_dc<T>(st.dc, d_out, nfull, (T)st.sf, s);
     SET_LAST(c, 1, "k_decompress_coarse_dc<%s>", tname<T>());
   } else {
     // a workgroup per stream tile
@@ -2686,31 +2698,29 @@ static int decompress_coarse_impl(dctzhip_ctx* c, const uint8_t* d_bin, const fl
   return ra_finish(c);
 }
 
-// the checks the two entry points share; n_out: elements of the output
-static int coarse_check(dctzhip_ctx* c, const char* what, int geom, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                        const uint32_t* d_index, const void* qtable_host, size_t n, size_t n_out, int dtype, int mode, int factor,
-                        const void* d_out) {
+// The checks the two entry points share; n_out: elements of the output.  Not streams_given: with factor == block edge the DC
+// stream alone is read and the other streams may be missing -- but for the flat short block, which is decoded in full.
+static int coarse_check(dctzhip_ctx* c, const char* what, int geom, const StreamSet& st, size_t n_out, int factor, const void* d_out) {
   const int k = coarse_k(geom, factor);
   if (!k)
     return fail(c, DCTZHIP_E_ARG, "%s: factor %d is not one of %s", what, factor,
                 geom == GEOM_1D ? "2, 4, 8, 16, 32, 64" : geom == GEOM_2D ? "2, 4, 8" : "2, 4");
-  // factor == block edge reads the DC stream only -- but for the flat short block, which is decoded in full
-  const bool need_ac = k > 1 || (n % 64) != 0;
-  if (!d_dc || !d_out) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (need_ac && (!d_bin || !d_index || (ac_count && !d_ac))) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(d_out) || ((uintptr_t)d_dc & 3u)) return fail(c, DCTZHIP_E_ARG, "the output must be 16-byte aligned, DC 4-byte aligned");
-  if (need_ac && (!aligned16(d_bin) || ((uintptr_t)d_ac & 3u) || ((uintptr_t)d_index & 3u)))
+  const bool need_ac = k > 1 || (st.n % 64) != 0;
+  if (!st.dc || !d_out) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (need_ac && (!st.bin || !st.index || (st.ac_count && !st.ac))) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+  if (!aligned16(d_out) || ((uintptr_t)st.dc & 3u)) return fail(c, DCTZHIP_E_ARG, "the output must be 16-byte aligned, DC 4-byte aligned");
+  if (need_ac && (!aligned16(st.bin) || ((uintptr_t)st.ac & 3u) || ((uintptr_t)st.index & 3u)))
     return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, AC_exact and the index 4-byte aligned");
-  if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  if (st.mode == DCTZHIP_QT && !st.qtable) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
   Span sp[5];
   size_t m = 0;
-  add_span(sp, &m, d_dc, (n + 63) / 64 * sizeof(float), SPAN_READ, 0);
   if (need_ac) {
-    add_span(sp, &m, d_bin, n, SPAN_READ, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_index, dctzhip_ac_index_len(n) * sizeof(uint32_t), SPAN_READ, 0);
+    tile_read_spans(sp, &m, st, 0, dctzhip_ac_index_len(st.n) - 1, 0);
+    add_span(sp, &m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, 0);
+  } else {
+    add_span(sp, &m, st.dc, (st.n + 63) / 64 * sizeof(float), SPAN_READ, 0);
   }
-  add_span(sp, &m, d_out, n_out * elem_size(dtype), SPAN_OUT, 0);
+  add_span(sp, &m, d_out, n_out * elem_size(st.dtype), SPAN_OUT, 0);
   return check_spans(c, sp, m, what, nullptr);
 }
 
@@ -2719,68 +2729,39 @@ extern "C" int dctzhip_decompress_coarse(dctzhip_ctx* c, const void* d_bin, cons
                                          int mode, int factor, void* d_out) {
   int rc = check_common(c, n, dtype, mode);
   if (rc) return rc;
-  rc = coarse_check(c, "dctzhip_decompress_coarse", GEOM_1D, d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dctzhip_coarse_len(n, factor),
-                    dtype, mode, factor, d_out);
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  rc = coarse_check(c, "dctzhip_decompress_coarse", GEOM_1D, st, dctzhip_coarse_len(n, factor), factor, d_out);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? decompress_coarse_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, nullptr, eb, sf, mode,
-                                              factor, (double*)d_out)
-             : decompress_coarse_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, nullptr, eb, sf, mode,
-                                             factor, (float*)d_out);
+  return (dtype == DCTZHIP_F64) ? decompress_coarse_impl<double>(c, st, nullptr, factor, (double*)d_out)
+                                : decompress_coarse_impl<float>(c, st, nullptr, factor, (float*)d_out);
 }
 
 extern "C" int dctzhip_decompress_coarse_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                             const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype,
                                             double eb, double sf, int mode, int factor, void* d_out) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64;
-  int rc = check_common(c, n_lin, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
   const int geom = ndims == 2 ? GEOM_2D : GEOM_3D;
   size_t n_out = 1;
   if (coarse_k(geom, factor))
     for (int i = 0; i < ndims; i++) n_out *= (dims[i] + (size_t)factor - 1) / (size_t)factor;
-  rc = coarse_check(c, "dctzhip_decompress_coarse_nd", geom, d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, n_out, dtype, mode, factor,
-                    d_out);
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
+  rc = coarse_check(c, "dctzhip_decompress_coarse_nd", geom, st, n_out, factor, d_out);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? decompress_coarse_impl<double>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, &sh, eb, sf, mode,
-                                              factor, (double*)d_out)
-             : decompress_coarse_impl<float>(c, (const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, &sh, eb, sf, mode,
-                                             factor, (float*)d_out);
+  return (dtype == DCTZHIP_F64) ? decompress_coarse_impl<double>(c, st, &sh, factor, (double*)d_out)
+                                : decompress_coarse_impl<float>(c, st, &sh, factor, (float*)d_out);
 }
 
 // ---- what the summary and correction-list calls share: a whole stream set with its index, flat or tiled ----------
-namespace {
-// the arguments that describe the streams, as an entry point gets them (host only)
-struct StreamSet {
-  const uint8_t* bin;
-  const float* dc;
-  const float* ac;
-  uint32_t ac_count;
-  const uint32_t* index;
-  const void* qtable;             // on the host, 64 entries of the data type (QT mode)
-  size_t n;                       // positions the streams cover: the elements of a flat array, 64 per block of a tiled one
-  int dtype;
-  double eb, sf;
-  int mode;
-};
-}
-// The streams are given and aligned and QT mode has its table (none of these messages names the entry point); what the
-// call reads of them -- all of it -- goes in front of the caller's own ranges in sp.
+// streams_given, and what the call reads of the streams -- all of it -- in front of the caller's own ranges in sp.
 static int streams_check(dctzhip_ctx* c, const StreamSet& st, Span* sp, size_t* m) {
-  if (!st.bin || !st.dc || !st.index || (st.ac_count && !st.ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
-  if (!aligned16(st.bin) || ((uintptr_t)st.dc & 3u) || ((uintptr_t)st.ac & 3u) || ((uintptr_t)st.index & 3u))
-    return fail(c, DCTZHIP_E_ARG, "bin_index must be 16-byte aligned, DC, AC_exact and the index 4-byte aligned");
-  if (st.mode == DCTZHIP_QT && !st.qtable) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
-  add_span(sp, m, st.bin, st.n, SPAN_READ, 0);
-  add_span(sp, m, st.dc, (st.n + 63) / 64 * sizeof(float), SPAN_READ, 0);
+  const int rc = streams_given(c, st, "");
+  if (rc) return rc;
+  tile_read_spans(sp, m, st, 0, dctzhip_ac_index_len(st.n) - 1, 0);
   add_span(sp, m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, 0);
-  add_span(sp, m, st.index, dctzhip_ac_index_len(st.n) * sizeof(uint32_t), SPAN_READ, 0);
   return DCTZHIP_OK;
 }
 // The entries of a correction list over n stream positions, written (SPAN_OUT, `entries` the capacity) or read (SPAN_READ,
@@ -2797,8 +2778,8 @@ static int fixlist_check(dctzhip_ctx* c, const char* what, size_t n, int dtype, 
 }
 // a tiled array in the last sh.nd of three axes
 static void ndfix_axes(const NdShape& sh, unsigned (&nb)[3], unsigned (&d)[3]) {
-  for (int i = 0; i < 3; i++) { nb[i] = 1u; d[i] = 1u; }
-  for (int i = 0; i < sh.nd; i++) { nb[3 - sh.nd + i] = (unsigned)sh.nb[i]; d[3 - sh.nd + i] = (unsigned)sh.d[i]; }
+  last_axes(sh.nd, nb, 1u, [&](int i) { return sh.nb[i]; });
+  last_axes(sh.nd, d, 1u, [&](int i) { return sh.d[i]; });
 }
 
 // ---- tile summaries (include/dctz_hip.h; dctz_kernels_summary.hip, tiled: dctz_kernels_ndsummary.hip) -----------
@@ -2820,7 +2801,7 @@ static int tile_summary_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape*
   const bool ref = d_ref != nullptr;
   // what the two parameter blocks share; ntiles: the stream tiles that hold a whole block (of a tiled array all m)
   auto fill = [&](auto& p) {
-    ra_fill_streams<T>(c, p, st.bin, st.dc, st.ac, st.index, st.ac_count, st.eb, st.sf);
+    ra_fill_streams<T>(c, p, st);
     p.ref = d_ref;
     p.recs = recs;
     p.n = (unsigned)st.n; p.nfull = nfull; p.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
@@ -2885,12 +2866,10 @@ extern "C" int dctzhip_tile_summary(dctzhip_ctx* c, const void* d_bin, const flo
 extern "C" int dctzhip_tile_summary_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
                                        const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb,
                                        double sf, int mode, const void* d_ref, dctzhip_tile_summary_t* d_tiles, dctzhip_tile_summary_t* total) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
-  int rc = check_common(c, n_lin, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
   // (the original is read element by element at its own coordinates: the rows of a ragged array are not 16-byte aligned anyway)
   if ((uintptr_t)d_ref & (elem_size(dtype) - 1)) return fail(c, DCTZHIP_E_ARG, "dctzhip_tile_summary_nd: the original must be aligned to its elements");
   const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, dtype, eb, sf, mode};
@@ -2914,7 +2893,7 @@ static int fixup_build_impl(dctzhip_ctx* c, const char* what, const StreamSet& s
   { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
   // what the two parameter blocks share; q: where a block keeps the streams.  ntiles as for tile_summary_impl
   auto fill = [&](auto& p, auto& q) {
-    ra_fill_streams<T>(c, q, st.bin, st.dc, st.ac, st.index, st.ac_count, st.eb, st.sf);
+    ra_fill_streams<T>(c, q, st);
     q.ref = d_ref;
     q.n = (unsigned)st.n; q.nfull = nfull; q.ntiles = (nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
     p.bound = (T)bound;
@@ -3006,12 +2985,10 @@ extern "C" int dctzhip_fixup_build_nd(dctzhip_ctx* c, const void* d_bin, const f
                                       const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype, double eb,
                                       double sf, int mode, const void* d_ref, double bound, uint32_t* d_fix_start, uint16_t* d_fix_off,
                                       void* d_fix_val, uint32_t capacity, uint32_t* count) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
-  int rc = check_common(c, n_lin, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
   const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n_lin, dtype, eb, sf, mode};
   return fixup_build_call(c, "dctzhip_fixup_build_nd", st, &sh, n_orig, d_ref, bound, d_fix_start, d_fix_off, d_fix_val, capacity, count);
 }
@@ -3042,8 +3019,8 @@ static int fixup_apply_impl(dctzhip_ctx* c, const uint32_t* d_fix_start, const u
     fill(p);
     p.nblk = (unsigned)sh->nblk; p.ntiles = (unsigned)dctzhip_fixup_tiles(n);
     ndfix_axes(*sh, p.nb, p.d);
-    for (int i = 0; i < 3; i++) { p.lo[i] = 0u; p.ext[i] = 1u; }
-    for (int i = 0; i < sh->nd; i++) { p.lo[3 - sh->nd + i] = (unsigned)lo[i]; p.ext[3 - sh->nd + i] = (unsigned)(hi[i] - lo[i]); }
+    last_axes(sh->nd, p.lo, 0u, [&](int i) { return lo[i]; });
+    last_axes(sh->nd, p.ext, 1u, [&](int i) { return hi[i] - lo[i]; });
     launch_ndfix_apply<T>(p, geom, grid, s);
     SET_LAST(c, 1, "k_ndfix_apply<%s, %d>", tname<T>(), geom);
   }
@@ -3075,10 +3052,8 @@ extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, 
                                    size_t n, int dtype, int ndim, const size_t* dims, const size_t* lo, const size_t* hi, void* d_out) {
   int rc = check_common(c, n, dtype, DCTZHIP_EC);
   if (rc) return rc;
-  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
-  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: null dims, lo or hi");
   size_t cnt = 1, first = 0, last = 0;
-  rc = box_extents(c, "dctzhip_fixup_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  rc = box_front(c, "dctzhip_fixup_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
   if (rc) return rc;
   if (count > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply: count %u exceeds n = %zu", count, n);
   const BoxGeo box = canonical_box(ndim, dims, lo, hi);
@@ -3089,25 +3064,16 @@ extern "C" int dctzhip_fixup_apply(dctzhip_ctx* c, const uint32_t* d_fix_start, 
 extern "C" int dctzhip_fixup_apply_nd(dctzhip_ctx* c, const uint32_t* d_fix_start, const uint16_t* d_fix_off, const void* d_fix_val,
                                       uint32_t count, int ndims, const size_t* dims, int dtype, const size_t* lo, const size_t* hi,
                                       void* d_out) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
-  int rc = check_common(c, n_lin, dtype, DCTZHIP_EC);
+  int rc = nd_front(c, ndims, dims, dtype, DCTZHIP_EC, &sh);
   if (rc) return rc;
-  if (!lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: null lo or hi");
-  const size_t edge = ndims == 2 ? 8 : 4;
-  size_t cnt = 1, first = 0, last = 0;              // first / last intersecting block of the row-major block grid
-  for (int i = 0; i < ndims; i++) {
-    if (lo[i] >= hi[i] || hi[i] > dims[i])
-      return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: [%zu, %zu) is not inside dimension %d of %zu", lo[i], hi[i], i, dims[i]);
-    cnt *= hi[i] - lo[i];
-    first = first * sh.nb[i] + lo[i] / edge;
-    last = last * sh.nb[i] + (hi[i] - 1) / edge;
-  }
+  const size_t n_lin = sh.nblk * 64, n_orig = sh.d[0] * sh.d[1] * sh.d[2];
+  size_t cnt = 1;
+  unsigned t0 = 0, t1 = 0;
+  if ((rc = nd_box_front(c, "dctzhip_fixup_apply_nd", sh, lo, hi, &cnt, &t0, &t1))) return rc;
   if (count > n_orig) return fail(c, DCTZHIP_E_ARG, "dctzhip_fixup_apply_nd: count %u exceeds the array's %zu elements", count, n_orig);
-  return fixup_apply_call(c, "dctzhip_fixup_apply_nd", d_fix_start, d_fix_off, d_fix_val, count, n_lin, dtype, &sh, nullptr, lo, hi,
-                          (unsigned)(first / TILE_BLKS), (unsigned)(last / TILE_BLKS + 1), cnt, d_out);
+  return fixup_apply_call(c, "dctzhip_fixup_apply_nd", d_fix_start, d_fix_off, d_fix_val, count, n_lin, dtype, &sh, nullptr, lo, hi, t0, t1, cnt,
+                          d_out);
 }
 
 // ---- missing values: a mask beside the streams (include/dctz_hip.h; dctz_kernels_mask.hip) ----------------------
@@ -3253,10 +3219,8 @@ static int check_mask_nd(dctzhip_ctx* c, const char* what, const void* d_in, con
 
 extern "C" int dctzhip_mask_build_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, const dctzhip_missing* miss,
                                      uint64_t* d_mask, void* d_filled, uint64_t* count) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  int rc = check_common(c, sh.nblk * 64, dtype, DCTZHIP_EC);
+  int rc = nd_front(c, ndims, dims, dtype, DCTZHIP_EC, &sh);
   if (rc) return rc;
   if (!d_in || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build_nd: the array, the mask and count must be given");
   Span sp[3];
@@ -3270,12 +3234,10 @@ extern "C" int dctzhip_mask_build_nd(dctzhip_ctx* c, const void* d_in, int ndims
 extern "C" int dctzhip_compress_masked_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, double eb, int mode,
                                           const dctzhip_missing* miss, void* d_bin, float* d_dc, float* d_ac, uint64_t* d_mask,
                                           void* d_filled, dctzhip_cinfo* info, uint64_t* count) {
-  if (!c) return DCTZHIP_E_ARG;
   NdShape sh;
-  if (!nd_shape(ndims, dims, &sh)) return fail(c, DCTZHIP_E_ARG, "multi-dimensional blocks: 2 or 3 non-zero extents whose tile count fits an int");
-  const size_t n_lin = sh.nblk * 64, n = sh.d[0] * sh.d[1] * sh.d[2];
-  int rc = check_common(c, n_lin, dtype, mode);
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
+  const size_t n_lin = sh.nblk * 64, n = sh.d[0] * sh.d[1] * sh.d[2];
   if (!d_in || !d_bin || !d_dc || !d_ac || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_masked_nd: null buffer or count");
   if (!aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac))
     return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_masked_nd: device buffers must be 16-byte aligned");
@@ -3318,10 +3280,8 @@ extern "C" int dctzhip_mask_apply(dctzhip_ctx* c, const uint64_t* d_mask, size_t
                                   const size_t* lo, const size_t* hi, void* d_out) {
   int rc = check_common(c, n, dtype, DCTZHIP_EC);
   if (rc) return rc;
-  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_apply: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
-  if (!dims || !lo || !hi) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_apply: null dims, lo or hi");
   size_t cnt = 1, first = 0, last = 0;
-  rc = box_extents(c, "dctzhip_mask_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
+  rc = box_front(c, "dctzhip_mask_apply", n, ndim, dims, lo, hi, &cnt, &first, &last);
   if (rc) return rc;
   const size_t es = elem_size(dtype);
   if (!d_mask || !d_out || ((uintptr_t)d_mask & 7u) || ((uintptr_t)d_out & (es - 1)))

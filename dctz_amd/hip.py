@@ -250,6 +250,11 @@ def _dt(torch_dtype):
     raise TypeError(f"unsupported dtype {torch_dtype}")
 
 
+def _host_ptr(a):
+    """A numpy array (or None) as a const void* argument; the caller keeps the array alive over the call."""
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
 class Context:
     """One dctzhip context on a GPU; kernels run on torch's current stream (bound before every call: the raw
     handle, where 0 = the legacy default stream, goes to dctzhip_set_stream as is)."""
@@ -419,13 +424,10 @@ class Context:
         self._bind_stream()
         if dst is None:
             dst = t.empty(n, dtype=dtype, device=self.device)
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        q = self._qtable(mode, qtable, dtype)
         rc = self.lib.dctzhip_decompress(
             self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(),
-            int(cnt), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype),
+            int(cnt), _host_ptr(q), n, _dt(dtype),
             float(eb), float(sf), mode, dst.data_ptr())
         self._check(rc, "dctzhip_decompress")
         return dst
@@ -448,13 +450,10 @@ class Context:
         self._bind_stream()
         if dst is None:
             dst = t.empty(max(int(hi) - int(lo), 0), dtype=dtype, device=self.device)
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        q = self._qtable(mode, qtable, dtype)
         rc = self.lib.dctzhip_decompress_range(
             self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb), float(sf),
+            index.data_ptr(), _host_ptr(q), n, _dt(dtype), float(eb), float(sf),
             mode, int(lo), int(hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_range")
         return dst
@@ -471,14 +470,11 @@ class Context:
         shape = [max(h - l, 0) for l, h in zip(lo, hi)]
         if dst is None:
             dst = t.empty(shape, dtype=dtype, device=self.device)
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        q = self._qtable(mode, qtable, dtype)
         arr = C.c_size_t * max(nd, 1)
         rc = self.lib.dctzhip_decompress_box(
             self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb), float(sf),
+            index.data_ptr(), _host_ptr(q), n, _dt(dtype), float(eb), float(sf),
             mode, nd, arr(*dims), arr(*lo), arr(*hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_box")
         return dst.view(shape)
@@ -500,10 +496,7 @@ class Context:
         if dsts is None:
             dsts = [t.empty(sh, dtype=dtype, device=self.device) for sh in shapes]
         assert len(dsts) == len(boxes)
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        q = self._qtable(mode, qtable, dtype)
         items = (BoxItem * max(len(boxes), 1))()
         for it, (lo, hi), d in zip(items, boxes, dsts):
             for i in range(min(nd, BOX_MAXDIM)):
@@ -512,7 +505,7 @@ class Context:
         arr = C.c_size_t * max(nd, 1)
         rc = self.lib.dctzhip_decompress_boxes(
             self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb), float(sf),
+            index.data_ptr(), _host_ptr(q), n, _dt(dtype), float(eb), float(sf),
             mode, nd, arr(*dims), len(boxes), C.cast(items, C.c_void_p))
         self._check(rc, "dctzhip_decompress_boxes")
         return [d.view(sh) for d, sh in zip(dsts, shapes)]
@@ -605,14 +598,11 @@ class Context:
         shape = tuple(shape)
         if dst is None:
             dst = t.empty(shape, dtype=dtype, device=self.device)
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        q = self._qtable(mode, qtable, dtype)
         dims = (C.c_size_t * len(shape))(*shape)
         rc = self.lib.dctzhip_decompress_nd(
             self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            q.ctypes.data_as(C.c_void_p) if q is not None else None, len(shape), dims, _dt(dtype), float(eb), float(sf),
+            _host_ptr(q), len(shape), dims, _dt(dtype), float(eb), float(sf),
             mode, dst.data_ptr())
         self._check(rc, "dctzhip_decompress_nd")
         return dst
@@ -628,27 +618,28 @@ class Context:
         ext = [max(h - l, 0) for l, h in zip(lo, hi)]
         if dst is None:
             dst = t.empty(ext, dtype=dtype, device=self.device)
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        q = self._qtable(mode, qtable, dtype)
         arr = C.c_size_t * max(nd, 1)
         rc = self.lib.dctzhip_decompress_box_nd(
             self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), q.ctypes.data_as(C.c_void_p) if q is not None else None, nd, arr(*shape), _dt(dtype),
+            index.data_ptr(), _host_ptr(q), nd, arr(*shape), _dt(dtype),
             float(eb), float(sf), mode, arr(*lo), arr(*hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_box_nd")
         return dst.view(ext)
 
+    def _qtable(self, mode, qtable, dtype):
+        """The QT table as a decode call passes it: 64 entries of the data type in host memory (QT mode), else None."""
+        if mode != QT:
+            return None
+        q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == self.torch.float64 else np.float32)
+        assert q.size == 64
+        return q
+
     def _stream_args(self, out, index, mode, qtable, dtype):
-        """The streams, the index and the QT table as the coarse, summary and correction-list calls pass them."""
-        t = self.torch
-        q = None
-        if mode == QT:
-            q = np.ascontiguousarray(qtable, dtype=np.float64 if dtype == t.float64 else np.float32)
-            assert q.size == 64
+        """The streams, the index and the QT table as the coarse, summary and correction-list calls pass them: a stream or an
+        index that is missing is a null pointer, for the C side to accept or refuse."""
         ptr = lambda v: v.data_ptr() if v is not None else None
-        return (ptr(out.get("bin_index")), ptr(out.get("dc")), ptr(out.get("ac_exact"))), ptr(index), q
+        return (ptr(out.get("bin_index")), ptr(out.get("dc")), ptr(out.get("ac_exact"))), ptr(index), self._qtable(mode, qtable, dtype)
 
     # ---- coarse decode (include/dctz_hip.h: the whole array at 1 / factor of its resolution) ----
     def decompress_coarse(self, out, cnt, n, dtype, eb, sf, factor, index=None, mode=EC, qtable=None, dst=None):
@@ -661,7 +652,7 @@ class Context:
             dst = t.empty(int(self.lib.dctzhip_coarse_len(n, int(factor))), dtype=dtype, device=self.device)
         (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
         rc = self.lib.dctzhip_decompress_coarse(
-            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, n, _dt(dtype), float(eb),
+            self.h, b, d, a, int(cnt), ix, _host_ptr(q), n, _dt(dtype), float(eb),
             float(sf), mode, int(factor), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_coarse")
         return dst
@@ -680,7 +671,7 @@ class Context:
         (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
         arr = C.c_size_t * max(len(shape), 1)
         rc = self.lib.dctzhip_decompress_coarse_nd(
-            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, len(shape), arr(*shape),
+            self.h, b, d, a, int(cnt), ix, _host_ptr(q), len(shape), arr(*shape),
             _dt(dtype), float(eb), float(sf), mode, int(factor), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_coarse_nd")
         return dst.view(ext)
@@ -710,7 +701,7 @@ class Context:
         total = TileSummary()
         (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
         rc = getattr(self.lib, name)(
-            self.h, b, d, a, int(cnt), ix, q.ctypes.data_as(C.c_void_p) if q is not None else None, *gargs, _dt(dtype), float(eb),
+            self.h, b, d, a, int(cnt), ix, _host_ptr(q), *gargs, _dt(dtype), float(eb),
             float(sf), mode, ref.data_ptr() if ref is not None else None, recs.data_ptr(), C.byref(total))
         self._check(rc, name)
         return recs, total
@@ -740,7 +731,7 @@ class Context:
         assert ref.is_cuda and ref.is_contiguous() and ref.dtype == dtype and is_original(ref)
         start = t.empty(int(self.lib.dctzhip_fixup_tiles(n_lin)) + 1, dtype=t.int32, device=self.device)
         (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
-        qp = q.ctypes.data_as(C.c_void_p) if q is not None else None
+        qp = _host_ptr(q)
         count = C.c_uint32(0)
 
         def call(off, val, cap):
