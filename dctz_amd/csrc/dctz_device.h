@@ -506,6 +506,21 @@ struct RdParams {
   double* out;                     // 2 + 2 k doubles: min x, max x, {sum err^2, count} per bound
 };
 template <typename T> void launch_rd_probe(const RdParams<T>& p, int grid, int rem, hipStream_t s);
+void launch_rd_final(const double* slab, unsigned nrows, double* out, int k, hipStream_t s);   // k_rd_final over rows [0, nrows)
+
+// The probe of an array in 8 x 8 / 4 x 4 x 4 tiles (dctz_kernels_ndrd.hip: k_ndrd_probe, k_ndrd_edge, then k_rd_final).
+// rd.x is the array itself, rd.nfull its tile count; the array sits in the last nd of three axes (d[2] fastest).
+template <typename T>
+struct NdRdParams {
+  RdParams<T> rd;
+  unsigned d[3];                   // extents (1 in front of a 2-D array)
+  unsigned nb[3];                  // tiles per axis
+  unsigned rag[3];                 // 1: the axis' last tile is padded (d % edge != 0)
+  unsigned vec;                    // every in-block row starts 16-byte aligned and ends inside its array row or is all padding
+  unsigned nedge;                  // blocks with padded positions = nblk - prod (nb - rag)
+  unsigned edge_row;               // k_ndrd_edge's first slab row (behind k_ndrd_probe's)
+};
+template <typename T> void launch_ndrd_probe(const NdRdParams<T>& p, int geom, int grid, int edge_grid, hipStream_t s);
 
 // Random access on decode (dctz_kernels_ra.hip: k_ac_index, k_ac_index_scan, k_ac_index_add, k_decompress_range,
 // k_decompress_range_rem).  The streams and the index describe the whole array; [lo, hi) is the range, [t0, t1) its tiles.

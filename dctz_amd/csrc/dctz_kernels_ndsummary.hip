@@ -27,21 +27,6 @@
 
 namespace dctz {
 
-// bit j: in-block place j of block (bz, by, bx) lies inside the array
-template <int GEOM>
-__device__ __forceinline__ unsigned long long nd_real_mask(const unsigned bz, const unsigned by, const unsigned bx, const unsigned dz,
-                                                           const unsigned dy, const unsigned dx) {
-  if (GEOM == GEOM_3D) {
-    const unsigned nx = min(4u, dx - bx * 4u), ny = min(4u, dy - by * 4u), nz = min(4u, dz - bz * 4u);
-    const unsigned plane = (((1u << nx) - 1u) * 0x1111u) & ((1u << (4u * ny)) - 1u);
-    const unsigned long long all = (unsigned long long)plane * 0x0001000100010001ull;
-    return nz == 4u ? all : all & ((1ull << (16u * nz)) - 1ull);
-  }
-  const unsigned nx = min(8u, dx - bx * 8u), ny = min(8u, dy - by * 8u);
-  const unsigned long long all = (unsigned long long)((1u << nx) - 1u) * 0x0101010101010101ull;
-  return ny == 8u ? all : all & ((1ull << (8u * ny)) - 1ull);
-}
-
 // One element into the running values when `ok`: r = v, and with REF the original o beside it
 template <typename T, bool REF>
 __device__ __forceinline__ void nd_summary_take(SumRec& a, double& s, double& q, double& eq, const bool ok, const T v, const T o) {

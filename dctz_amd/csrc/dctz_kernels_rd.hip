@@ -19,37 +19,9 @@
 // bound of each tile the wave's sums go through a fixed shuffle tree into the wave's own LDS slot.  Workgroups leave
 // one slab row each, and k_rd_final adds the rows up in index order: the results are bitwise reproducible, no float
 // atomics anywhere.  The short last block (n % 64) is k_rd_probe_rem's, as k_compress_rem's is on compress.
-#include "dctz_kernel_common.h"
+#include "dctz_rd_coef.h"
 
 namespace dctz {
-
-__device__ __forceinline__ void rd_wave_sum(double& e, unsigned& c) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    e += __shfl_xor(e, d);
-    c += __shfl_xor(c, d);
-  }
-}
-
-// The work of one bound on one coefficient at position j >= 1.  `x` is the scaled, transformed coefficient.
-template <typename T>
-__device__ __forceinline__ void rd_coef(T x, T rmin, T rmax, T bw, const FastDiv<T>& bwd, bool fast, double& e2, unsigned& c) {
-  const T u = x - rmin;                                   // dctz-comp-lib.c:377 / :402
-  const T q = fast ? bwd.core(u) : u / bwd.d;             // (k_compress makes the same choice, per launch)
-  const float h = bin_value<T, true>(x, q, rmax);
-  const bool ex = h >= 255.0f;                            // v_cvt_pk_u8_f32 saturates this to 255: stored exactly
-  const T centre = (floor(q) - T(127)) * bw;              // the decoder's bin centre (see the top of the file)
-  const T r = ex ? (T)(float)x : centre;
-  const double d = (double)x - (double)r;
-  e2 = __builtin_fma(d, d, e2);
-  c += ex ? 1u : 0u;
-}
-
-template <typename T>
-__device__ __forceinline__ double rd_dc_err2(T c0) {
-  const double d = (double)c0 - (double)(float)c0;        // :350-351 USE_TRUNCATE
-  return d * d;
-}
 
 // One pass over the whole blocks.  Wave w of workgroup g takes tiles g * NW + w, then every gridDim.x * NW-th.
 template <typename T>
@@ -208,11 +180,15 @@ __global__ __launch_bounds__(SWG) void k_rd_final(const double* __restrict__ sla
   }
 }
 
+void launch_rd_final(const double* slab, unsigned nrows, double* out, int k, hipStream_t s) {
+  hipLaunchKernelGGL(k_rd_final, dim3(2 + 2 * k), dim3(SWG), 0, s, slab, nrows, out);
+}
+
 template <typename T>
 void launch_rd_probe(const RdParams<T>& p, int grid, int rem, hipStream_t s) {
   if (grid > 0) hipLaunchKernelGGL(k_rd_probe<T>, dim3(grid), dim3(RD_WG), 0, s, p);
   if (rem) hipLaunchKernelGGL(k_rd_probe_rem<T>, dim3(1), dim3(64), 0, s, p, rem, (unsigned)grid);
-  hipLaunchKernelGGL(k_rd_final, dim3(2 + 2 * p.k), dim3(SWG), 0, s, (const double*)p.slab, (unsigned)grid + (rem ? 1u : 0u), p.out);
+  launch_rd_final(p.slab, (unsigned)grid + (rem ? 1u : 0u), p.out, p.k, s);
 }
 template void launch_rd_probe<double>(const RdParams<double>&, int, int, hipStream_t);
 template void launch_rd_probe<float>(const RdParams<float>&, int, int, hipStream_t);

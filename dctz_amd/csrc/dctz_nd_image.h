@@ -40,4 +40,19 @@ __device__ __forceinline__ void ndfix_place(const unsigned bz, const unsigned by
   else { z = 0u; y = by * 8u + (j >> 3); x = bx * 8u + (j & 7u); }
 }
 
+// bit j: in-block place j of block (bz, by, bx) lies inside the array
+template <int GEOM>
+__device__ __forceinline__ unsigned long long nd_real_mask(const unsigned bz, const unsigned by, const unsigned bx, const unsigned dz,
+                                                           const unsigned dy, const unsigned dx) {
+  if (GEOM == GEOM_3D) {
+    const unsigned nx = min(4u, dx - bx * 4u), ny = min(4u, dy - by * 4u), nz = min(4u, dz - bz * 4u);
+    const unsigned plane = (((1u << nx) - 1u) * 0x1111u) & ((1u << (4u * ny)) - 1u);
+    const unsigned long long all = (unsigned long long)plane * 0x0001000100010001ull;
+    return nz == 4u ? all : all & ((1ull << (16u * nz)) - 1ull);
+  }
+  const unsigned nx = min(8u, dx - bx * 8u), ny = min(8u, dy - by * 8u);
+  const unsigned long long all = (unsigned long long)((1u << nx) - 1u) * 0x0101010101010101ull;
+  return ny == 8u ? all : all & ((1ull << (8u * ny)) - 1ull);
+}
+
 }  // namespace dctz

@@ -3344,21 +3344,43 @@ extern "C" int dctzhip_psnr_terms(dctzhip_ctx* c, const void* d_x, const void* d
 // calc_psnr (util.c:54-104): 20 log10(range / rmse), rmse = sqrt(sse / N)
 static double psnr_of(double lo, double hi, double sse, size_t n) { return 20.0 * log10((hi - lo) / sqrt(sse / (double)(int)n)); }
 
+// sh == NULL: n elements in flat blocks.  Else the array of sh (n = its elements) in 8 x 8 / 4 x 4 x 4 tiles, read in place.
 template <typename T>
-static int rd_probe_impl(dctzhip_ctx* c, const T* d_in, size_t n, int k, const double* ebs, dctzhip_rd_point* pts, double range[2]) {
+static int rd_probe_impl(dctzhip_ctx* c, const T* d_in, size_t n, const NdShape* sh, int k, const double* ebs, dctzhip_rd_point* pts,
+                         double range[2]) {
   const int dtype = sizeof(T) == 8 ? DCTZHIP_F64 : DCTZHIP_F32;
   hipStream_t s = c->stream;
   double mx, mn, sum;
   int rc = stats_impl<T>(c, d_in, n, &mx, &mn, &sum);          // calc_data_stat: only sf is needed (util.c:29)
   if (rc) return rc;
-  const unsigned nfull = (unsigned)(n / 64);
-  const int rem = (int)(n % 64);
+  const unsigned nfull = sh ? (unsigned)sh->nblk : (unsigned)(n / 64);
+  const int rem = sh ? 0 : (int)(n % 64);
   const unsigned ntiles = (nfull + TILE_BLKS - 1) / TILE_BLKS;
   constexpr unsigned NW = RD_WG / 64;
   // one workgroup per CU (fp64: one wave per SIMD, the kernel's register budget) / two (fp32); fewer for small arrays
   unsigned grid = (unsigned)c->num_cu * (sizeof(T) == 8 ? 1u : 2u);
   if (grid > (ntiles + NW - 1) / NW) grid = (ntiles + NW - 1) / NW;
-  const size_t need = ((size_t)grid + 1) * RD_SLOT + 128;           // rows, then 64 doubles of bound constants, 64 of results
+  // a tiled array: the blocks with padded places (the last tile of every ragged axis), a wave per 64 of them
+  NdRdParams<T> q;
+  memset(&q, 0, sizeof(q));
+  unsigned edge_grid = 0;
+  if (sh) {
+    const size_t edge = sh->nd == 2 ? 8 : 4;
+    size_t whole = 1;
+    for (int i = 0; i < 3; i++) { q.d[i] = 1u; q.nb[i] = 1u; }
+    for (int i = 0; i < sh->nd; i++) {
+      const int a = 3 - sh->nd + i;
+      q.d[a] = (unsigned)sh->d[i]; q.nb[a] = (unsigned)sh->nb[i]; q.rag[a] = sh->d[i] % edge ? 1u : 0u;
+      whole *= sh->nb[i] - q.rag[a];
+    }
+    q.vec = sh->d[sh->nd - 1] % Traits<T>::EPV == 0 ? 1u : 0u;
+    q.nedge = (unsigned)(sh->nblk - whole);
+    edge_grid = (q.nedge + TILE_BLKS - 1) / TILE_BLKS;
+    if (edge_grid > (unsigned)c->num_cu * 4u) edge_grid = (unsigned)c->num_cu * 4u;
+    q.edge_row = grid;
+  }
+  const size_t rows = (size_t)grid + (sh ? edge_grid : 1u);
+  const size_t need = rows * RD_SLOT + 128;                         // rows, then 64 doubles of bound constants, 64 of results
   {
     rc = regrow(c, &c->rd_slab, &c->rd_slab_cap, need, sizeof(double));
     if (rc) return rc;
@@ -3381,19 +3403,26 @@ static int rd_probe_impl(dctzhip_ctx* c, const T* d_in, size_t n, int k, const d
     hb[3 * i + 2] = (T)(eb * 2.0 * 1.0);
     if (c->fastdiv && divisor_in_window(dtype, (double)hb[3 * i + 2])) p.fast_bw |= 1u << i;
   }
-  double* d_bounds = c->rd_slab + ((size_t)grid + 1) * RD_SLOT;
+  double* d_bounds = c->rd_slab + rows * RD_SLOT;
   p.bounds = reinterpret_cast<const T*>(d_bounds);
   p.tab = tab_of<T>(c); p.rtab = reinterpret_cast<const T*>(c->rtab);
   p.slab = c->rd_slab;
   p.out = d_bounds + 64;
   HIPCHK(c, hipMemcpyAsync(d_bounds, hb, sizeof(T) * 3 * (size_t)k, hipMemcpyHostToDevice, s));
-  launch_rd_probe<T>(p, (int)grid, rem, s);
+  if (sh) {
+    q.rd = p;
+    launch_ndrd_probe<T>(q, sh->nd == 2 ? GEOM_2D : GEOM_3D, (int)grid, (int)edge_grid, s);
+  } else {
+    launch_rd_probe<T>(p, (int)grid, rem, s);
+  }
   HIPCHK(c, hipGetLastError());
   double* ho = reinterpret_cast<double*>(c->h_pin + PIN_TAB + 1024);
   HIPCHK(c, hipMemcpyAsync(ho, p.out, sizeof(double) * (2 + 2 * (size_t)k), hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   const double sf2 = (double)p.sf * (double)p.sf;
-  const size_t nblk = (n + 63) / 64;
+  const size_t nblk = sh ? sh->nblk : (n + 63) / 64;
+  // the container's bytes before the entropy stage: bin ids (one per stream position), DC, AC_exact, header [, "DZND" trailer]
+  const uint64_t fixed = (sh ? 64 * (uint64_t)nblk + 16 : (uint64_t)n) + 4 * (uint64_t)nblk + DCTZHIP_RD_HEADER_BYTES;
   for (int i = 0; i < k; i++) {
     uint64_t cnt;
     memcpy(&cnt, &ho[3 + 2 * i], sizeof(cnt));
@@ -3402,29 +3431,49 @@ static int rd_probe_impl(dctzhip_ctx* c, const T* d_in, size_t n, int k, const d
     r.cnt = cnt;
     r.sse = sf2 * ho[2 + 2 * i] / (double)c->rd_sse_div;
     r.psnr = psnr_of(ho[0], ho[1], r.sse, n);
-    r.raw_bytes = (uint64_t)n + 4 * (uint64_t)nblk + 4 * cnt + DCTZHIP_RD_HEADER_BYTES;
+    r.raw_bytes = fixed + 4 * cnt;
   }
   if (range) { range[0] = ho[0]; range[1] = ho[1]; }
   return DCTZHIP_OK;
 }
 
-static int rd_probe_checked(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, int k, const double* ebs, dctzhip_rd_point* pts,
-                            double range[2]) {
-  return dtype == DCTZHIP_F64 ? rd_probe_impl<double>(c, (const double*)d_in, n, k, ebs, pts, range)
-                              : rd_probe_impl<float>(c, (const float*)d_in, n, k, ebs, pts, range);
+static int rd_probe_checked(dctzhip_ctx* c, const void* d_in, size_t n, const NdShape* sh, int dtype, int k, const double* ebs,
+                            dctzhip_rd_point* pts, double range[2]) {
+  return dtype == DCTZHIP_F64 ? rd_probe_impl<double>(c, (const double*)d_in, n, sh, k, ebs, pts, range)
+                              : rd_probe_impl<float>(c, (const float*)d_in, n, sh, k, ebs, pts, range);
+}
+
+// What dctzhip_rd_probe and dctzhip_rd_probe_nd ask of their arguments behind the shape
+static int rd_probe_front(dctzhip_ctx* c, const char* what, const void* d_in, int k, const double* error_bounds, const dctzhip_rd_point* pts) {
+  if (!d_in || !error_bounds || !pts) return fail(c, DCTZHIP_E_ARG, "%s: null pointer", what);
+  if (!aligned16(d_in)) return fail(c, DCTZHIP_E_ARG, "%s: d_in must be 16-byte aligned", what);
+  if (k < 1 || k > DCTZHIP_RD_MAXK) return fail(c, DCTZHIP_E_ARG, "%s: k = %d, must be 1 .. %d", what, k, DCTZHIP_RD_MAXK);
+  for (int i = 0; i < k; i++)
+    if (!(error_bounds[i] >= 1E-6)) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
+  return DCTZHIP_OK;
 }
 
 extern "C" int dctzhip_rd_probe(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, int k, const double* error_bounds,
                                 dctzhip_rd_point* pts, double range[2]) {
   int rc = check_common(c, n, dtype, DCTZHIP_EC);
   if (rc) return rc;
-  if (!d_in || !error_bounds || !pts) return fail(c, DCTZHIP_E_ARG, "dctzhip_rd_probe: null pointer");
-  if (!aligned16(d_in)) return fail(c, DCTZHIP_E_ARG, "dctzhip_rd_probe: d_in must be 16-byte aligned");
-  if (k < 1 || k > DCTZHIP_RD_MAXK) return fail(c, DCTZHIP_E_ARG, "dctzhip_rd_probe: k = %d, must be 1 .. %d", k, DCTZHIP_RD_MAXK);
-  for (int i = 0; i < k; i++)
-    if (!(error_bounds[i] >= 1E-6)) return fail(c, DCTZHIP_E_BOUND, "ERROR BOUND is not acceptable");   // dctz-comp-lib.c:135-138
+  rc = rd_probe_front(c, "dctzhip_rd_probe", d_in, k, error_bounds, pts);
+  if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  return rd_probe_checked(c, d_in, n, dtype, k, error_bounds, pts, range);
+  return rd_probe_checked(c, d_in, n, nullptr, dtype, k, error_bounds, pts, range);
+}
+
+static size_t nd_elems(const NdShape& sh) { return sh.d[0] * sh.d[1] * sh.d[2]; }
+
+extern "C" int dctzhip_rd_probe_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, int k,
+                                   const double* error_bounds, dctzhip_rd_point* pts, double range[2]) {
+  NdShape sh;
+  int rc = nd_front(c, ndims, dims, dtype, DCTZHIP_EC, &sh);
+  if (rc) return rc;
+  rc = rd_probe_front(c, "dctzhip_rd_probe_nd", d_in, k, error_bounds, pts);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return rd_probe_checked(c, d_in, nd_elems(sh), &sh, dtype, k, error_bounds, pts, range);
 }
 
 // The candidate grid of dctzhip_compress_psnr, ascending: the doubles nearest to m * 10^e, e = -6 .. -1, then 1.
@@ -3441,23 +3490,13 @@ static void rd_grid(double g[RD_GRID_N]) {
   g[i] = 1.0;
 }
 
-extern "C" int dctzhip_compress_psnr(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, double target_psnr, void* d_bin,
-                                     float* d_dc, float* d_ac, dctzhip_cinfo* info, double* error_bound_used, double* psnr_measured) {
-  int rc = check_common(c, n, dtype, DCTZHIP_EC);
-  if (rc) return rc;
-  if (!d_in || !d_bin || !d_dc || !d_ac || !info || !error_bound_used || !psnr_measured)
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: null pointer");
-  if (!aligned16(d_in) || !aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac))
-    return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
-  if (!std::isfinite(target_psnr)) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: the target must be finite");
-  {
-    Span sp[6];
-    size_t m = 0;
-    compress_spans(sp, &m, 0, d_in, n, dtype, d_bin, d_dc, d_ac, nullptr, nullptr);
-    rc = check_spans(c, sp, m, "dctzhip_compress_psnr", nullptr);
-    if (rc) return rc;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
+// The search of dctzhip_compress_psnr / dctzhip_compress_psnr_nd over the n elements of d_in.  The layout gives
+//   probe(k, ebs, pts, range)   its rate-distortion probe,
+//   compress(eb)                its ordinary compress into the caller's streams and *info,
+//   decode(eb, d_rec)           its ordinary decode of those streams into d_rec (n elements).
+template <typename Probe, typename Compress, typename Decode>
+static int compress_psnr_search(dctzhip_ctx* c, const char* what, const void* d_in, size_t n, int dtype, double target_psnr,
+                                double* error_bound_used, double* psnr_measured, Probe probe, Compress compress, Decode decode) {
   double g[RD_GRID_N];
   rd_grid(g);
   // call 1: the decade points 1e-6 .. 1 (grid indices 0, 10, ..., 60); the largest whose prediction reaches the target
@@ -3465,21 +3504,21 @@ extern "C" int dctzhip_compress_psnr(dctzhip_ctx* c, const void* d_in, size_t n,
   dctzhip_rd_point pts[DCTZHIP_RD_MAXK];
   double range[2];
   for (int d = 0; d < 7; d++) ebs[d] = g[10 * d];
-  rc = rd_probe_checked(c, d_in, n, dtype, 7, ebs, pts, range);
+  int rc = probe(7, ebs, pts, range);
   if (rc) return rc;
   if (!std::isfinite(range[0]) || !std::isfinite(range[1]))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: the array's range is not finite (PSNR undefined)");
-  if (range[0] == range[1]) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: constant array (PSNR undefined)");
+    return fail(c, DCTZHIP_E_ARG, "%s: the array's range is not finite (PSNR undefined)", what);
+  if (range[0] == range[1]) return fail(c, DCTZHIP_E_ARG, "%s: constant array (PSNR undefined)", what);
   for (int d = 0; d < 7; d++)
-    if (std::isnan(pts[d].sse)) return fail(c, DCTZHIP_E_ARG, "dctzhip_compress_psnr: the array holds a NaN (PSNR undefined)");
+    if (std::isnan(pts[d].sse)) return fail(c, DCTZHIP_E_ARG, "%s: the array holds a NaN (PSNR undefined)", what);
   int at = -1;
   for (int d = 6; d >= 0 && at < 0; d--)
     if (pts[d].psnr >= target_psnr) at = 10 * d;
-  if (at < 0) return fail(c, DCTZHIP_E_BOUND, "dctzhip_compress_psnr: no error bound >= 1e-6 reaches %.3f dB", target_psnr);
+  if (at < 0) return fail(c, DCTZHIP_E_BOUND, "%s: no error bound >= 1e-6 reaches %.3f dB", what, target_psnr);
   // call 2: the nine interior points above that decade point; the largest whose prediction reaches the target
   if (at < RD_GRID_N - 1) {
     for (int i = 0; i < 9; i++) ebs[i] = g[at + 1 + i];
-    rc = rd_probe_checked(c, d_in, n, dtype, 9, ebs, pts, nullptr);
+    rc = probe(9, ebs, pts, nullptr);
     if (rc) return rc;
     for (int i = 8; i >= 0; i--)
       if (pts[i].psnr >= target_psnr) { at = at + 1 + i; break; }
@@ -3494,9 +3533,9 @@ extern "C" int dctzhip_compress_psnr(dctzhip_ctx* c, const void* d_in, size_t n,
   }
   for (;; at--) {
     const double eb = g[at];
-    rc = dctzhip_compress(c, d_in, n, dtype, eb, DCTZHIP_EC, d_bin, d_dc, d_ac, nullptr, nullptr, info);
+    rc = compress(eb);
     if (rc) return rc;
-    rc = dctzhip_decompress(c, d_bin, d_dc, d_ac, info->cnt, nullptr, n, dtype, eb, info->sf, DCTZHIP_EC, c->rd_rec);
+    rc = decode(eb, c->rd_rec);
     if (rc) return rc;
     double t[4];
     rc = dctzhip_psnr_terms(c, d_in, c->rd_rec, n, dtype, t);
@@ -3505,9 +3544,69 @@ extern "C" int dctzhip_compress_psnr(dctzhip_ctx* c, const void* d_in, size_t n,
     *error_bound_used = eb;
     *psnr_measured = psnr;
     if (psnr >= target_psnr) return DCTZHIP_OK;
-    if (at == 0) return fail(c, DCTZHIP_E_BOUND, "dctzhip_compress_psnr: measured %.3f dB at 1e-6, under the target %.3f dB", psnr, target_psnr);
+    if (at == 0) return fail(c, DCTZHIP_E_BOUND, "%s: measured %.3f dB at 1e-6, under the target %.3f dB", what, psnr, target_psnr);
     c->rd_stepdowns++;
   }
+}
+
+// What both target-PSNR calls ask of their pointers and the target
+static int compress_psnr_front(dctzhip_ctx* c, const char* what, const void* d_in, const void* d_bin, const float* d_dc, const float* d_ac,
+                               const dctzhip_cinfo* info, const double* error_bound_used, const double* psnr_measured, double target_psnr) {
+  if (!d_in || !d_bin || !d_dc || !d_ac || !info || !error_bound_used || !psnr_measured) return fail(c, DCTZHIP_E_ARG, "%s: null pointer", what);
+  if (!aligned16(d_in) || !aligned16(d_bin) || !aligned16(d_dc) || !aligned16(d_ac))
+    return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
+  if (!std::isfinite(target_psnr)) return fail(c, DCTZHIP_E_ARG, "%s: the target must be finite", what);
+  return DCTZHIP_OK;
+}
+
+extern "C" int dctzhip_compress_psnr(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, double target_psnr, void* d_bin,
+                                     float* d_dc, float* d_ac, dctzhip_cinfo* info, double* error_bound_used, double* psnr_measured) {
+  int rc = check_common(c, n, dtype, DCTZHIP_EC);
+  if (rc) return rc;
+  rc = compress_psnr_front(c, "dctzhip_compress_psnr", d_in, d_bin, d_dc, d_ac, info, error_bound_used, psnr_measured, target_psnr);
+  if (rc) return rc;
+  {
+    Span sp[6];
+    size_t m = 0;
+    compress_spans(sp, &m, 0, d_in, n, dtype, d_bin, d_dc, d_ac, nullptr, nullptr);
+    rc = check_spans(c, sp, m, "dctzhip_compress_psnr", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return compress_psnr_search(
+      c, "dctzhip_compress_psnr", d_in, n, dtype, target_psnr, error_bound_used, psnr_measured,
+      [&](int k, const double* ebs, dctzhip_rd_point* pts, double* range) { return rd_probe_checked(c, d_in, n, nullptr, dtype, k, ebs, pts, range); },
+      [&](double eb) { return dctzhip_compress(c, d_in, n, dtype, eb, DCTZHIP_EC, d_bin, d_dc, d_ac, nullptr, nullptr, info); },
+      [&](double eb, void* d_rec) { return dctzhip_decompress(c, d_bin, d_dc, d_ac, info->cnt, nullptr, n, dtype, eb, info->sf, DCTZHIP_EC, d_rec); });
+}
+
+extern "C" int dctzhip_compress_psnr_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, double target_psnr,
+                                        void* d_bin, float* d_dc, float* d_ac, dctzhip_cinfo* info, double* error_bound_used,
+                                        double* psnr_measured) {
+  NdShape sh;
+  int rc = nd_front(c, ndims, dims, dtype, DCTZHIP_EC, &sh);
+  if (rc) return rc;
+  rc = compress_psnr_front(c, "dctzhip_compress_psnr_nd", d_in, d_bin, d_dc, d_ac, info, error_bound_used, psnr_measured, target_psnr);
+  if (rc) return rc;
+  const size_t n = nd_elems(sh);
+  {
+    Span sp[4];                                        // the array, and the streams' 64 nblk positions as dctzhip_compress_nd writes them
+    size_t m = 0;
+    add_span(sp, &m, d_in, n * elem_size(dtype), SPAN_READ, 0);
+    add_span(sp, &m, d_bin, sh.nblk * 64, SPAN_OUT, 0);
+    add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_OUT, 0);
+    add_span(sp, &m, d_ac, sh.nblk * 64 * sizeof(float), SPAN_OUT, 0);
+    rc = check_spans(c, sp, m, "dctzhip_compress_psnr_nd", nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return compress_psnr_search(
+      c, "dctzhip_compress_psnr_nd", d_in, n, dtype, target_psnr, error_bound_used, psnr_measured,
+      [&](int k, const double* ebs, dctzhip_rd_point* pts, double* range) { return rd_probe_checked(c, d_in, n, &sh, dtype, k, ebs, pts, range); },
+      [&](double eb) { return dctzhip_compress_nd(c, d_in, ndims, dims, dtype, eb, DCTZHIP_EC, d_bin, d_dc, d_ac, nullptr, info); },
+      [&](double eb, void* d_rec) {
+        return dctzhip_decompress_nd(c, d_bin, d_dc, d_ac, info->cnt, nullptr, ndims, dims, dtype, eb, info->sf, DCTZHIP_EC, d_rec);
+      });
 }
 
 // ---- batches of arrays (include/dctz_hip.h: dctzhip_compress_batch / dctzhip_decompress_batch) ---------------------

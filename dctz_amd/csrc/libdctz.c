@@ -1191,6 +1191,47 @@ int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double 
 #endif
 }
 
+/* The same for an array compressed in tiles: dctzhip_compress_psnr_nd chooses the bound, and the container is byte for byte
+ * dctz_set_block_dims(ndims, dims) + dctz_compress(var, prod dims, outSize, var_z, bound).  A request of the caller's that is
+ * still pending is not consumed: the call is refused.  Every refusal that does not need the data comes before a device is
+ * asked for. */
+int dctz_compress_psnr_nd(t_var *var, int ndims, const size_t *dims, size_t *outSize, t_var *var_z, double target_psnr,
+                          double *error_bound_used) {
+#ifdef USE_QTABLE
+  (void)var; (void)ndims; (void)dims; (void)outSize; (void)var_z; (void)target_psnr; (void)error_bound_used;
+  return DCTZHIP_E_ARG;                          /* QT bin widths come from a whole-array table: no probe for them */
+#else
+  if (!var || !var_z || !outSize || !error_bound_used) return DCTZHIP_E_ARG;
+  if ((ndims != 2 && ndims != 3) || !dims || g_nd) return DCTZHIP_E_ARG;
+  const int is_d = (var->datatype == DOUBLE);
+  if (!is_d && var->datatype != FLOAT) return DCTZHIP_E_ARG;
+  const void *host_in = var_bytes(var);
+  if (!host_in || isnan(target_psnr) || isinf(target_psnr)) return DCTZHIP_E_ARG;
+  size_t n = 1;
+  for (int i = 0; i < ndims; i++) {
+    if (dims[i] == 0 || dims[i] > 0x7FFFFFFFu || n > (size_t)0x7FFFFFFF / dims[i]) return DCTZHIP_E_ARG;
+    n *= dims[i];
+  }
+  const size_t nblk = dctzhip_nd_blocks(ndims, dims);
+  if (nblk == 0) return DCTZHIP_E_ARG;             /* (more tiles than the streams can number) */
+  const size_t ts = is_d ? sizeof(double) : sizeof(float);
+  dctzhip_ctx *c = ctx();
+  grow(&g_dev.in, &g_dev.in_cap, n * ts);
+  grow(&g_dev.bin, &g_dev.bin_cap, nblk * BLK_SZ);
+  grow(&g_dev.dc, &g_dev.dc_cap, nblk * sizeof(float));
+  grow(&g_dev.ac, &g_dev.ac_cap, nblk * BLK_SZ * sizeof(float));
+  if (dctzhip_memcpy_h2d(c, g_dev.in, host_in, n * ts) != DCTZHIP_OK) die("H2D");
+  dctzhip_cinfo info;
+  double eb = 0.0, psnr = 0.0;
+  const int rc = dctzhip_compress_psnr_nd(c, g_dev.in, ndims, dims, is_d ? DCTZHIP_F64 : DCTZHIP_F32, target_psnr, g_dev.bin,
+                                          (float *)g_dev.dc, (float *)g_dev.ac, &info, &eb, &psnr);
+  if (rc != DCTZHIP_OK) return rc;
+  if (dctz_set_block_dims(ndims, dims) != 0) return DCTZHIP_E_ARG;
+  *error_bound_used = eb;
+  return dctz_compress(var, (int)n, outSize, var_z, eb);
+#endif
+}
+
 static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 static struct { void *pin; size_t pin_cap; void *dev; size_t dev_cap; } g_batch;
 static void batch_buffers(dctzhip_ctx *c, size_t host_bytes, size_t dev_bytes) {

@@ -196,6 +196,11 @@ _PROTOS = {
                                    C.POINTER(RdPoint), C.POINTER(C.c_double)]),
     "dctzhip_compress_psnr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(CompressInfo), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dctzhip_rd_probe_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_int,
+                                      C.POINTER(C.c_double), C.POINTER(RdPoint), C.POINTER(C.c_double)]),
+    "dctzhip_compress_psnr_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(CompressInfo), C.POINTER(C.c_double),
+                                           C.POINTER(C.c_double)]),
     "dctzhip_deflate_bound": (C.c_size_t, [C.c_size_t]),
     "dctzhip_deflate_chunk_bytes": (C.c_size_t, []),
     "dctzhip_deflate_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
@@ -949,6 +954,35 @@ class Context:
         rc = self.lib.dctzhip_compress_psnr(self.h, x.data_ptr(), n, _dt(x.dtype), float(target), out["bin_index"].data_ptr(),
                                             out["dc"].data_ptr(), out["ac_exact"].data_ptr(), C.byref(info), C.byref(eb), C.byref(ps))
         self._check(rc, "dctzhip_compress_psnr")
+        return out, info, eb.value, ps.value
+
+    def rd_probe_nd(self, x, ebs):
+        """rd_probe() for a contiguous 2-D or 3-D CUDA tensor compressed in 8 x 8 / 4 x 4 x 4 tiles (dctzhip_rd_probe_nd): the
+        counts are compress_nd's, the predicted SSE / PSNR cover the array's own elements (no edge padding)."""
+        assert x.is_cuda and x.is_contiguous() and x.dim() in (2, 3)
+        self._bind_stream()
+        k = len(ebs)
+        shape = tuple(x.shape)
+        e = (C.c_double * max(k, 1))(*[float(v) for v in ebs])
+        pts = (RdPoint * max(k, 1))()
+        rng = (C.c_double * 2)()
+        rc = self.lib.dctzhip_rd_probe_nd(self.h, x.data_ptr(), len(shape), (C.c_size_t * len(shape))(*shape), _dt(x.dtype), k, e, pts, rng)
+        self._check(rc, "dctzhip_rd_probe_nd")
+        return [{f: getattr(pts[i], f) for f, _ in RdPoint._fields_} for i in range(k)], (rng[0], rng[1])
+
+    def compress_psnr_nd(self, x, target, out=None):
+        """compress_psnr() for a contiguous 2-D or 3-D CUDA tensor in tiles (dctzhip_compress_psnr_nd).  Returns
+        (out, info, eb, psnr): the streams are those of compress_nd(x, eb)."""
+        assert x.is_cuda and x.is_contiguous() and x.dim() in (2, 3)
+        self._bind_stream()
+        shape = tuple(x.shape)
+        if out is None:
+            out = self.alloc_outputs(self.nd_blocks(shape) * 64, x.dtype)
+        info, eb, ps = CompressInfo(), C.c_double(0.0), C.c_double(0.0)
+        rc = self.lib.dctzhip_compress_psnr_nd(self.h, x.data_ptr(), len(shape), (C.c_size_t * len(shape))(*shape), _dt(x.dtype),
+                                               float(target), out["bin_index"].data_ptr(), out["dc"].data_ptr(),
+                                               out["ac_exact"].data_ptr(), C.byref(info), C.byref(eb), C.byref(ps))
+        self._check(rc, "dctzhip_compress_psnr_nd")
         return out, info, eb.value, ps.value
 
     def deflate(self, sections, want_index=False, literals=None):

@@ -143,6 +143,16 @@ int dctz_decompress_batch(int k, t_var *const *vars_z, t_var *const *vars_r);
  * target, DCTZHIP_E_ARG (-1) for bad arguments, a constant array or a NaN (PSNR undefined), pending multi-dimensional
  * blocks (flat blocks only), and always in the QT library (its bin widths come from a whole-array table). */
 int dctz_compress_psnr(t_var *var, int N, size_t *outSize, t_var *var_z, double target_psnr, double *error_bound_used);
+/* Its twin for an array compressed in 8 x 8 (ndims = 2) or 4 x 4 x 4 (ndims = 3) tiles (ADDITION, EC).  The bound is chosen by
+ * dctzhip_compress_psnr_nd (the same grid and search over the array's own prod dims elements, no edge padding), and the
+ * container is then dctz_set_block_dims(ndims, dims) + dctz_compress(var, prod dims, outSize, var_z, *error_bound_used):
+ * byte for byte those calls' output, the in-place x /= sf of var->buf included.  Returns what dctz_compress returns (1), or
+ * without writing anything: DCTZHIP_E_BOUND (-2) when no bound >= 1e-6 reaches the target, DCTZHIP_E_ARG (-1) for bad
+ * arguments, ndims other than 2 or 3, an extent of 0, a product or tile count beyond an int, a constant array or a NaN, while
+ * a dctz_set_block_dims request of the caller's is pending (it stays pending), and always in the QT library.  Every refusal
+ * that does not need the data comes before a device is asked for. */
+int dctz_compress_psnr_nd(t_var *var, int ndims, const size_t *dims, size_t *outSize, t_var *var_z, double target_psnr,
+                          double *error_bound_used);
 /* Part of a container (ADDITION, EC and QT builds): elements [lo, hi), 0 <= lo < hi <= N, of what dctz_decompress(var_z,
  * ...) reconstructs, bit for bit, into var_r->buf (allocated by the caller: at least hi - lo elements of the container's
  * type).  Returns 1 like dctz_decompress, or -1 for a bad range, a multi-dimensional (DZND) container -- its element

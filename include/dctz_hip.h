@@ -154,14 +154,14 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
 /* (tests and tools)  Counters of the context -- which: 0 one-launch calls, 1 one-launch launches that gave up (run again
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
- * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr, 11 / 12 workgroups and
+ * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr / _psnr_nd, 11 / 12 workgroups and
  * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran), 13 / 14 / 15 items
  * in the list of the last dctzhip_decompress_boxes call, workgroups of its decode launch and the list's bound, 16 / 17
  * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again, 18 / 19 guesses of the
  * scaling factor taken from the remembered statistics of the same input that verified / that did not -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
- * 3: every predicted SSE of dctzhip_rd_probe is divided by value (value <= 1: off). */
+ * 3: every predicted SSE of dctzhip_rd_probe / _rd_probe_nd is divided by value (value <= 1: off). */
 int dctzhip_debug_counter(dctzhip_ctx *ctx, int which, unsigned long long *value);
 int dctzhip_debug_knob(dctzhip_ctx *ctx, int key, int value);
 /* (tools) the name rocprofv3 lists the big kernel of the last call under, every template argument: which = 0 compress,
@@ -898,6 +898,29 @@ int dctzhip_rd_probe(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, in
 int dctzhip_compress_psnr(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, double target_psnr,
                           void *d_bin_index, float *d_dc, float *d_ac_exact, dctzhip_cinfo *info,
                           double *error_bound_used, double *psnr_measured);
+/* The same two calls for an array compressed in 8 x 8 (ndims = 2) or 4 x 4 x 4 (ndims = 3) tiles: whatever
+ * dctzhip_compress_nd accepts, aligned and ragged extents alike, fp32 and fp64, EC.  d_in is the array itself in C order
+ * (16-byte aligned, not modified), read in place: one pass, the tiles scaled by the sf of the array's own statistics and
+ * put through the separable transform as dctzhip_compress_nd does it, then the flat probe's work per coefficient and bound.
+ *   cnt        exactly the info.cnt dctzhip_compress_nd reports at that bound (in place or through its gather pass)
+ *   sse        the predicted sum (x - x')^2 over the array's own prod dims elements, x' what dctzhip_decompress_nd writes.
+ *              The edge padding of the streams enters no field: orthonormality gives the error over all 64 places of a tile,
+ *              and for the tiles that hang over an extent the share of their padded places -- the inverse transform of the
+ *              coefficients' errors, squared there, exact up to that transform's rounding -- is taken out again
+ *   psnr       from min, max, sse and prod dims
+ *   raw_bytes  64 nblk + 4 nblk + 4 cnt + DCTZHIP_RD_HEADER_BYTES + 16 (the "DZND" trailer), nblk = dctzhip_nd_blocks
+ *   range      min x and max x of the array (= dctzhip_psnr_terms' out[0], out[1])
+ * Bounds, k, reproducibility, independence of the other bounds and debug knob 3 are dctzhip_rd_probe's. */
+int dctzhip_rd_probe_nd(dctzhip_ctx *ctx, const void *d_in, int ndims, const size_t *dims, int dtype, int k,
+                        const double *error_bounds, dctzhip_rd_point *pts, double range[2]);
+/* dctzhip_compress_psnr's contract word for word, the search itself being one function for both layouts: the same grid and
+ * probes (dctzhip_rd_probe_nd), the streams and *info bit for bit those of dctzhip_compress_nd(d_in, ndims, dims, ...,
+ * *error_bound_used, DCTZHIP_EC, ..., d_scaled = NULL), decoded with dctzhip_decompress_nd into the context's scratch
+ * and measured with dctzhip_psnr_terms over the prod dims elements; the same step down, guarantee and refusals.  Buffers
+ * as dctzhip_compress_nd's (64 nblk bytes, nblk floats, 64 nblk floats); overlaps are refused with DCTZHIP_E_ARG. */
+int dctzhip_compress_psnr_nd(dctzhip_ctx *ctx, const void *d_in, int ndims, const size_t *dims, int dtype,
+                             double target_psnr, void *d_bin_index, float *d_dc, float *d_ac_exact,
+                             dctzhip_cinfo *info, double *error_bound_used, double *psnr_measured);
 
 /* ---- entropy stage on the GPU -------------------------- */
 /* Replaces the reference's zlib tail on the compress side -- deflateInit / deflate of bin_index, DC and AC_exact on
