@@ -674,6 +674,32 @@ struct NdBoxParams {
 template <typename T> int ndbox_occupancy(int mode, int geom);
 template <typename T> void launch_decompress_ndbox(const NdBoxParams<T>& p, int mode, int geom, int grid, hipStream_t s);
 
+// A list of boxes of such an array in one call (dctz_kernels_mboxnd.hip: k_decompress_mbox_nd; the list is
+// k_boxlist_build's).  Per box one BoxRec -- g the box of the block grid as NdBoxParams::blocks, [t0, t1) the candidate
+// stream tiles, the builder's unit TILE_BLKS blocks and its end nblk -- and, in a second table, the box in elements.
+struct NdBoxElems { unsigned lo[3], ext[3]; };       // the array in the last axes, as NdBoxParams::lo / ext
+static_assert(sizeof(NdBoxElems) == 24, "NdBoxElems is read word by word");
+template <typename T>
+struct MBoxNdParams {
+  const uint8_t* bin;
+  const float* dc;
+  const float* ac;
+  const unsigned* idx;             // exception index, entries idx[t], idx[t + 1] of listed tiles are read
+  const T* tab;
+  const T* qtab;
+  Ctl* ctl;                        // cnt_total: items in the list (k_boxlist_build); error = 2: as RangeParams
+  const BoxRec* recs;              // `out` is read
+  const NdBoxElems* elems;
+  const BoxItem* items;
+  unsigned cap;                    // capacity of items
+  unsigned n, nfull, ac_count;     // n = 64 nblk, nfull = nblk
+  T sf, bin_width, range_min, range_max;
+  double eb;
+  unsigned nb[3];                  // blocks per axis
+};
+template <typename T> int mboxnd_occupancy(int mode, int geom);
+template <typename T> void launch_decompress_mbox_nd(const MBoxNdParams<T>& p, int mode, int geom, int grid, hipStream_t s);
+
 // Coarse decode (dctz_kernels_coarse.hip: k_decompress_coarse, k_decompress_coarse_nd, k_decompress_coarse_rem,
 // k_decompress_coarse_dc): the whole array at 1 / factor of its resolution along every axis, from the K = edge / factor low
 // coefficients of every block.  The streams and the index describe the whole array as for RangeParams; a tiled array

@@ -114,6 +114,7 @@ struct dctzhip_ctx {
   BoxItem* mb_items = nullptr;
   size_t mb_items_cap = 0;          // items
   int mbox_occ[2][2] = {{0, 0}, {0, 0}};
+  int mboxnd_occ[2][2][2] = {};     // dctzhip_decompress_boxes_nd: the same of k_decompress_mbox_nd, [fp64][QT][3-D]; table, list and counters are shared
   unsigned mbox_items = 0, mbox_grid = 0, mbox_bound = 0;   // ... its last call: items listed, workgroups of the decode launch, the bound B (dctzhip_debug_counter 13 / 14 / 15)
   int dec_il = 1;                   // 0: k_decompress with a contiguous tile range per workgroup; 1: interleaved for fp64 EC; 2: for all (DCTZHIP_DEC_IL)
   size_t qcnt_cap = 0;              // tiles the two hold
@@ -466,7 +467,7 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
     case 11: *value = c->box_grid; break;            // dctzhip_decompress_box / _box_nd, last call: workgroups of its kernel
     case 12: *value = c->box_tiles; break;           // ... candidate tiles (more than workgroups: the grid-stride loop ran)
-    case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes, last call: (box, hit tile) items in its list
+    case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes / _boxes_nd, last call of either: (box, hit tile) items in its list
     case 14: *value = c->mbox_grid; break;           // ... workgroups of its decode launch (fewer than items: they took several each)
     case 15: *value = c->mbox_bound; break;          // ... the host's bound B of the items, the list's capacity
     case 16: *value = c->memo_decodes; break;        // dctzhip_decompress calls launched on the last compress call's tile counts (the decode memo)
@@ -2317,7 +2318,15 @@ extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const f
 
 // ---- a list of boxes in one call (include/dctz_hip.h; dctz_kernels_mbox.hip) ------------------------------------
 static constexpr size_t MBOX_LIST_MAX = (size_t)1 << 24;                // items: the bound B of a call may not exceed it
-static constexpr size_t MBOX_TABLE_BYTES = (size_t)DCTZHIP_BOXES_MAX * (sizeof(BoxRec) + sizeof(unsigned));
+// the table of a call: the records, then per box an unsigned (flat arrays: the boxes of the short block) or the box in elements (tiled arrays)
+static constexpr size_t MBOX_TABLE_BYTES = (size_t)DCTZHIP_BOXES_MAX * (sizeof(BoxRec) + std::max(sizeof(unsigned), sizeof(NdBoxElems)));
+static int mbox_table(dctzhip_ctx* c) {
+  if (!c->mb_pin) {
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mb_pin), MBOX_TABLE_BYTES, hipHostMallocDefault));
+    HIPCHK(c, hipMalloc(&c->mb_dev, MBOX_TABLE_BYTES));
+  }
+  return DCTZHIP_OK;
+}
 
 // recs[0, k) are complete but for the device side of the table; rem_boxes[0, nrem) reach into the short block; B bounds the hits.
 template <typename T>
@@ -2329,10 +2338,7 @@ static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, int k, con
   const unsigned nfull = (unsigned)(n / 64);
   const int rem = (int)(n % 64);
   int rc;
-  if (!c->mb_pin) {
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mb_pin), MBOX_TABLE_BYTES, hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(&c->mb_dev, MBOX_TABLE_BYTES));
-  }
+  if ((rc = mbox_table(c))) return rc;
   if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
   c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
   if ((rc = ra_begin<T>(c, mode, st.qtable))) return rc;
@@ -2588,26 +2594,32 @@ extern "C" int dctzhip_decompress_nd(dctzhip_ctx* c, const void* d_bin, const fl
 }
 
 // ---- a box of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndbox.hip) -------------------------
+// The checked box [lo, hi) as the kernels take it: the array in the last sh.nd of three axes (nb: blocks per axis; blo, ext:
+// the box in elements), and the intersecting blocks as a box of the block grid (dim = nb; rank() is the hit test).
+static void nd_box_geometry(const NdShape& sh, const size_t* lo, const size_t* hi, unsigned (&nb)[3], unsigned (&blo)[3], unsigned (&ext)[3],
+                            BoxGeo* blocks) {
+  const unsigned edge = sh.nd == 2 ? 8u : 4u;
+  memset(blocks, 0, sizeof(*blocks));
+  for (int i = 0; i < BOX_ND; i++) { blocks->dim[i] = 1u; blocks->lo[i] = 0u; blocks->ext[i] = 1u; }
+  for (int i = 0; i < 3; i++) { nb[i] = 1u; blo[i] = 0u; ext[i] = 1u; }
+  for (int i = 0; i < sh.nd; i++) {
+    const int a = 3 - sh.nd + i;
+    nb[a] = (unsigned)sh.nb[i]; blo[a] = (unsigned)lo[i]; ext[a] = (unsigned)(hi[i] - lo[i]);
+    const unsigned bl = (unsigned)lo[i] / edge, bh = (unsigned)(hi[i] - 1) / edge;
+    blocks->dim[a + 1] = (unsigned)sh.nb[i]; blocks->lo[a + 1] = bl; blocks->ext[a + 1] = bh - bl + 1u;
+  }
+}
+
 template <typename T>
 static int decompress_box_nd_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape& sh, const size_t* lo, const size_t* hi, unsigned t0,
                                   unsigned t1, T* d_out) {
   hipStream_t s = c->stream;
   const int mode = st.mode;
   { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
-  const unsigned edge = sh.nd == 2 ? 8u : 4u;
   NdBoxParams<T> p;
   ra_fill<T>(c, p, st, d_out);
   p.n = (unsigned)(sh.nblk * 64); p.nfull = (unsigned)sh.nblk; p.t0 = t0; p.t1 = t1;
-  // the array in the last sh.nd of three axes; the intersecting blocks as a box of the block grid
-  memset(&p.blocks, 0, sizeof(p.blocks));
-  for (int i = 0; i < BOX_ND; i++) { p.blocks.dim[i] = 1u; p.blocks.lo[i] = 0u; p.blocks.ext[i] = 1u; }
-  for (int i = 0; i < 3; i++) { p.nb[i] = 1u; p.lo[i] = 0u; p.ext[i] = 1u; }
-  for (int i = 0; i < sh.nd; i++) {
-    const int a = 3 - sh.nd + i;
-    p.nb[a] = (unsigned)sh.nb[i]; p.lo[a] = (unsigned)lo[i]; p.ext[a] = (unsigned)(hi[i] - lo[i]);
-    const unsigned bl = (unsigned)lo[i] / edge, bh = (unsigned)(hi[i] - 1) / edge;
-    p.blocks.dim[a + 1] = (unsigned)sh.nb[i]; p.blocks.lo[a + 1] = bl; p.blocks.ext[a + 1] = bh - bl + 1u;
-  }
+  nd_box_geometry(sh, lo, hi, p.nb, p.lo, p.ext, &p.blocks);
   // a workgroup per candidate tile
   const int geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
   const unsigned tiles = t1 - t0;
@@ -2649,6 +2661,96 @@ extern "C" int dctzhip_decompress_box_nd(dctzhip_ctx* c, const void* d_bin, cons
   HIPCHK(c, hipSetDevice(c->device));
   return (dtype == DCTZHIP_F64) ? decompress_box_nd_impl<double>(c, st, sh, lo, hi, t0, t1, (double*)d_out)
                                 : decompress_box_nd_impl<float>(c, st, sh, lo, hi, t0, t1, (float*)d_out);
+}
+
+// ---- a list of boxes of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_mboxnd.hip) --------------
+// decompress_boxes_impl for a tiled array.  recs[0, k) are complete but for the device side of the table, elems[0, k) the
+// boxes in elements; B bounds the hits.  The table is the records, then the element boxes.
+template <typename T>
+static int decompress_boxes_nd_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape& sh, int k, const BoxRec* recs, const NdBoxElems* elems,
+                                    unsigned total, size_t B) {
+  hipStream_t s = c->stream;
+  const int mode = st.mode, geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
+  int rc;
+  if ((rc = mbox_table(c))) return rc;
+  if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
+  c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
+  if ((rc = ra_begin<T>(c, mode, st.qtable))) return rc;
+  // (the table in one transfer behind everything of the prologue that can fail, as in decompress_boxes_impl)
+  const size_t rec_bytes = (size_t)k * sizeof(BoxRec), elem_bytes = (size_t)k * sizeof(NdBoxElems);
+  memcpy(c->mb_pin, recs, rec_bytes);
+  memcpy(c->mb_pin + rec_bytes, elems, elem_bytes);
+  {
+    const hipError_t e = hipMemcpyAsync(c->mb_dev, c->mb_pin, rec_bytes + elem_bytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+      (void)hipStreamSynchronize(s);
+      return fail(c, DCTZHIP_E_HIP, "copy of the box table failed: %s", hipGetErrorString(e));
+    }
+  }
+  BoxListParams lp;
+  lp.recs = reinterpret_cast<const BoxRec*>(c->mb_dev);
+  lp.nbox = (unsigned)k; lp.total = total; lp.unit = (unsigned)TILE_BLKS; lp.end = (unsigned)sh.nblk;
+  lp.items = c->mb_items; lp.cap = (unsigned)B; lp.ctl = c->ctl;
+  MBoxNdParams<T> p;
+  ra_fill_streams<T>(c, p, st);
+  p.recs = lp.recs; p.elems = reinterpret_cast<const NdBoxElems*>(c->mb_dev + rec_bytes); p.items = c->mb_items;
+  p.cap = (unsigned)B; p.n = (unsigned)(sh.nblk * 64); p.nfull = (unsigned)sh.nblk;
+  last_axes(sh.nd, p.nb, 1u, [&](int i) { return sh.nb[i]; });
+  // workgroups that take items off the list: at most one per item the list can hold
+  const int grid = (int)resident_grid(c, c->mboxnd_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3], B, [&] { return mboxnd_occupancy<T>(mode, geom); });
+  c->mbox_grid = (unsigned)grid; c->mbox_bound = (unsigned)B; c->mbox_items = 0;
+  launch_boxlist_build(lp, s);
+  launch_decompress_mbox_nd<T>(p, mode, geom, grid, s);
+  SET_LAST(c, 1, "k_decompress_mbox_nd<%s, %d, %d>", tname<T>(), mode, geom);
+  rc = ra_finish(c, &c->mbox_items);
+  if (rc == DCTZHIP_E_HIP) (void)hipStreamSynchronize(s);   // (a failed launch or read-back: the table's copy may still be in flight)
+  return rc;
+}
+
+extern "C" int dctzhip_decompress_boxes_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                           const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims, int dtype,
+                                           double eb, double sf, int mode, int k, const dctzhip_box_item* boxes) {
+  NdShape sh;
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
+  if (rc) return rc;
+  if (k < 1 || k > DCTZHIP_BOXES_MAX) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes_nd: k must be in [1, %d]", DCTZHIP_BOXES_MAX);
+  if (!boxes) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes_nd: null boxes");
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
+  if ((rc = streams_given(c, st, " and the outputs"))) return rc;           // (the outputs themselves: box by box, below)
+  std::vector<BoxRec> recs((size_t)k);
+  std::vector<NdBoxElems> elems((size_t)k);
+  // every buffer of the call against every other: the outputs may overlap nothing, neither each other nor what any box reads
+  std::vector<Span> sp((size_t)k * 4 + 1);
+  size_t m = 0, B = 0, total = 0;
+  add_span(sp.data(), &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, -1);
+  for (int i = 0; i < k; i++) {
+    char what[48];
+    snprintf(what, sizeof(what), "dctzhip_decompress_boxes_nd: box %d", i);
+    size_t cnt = 1;
+    BoxRec& r = recs[(size_t)i];
+    if ((rc = nd_box_front(c, what, sh, boxes[i].lo, boxes[i].hi, &cnt, &r.t0, &r.t1))) return rc;
+    if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", what);
+    if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", what);
+    tile_read_spans(sp.data(), &m, st, r.t0, r.t1, i);
+    add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(dtype), SPAN_OUT, i);
+    unsigned nb[3];
+    nd_box_geometry(sh, boxes[i].lo, boxes[i].hi, nb, elems[(size_t)i].lo, elems[(size_t)i].ext, &r.g);
+    r.cand0 = (unsigned)total;                      // (k <= 2^12 boxes of <= 2^19 candidates each)
+    r.out = boxes[i].d_out;
+    const size_t cand = r.t1 - r.t0;
+    total += cand;
+    // a run of L consecutive blocks touches at most ceil((L - 1) / 64) + 1 stream tiles
+    size_t runs = 1;
+    for (int d = 0; d < BOX_ND - 1; d++) runs *= r.g.ext[d];
+    const size_t runlen = r.g.ext[BOX_ND - 1];
+    B += std::min(cand, runs * ((runlen - 1 + TILE_BLKS - 1) / TILE_BLKS + 1));
+  }
+  if ((rc = check_spans(c, sp.data(), m, "dctzhip_decompress_boxes_nd", nullptr, "box"))) return rc;
+  if (B > MBOX_LIST_MAX)
+    return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes_nd: the boxes may hit %zu tiles, more than the %zu a call lists", B, MBOX_LIST_MAX);
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64) ? decompress_boxes_nd_impl<double>(c, st, sh, k, recs.data(), elems.data(), (unsigned)total, B)
+                                : decompress_boxes_nd_impl<float>(c, st, sh, k, recs.data(), elems.data(), (unsigned)total, B);
 }
 
 // ---- the whole array at reduced resolution (include/dctz_hip.h; dctz_kernels_coarse.hip) ------------------------

@@ -1771,7 +1771,7 @@ static int decompress_whole(t_var *var_z, t_var *var_r, const unsigned char *fix
   return 1;
 }
 
-/* ------------- dctz_decompress_range, dctz_decompress_box, dctz_decompress_boxes, dctz_decompress_box_nd -- */
+/* ------------- dctz_decompress_range, dctz_decompress_box, dctz_decompress_boxes, dctz_decompress_box_nd, dctz_decompress_boxes_nd -- */
 /* The first `want` bytes of one section into dst.  Indexed (sizes != NULL): only the chunks that hold them, side by side
  * on host threads (dst has room for whole chunks: min(raw, chunks * chunk) bytes); a chunk that does not inflate sends the
  * section to the streaming inflate.  Otherwise one inflate that stops once `want` bytes are out.  Returns the bytes made. */
@@ -1885,7 +1885,9 @@ static void part_times(const dev_streams *s, double t_begin, double t_gpu, doubl
 #define PART_TILED (-1)
 /* dctz_decompress_boxes: k boxes (rows of ndim entries) of one container through the same machinery ONCE -- the prefix of
  * the sections up to the last element of any box, one index, one dctzhip_decompress_boxes into one device arena, k copies
- * back. */
+ * back.  dctz_decompress_boxes_nd (PART_TILED with a list): the same for a DZND container, rows of the container's own
+ * number of dimensions, the span from 64 * the first intersecting block of any box to 64 * (the last of any + 1), one
+ * dctzhip_decompress_boxes_nd. */
 typedef struct { int k; const size_t *lo, *hi; t_var *const *var_r; } part_list;
 /* A box against n elements seen as dims: 0 and its first and last flat element and its element count, or -1. */
 static int box_span(size_t n, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, size_t *first, size_t *last, size_t *elems) {
@@ -1901,6 +1903,21 @@ static int box_span(size_t n, int ndim, const size_t *dims, const size_t *blo, c
   }
   return prod == n ? 0 : -1;
 }
+/* A box against the extents of a DZND container: 0 and its first and last intersecting block of the row-major block grid and
+ * its element count, or -1. */
+static int tiled_span(const dzc_view *v, const size_t *blo, const size_t *bhi, size_t *first, size_t *last, size_t *elems) {
+  if (!blo || !bhi) return -1;
+  const size_t edge = v->nd == 2 ? 8 : 4;
+  *first = 0; *last = 0; *elems = 1;
+  for (int i = 0; i < v->nd; i++) {
+    if (blo[i] >= bhi[i] || bhi[i] > v->dims[i]) return -1;
+    const size_t nb = (v->dims[i] + edge - 1) / edge;
+    *elems *= bhi[i] - blo[i];
+    *first = *first * nb + blo[i] / edge;
+    *last = *last * nb + (bhi[i] - 1) / edge;
+  }
+  return 0;
+}
 static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const size_t *dims, const size_t *blo, const size_t *bhi, t_var *var_r,
                            const part_list *list) {
   const double t_begin = now_s();
@@ -1913,36 +1930,31 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
   size_t out_elems;
   dctzhip_box_item *items = NULL;
-  if (tiled) {
-    if (!blo || !bhi || n == 0) return -1;
-    const size_t edge = v.nd == 2 ? 8 : 4;
-    size_t first = 0, last = 0;                                    /* intersecting blocks of the row-major block grid */
-    out_elems = 1;
-    for (int i = 0; i < v.nd; i++) {
-      if (blo[i] >= bhi[i] || bhi[i] > v.dims[i]) return -1;
-      const size_t nb = (v.dims[i] + edge - 1) / edge;
-      out_elems *= bhi[i] - blo[i];
-      first = first * nb + blo[i] / edge;
-      last = last * nb + (bhi[i] - 1) / edge;
-    }
-    lo = first * BLK_SZ; hi = (last + 1) * BLK_SZ;
-  } else if (list) {                                           /* [lo, hi): from the first element of any box to the last of any */
+  const int rows = tiled ? v.nd : ndim;                        /* entries per row of a list's lo / hi */
+  if (tiled && n == 0) return -1;
+  if (list) {                                                  /* [lo, hi): from the first position of any box to the last of any */
     if (list->k < 1 || list->k > DCTZHIP_BOXES_MAX || !list->lo || !list->hi || !list->var_r) return -1;
     items = (dctzhip_box_item *)calloc((size_t)list->k, sizeof(dctzhip_box_item));
     if (!items) { fprintf(stderr, "Out of memory: box list\n"); exit(1); }
     out_elems = 0;                                             /* the arena: every output at a multiple of 16 bytes */
     for (int j = 0; j < list->k; j++) {
       size_t first, last, elems;
-      if (!list->var_r[j] || box_span(n, ndim, dims, list->lo + (size_t)j * ndim, list->hi + (size_t)j * ndim, &first, &last, &elems) != 0) {
+      const size_t *jlo = list->lo + (size_t)j * rows, *jhi = list->hi + (size_t)j * rows;
+      if (!list->var_r[j] || (tiled ? tiled_span(&v, jlo, jhi, &first, &last, &elems) : box_span(n, ndim, dims, jlo, jhi, &first, &last, &elems)) != 0) {
         free(items);
         return -1;
       }
+      if (tiled) { first *= BLK_SZ; last = (last + 1) * BLK_SZ - 1; }   /* blocks -> stream positions */
       if (j == 0 || first < lo) lo = first;
       if (j == 0 || last + 1 > hi) hi = last + 1;
-      for (int i = 0; i < ndim; i++) { items[j].lo[i] = list->lo[(size_t)j * ndim + i]; items[j].hi[i] = list->hi[(size_t)j * ndim + i]; }
+      for (int i = 0; i < rows; i++) { items[j].lo[i] = jlo[i]; items[j].hi[i] = jhi[i]; }
       items[j].d_out = (void *)(uintptr_t)(out_elems * ts);    /* offset for now: the arena may still move */
       out_elems += (elems * ts + 15) / 16 * 16 / ts;
     }
+  } else if (tiled) {
+    size_t first, last;
+    if (tiled_span(&v, blo, bhi, &first, &last, &out_elems) != 0) return -1;
+    lo = first * BLK_SZ; hi = (last + 1) * BLK_SZ;
   } else if (ndim != 0) {
     size_t last;
     if (box_span(n, ndim, dims, blo, bhi, &lo, &last, &out_elems) != 0) return -1;
@@ -1962,18 +1974,19 @@ static int decompress_part(t_var *var_z, size_t lo, size_t hi, int ndim, const s
   const double t0 = now_s();
   grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
   if (list) for (int j = 0; j < list->k; j++) items[j].d_out = (unsigned char *)g_dev.out + (uintptr_t)items[j].d_out;
-  const int rc = list      ? dctzhip_decompress_boxes(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims, list->k, items)
+  const int rc = list && tiled ? dctzhip_decompress_boxes_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, list->k, items)
+                 : list    ? dctzhip_decompress_boxes(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims, list->k, items)
                  : tiled   ? dctzhip_decompress_box_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, blo, bhi, g_dev.out)
                  : ndim == 0 ? dctzhip_decompress_range(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, lo, hi, g_dev.out)
                            : dctzhip_decompress_box(DEV_STREAMS(s), n, dtype, v.h.error_bound, v.sf, DCTZ_MODE, ndim, dims, blo, bhi, g_dev.out);
   if (rc == DCTZHIP_E_ARG) goto out;                         /* the streams disagree with each other */
   if (rc != DCTZHIP_OK)
-    die(list ? "dctzhip_decompress_boxes" : tiled ? "dctzhip_decompress_box_nd" : ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
+    die(list && tiled ? "dctzhip_decompress_boxes_nd" : list ? "dctzhip_decompress_boxes" : tiled ? "dctzhip_decompress_box_nd" : ndim == 0 ? "dctzhip_decompress_range" : "dctzhip_decompress_box");
   const double t1s = now_s();
   if (list) {
     for (int j = 0; j < list->k; j++) {
       size_t elems = 1;
-      for (int i = 0; i < ndim; i++) elems *= items[j].hi[i] - items[j].lo[i];
+      for (int i = 0; i < rows; i++) elems *= items[j].hi[i] - items[j].lo[i];
       if (dctzhip_memcpy_d2h(c, var_bytes(list->var_r[j]), items[j].d_out, elems * ts) != DCTZHIP_OK) die("D2H output");
     }
   } else if (dctzhip_memcpy_d2h(c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
@@ -1999,6 +2012,11 @@ int dctz_decompress_boxes(t_var *var_z, int ndim, const size_t *dims, int k, con
 
 int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_var *var_r) {
   return decompress_part(var_z, 0, 0, PART_TILED, NULL, lo, hi, var_r, NULL);
+}
+
+int dctz_decompress_boxes_nd(t_var *var_z, int k, const size_t *lo, const size_t *hi, t_var *const *var_r) {
+  const part_list list = {k, lo, hi, var_r};
+  return decompress_part(var_z, 0, 0, PART_TILED, NULL, NULL, NULL, NULL, &list);
 }
 
 /* ------------------------------------------------------------- dctz_decompress_coarse -- */

@@ -147,6 +147,9 @@ _PROTOS = {
     "dctzhip_decompress_box_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int,
                                             C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_decompress_boxes_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int,
+                                              C.c_int, C.c_void_p]),
     "dctzhip_coarse_len": (C.c_size_t, [C.c_size_t, C.c_int]),
     "dctzhip_decompress_coarse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]),
@@ -631,6 +634,36 @@ class Context:
             float(eb), float(sf), mode, arr(*lo), arr(*hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_box_nd")
         return dst.view(ext)
+
+    def decompress_boxes_nd(self, out, cnt, shape, dtype, eb, sf, boxes, index, mode=EC, qtable=None, dsts=None):
+        """The boxes (lo, hi) of `boxes`, each what decompress_box_nd() gives for it, in ONE call (one work list of the hit
+        stream tiles of all boxes, one decode launch, one synchronisation).  Boxes may overlap or repeat.  Returns the list
+        of tensors shaped hi - lo; `dsts` (or None: allocated) are the outputs, one per box."""
+        t = self.torch
+        self._bind_stream()
+        shape = [int(v) for v in shape]
+        nd = len(shape)
+        boxes = [([int(v) for v in lo], [int(v) for v in hi]) for lo, hi in boxes]
+        exts = []
+        for lo, hi in boxes:
+            assert len(lo) == nd and len(hi) == nd
+            exts.append([max(h - l, 0) for l, h in zip(lo, hi)])
+        if dsts is None:
+            dsts = [t.empty(e, dtype=dtype, device=self.device) for e in exts]
+        assert len(dsts) == len(boxes)
+        q = self._qtable(mode, qtable, dtype)
+        items = (BoxItem * max(len(boxes), 1))()
+        for it, (lo, hi), d in zip(items, boxes, dsts):
+            for i in range(min(nd, BOX_MAXDIM)):
+                it.lo[i], it.hi[i] = lo[i], hi[i]
+            it.d_out = d.data_ptr()
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_decompress_boxes_nd(
+            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
+            index.data_ptr(), _host_ptr(q), nd, arr(*shape), _dt(dtype),
+            float(eb), float(sf), mode, len(boxes), C.cast(items, C.c_void_p))
+        self._check(rc, "dctzhip_decompress_boxes_nd")
+        return [d.view(e) for d, e in zip(dsts, exts)]
 
     def _qtable(self, mode, qtable, dtype):
         """The QT table as a decode call passes it: 64 entries of the data type in host memory (QT mode), else None."""

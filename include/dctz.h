@@ -193,6 +193,18 @@ int dctz_decompress_boxes(t_var *var_z, int ndim, const size_t *dims, int k,
  * dctzhip_decompress_box_nd), and only the box is copied back.  dctz_decompress_range and dctz_decompress_box keep
  * refusing DZND containers. */
 int dctz_decompress_box_nd(t_var *var_z, const size_t *lo, const size_t *hi, t_var *var_r);
+/* k boxes of ONE container compressed in tiles in one call (ADDITION, EC and QT builds), 1 <= k <= 4096: lo and hi hold k
+ * rows of as many entries as the container has dimensions, var_r[j]->buf (allocated by the caller) receives box j, the
+ * bytes dctz_decompress_box_nd gives for it.  Boxes may overlap or repeat.  The container is gone through ONCE: the
+ * sections are inflated up to what the stream positions [64 * first intersecting block of any box, 64 * (last intersecting
+ * block of any box + 1)) need (plain and DZIX), one exception index is built, one device call (include/dctz_hip.h:
+ * dctzhip_decompress_boxes_nd) decodes the hit stream tiles of every box into one device arena, and k copies bring the
+ * boxes back.  Return values are dctz_decompress_box_nd's, for any box of the list (nothing is written then); a flat
+ * container, a k outside 1 .. 4096 and a null lo, hi, var_r or var_r[j] return -1 as well.  dctz_decompress_boxes keeps
+ * refusing DZND containers. */
+int dctz_decompress_boxes_nd(t_var *var_z, int k,
+                             const size_t *lo, const size_t *hi,   /* k rows of the container's dimensions */
+                             t_var *const *var_r);                 /* k caller-allocated outputs */
 /* The whole array at reduced resolution (ADDITION, EC and QT builds): an overview at 1 / factor of the resolution along
  * every axis, computed from the low coefficients of every block without decoding the array (include/dctz_hip.h:
  * dctzhip_decompress_coarse / dctzhip_decompress_coarse_nd hold the definition).  var_z is a flat container (factor 2, 4,

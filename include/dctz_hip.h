@@ -156,7 +156,8 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr / _psnr_nd, 11 / 12 workgroups and
  * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran), 13 / 14 / 15 items
- * in the list of the last dctzhip_decompress_boxes call, workgroups of its decode launch and the list's bound, 16 / 17
+ * in the list of the last dctzhip_decompress_boxes or dctzhip_decompress_boxes_nd call (whichever of the two ran last),
+ * workgroups of its decode launch and the list's bound, 16 / 17
  * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again, 18 / 19 guesses of the
  * scaling factor taken from the remembered statistics of the same input that verified / that did not -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
@@ -482,6 +483,33 @@ int dctzhip_decompress_box_nd(dctzhip_ctx *ctx, const void *d_bin_index, const f
                               uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
                               const size_t *dims, int dtype, double error_bound, double sf, int mode,
                               const size_t *lo, const size_t *hi, void *d_out);
+/* k boxes of the SAME tiled array in one call: dctzhip_decompress_boxes for the streams of dctzhip_compress_nd.  Everything
+ * but the last two arguments is dctzhip_decompress_box_nd's; boxes is a HOST array of 1 <= k <= DCTZHIP_BOXES_MAX items, the
+ * first ndims entries of lo / hi are used.  One box table handed over in one transfer, one work list of (box, hit stream
+ * tile) pairs built on the device from the boxes of the block grid, one persistent decode launch whose workgroups take list
+ * items -- none of them ever meets a candidate tile that is not hit -- and one synchronisation.
+ *   boxes[i].d_out  receives exactly the bytes dctzhip_decompress_box_nd writes for box i with the same remaining
+ *               arguments (EC and QT, fp32 and fp64, block-aligned and ragged extents)
+ *   overlap     boxes may overlap, nest or repeat.  A stream tile hit by m boxes is decoded m times: de-duplication is
+ *               not part of this call.
+ *   locality    the call reads the bin ids, DC values, idx[t], idx[t + 1] and AC_exact[idx[t], idx[t + 1]) of stream tiles
+ *               hit by at least one box and nothing else of the streams; it writes nothing outside the k outputs (padded
+ *               positions of edge blocks are never stored).
+ *   refusals    before anything is launched or written, all or nothing, DCTZHIP_E_ARG: k < 1, k > DCTZHIP_BOXES_MAX, a null
+ *               boxes; whatever dctzhip_decompress_box_nd refuses for ctx, ndims, dims, the streams and the QT table; for
+ *               any box what it refuses for lo, hi and d_out (the message names "box i"); an output that overlaps another
+ *               output or what any box of the call may read (its candidate tiles' bin ids, DC values and index entries,
+ *               AC_exact[0, ac_count)); boxes that may hit more than 2^24 stream tiles in all (the bound of the work list:
+ *               per box the smaller of its candidate tiles and the tiles its runs of blocks along the fastest axis can
+ *               touch).  On the device, for listed tiles only, dctzhip_decompress_box_nd's index check: a failing tile
+ *               reads no AC_exact, the call returns DCTZHIP_E_ARG, the outputs are undefined and the context stays usable.
+ * Returns once that check is known, having synchronised the context's stream once.
+ * dctzhip_debug_counter 13 / 14 / 15 report the last list call of either kind (this one or dctzhip_decompress_boxes):
+ * items of its list, workgroups of its decode launch, the list's bound. */
+int dctzhip_decompress_boxes_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                                uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                                const size_t *dims, int dtype, double error_bound, double sf, int mode,
+                                int k, const dctzhip_box_item *boxes /* host */);
 
 /* ---- coarse decode: the whole array at reduced resolution -------------------- */
 /* An overview of the whole array at 1 / factor of its resolution along every axis, from the low coefficients of every

@@ -19,6 +19,11 @@
                  (the same bricks as 64 dctzhip_decompress_box calls), --via one (the single brick at 224^3 through the
                  list call), --via dropin (8 of the bricks from the shard's 1 GiB DZIX container: dctz_decompress_boxes
                  against 8 dctz_decompress_box calls, wall clock, host buffers)
+  --what ndboxes the same lists for the shard compressed in 4 x 4 x 4 tiles (compress_nd): --via list (the 64 bricks through
+                 ONE dctzhip_decompress_boxes_nd call: k_boxlist_build + k_decompress_mbox_nd), --via loop (64
+                 dctzhip_decompress_box_nd calls), --via one (--box brick | xplane | zplane | full as a one-item list),
+                 --via dropin (8 of the bricks from the shard's DZIX DZND container: dctz_decompress_boxes_nd against 8
+                 dctz_decompress_box_nd calls, wall clock, host buffers)
 Every other run also times dctzhip_decompress of the whole shard.  Wall-clock medians go to stdout as one JSON line; for device
 times run one --what per process under `rocprofv3 --kernel-trace --stats -- python tools/range_bench.py --what ...`."""
 import argparse
@@ -33,7 +38,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin", "box", "ndbox", "boxes"], required=True)
+    ap.add_argument("--what", choices=["index", "range", "one", "full", "dropin", "box", "ndbox", "boxes", "ndboxes"], required=True)
     ap.add_argument("--box", choices=["brick", "zplane", "xplane", "full", "c2"], default="brick")
     ap.add_argument("--via", choices=["box", "ranges", "slice", "list", "loop", "one", "dropin"], default="box")
     ap.add_argument("--n", type=int, default=512, help="edge of the cube")
@@ -52,6 +57,8 @@ def main():
         return ndbox(a, W)
     if a.what == "boxes":
         return boxes_dropin(a, W) if a.via == "dropin" else boxes(a, W)
+    if a.what == "ndboxes":
+        return ndboxes_dropin(a, W) if a.via == "dropin" else ndboxes(a, W)
     ctx = dctz_amd.Context(0)
     x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device)
     n = x.numel()
@@ -354,6 +361,136 @@ def ndbox(a, W):
                       "hit_tiles": int(hit.sum()), "candidate_tiles": int(t[-1] - t[0] + 1), "grid": ctx.counter(11),
                       "kernel": ctx.last_kernel(1), "wall_ms_decompress_nd": round(ms_full, 4), "wall_ms_box_nd": round(ms_what, 4)}))
     ctx.close()
+
+
+def ndboxes(a, W):
+    import numpy as np
+    import torch
+    import dctz_amd
+
+    if a.via not in ("list", "loop", "one"):
+        raise SystemExit("--what ndboxes takes --via list | loop | one | dropin")
+    if a.box == "c2":
+        raise SystemExit("--what ndboxes --via one runs the boxes of the cube: brick, zplane, xplane, full")
+    ctx = dctz_amd.Context(0)
+    e, tdt = a.n, torch.float64
+    dims = (e, e, e)
+    x = torch.from_numpy(W.c3(a.n, seed=512)).to(ctx.device).reshape(dims)
+    eb = 1e-3
+    out, info = ctx.compress_nd(x, eb, dctz_amd.EC)
+    del x
+    nblk = ctx.nd_blocks(dims)
+    full = torch.empty(dims, dtype=tdt, device=ctx.device)
+    idx, tot = ctx.ac_index(out, 64 * nblk)
+    assert tot == info.cnt
+    single = {"brick": ((224 * e // 512,) * 3, (224 * e // 512 + 64,) * 3), "zplane": ((100, 0, 0), (101, e, e)),
+              "xplane": ((0, 0, 100), (e, e, 101)), "full": ((0, 0, 0), dims)}[a.box]
+    bx = [single] if a.via == "one" else lattice(e)
+    dsts = [torch.empty(tuple(h - l for l, h in zip(lo, hi)), dtype=tdt, device=ctx.device) for lo, hi in bx]
+
+    def t_full():
+        ctx.decompress_nd(out, info.cnt, dims, tdt, eb, info.sf, dctz_amd.EC, dst=full)
+
+    def t_list():
+        ctx.decompress_boxes_nd(out, info.cnt, dims, tdt, eb, info.sf, bx, idx, dctz_amd.EC, dsts=dsts)
+
+    def t_loop():
+        for (lo, hi), d in zip(bx, dsts):
+            ctx.decompress_box_nd(out, info.cnt, dims, tdt, eb, info.sf, lo, hi, idx, dctz_amd.EC, dst=d)
+
+    f_what = t_loop if a.via == "loop" else t_list
+
+    def med(f, reps):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    for f in (t_full, f_what):                      # warm-up
+        f()
+    ms_full, ms_what = med(t_full, a.reps), med(f_what, a.reps)
+    for (lo, hi), d in zip(bx, dsts):
+        sl = tuple(slice(l, h) for l, h in zip(lo, hi))
+        assert torch.equal(d.contiguous().view(torch.int64), full[sl].contiguous().view(torch.int64))
+    res = {"what": "ndboxes", "via": a.via, "n": e ** 3, "cnt": info.cnt, "boxes": len(bx), "kernel": ctx.last_kernel(1),
+           "wall_ms_decompress_nd": round(ms_full, 4), "wall_ms_" + a.via: round(ms_what, 4)}
+    if a.via == "one":
+        res.update(box=a.box)
+    if a.via != "loop":
+        res.update(items=ctx.counter(13), grid=ctx.counter(14), bound=ctx.counter(15))
+    else:
+        res.update(grid_per_call=ctx.counter(11), candidates_per_call=ctx.counter(12))
+    print(json.dumps(res))
+    ctx.close()
+
+
+def ndboxes_dropin(a, W):
+    import ctypes as C
+    import numpy as np
+
+    class Buf(C.Union):
+        _fields_ = [("f", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_double))]
+
+    class TVar(C.Structure):                        # include/dctz.h: t_var
+        _fields_ = [("datatype", C.c_int), ("err_bound", C.c_double), ("var_name", C.c_char_p), ("buf", Buf)]
+
+    def tv(arr):
+        v = TVar()
+        v.datatype = 1
+        v.buf.d = arr.ctypes.data_as(C.POINTER(C.c_double))
+        return v
+
+    os.environ["DCTZ_QUIET"] = "1"
+    lib = C.CDLL(os.path.join(ROOT, "dctz_amd", "lib", "libdctz-ec.so"))
+    lib.dctz_compress.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(TVar), C.c_double]
+    lib.dctz_set_block_dims.argtypes = [C.c_int, C.POINTER(C.c_size_t)]
+    lib.dctz_decompress_box_nd.argtypes = [C.POINTER(TVar), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(TVar)]
+    lib.dctz_decompress_boxes_nd.argtypes = [C.POINTER(TVar), C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                             C.POINTER(C.POINTER(TVar))]
+    e = a.n
+    dims = (e, e, e)
+    arr = lambda v: (C.c_size_t * len(v))(*v)
+    x = W.c3(e, seed=512)
+    n = x.size
+    z = np.empty(n + (1 << 20), np.float64)
+    sz = C.c_size_t(0)
+    os.environ["DCTZ_ZLIB_GPU"] = "1"
+    assert lib.dctz_set_block_dims(3, arr(dims)) == 0
+    assert lib.dctz_compress(C.byref(tv(x)), n, C.byref(sz), C.byref(tv(z)), 1e-3) == 1
+    del os.environ["DCTZ_ZLIB_GPU"]
+    bx = lattice(e)[21:43:3]                        # 8 bricks from the middle of the lattice
+    assert len(bx) == 8
+    one = [np.empty(64 ** 3, np.float64) for _ in bx]
+    many = [np.empty(64 ** 3, np.float64) for _ in bx]
+    tvs = [tv(o) for o in many]
+    ptrs = (C.POINTER(TVar) * len(bx))(*[C.pointer(t) for t in tvs])
+    los, his = arr([v for lo, hi in bx for v in lo]), arr([v for lo, hi in bx for v in hi])
+
+    def t_loop():
+        for (lo, hi), o in zip(bx, one):
+            assert lib.dctz_decompress_box_nd(C.byref(tv(z)), arr(lo), arr(hi), C.byref(tv(o))) == 1
+
+    def t_list():
+        assert lib.dctz_decompress_boxes_nd(C.byref(tv(z)), len(bx), los, his, ptrs) == 1
+
+    def med(f):
+        f()
+        ts = []
+        for _ in range(max(3, a.reps // 4)):
+            t0 = time.perf_counter()
+            f()
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    ms_loop, ms_list = med(t_loop), med(t_list)
+    for o, m in zip(one, many):
+        assert np.array_equal(o.view(np.uint64), m.view(np.uint64))
+    print(json.dumps({"what": "ndboxes", "via": "dropin", "n": n, "container_bytes": sz.value, "boxes": len(bx),
+                      "wall_ms_8x_dctz_decompress_box_nd": round(ms_loop, 3), "wall_ms_dctz_decompress_boxes_nd": round(ms_list, 3)}))
 
 
 def dropin(a, W):
