@@ -2101,6 +2101,15 @@ static void tile_read_spans(Span* sp, size_t* m, const StreamSet& st, size_t t0,
   add_span(sp, m, st.index + t0, (t1 - t0 + 1) * sizeof(uint32_t), SPAN_READ, item);
 }
 static_assert(DCTZHIP_INDEX_STRIDE == TILE_ELEMS && TILE_ELEMS % 64 == 0, "index entries are per stream tile, tiles hold whole blocks");
+// The buffers of a call with one output against each other: what the stream tiles [t0, t1) read, AC_exact, the output.
+static int ra_check_spans(dctzhip_ctx* c, const char* what, const StreamSet& st, size_t t0, size_t t1, const void* d_out, size_t out_bytes) {
+  Span sp[5];
+  size_t m = 0;
+  tile_read_spans(sp, &m, st, t0, t1, 0);
+  add_span(sp, &m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, 0);
+  add_span(sp, &m, d_out, out_bytes, SPAN_OUT, 0);
+  return check_spans(c, sp, m, what, nullptr);
+}
 
 // What the random-access calls share around their launch.  ra_begin: the control block is clean and the QT table staged;
 // ra_fill: the fields every parameter block has; ra_finish: the error word read back -- the call returns once the index
@@ -2191,16 +2200,9 @@ extern "C" int dctzhip_decompress_range(dctzhip_ctx* c, const void* d_bin, const
   if (lo >= hi || hi > n) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_range: the range [%zu, %zu) is not inside [0, %zu)", lo, hi, n);
   const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
   if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
-  {
-    // what the call reads: the range's tiles and AC_exact
-    Span sp[5];
-    size_t m = 0;
-    tile_read_spans(sp, &m, st, lo / TILE_ELEMS, (hi + TILE_ELEMS - 1) / TILE_ELEMS, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_out, (hi - lo) * elem_size(dtype), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_decompress_range", nullptr);
-    if (rc) return rc;
-  }
+  // what the call reads: the range's tiles and AC_exact
+  rc = ra_check_spans(c, "dctzhip_decompress_range", st, lo / TILE_ELEMS, (hi + TILE_ELEMS - 1) / TILE_ELEMS, d_out, (hi - lo) * elem_size(dtype));
+  if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return (dtype == DCTZHIP_F64) ? decompress_range_impl<double>(c, st, lo, hi, (double*)d_out)
                                 : decompress_range_impl<float>(c, st, lo, hi, (float*)d_out);
@@ -2300,131 +2302,13 @@ extern "C" int dctzhip_decompress_box(dctzhip_ctx* c, const void* d_bin, const f
   if (rc) return rc;
   const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
   if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
-  {
-    // what the call may read: what dctzhip_decompress_range reads for [first box element, last box element + 1)
-    Span sp[5];
-    size_t m = 0;
-    tile_read_spans(sp, &m, st, first / TILE_ELEMS, last / TILE_ELEMS + 1, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_decompress_box", nullptr);
-    if (rc) return rc;
-  }
+  // what the call may read: what dctzhip_decompress_range reads for [first box element, last box element + 1)
+  rc = ra_check_spans(c, "dctzhip_decompress_box", st, first / TILE_ELEMS, last / TILE_ELEMS + 1, d_out, cnt * elem_size(dtype));
+  if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const BoxGeo box = canonical_box(ndim, dims, lo, hi);
   return (dtype == DCTZHIP_F64) ? decompress_box_impl<double>(c, st, box, first, last, (double*)d_out)
                                 : decompress_box_impl<float>(c, st, box, first, last, (float*)d_out);
-}
-
-// ---- a list of boxes in one call (include/dctz_hip.h; dctz_kernels_mbox.hip) ------------------------------------
-static constexpr size_t MBOX_LIST_MAX = (size_t)1 << 24;                // items: the bound B of a call may not exceed it
-// the table of a call: the records, then per box an unsigned (flat arrays: the boxes of the short block) or the box in elements (tiled arrays)
-static constexpr size_t MBOX_TABLE_BYTES = (size_t)DCTZHIP_BOXES_MAX * (sizeof(BoxRec) + std::max(sizeof(unsigned), sizeof(NdBoxElems)));
-static int mbox_table(dctzhip_ctx* c) {
-  if (!c->mb_pin) {
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mb_pin), MBOX_TABLE_BYTES, hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(&c->mb_dev, MBOX_TABLE_BYTES));
-  }
-  return DCTZHIP_OK;
-}
-
-// recs[0, k) are complete but for the device side of the table; rem_boxes[0, nrem) reach into the short block; B bounds the hits.
-template <typename T>
-static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, int k, const BoxRec* recs, const unsigned* rem_boxes, int nrem,
-                                 unsigned total, size_t B) {
-  hipStream_t s = c->stream;
-  const size_t n = st.n;
-  const int mode = st.mode;
-  const unsigned nfull = (unsigned)(n / 64);
-  const int rem = (int)(n % 64);
-  int rc;
-  if ((rc = mbox_table(c))) return rc;
-  if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
-  c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
-  if ((rc = ra_begin<T>(c, mode, st.qtable))) return rc;
-  if (nrem) { if ((rc = upload_rtab<T>(c, rem))) return rc; }
-  // the table in one transfer, on the call's stream, behind everything of the prologue that can fail: from here on the call
-  // reaches its synchronisation (ra_finish), or the stream is synchronised before the error is returned, so the pinned
-  // copy is never rewritten under a copy in flight
-  const size_t rec_bytes = (size_t)k * sizeof(BoxRec);
-  memcpy(c->mb_pin, recs, rec_bytes);
-  memcpy(c->mb_pin + rec_bytes, rem_boxes, (size_t)nrem * sizeof(unsigned));
-  {
-    const hipError_t e = hipMemcpyAsync(c->mb_dev, c->mb_pin, rec_bytes + (size_t)nrem * sizeof(unsigned), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-      (void)hipStreamSynchronize(s);
-      return fail(c, DCTZHIP_E_HIP, "copy of the box table failed: %s", hipGetErrorString(e));
-    }
-  }
-  BoxListParams lp;
-  lp.recs = reinterpret_cast<const BoxRec*>(c->mb_dev);
-  lp.nbox = (unsigned)k; lp.total = total; lp.unit = (unsigned)TILE_ELEMS; lp.end = (unsigned)n;
-  lp.items = c->mb_items; lp.cap = (unsigned)B; lp.ctl = c->ctl;
-  MBoxParams<T> p;
-  ra_fill_streams<T>(c, p, st);
-  p.rtab = reinterpret_cast<const T*>(c->rtab);
-  p.recs = lp.recs; p.items = c->mb_items; p.rem_boxes = reinterpret_cast<const unsigned*>(c->mb_dev + rec_bytes);
-  p.cap = (unsigned)B; p.n = (unsigned)n; p.nfull = nfull;
-  // workgroups that take items off the list: at most one per item the list can hold
-  const int grid = (int)resident_grid(c, c->mbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT], B, [&] { return mbox_occupancy<T>(mode); });
-  c->mbox_grid = (unsigned)grid; c->mbox_bound = (unsigned)B; c->mbox_items = 0;
-  launch_boxlist_build(lp, s);
-  launch_decompress_mbox<T>(p, mode, grid, nrem, s);
-  SET_LAST(c, 1, "k_decompress_mbox<%s, %d>", tname<T>(), mode);
-  rc = ra_finish(c, &c->mbox_items);
-  if (rc == DCTZHIP_E_HIP) (void)hipStreamSynchronize(s);   // (a failed launch or read-back: the table's copy may still be in flight)
-  return rc;
-}
-
-extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
-                                        const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf,
-                                        int mode, int ndim, const size_t* dims, int k, const dctzhip_box_item* boxes) {
-  int rc = check_common(c, n, dtype, mode);
-  if (rc) return rc;
-  if (k < 1 || k > DCTZHIP_BOXES_MAX) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: k must be in [1, %d]", DCTZHIP_BOXES_MAX);
-  if (!boxes) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: null boxes");
-  if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: ndim must be in [1, %d]", DCTZHIP_BOX_MAXDIM);
-  if (!dims) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: null dims");
-  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
-  if ((rc = streams_given(c, st, " and the outputs"))) return rc;           // (the outputs themselves: box by box, below)
-  const unsigned nfull = (unsigned)(n / 64);
-  const bool rem = n % 64 != 0;
-  std::vector<BoxRec> recs((size_t)k);
-  std::vector<unsigned> rem_boxes;
-  // every buffer of the call against every other: the outputs may overlap nothing, neither each other nor what any box reads
-  std::vector<Span> sp((size_t)k * 4 + 1);
-  size_t m = 0, B = 0, total = 0;
-  add_span(sp.data(), &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, -1);
-  for (int i = 0; i < k; i++) {
-    char what[48];
-    snprintf(what, sizeof(what), "dctzhip_decompress_boxes: box %d", i);
-    size_t cnt, first, last;
-    if ((rc = box_extents(c, what, n, ndim, dims, boxes[i].lo, boxes[i].hi, &cnt, &first, &last))) return rc;
-    if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", what);
-    if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", what);
-    tile_read_spans(sp.data(), &m, st, first / TILE_ELEMS, last / TILE_ELEMS + 1, i);
-    add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(dtype), SPAN_OUT, i);
-    BoxRec& r = recs[(size_t)i];
-    r.g = canonical_box(ndim, dims, boxes[i].lo, boxes[i].hi);
-    r.t0 = (unsigned)(first / TILE_ELEMS); r.t1 = (unsigned)(last / TILE_ELEMS + 1);
-    r.cand0 = (unsigned)total;                      // (k <= 2^12 boxes of <= 2^19 candidates each)
-    r.out = boxes[i].d_out;
-    const size_t cand = r.t1 - r.t0;
-    total += cand;
-    // a run of L consecutive elements touches at most ceil((L - 1) / 4096) + 1 tiles
-    size_t runs = 1;
-    for (int d = 0; d < BOX_ND - 1; d++) runs *= r.g.ext[d];
-    const size_t runlen = r.g.ext[BOX_ND - 1];
-    B += std::min(cand, runs * ((runlen - 1 + TILE_ELEMS - 1) / TILE_ELEMS + 1));
-    if (rem && r.g.rank((unsigned)n) != r.g.rank(nfull * 64u)) rem_boxes.push_back((unsigned)i);
-  }
-  if ((rc = check_spans(c, sp.data(), m, "dctzhip_decompress_boxes", nullptr, "box"))) return rc;
-  if (B > MBOX_LIST_MAX)
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes: the boxes may hit %zu tiles, more than the %zu a call lists", B, MBOX_LIST_MAX);
-  HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64)
-             ? decompress_boxes_impl<double>(c, st, k, recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B)
-             : decompress_boxes_impl<float>(c, st, k, recs.data(), rem_boxes.data(), (int)rem_boxes.size(), (unsigned)total, B);
 }
 
 // ---- multi-dimensional blocks (include/dctz_hip.h) -------------------------------------------------
@@ -2648,40 +2532,48 @@ extern "C" int dctzhip_decompress_box_nd(dctzhip_ctx* c, const void* d_bin, cons
   if ((rc = nd_box_front(c, "dctzhip_decompress_box_nd", sh, lo, hi, &cnt, &t0, &t1))) return rc;
   const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
   if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
-  {
-    // what the call may read: the candidate tiles and AC_exact
-    Span sp[5];
-    size_t m = 0;
-    tile_read_spans(sp, &m, st, t0, t1, 0);
-    add_span(sp, &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, 0);
-    add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_decompress_box_nd", nullptr);
-    if (rc) return rc;
-  }
+  // what the call may read: the candidate tiles and AC_exact
+  if ((rc = ra_check_spans(c, "dctzhip_decompress_box_nd", st, t0, t1, d_out, cnt * elem_size(dtype)))) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return (dtype == DCTZHIP_F64) ? decompress_box_nd_impl<double>(c, st, sh, lo, hi, t0, t1, (double*)d_out)
                                 : decompress_box_nd_impl<float>(c, st, sh, lo, hi, t0, t1, (float*)d_out);
 }
 
-// ---- a list of boxes of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_mboxnd.hip) --------------
-// decompress_boxes_impl for a tiled array.  recs[0, k) are complete but for the device side of the table, elems[0, k) the
-// boxes in elements; B bounds the hits.  The table is the records, then the element boxes.
+// ---- a list of boxes in one call (include/dctz_hip.h; dctz_kernels_mbox.hip, tiled: dctz_kernels_mboxnd.hip) -----
+static constexpr size_t MBOX_LIST_MAX = (size_t)1 << 24;                // items: the bound B of a call may not exceed it
+// the table of a call: the records, then per box an unsigned (flat arrays: the boxes of the short block) or the box in elements (tiled arrays)
+static constexpr size_t MBOX_TABLE_BYTES = (size_t)DCTZHIP_BOXES_MAX * (sizeof(BoxRec) + std::max(sizeof(unsigned), sizeof(NdBoxElems)));
+static int mbox_table(dctzhip_ctx* c) {
+  if (!c->mb_pin) {
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->mb_pin), MBOX_TABLE_BYTES, hipHostMallocDefault));
+    HIPCHK(c, hipMalloc(&c->mb_dev, MBOX_TABLE_BYTES));
+  }
+  return DCTZHIP_OK;
+}
+
+// sh null: st.n elements in flat blocks; else the tiles of sh (st.n = 64 sh->nblk, no short block).  recs[0, k) are complete
+// but for the device side of the table; side[0, side_bytes) is the table's second half -- flat: the boxes that reach into
+// the short block, an unsigned each; tiled: the k boxes in elements, an NdBoxElems each; B bounds the hits.
 template <typename T>
-static int decompress_boxes_nd_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape& sh, int k, const BoxRec* recs, const NdBoxElems* elems,
-                                    unsigned total, size_t B) {
+static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape* sh, int k, const BoxRec* recs, const void* side,
+                                 size_t side_bytes, unsigned total, size_t B) {
   hipStream_t s = c->stream;
-  const int mode = st.mode, geom = sh.nd == 2 ? GEOM_2D : GEOM_3D;
+  const int mode = st.mode;
+  const int nrem = sh ? 0 : (int)(side_bytes / sizeof(unsigned));
   int rc;
   if ((rc = mbox_table(c))) return rc;
   if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
   c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
   if ((rc = ra_begin<T>(c, mode, st.qtable))) return rc;
-  // (the table in one transfer behind everything of the prologue that can fail, as in decompress_boxes_impl)
-  const size_t rec_bytes = (size_t)k * sizeof(BoxRec), elem_bytes = (size_t)k * sizeof(NdBoxElems);
+  if (nrem) { if ((rc = upload_rtab<T>(c, (int)(st.n % 64)))) return rc; }      // (it can fail: in front of the table's copy)
+  // the table in one transfer, on the call's stream, behind everything of the prologue that can fail: from here on the call
+  // reaches its synchronisation (ra_finish), or the stream is synchronised before the error is returned, so the pinned
+  // copy is never rewritten under a copy in flight
+  const size_t rec_bytes = (size_t)k * sizeof(BoxRec);
   memcpy(c->mb_pin, recs, rec_bytes);
-  memcpy(c->mb_pin + rec_bytes, elems, elem_bytes);
+  memcpy(c->mb_pin + rec_bytes, side, side_bytes);
   {
-    const hipError_t e = hipMemcpyAsync(c->mb_dev, c->mb_pin, rec_bytes + elem_bytes, hipMemcpyHostToDevice, s);
+    const hipError_t e = hipMemcpyAsync(c->mb_dev, c->mb_pin, rec_bytes + side_bytes, hipMemcpyHostToDevice, s);
     if (e != hipSuccess) {
       (void)hipStreamSynchronize(s);
       return fail(c, DCTZHIP_E_HIP, "copy of the box table failed: %s", hipGetErrorString(e));
@@ -2689,22 +2581,113 @@ static int decompress_boxes_nd_impl(dctzhip_ctx* c, const StreamSet& st, const N
   }
   BoxListParams lp;
   lp.recs = reinterpret_cast<const BoxRec*>(c->mb_dev);
-  lp.nbox = (unsigned)k; lp.total = total; lp.unit = (unsigned)TILE_BLKS; lp.end = (unsigned)sh.nblk;
+  lp.nbox = (unsigned)k; lp.total = total;
+  lp.unit = (unsigned)(sh ? TILE_BLKS : TILE_ELEMS); lp.end = (unsigned)(sh ? sh->nblk : st.n);
   lp.items = c->mb_items; lp.cap = (unsigned)B; lp.ctl = c->ctl;
-  MBoxNdParams<T> p;
-  ra_fill_streams<T>(c, p, st);
-  p.recs = lp.recs; p.elems = reinterpret_cast<const NdBoxElems*>(c->mb_dev + rec_bytes); p.items = c->mb_items;
-  p.cap = (unsigned)B; p.n = (unsigned)(sh.nblk * 64); p.nfull = (unsigned)sh.nblk;
-  last_axes(sh.nd, p.nb, 1u, [&](int i) { return sh.nb[i]; });
+  // what the two parameter blocks share
+  auto fill = [&](auto& p) {
+    ra_fill_streams<T>(c, p, st);
+    p.recs = lp.recs; p.items = c->mb_items;
+    p.cap = (unsigned)B; p.n = (unsigned)st.n; p.nfull = (unsigned)(st.n / 64);
+  };
+  c->mbox_bound = (unsigned)B; c->mbox_items = 0;
   // workgroups that take items off the list: at most one per item the list can hold
-  const int grid = (int)resident_grid(c, c->mboxnd_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh.nd == 3], B, [&] { return mboxnd_occupancy<T>(mode, geom); });
-  c->mbox_grid = (unsigned)grid; c->mbox_bound = (unsigned)B; c->mbox_items = 0;
-  launch_boxlist_build(lp, s);
-  launch_decompress_mbox_nd<T>(p, mode, geom, grid, s);
-  SET_LAST(c, 1, "k_decompress_mbox_nd<%s, %d, %d>", tname<T>(), mode, geom);
+  if (!sh) {
+    MBoxParams<T> p;
+    fill(p);
+    p.rtab = reinterpret_cast<const T*>(c->rtab);
+    p.rem_boxes = reinterpret_cast<const unsigned*>(c->mb_dev + rec_bytes);
+    const int grid = (int)resident_grid(c, c->mbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT], B, [&] { return mbox_occupancy<T>(mode); });
+    c->mbox_grid = (unsigned)grid;
+    launch_boxlist_build(lp, s);
+    launch_decompress_mbox<T>(p, mode, grid, nrem, s);
+    SET_LAST(c, 1, "k_decompress_mbox<%s, %d>", tname<T>(), mode);
+  } else {
+    const int geom = sh->nd == 2 ? GEOM_2D : GEOM_3D;
+    MBoxNdParams<T> p;
+    fill(p);
+    p.elems = reinterpret_cast<const NdBoxElems*>(c->mb_dev + rec_bytes);
+    last_axes(sh->nd, p.nb, 1u, [&](int i) { return sh->nb[i]; });
+    const int grid = (int)resident_grid(c, c->mboxnd_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh->nd == 3], B, [&] { return mboxnd_occupancy<T>(mode, geom); });
+    c->mbox_grid = (unsigned)grid;
+    launch_boxlist_build(lp, s);
+    launch_decompress_mbox_nd<T>(p, mode, geom, grid, s);
+    SET_LAST(c, 1, "k_decompress_mbox_nd<%s, %d, %d>", tname<T>(), mode, geom);
+  }
   rc = ra_finish(c, &c->mbox_items);
   if (rc == DCTZHIP_E_HIP) (void)hipStreamSynchronize(s);   // (a failed launch or read-back: the table's copy may still be in flight)
   return rc;
+}
+
+// What the two entry points share from the k check on.  sh null: the flat array of st.n elements seen with the shape dims[0, ndim),
+// which is checked here; else the tiles of sh.
+static int decompress_boxes_call(dctzhip_ctx* c, const char* what, const StreamSet& st, const NdShape* sh, int ndim, const size_t* dims, int k,
+                                 const dctzhip_box_item* boxes) {
+  int rc;
+  if (k < 1 || k > DCTZHIP_BOXES_MAX) return fail(c, DCTZHIP_E_ARG, "%s: k must be in [1, %d]", what, DCTZHIP_BOXES_MAX);
+  if (!boxes) return fail(c, DCTZHIP_E_ARG, "%s: null boxes", what);
+  if (!sh) {
+    if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "%s: ndim must be in [1, %d]", what, DCTZHIP_BOX_MAXDIM);
+    if (!dims) return fail(c, DCTZHIP_E_ARG, "%s: null dims", what);
+  }
+  if ((rc = streams_given(c, st, " and the outputs"))) return rc;           // (the outputs themselves: box by box, below)
+  const unsigned nfull = (unsigned)(st.n / 64);
+  const bool rem = st.n % 64 != 0;
+  const size_t unit = sh ? TILE_BLKS : TILE_ELEMS;  // what a candidate spans: the blocks, or of a flat array the elements, of a stream tile
+  std::vector<BoxRec> recs((size_t)k);
+  // the second half of the table: the boxes that reach into the short block (flat), or every box in elements (tiled)
+  std::vector<unsigned> rem_boxes;
+  std::vector<NdBoxElems> elems(sh ? (size_t)k : 0);
+  // every buffer of the call against every other: the outputs may overlap nothing, neither each other nor what any box reads
+  std::vector<Span> sp((size_t)k * 4 + 1);
+  size_t m = 0, B = 0, total = 0;
+  add_span(sp.data(), &m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, -1);
+  for (int i = 0; i < k; i++) {
+    char box[56];
+    snprintf(box, sizeof(box), "%s: box %d", what, i);
+    size_t cnt = 1;
+    BoxRec& r = recs[(size_t)i];
+    if (!sh) {
+      size_t first, last;
+      if ((rc = box_extents(c, box, st.n, ndim, dims, boxes[i].lo, boxes[i].hi, &cnt, &first, &last))) return rc;
+      r.t0 = (unsigned)(first / TILE_ELEMS); r.t1 = (unsigned)(last / TILE_ELEMS + 1);
+      r.g = canonical_box(ndim, dims, boxes[i].lo, boxes[i].hi);
+      if (rem && r.g.rank((unsigned)st.n) != r.g.rank(nfull * 64u)) rem_boxes.push_back((unsigned)i);
+    } else {
+      if ((rc = nd_box_front(c, box, *sh, boxes[i].lo, boxes[i].hi, &cnt, &r.t0, &r.t1))) return rc;
+      unsigned nb[3];
+      nd_box_geometry(*sh, boxes[i].lo, boxes[i].hi, nb, elems[(size_t)i].lo, elems[(size_t)i].ext, &r.g);
+    }
+    if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", box);
+    if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", box);
+    tile_read_spans(sp.data(), &m, st, r.t0, r.t1, i);
+    add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(st.dtype), SPAN_OUT, i);
+    r.cand0 = (unsigned)total;                      // (k <= 2^12 boxes of <= 2^19 candidates each)
+    r.out = boxes[i].d_out;
+    const size_t cand = r.t1 - r.t0;
+    total += cand;
+    // a run of L consecutive elements (blocks) touches at most ceil((L - 1) / unit) + 1 stream tiles
+    size_t runs = 1;
+    for (int d = 0; d < BOX_ND - 1; d++) runs *= r.g.ext[d];
+    const size_t runlen = r.g.ext[BOX_ND - 1];
+    B += std::min(cand, runs * ((runlen - 1 + unit - 1) / unit + 1));
+  }
+  if ((rc = check_spans(c, sp.data(), m, what, nullptr, "box"))) return rc;
+  if (B > MBOX_LIST_MAX) return fail(c, DCTZHIP_E_ARG, "%s: the boxes may hit %zu tiles, more than the %zu a call lists", what, B, MBOX_LIST_MAX);
+  HIPCHK(c, hipSetDevice(c->device));
+  const void* side = sh ? (const void*)elems.data() : (const void*)rem_boxes.data();
+  const size_t side_bytes = sh ? elems.size() * sizeof(NdBoxElems) : rem_boxes.size() * sizeof(unsigned);
+  return (st.dtype == DCTZHIP_F64) ? decompress_boxes_impl<double>(c, st, sh, k, recs.data(), side, side_bytes, (unsigned)total, B)
+                                   : decompress_boxes_impl<float>(c, st, sh, k, recs.data(), side, side_bytes, (unsigned)total, B);
+}
+
+extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                        const uint32_t* d_index, const void* qtable_host, size_t n, int dtype, double eb, double sf,
+                                        int mode, int ndim, const size_t* dims, int k, const dctzhip_box_item* boxes) {
+  int rc = check_common(c, n, dtype, mode);
+  if (rc) return rc;
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, n, dtype, eb, sf, mode};
+  return decompress_boxes_call(c, "dctzhip_decompress_boxes", st, nullptr, ndim, dims, k, boxes);
 }
 
 extern "C" int dctzhip_decompress_boxes_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -2713,44 +2696,8 @@ extern "C" int dctzhip_decompress_boxes_nd(dctzhip_ctx* c, const void* d_bin, co
   NdShape sh;
   int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
   if (rc) return rc;
-  if (k < 1 || k > DCTZHIP_BOXES_MAX) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes_nd: k must be in [1, %d]", DCTZHIP_BOXES_MAX);
-  if (!boxes) return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes_nd: null boxes");
   const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
-  if ((rc = streams_given(c, st, " and the outputs"))) return rc;           // (the outputs themselves: box by box, below)
-  std::vector<BoxRec> recs((size_t)k);
-  std::vector<NdBoxElems> elems((size_t)k);
-  // every buffer of the call against every other: the outputs may overlap nothing, neither each other nor what any box reads
-  std::vector<Span> sp((size_t)k * 4 + 1);
-  size_t m = 0, B = 0, total = 0;
-  add_span(sp.data(), &m, d_ac, (size_t)ac_count * sizeof(float), SPAN_READ, -1);
-  for (int i = 0; i < k; i++) {
-    char what[48];
-    snprintf(what, sizeof(what), "dctzhip_decompress_boxes_nd: box %d", i);
-    size_t cnt = 1;
-    BoxRec& r = recs[(size_t)i];
-    if ((rc = nd_box_front(c, what, sh, boxes[i].lo, boxes[i].hi, &cnt, &r.t0, &r.t1))) return rc;
-    if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", what);
-    if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", what);
-    tile_read_spans(sp.data(), &m, st, r.t0, r.t1, i);
-    add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(dtype), SPAN_OUT, i);
-    unsigned nb[3];
-    nd_box_geometry(sh, boxes[i].lo, boxes[i].hi, nb, elems[(size_t)i].lo, elems[(size_t)i].ext, &r.g);
-    r.cand0 = (unsigned)total;                      // (k <= 2^12 boxes of <= 2^19 candidates each)
-    r.out = boxes[i].d_out;
-    const size_t cand = r.t1 - r.t0;
-    total += cand;
-    // a run of L consecutive blocks touches at most ceil((L - 1) / 64) + 1 stream tiles
-    size_t runs = 1;
-    for (int d = 0; d < BOX_ND - 1; d++) runs *= r.g.ext[d];
-    const size_t runlen = r.g.ext[BOX_ND - 1];
-    B += std::min(cand, runs * ((runlen - 1 + TILE_BLKS - 1) / TILE_BLKS + 1));
-  }
-  if ((rc = check_spans(c, sp.data(), m, "dctzhip_decompress_boxes_nd", nullptr, "box"))) return rc;
-  if (B > MBOX_LIST_MAX)
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_decompress_boxes_nd: the boxes may hit %zu tiles, more than the %zu a call lists", B, MBOX_LIST_MAX);
-  HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64) ? decompress_boxes_nd_impl<double>(c, st, sh, k, recs.data(), elems.data(), (unsigned)total, B)
-                                : decompress_boxes_nd_impl<float>(c, st, sh, k, recs.data(), elems.data(), (unsigned)total, B);
+  return decompress_boxes_call(c, "dctzhip_decompress_boxes_nd", st, &sh, ndims, dims, k, boxes);
 }
 
 // ---- the whole array at reduced resolution (include/dctz_hip.h; dctz_kernels_coarse.hip) ------------------------
@@ -3192,24 +3139,90 @@ static int check_missing(dctzhip_ctx* c, const char* what, const dctzhip_missing
   return DCTZHIP_OK;
 }
 
-// The arguments are checked.  The count is the control block's counter, read back with the error word.
+// The arguments are checked.  sh null: n elements in flat blocks (dctz_kernels_mask.hip); else the tiles of sh, n = prod dims
+// <= 64 nblk <= INT_MAX (nd_shape; dctz_kernels_ndmask.hip).  The count is the control block's counter, read back with the
+// error word.
 template <typename T>
-static int mask_build_impl(dctzhip_ctx* c, const T* d_in, size_t n, const dctzhip_missing* miss, uint64_t* d_mask, T* d_filled, uint64_t* count) {
+static int mask_build_impl(dctzhip_ctx* c, const T* d_in, size_t n, const NdShape* sh, const dctzhip_missing* miss, uint64_t* d_mask,
+                           T* d_filled, uint64_t* count) {
   c->ctl_dirty = 1;                                    // the kernel ADDS to the control block's counter: cleared in stream order, always
   { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
-  MaskFillParams<T> p;
-  p.in = d_in; p.out = d_filled; p.mask32 = reinterpret_cast<unsigned*>(d_mask); p.ctl = c->ctl;
-  p.n = (unsigned)n; p.flags = miss->flags;
-  p.value = (T)miss->value; p.limit = (T)miss->limit;
+  // what the two parameter blocks share
+  auto fill = [&](auto& p) {
+    p.in = d_in; p.out = d_filled; p.mask32 = reinterpret_cast<unsigned*>(d_mask); p.ctl = c->ctl;
+    p.flags = miss->flags;
+    p.value = (T)miss->value; p.limit = (T)miss->limit;
+  };
   // a wave trip is 1 KiB of the array, MASK_TRIPS of them at a time; eight waves per SIMD (a few registers, no LDS), persistent beyond that
-  const size_t trips = (n * sizeof(T) + 1023) / 1024, per_wg = (size_t)(MASK_WG / 64) * MASK_TRIPS, wgs = (trips + per_wg - 1) / per_wg;
-  launch_mask_fill<T>(p, (int)std::min<size_t>(wgs, (size_t)c->num_cu * 8), c->stream);
-  SET_LAST(c, 1, "k_mask_fill<%s>", tname<T>());
+  auto grid = [&](size_t trips) {
+    const size_t per_wg = (size_t)(MASK_WG / 64) * MASK_TRIPS, wgs = (trips + per_wg - 1) / per_wg;
+    return (int)std::min<size_t>(wgs, (size_t)c->num_cu * 8);
+  };
+  if (!sh) {
+    MaskFillParams<T> p;
+    fill(p);
+    p.n = (unsigned)n;
+    launch_mask_fill<T>(p, grid((n * sizeof(T) + 1023) / 1024), c->stream);
+    SET_LAST(c, 1, "k_mask_fill<%s>", tname<T>());
+  } else {
+    constexpr size_t E = 16 / sizeof(T);
+    const size_t width = (sh->nd == 2 ? 8 : 4) * E;                                      // elements of a trip row
+    NdMaskFillParams<T> p;
+    fill(p);
+    p.dz = sh->nd == 3 ? (unsigned)sh->d[0] : 1u; p.dy = (unsigned)sh->d[sh->nd - 2]; p.dx = (unsigned)sh->d[sh->nd - 1];
+    p.nby = (unsigned)sh->nb[sh->nd - 2];
+    p.ntx = (unsigned)((sh->nb[sh->nd - 1] + E - 1) / E);
+    const size_t trips = (sh->nd == 3 ? sh->nb[0] : 1) * p.nby * (size_t)p.ntx;          // <= nblk
+    p.trips = (unsigned)trips;
+    p.pitch16 = sh->d[sh->nd - 1] * sizeof(T) % 16 == 0;
+    p.plain = sh->d[sh->nd - 1] % width == 0;
+    // plain: the trip rows are the bytes of the bits below n, all stored; what the last word has beyond n is cleared here.
+    // Else every row is ORed into a cleared mask.
+    const size_t words = dctzhip_mask_words(n);
+    if (!p.plain) HIPCHK(c, hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), c->stream));
+    else if (n % 64) HIPCHK(c, hipMemsetAsync(d_mask + words - 1, 0, sizeof(uint64_t), c->stream));
+    launch_ndmask_fill<T>(p, sh->nd == 2 ? GEOM_2D : GEOM_3D, grid(trips), c->stream);
+    SET_LAST(c, 1, "k_ndmask_fill<%s, %d>", tname<T>(), sh->nd == 2 ? GEOM_2D : GEOM_3D);
+  }
   unsigned total = 0;
   const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
   if (rc) return rc;
   *count = total;
   return DCTZHIP_OK;
+}
+// the only dtype dispatch of the build
+static int mask_build_call(dctzhip_ctx* c, const void* d_in, size_t n, const NdShape* sh, int dtype, const dctzhip_missing* miss, uint64_t* d_mask,
+                           void* d_filled, uint64_t* count) {
+  return (dtype == DCTZHIP_F64) ? mask_build_impl<double>(c, (const double*)d_in, n, sh, miss, d_mask, (double*)d_filled, count)
+                                : mask_build_impl<float>(c, (const float*)d_in, n, sh, miss, d_mask, (float*)d_filled, count);
+}
+// The tail the two masked compress calls share in front of their compress: the filled copy is the context's where the caller
+// gives none (*d_filled is set to it), then the build.
+static int masked_build(dctzhip_ctx* c, const void* d_in, size_t n, const NdShape* sh, int dtype, const dctzhip_missing* miss, uint64_t* d_mask,
+                        void** d_filled, uint64_t* count) {
+  if (!*d_filled) {
+    const int rc = regrow(c, &c->mask_filled, &c->mask_filled_cap, n * elem_size(dtype), 1);
+    if (rc) return rc;
+    *d_filled = c->mask_filled;
+  }
+  return mask_build_call(c, d_in, n, sh, dtype, miss, d_mask, *d_filled, count);
+}
+
+// The refusals the two builds share, and the tiled masked compress with them, behind the geometry, dtype and NULL checks of
+// each: the rule, alignment, and the buffers against each other.  n: the array's elements; d_filled: NULL, d_in itself (where
+// in_place_ok) or disjoint; sp[0 .. m) holds the spans of the caller's other buffers and has room for three more.
+static int check_mask(dctzhip_ctx* c, const char* what, const void* d_in, size_t n, int dtype, const dctzhip_missing* miss,
+                      const uint64_t* d_mask, const void* d_filled, bool in_place_ok, Span* sp, size_t m) {
+  int rc = check_missing(c, what, miss);
+  if (rc) return rc;
+  if (!aligned16(d_in) || !aligned16(d_filled) || ((uintptr_t)d_mask & 7u))
+    return fail(c, DCTZHIP_E_ARG, "%s: the arrays must be 16-byte aligned, the mask 8-byte aligned", what);
+  const size_t es = elem_size(dtype);
+  const bool in_place = in_place_ok && d_filled == d_in;
+  add_span(sp, &m, d_in, n * es, in_place ? SPAN_IN_PLACE : SPAN_READ, 0);
+  if (!in_place) add_span(sp, &m, d_filled, n * es, SPAN_OUT, 0);
+  add_span(sp, &m, d_mask, dctzhip_mask_words(n) * sizeof(uint64_t), SPAN_OUT, 0);
+  return check_spans(c, sp, m, what, nullptr);
 }
 
 extern "C" int dctzhip_mask_build(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, const dctzhip_missing* miss, uint64_t* d_mask,
@@ -3217,22 +3230,11 @@ extern "C" int dctzhip_mask_build(dctzhip_ctx* c, const void* d_in, size_t n, in
   int rc = check_common(c, n, dtype, DCTZHIP_EC);
   if (rc) return rc;
   if (!d_in || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build: the array, the mask and count must be given");
-  rc = check_missing(c, "dctzhip_mask_build", miss);
+  Span sp[3];
+  rc = check_mask(c, "dctzhip_mask_build", d_in, n, dtype, miss, d_mask, d_filled, true, sp, 0);
   if (rc) return rc;
-  if (!aligned16(d_in) || !aligned16(d_filled) || ((uintptr_t)d_mask & 7u))
-    return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build: the arrays must be 16-byte aligned, the mask 8-byte aligned");
-  {
-    Span sp[3];
-    size_t m = 0;
-    add_span(sp, &m, d_in, n * elem_size(dtype), d_filled == d_in ? SPAN_IN_PLACE : SPAN_READ, 0);
-    if (d_filled != d_in) add_span(sp, &m, d_filled, n * elem_size(dtype), SPAN_OUT, 0);
-    add_span(sp, &m, d_mask, dctzhip_mask_words(n) * sizeof(uint64_t), SPAN_OUT, 0);
-    rc = check_spans(c, sp, m, "dctzhip_mask_build", nullptr);
-    if (rc) return rc;
-  }
   HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64) ? mask_build_impl<double>(c, (const double*)d_in, n, miss, d_mask, (double*)d_filled, count)
-                                : mask_build_impl<float>(c, (const float*)d_in, n, miss, d_mask, (float*)d_filled, count);
+  return mask_build_call(c, d_in, n, nullptr, dtype, miss, d_mask, d_filled, count);
 }
 
 extern "C" int dctzhip_compress_masked(dctzhip_ctx* c, const void* d_in, size_t n, int dtype, double eb, int mode, const dctzhip_missing* miss,
@@ -3256,81 +3258,23 @@ extern "C" int dctzhip_compress_masked(dctzhip_ctx* c, const void* d_in, size_t 
     if (rc) return rc;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  if (!d_filled) {
-    rc = regrow(c, &c->mask_filled, &c->mask_filled_cap, n * elem_size(dtype), 1);
-    if (rc) return rc;
-    d_filled = c->mask_filled;
-  }
-  rc = (dtype == DCTZHIP_F64) ? mask_build_impl<double>(c, (const double*)d_in, n, miss, d_mask, (double*)d_filled, count)
-                              : mask_build_impl<float>(c, (const float*)d_in, n, miss, d_mask, (float*)d_filled, count);
-  if (rc) return rc;
+  if ((rc = masked_build(c, d_in, n, nullptr, dtype, miss, d_mask, &d_filled, count))) return rc;
   return dctzhip_compress(c, d_filled, n, dtype, eb, mode, d_bin, d_dc, d_ac, nullptr, nullptr, info);
 }
 
-// The tiled twin (dctz_kernels_ndmask.hip).  The arguments are checked; n = prod dims <= 64 nblk <= INT_MAX (nd_shape).
-template <typename T>
-static int mask_build_nd_impl(dctzhip_ctx* c, const T* d_in, const NdShape& sh, const dctzhip_missing* miss, uint64_t* d_mask, T* d_filled,
-                              uint64_t* count) {
-  constexpr size_t E = 16 / sizeof(T);
-  const size_t n = sh.d[0] * sh.d[1] * sh.d[2], width = (sh.nd == 2 ? 8 : 4) * E;      // elements of a trip row
-  c->ctl_dirty = 1;                                    // the kernel ADDS to the control block's counter: cleared in stream order, always
-  { int rc = ra_begin<T>(c, DCTZHIP_EC, nullptr); if (rc) return rc; }
-  NdMaskFillParams<T> p;
-  p.in = d_in; p.out = d_filled; p.mask32 = reinterpret_cast<unsigned*>(d_mask); p.ctl = c->ctl;
-  p.dz = sh.nd == 3 ? (unsigned)sh.d[0] : 1u; p.dy = (unsigned)sh.d[sh.nd - 2]; p.dx = (unsigned)sh.d[sh.nd - 1];
-  p.nby = (unsigned)sh.nb[sh.nd - 2];
-  p.ntx = (unsigned)((sh.nb[sh.nd - 1] + E - 1) / E);
-  const size_t trips = (sh.nd == 3 ? sh.nb[0] : 1) * p.nby * (size_t)p.ntx;           // <= nblk
-  p.trips = (unsigned)trips;
-  p.pitch16 = sh.d[sh.nd - 1] * sizeof(T) % 16 == 0;
-  p.plain = sh.d[sh.nd - 1] % width == 0;
-  p.flags = miss->flags;
-  p.value = (T)miss->value; p.limit = (T)miss->limit;
-  // plain: the trip rows are the bytes of the bits below n, all stored; what the last word has beyond n is cleared here.
-  // Else every row is ORed into a cleared mask.
-  const size_t words = dctzhip_mask_words(n);
-  if (!p.plain) HIPCHK(c, hipMemsetAsync(d_mask, 0, words * sizeof(uint64_t), c->stream));
-  else if (n % 64) HIPCHK(c, hipMemsetAsync(d_mask + words - 1, 0, sizeof(uint64_t), c->stream));
-  // a wave trip is 1 KiB of the array, MASK_TRIPS of them at a time; the flat build's grid
-  const size_t per_wg = (size_t)(MASK_WG / 64) * MASK_TRIPS, wgs = (trips + per_wg - 1) / per_wg;
-  launch_ndmask_fill<T>(p, sh.nd == 2 ? GEOM_2D : GEOM_3D, (int)std::min<size_t>(wgs, (size_t)c->num_cu * 8), c->stream);
-  SET_LAST(c, 1, "k_ndmask_fill<%s, %d>", tname<T>(), sh.nd == 2 ? GEOM_2D : GEOM_3D);
-  unsigned total = 0;
-  const int rc = ra_finish(c, &total);                 // (the control block's counter was used: the next call clears the block)
-  if (rc) return rc;
-  *count = total;
-  return DCTZHIP_OK;
-}
-
-// The refusals a tiled build shares with the masked tiled compress, behind the shape, dtype and NULL checks of either: the rule,
-// alignment, and the buffers against each other.  d_filled: NULL, d_in itself (where in_place_ok) or disjoint; sp[0 .. m) holds
-// the spans of the caller's other buffers and has room for three more.
-static int check_mask_nd(dctzhip_ctx* c, const char* what, const void* d_in, const NdShape& sh, int dtype, const dctzhip_missing* miss,
-                         const uint64_t* d_mask, const void* d_filled, bool in_place_ok, Span* sp, size_t m) {
-  int rc = check_missing(c, what, miss);
-  if (rc) return rc;
-  if (!aligned16(d_in) || !aligned16(d_filled) || ((uintptr_t)d_mask & 7u))
-    return fail(c, DCTZHIP_E_ARG, "%s: the arrays must be 16-byte aligned, the mask 8-byte aligned", what);
-  const size_t n = sh.d[0] * sh.d[1] * sh.d[2], es = elem_size(dtype);
-  const bool in_place = in_place_ok && d_filled == d_in;
-  add_span(sp, &m, d_in, n * es, in_place ? SPAN_IN_PLACE : SPAN_READ, 0);
-  if (!in_place) add_span(sp, &m, d_filled, n * es, SPAN_OUT, 0);
-  add_span(sp, &m, d_mask, dctzhip_mask_words(n) * sizeof(uint64_t), SPAN_OUT, 0);
-  return check_spans(c, sp, m, what, nullptr);
-}
-
+// The tiled twins.
 extern "C" int dctzhip_mask_build_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, const dctzhip_missing* miss,
                                      uint64_t* d_mask, void* d_filled, uint64_t* count) {
   NdShape sh;
   int rc = nd_front(c, ndims, dims, dtype, DCTZHIP_EC, &sh);
   if (rc) return rc;
   if (!d_in || !d_mask || !count) return fail(c, DCTZHIP_E_ARG, "dctzhip_mask_build_nd: the array, the mask and count must be given");
+  const size_t n = sh.d[0] * sh.d[1] * sh.d[2];
   Span sp[3];
-  rc = check_mask_nd(c, "dctzhip_mask_build_nd", d_in, sh, dtype, miss, d_mask, d_filled, true, sp, 0);
+  rc = check_mask(c, "dctzhip_mask_build_nd", d_in, n, dtype, miss, d_mask, d_filled, true, sp, 0);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  return (dtype == DCTZHIP_F64) ? mask_build_nd_impl<double>(c, (const double*)d_in, sh, miss, d_mask, (double*)d_filled, count)
-                                : mask_build_nd_impl<float>(c, (const float*)d_in, sh, miss, d_mask, (float*)d_filled, count);
+  return mask_build_call(c, d_in, n, &sh, dtype, miss, d_mask, d_filled, count);
 }
 
 extern "C" int dctzhip_compress_masked_nd(dctzhip_ctx* c, const void* d_in, int ndims, const size_t* dims, int dtype, double eb, int mode,
@@ -3349,17 +3293,10 @@ extern "C" int dctzhip_compress_masked_nd(dctzhip_ctx* c, const void* d_in, int 
   add_span(sp, &m, d_bin, n_lin, SPAN_OUT, 0);
   add_span(sp, &m, d_dc, sh.nblk * sizeof(float), SPAN_OUT, 0);
   add_span(sp, &m, d_ac, n_lin * sizeof(float), SPAN_OUT, 0);
-  rc = check_mask_nd(c, "dctzhip_compress_masked_nd", d_in, sh, dtype, miss, d_mask, d_filled, false, sp, m);   // (d_in is not modified)
+  rc = check_mask(c, "dctzhip_compress_masked_nd", d_in, n, dtype, miss, d_mask, d_filled, false, sp, m);   // (d_in is not modified)
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  if (!d_filled) {
-    rc = regrow(c, &c->mask_filled, &c->mask_filled_cap, n * elem_size(dtype), 1);
-    if (rc) return rc;
-    d_filled = c->mask_filled;
-  }
-  rc = (dtype == DCTZHIP_F64) ? mask_build_nd_impl<double>(c, (const double*)d_in, sh, miss, d_mask, (double*)d_filled, count)
-                              : mask_build_nd_impl<float>(c, (const float*)d_in, sh, miss, d_mask, (float*)d_filled, count);
-  if (rc) return rc;
+  if ((rc = masked_build(c, d_in, n, &sh, dtype, miss, d_mask, &d_filled, count))) return rc;
   return dctzhip_compress_nd(c, d_filled, ndims, dims, dtype, eb, mode, d_bin, d_dc, d_ac, nullptr, info);
 }
 

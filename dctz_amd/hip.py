@@ -466,43 +466,44 @@ class Context:
         self._check(rc, "dctzhip_decompress_range")
         return dst
 
-    def decompress_box(self, out, cnt, dims, dtype, eb, sf, lo, hi, index, mode=EC, qtable=None, dst=None):
-        """The box lo[i] <= c[i] < hi[i] of what decompress() rebuilds from the same arguments, seen as an array of shape
-        `dims` in C order (1 to 4 dimensions), bit for bit; `index` from ac_index().  Returns dst shaped hi - lo."""
+    # flat and tiled boxes through one body per operation.  What differs is where the C call takes its geometry: a flat call
+    # has n in front of (dtype, eb, sf, mode) and the shape behind them, a tiled call the shape in front.
+    def _decompress_box(self, flat, out, cnt, dims, dtype, eb, sf, lo, hi, index, mode, qtable, dst):
         t = self.torch
         self._bind_stream()
         dims, lo, hi = [int(v) for v in dims], [int(v) for v in lo], [int(v) for v in hi]
         nd = len(dims)
         assert len(lo) == nd and len(hi) == nd
-        n = int(np.prod(dims, dtype=np.int64)) if nd else 0
-        shape = [max(h - l, 0) for l, h in zip(lo, hi)]
+        ext = [max(h - l, 0) for l, h in zip(lo, hi)]
         if dst is None:
-            dst = t.empty(shape, dtype=dtype, device=self.device)
+            dst = t.empty(ext, dtype=dtype, device=self.device)
         q = self._qtable(mode, qtable, dtype)
         arr = C.c_size_t * max(nd, 1)
-        rc = self.lib.dctzhip_decompress_box(
-            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), _host_ptr(q), n, _dt(dtype), float(eb), float(sf),
-            mode, nd, arr(*dims), arr(*lo), arr(*hi), dst.data_ptr())
-        self._check(rc, "dctzhip_decompress_box")
-        return dst.view(shape)
+        b, d, a, ix, qp = out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), index.data_ptr(), _host_ptr(q)
+        if flat:
+            name = "dctzhip_decompress_box"
+            n = int(np.prod(dims, dtype=np.int64)) if nd else 0
+            rc = self.lib.dctzhip_decompress_box(self.h, b, d, a, int(cnt), ix, qp, n, _dt(dtype), float(eb), float(sf),
+                                                 mode, nd, arr(*dims), arr(*lo), arr(*hi), dst.data_ptr())
+        else:
+            name = "dctzhip_decompress_box_nd"
+            rc = self.lib.dctzhip_decompress_box_nd(self.h, b, d, a, int(cnt), ix, qp, nd, arr(*dims), _dt(dtype),
+                                                    float(eb), float(sf), mode, arr(*lo), arr(*hi), dst.data_ptr())
+        self._check(rc, name)
+        return dst.view(ext)
 
-    def decompress_boxes(self, out, cnt, dims, dtype, eb, sf, boxes, index, mode=EC, qtable=None, dsts=None):
-        """The boxes (lo, hi) of `boxes`, each what decompress_box() gives for it, in ONE call (one work list of the hit tiles
-        of all boxes, one decode launch, one synchronisation).  Boxes may overlap or repeat.  Returns the list of tensors
-        shaped hi - lo; `dsts` (or None: allocated) are the outputs, one per box."""
+    def _decompress_boxes(self, flat, out, cnt, dims, dtype, eb, sf, boxes, index, mode, qtable, dsts):
         t = self.torch
         self._bind_stream()
         dims = [int(v) for v in dims]
         nd = len(dims)
-        n = int(np.prod(dims, dtype=np.int64)) if nd else 0
         boxes = [([int(v) for v in lo], [int(v) for v in hi]) for lo, hi in boxes]
-        shapes = []
+        exts = []
         for lo, hi in boxes:
             assert len(lo) == nd and len(hi) == nd
-            shapes.append([max(h - l, 0) for l, h in zip(lo, hi)])
+            exts.append([max(h - l, 0) for l, h in zip(lo, hi)])
         if dsts is None:
-            dsts = [t.empty(sh, dtype=dtype, device=self.device) for sh in shapes]
+            dsts = [t.empty(e, dtype=dtype, device=self.device) for e in exts]
         assert len(dsts) == len(boxes)
         q = self._qtable(mode, qtable, dtype)
         items = (BoxItem * max(len(boxes), 1))()
@@ -511,12 +512,29 @@ class Context:
                 it.lo[i], it.hi[i] = lo[i], hi[i]
             it.d_out = d.data_ptr()
         arr = C.c_size_t * max(nd, 1)
-        rc = self.lib.dctzhip_decompress_boxes(
-            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), _host_ptr(q), n, _dt(dtype), float(eb), float(sf),
-            mode, nd, arr(*dims), len(boxes), C.cast(items, C.c_void_p))
-        self._check(rc, "dctzhip_decompress_boxes")
-        return [d.view(sh) for d, sh in zip(dsts, shapes)]
+        b, d, a, ix, qp = out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), index.data_ptr(), _host_ptr(q)
+        if flat:
+            name = "dctzhip_decompress_boxes"
+            n = int(np.prod(dims, dtype=np.int64)) if nd else 0
+            rc = self.lib.dctzhip_decompress_boxes(self.h, b, d, a, int(cnt), ix, qp, n, _dt(dtype), float(eb), float(sf),
+                                                   mode, nd, arr(*dims), len(boxes), C.cast(items, C.c_void_p))
+        else:
+            name = "dctzhip_decompress_boxes_nd"
+            rc = self.lib.dctzhip_decompress_boxes_nd(self.h, b, d, a, int(cnt), ix, qp, nd, arr(*dims), _dt(dtype),
+                                                      float(eb), float(sf), mode, len(boxes), C.cast(items, C.c_void_p))
+        self._check(rc, name)
+        return [d.view(e) for d, e in zip(dsts, exts)]
+
+    def decompress_box(self, out, cnt, dims, dtype, eb, sf, lo, hi, index, mode=EC, qtable=None, dst=None):
+        """The box lo[i] <= c[i] < hi[i] of what decompress() rebuilds from the same arguments, seen as an array of shape
+        `dims` in C order (1 to 4 dimensions), bit for bit; `index` from ac_index().  Returns dst shaped hi - lo."""
+        return self._decompress_box(True, out, cnt, dims, dtype, eb, sf, lo, hi, index, mode, qtable, dst)
+
+    def decompress_boxes(self, out, cnt, dims, dtype, eb, sf, boxes, index, mode=EC, qtable=None, dsts=None):
+        """The boxes (lo, hi) of `boxes`, each what decompress_box() gives for it, in ONE call (one work list of the hit tiles
+        of all boxes, one decode launch, one synchronisation).  Boxes may overlap or repeat.  Returns the list of tensors
+        shaped hi - lo; `dsts` (or None: allocated) are the outputs, one per box."""
+        return self._decompress_boxes(True, out, cnt, dims, dtype, eb, sf, boxes, index, mode, qtable, dsts)
 
     # ---- batches of arrays (include/dctz_hip.h: dctzhip_compress_batch / dctzhip_decompress_batch) ----
     def compress_batch(self, xs, ebs, mode=EC, outs=None, scaled=None, prepared=None):
@@ -618,52 +636,13 @@ class Context:
     def decompress_box_nd(self, out, cnt, shape, dtype, eb, sf, lo, hi, index, mode=EC, qtable=None, dst=None):
         """The box lo[i] <= c[i] < hi[i] of what decompress_nd() rebuilds from the same arguments, bit for bit; `index` from
         ac_index(out, 64 * nd_blocks(shape)).  Returns dst shaped hi - lo."""
-        t = self.torch
-        self._bind_stream()
-        shape, lo, hi = [int(v) for v in shape], [int(v) for v in lo], [int(v) for v in hi]
-        nd = len(shape)
-        assert len(lo) == nd and len(hi) == nd
-        ext = [max(h - l, 0) for l, h in zip(lo, hi)]
-        if dst is None:
-            dst = t.empty(ext, dtype=dtype, device=self.device)
-        q = self._qtable(mode, qtable, dtype)
-        arr = C.c_size_t * max(nd, 1)
-        rc = self.lib.dctzhip_decompress_box_nd(
-            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), _host_ptr(q), nd, arr(*shape), _dt(dtype),
-            float(eb), float(sf), mode, arr(*lo), arr(*hi), dst.data_ptr())
-        self._check(rc, "dctzhip_decompress_box_nd")
-        return dst.view(ext)
+        return self._decompress_box(False, out, cnt, shape, dtype, eb, sf, lo, hi, index, mode, qtable, dst)
 
     def decompress_boxes_nd(self, out, cnt, shape, dtype, eb, sf, boxes, index, mode=EC, qtable=None, dsts=None):
         """The boxes (lo, hi) of `boxes`, each what decompress_box_nd() gives for it, in ONE call (one work list of the hit
         stream tiles of all boxes, one decode launch, one synchronisation).  Boxes may overlap or repeat.  Returns the list
         of tensors shaped hi - lo; `dsts` (or None: allocated) are the outputs, one per box."""
-        t = self.torch
-        self._bind_stream()
-        shape = [int(v) for v in shape]
-        nd = len(shape)
-        boxes = [([int(v) for v in lo], [int(v) for v in hi]) for lo, hi in boxes]
-        exts = []
-        for lo, hi in boxes:
-            assert len(lo) == nd and len(hi) == nd
-            exts.append([max(h - l, 0) for l, h in zip(lo, hi)])
-        if dsts is None:
-            dsts = [t.empty(e, dtype=dtype, device=self.device) for e in exts]
-        assert len(dsts) == len(boxes)
-        q = self._qtable(mode, qtable, dtype)
-        items = (BoxItem * max(len(boxes), 1))()
-        for it, (lo, hi), d in zip(items, boxes, dsts):
-            for i in range(min(nd, BOX_MAXDIM)):
-                it.lo[i], it.hi[i] = lo[i], hi[i]
-            it.d_out = d.data_ptr()
-        arr = C.c_size_t * max(nd, 1)
-        rc = self.lib.dctzhip_decompress_boxes_nd(
-            self.h, out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), int(cnt),
-            index.data_ptr(), _host_ptr(q), nd, arr(*shape), _dt(dtype),
-            float(eb), float(sf), mode, len(boxes), C.cast(items, C.c_void_p))
-        self._check(rc, "dctzhip_decompress_boxes_nd")
-        return [d.view(e) for d, e in zip(dsts, exts)]
+        return self._decompress_boxes(False, out, cnt, shape, dtype, eb, sf, boxes, index, mode, qtable, dsts)
 
     def _qtable(self, mode, qtable, dtype):
         """The QT table as a decode call passes it: 64 entries of the data type in host memory (QT mode), else None."""
