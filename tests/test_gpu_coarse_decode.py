@@ -431,3 +431,94 @@ def test_tiled_refusals_leave_the_context_usable(ctx, shape):
     after()
     assert call(cnt=info.cnt - 1) == H.E_ARG
     after()
+
+
+# ---- more tiles than resident workgroups ------------------------------------------------------------------------------------
+# k_decompress_coarse and k_decompress_coarse_nd take tiles t, t + gridDim.x, ... and reuse their LDS image between the trips;
+# k_decompress_coarse_dc caps its grid at 4096 workgroups and strides.  The arrays are tests/size_cases.py's: a pattern of 257
+# (513, 481) stream tiles repeated, then a ragged tail; the model [pattern | tail] is held to the operator above, and the big
+# array's coarse decode is, bit for bit, the model's extended period after period.
+def _nd_from(ctx, x, mode):
+    """_nd's tuple for an array given as such."""
+    import torch
+    out, info = ctx.compress_nd(torch.from_numpy(x).to(ctx.device), EB, mode)
+    q = np.array(info.qtable[:]) if mode == H.QT else None
+    full = ctx.decompress_nd(out, info.cnt, x.shape, _tdt(x.dtype.type), EB, info.sf, mode, qtable=q).cpu().numpy()
+    idx, tot = ctx.ac_index(out, 64 * ctx.nd_blocks(x.shape))
+    assert tot == info.cnt
+    return out, info, full, idx, q
+
+
+@pytest.mark.parametrize("mode", [H.EC, H.QT], ids=["EC", "QT"])
+@pytest.mark.parametrize("kind", ["smooth", "noisy"])
+def test_flat_more_tiles_than_resident_workgroups(ctx, kind, mode):
+    import torch
+    from tests import size_cases as Z
+    w, dtype, tdt = Z.C, np.float64, torch.float64
+    assert w.tiles > Z.RESIDENT_WAVES
+    s = Z.model(w, Z.pattern(w, kind))
+    ns = s.size
+    sd = torch.from_numpy(s).to(ctx.device)
+    outs, infos = ctx.compress(sd, EB, mode)
+    q = np.array(infos.qtable[:]) if mode == H.QT else None
+    fulls = ctx.decompress(outs, infos.cnt, ns, tdt, EB, infos.sf, mode, qtable=q).cpu().numpy()
+    idxs, tot = ctx.ac_index(outs, ns)
+    assert tot == infos.cnt and infos.sf == 100.0
+    b = Z.expand(sd, w.reps, w.period)
+    assert b.numel() == w.n and w.n % 64 == 37
+    outb, infob = ctx.compress(b, EB, mode)
+    assert infob.sf == infos.sf and bytes(infob.qtable) == bytes(infos.qtable)
+    assert Z.streams_ok(w, outb, infob.cnt, outs, infos.cnt)
+    idxb, tot = ctx.ac_index(outb, w.n)
+    assert tot == infob.cnt
+    del b
+    fl = _flags_by_position(outs, ns)
+    for f in FLAT_F:
+        K = 64 // f
+        if kind == "noisy" and K >= 2:
+            assert fl[1:K].sum() > 0 and fl[K:].sum() > 0, (f, fl)
+        rs = ctx.decompress_coarse(outs, infos.cnt, ns, tdt, EB, infos.sf, f, index=idxs, mode=mode, qtable=q)
+        _check_flat(rs.cpu().numpy(), fulls, ns, f, dtype, f"model of C {kind} f={f}")
+        rb = ctx.decompress_coarse(outb, infob.cnt, w.n, tdt, EB, infob.sf, f, index=idxb, mode=mode, qtable=q)
+        assert ctx.last_kernel(1) == ("k_decompress_coarse_dc<double>" if K == 1 else f"k_decompress_coarse<double, {mode}, {K}>")
+        assert rb.numel() == -(-w.n // f)
+        assert Z.periodic(rb, rs, w.reps, w.period // f), f                     # (the short block's cells are the model's tail)
+
+
+@pytest.mark.parametrize("mode", [H.EC, H.QT], ids=["EC", "QT"])
+@pytest.mark.parametrize("kind", ["smooth", "noisy"])
+@pytest.mark.parametrize("which", ["G2", "G3"])
+def test_tiled_more_tiles_than_resident_workgroups(ctx, which, kind, mode):
+    """The array-side prefixes of size_cases' G2 (8453 x 8203) and G3 (2307 x 101 x 145), ragged on every axis.  G2's has
+    more than 4096 x 256 blocks: at factor 8 k_decompress_coarse_dc strides."""
+    import torch
+    from tests import size_cases as Z
+    w = {"G2": Z.G2_COARSE, "G3": Z.G3_COARSE}[which]
+    dtype, tdt, nd = np.float64, torch.float64, len(w.shape)
+    assert w.tiles > Z.RESIDENT_WAVES and (which != "G2" or w.stream_n // 64 > Z.DC_GRID_BLOCKS)
+    s = Z.model(w, Z.pattern(w, kind))
+    shape_s, pshape = s.shape, _padded_shape(s.shape)
+    # the model: the padded one against the operator, the ragged one its corner (test_ragged_coarse_is_the_corner_of_the_padded_one)
+    outs, infos, fulls, idxs, q = _nd_from(ctx, s, mode)
+    pout, pinfo, pfull, pidx, pq = pdata = _nd_from(ctx, np.ascontiguousarray(np.pad(s, [(0, p - d) for d, p in zip(shape_s, pshape)], mode="edge")), mode)
+    _check_tiled(ctx, (pshape, dtype, mode, kind), pdata)
+    assert infos.sf == pinfo.sf == 100.0 and infos.cnt == pinfo.cnt
+    b = Z.expand(torch.from_numpy(s).to(ctx.device), w.reps, w.period)
+    assert tuple(b.shape) == w.shape
+    outb, infob = ctx.compress_nd(b, EB, mode)
+    assert infob.sf == infos.sf and bytes(infob.qtable) == bytes(infos.qtable)
+    assert ctx.nd_blocks(w.shape) * 64 == w.stream_n
+    assert Z.streams_ok(w, outb, infob.cnt, outs, infos.cnt)
+    idxb, tot = ctx.ac_index(outb, w.stream_n)
+    assert tot == infob.cnt
+    del b
+    for f in ND_F[nd]:
+        K = EDGE[nd] // f
+        rs = ctx.decompress_coarse_nd(outs, infos.cnt, shape_s, tdt, EB, infos.sf, f, index=idxs, mode=mode, qtable=q)
+        p = ctx.decompress_coarse_nd(pout, pinfo.cnt, pshape, tdt, EB, pinfo.sf, f, index=pidx, mode=mode, qtable=pq)
+        ext = [-(-d // f) for d in shape_s]
+        assert list(rs.shape) == ext and Z.same(rs, p[tuple(slice(0, v) for v in ext)].contiguous()), f
+        rb = ctx.decompress_coarse_nd(outb, infob.cnt, w.shape, tdt, EB, infob.sf, f, index=idxb, mode=mode, qtable=q)
+        assert ctx.last_kernel(1) == ("k_decompress_coarse_dc<double>" if K == 1 else f"k_decompress_coarse_nd<double, {mode}, {nd - 1}, {K}>")
+        assert list(rb.shape) == [-(-d // f) for d in w.shape]
+        assert Z.periodic(rb, rs, w.reps, w.period // f), f

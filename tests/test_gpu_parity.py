@@ -587,3 +587,38 @@ def test_under_run_is_refused_on_the_large_array_path(ctx, dtype):
     assert _same(good, again)
     ref = O.decompress(O.compress(x, 1e-3, O.EC, O.FAST), O.FAST)
     assert _same(good, ref)
+
+
+ONE_LAUNCH_TILES = {np.float64: 1024, np.float32: 2048}      # include/dctz_hip.h, "One launch per call": the documented capacity
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["float64", "float32"])
+@pytest.mark.parametrize("mode", [O.EC, O.QT], ids=["EC", "QT"])
+@pytest.mark.parametrize("at", [-1, 0, 1], ids=["cap-1", "cap", "cap+1"])
+def test_at_the_one_launch_capacity(ctx, dtype, mode, at):
+    """T = capacity - 1, capacity, capacity + 1 tiles, the last one ending in a short block (n = 4096 T - 27): whichever
+    side of its limit the library puts each of them -- the limit follows the kernels' occupancy; INFO_ONE_LAUNCH is reported
+    here, not asserted -- streams and reconstruction are the oracle's bit for bit, and no launch gives up (counter 1)."""
+    import torch
+    tiles = ONE_LAUNCH_TILES[dtype] + at
+    n = 4096 * tiles - 27
+    assert -(-n // 4096) == tiles and n % 64 == 37
+    x = W.ragged(n, dtype, scale=37.0)
+    c = O.compress(x, 1e-3, mode, O.FAST)
+    ref = O.decompress(c, O.FAST)
+    gave_up = ctx.counter(1)
+    out, info = ctx.compress(_dev(ctx, x), 1e-3, mode)
+    one = bool(info.flags & H.INFO_ONE_LAUNCH)
+    what = f"{tiles} tiles {np.dtype(dtype).name}: compress ONE_LAUNCH={one}"
+    assert (info.sf, info.cnt, info.nblk) == (c.sf, c.cnt, (n + 63) // 64), what
+    assert np.array_equal(out["bin_index"].cpu().numpy(), c.bin_index), what
+    assert _same(out["dc"].cpu().numpy(), c.dc), what
+    assert _same(out["ac_exact"][:c.cnt].cpu().numpy(), c.ac_exact), what
+    if mode == O.QT:
+        assert _same(np.array(info.qtable[:], dtype=dtype), c.qtable), what
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    r = ctx.decompress(out, info.cnt, n, tdt, 1e-3, info.sf, mode, qtable=np.array(info.qtable[:]))
+    what += f", decode kernel {ctx.last_kernel(1)}"
+    print(what)
+    assert _same(r.cpu().numpy(), ref), what
+    assert ctx.counter(1) == gave_up, what
