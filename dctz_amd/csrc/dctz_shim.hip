@@ -180,6 +180,8 @@ struct dctzhip_ctx {
   SpecMemory spec_mem;              // the last verified statistics per (input, length, element type): a guess that needs no sample (dctz_spec_memory.h)
   int spec_memory = 1;              // 0: every speculative call samples (DCTZHIP_SPEC_MEMORY, dctzhip_set_spec_memory)
   unsigned long long hist_hits = 0, hist_misses = 0;   // guesses taken from spec_mem that verified / that did not (dctzhip_debug_counter 18 / 19)
+  unsigned pass_fast_bw = 0;        // FwdParams::fast_bw of the last compress_pass / compress_one launch
+  unsigned variant = 0;             // fast_sf | fast_bw << 8 of the last verified pass of a single-array compress call (dctzhip_debug_counter 20)
   int profiling = 0;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   dctzhip_timings last = {0, 0, 0, 0};
@@ -474,6 +476,7 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 17: *value = c->memo_redos; break;          // ... of them, found stale by the decoder and done again behind k_count_tiles
     case 18: *value = c->hist_hits; break;           // speculative compress calls that took their guess from the remembered statistics of the same input, verified
     case 19: *value = c->hist_misses; break;         // ... refused by the true statistics (done again, like a sampled miss)
+    case 20: *value = c->variant; break;             // dctzhip_compress / _compress_nd, last call: fast_sf | fast_bw << 8 of the pass that stands
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_counter: no counter %d", which);
   }
   return DCTZHIP_OK;
@@ -1262,6 +1265,7 @@ static int compress_one(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int 
     volatile T q = (T)(u / p.bin_width);
     if (p.fast_bw && c->fastdiv >= 2 && q >= (T)255) p.fast_bw |= 2u;
   }
+  c->pass_fast_bw = p.fast_bw;
   a.b.ga = c->one_ga; a.b.gb = c->one_gb; a.b.rec = c->one_rec; a.b.epoch = epoch; a.b.nwg = nwg; a.b.dbg = c->one_dbg;
   a.sft = {c->sf_thr[dtype], c->sf_pw[dtype], c->sf_nk[dtype], c->fastdiv, dtype};
   a.box = c->box_dev;
@@ -1296,6 +1300,7 @@ static int compress_one(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int 
     rc = one_gave_up(c);
     return rc ? rc : ONE_DECLINED;
   }
+  c->variant = hb->fast_used | c->pass_fast_bw << 8;
   if (info) fill_cinfo(info, dtype, mode, true_sf, st, n, hb->cnt_total, nfull + (rem ? 1u : 0u), DCTZHIP_INFO_STATS_FUSED | DCTZHIP_INFO_ONE_LAUNCH,
                        const_cast<const unsigned long long*>(hb->qraw), hb->q0);
   return DCTZHIP_OK;
@@ -1400,6 +1405,7 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
     if (p.fast_bw && c->fastdiv >= 2 && q >= (T)255) p.fast_bw |= 2u;
   }
   *sf_t_out = p.sf; *fast_sf_out = p.fast_sf;
+  c->pass_fast_bw = p.fast_bw;
   if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
 
   if (c->profiling) HIPCHK(c, hipEventRecord(c->ev[2], s));
@@ -1709,6 +1715,7 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
     HIPCHK(c, hipGetLastError());
   }
 
+  c->variant = fast_sf | c->pass_fast_bw << 8;        // (fast_sf: what the device reported where it chose sf itself)
   if (c->eo_calls > eo0) flags |= DCTZHIP_INFO_SPLIT;
   if (c->eo_lb_fallbacks > eof0) flags |= DCTZHIP_INFO_LB_FALLBACK;
   else if (c->eo_direct_calls > eod0) flags |= DCTZHIP_INFO_SINGLE_PASS;

@@ -333,7 +333,9 @@ class Context:
         self._check(self.lib.dctzhip_set_decode_memo(self.h, int(on)), "set_decode_memo")
 
     def counter(self, which):
-        """dctzhip_debug_counter (include/dctz_hip.h): 0 one-launch calls, 1 launches that gave up, 2 cooldown, 3 split calls, ..."""
+        """dctzhip_debug_counter (include/dctz_hip.h): 0 one-launch calls, 1 launches that gave up, 2 cooldown, 3 split calls, ...,
+        20 fast_sf | fast_bw << 8 of the last verified pass of the last compress / compress_nd call (which division and
+        binning variant the kernels ran)."""
         v = C.c_ulonglong(0)
         self._check(self.lib.dctzhip_debug_counter(self.h, int(which), C.byref(v)), "debug_counter")
         return int(v.value)

@@ -159,7 +159,11 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
  * in the list of the last dctzhip_decompress_boxes or dctzhip_decompress_boxes_nd call (whichever of the two ran last),
  * workgroups of its decode launch and the list's bound, 16 / 17
  * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again, 18 / 19 guesses of the
- * scaling factor taken from the remembered statistics of the same input that verified / that did not -- and knobs that
+ * scaling factor taken from the remembered statistics of the same input that verified / that did not, 20 the division
+ * and binning variant of the last verified pass of the last dctzhip_compress / _compress_nd call: fast_sf | fast_bw << 8
+ * (fast_sf 0 plain x / sf, 1 FastDiv with a per-element window test, 2 without; fast_bw bit 0 the bin width is in
+ * FastDiv's divisor window, bit 1 the kernels drop the range test of the binning: 3, 1 or 0; where the device chose sf,
+ * fast_sf is what it reported) -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
  * 3: every predicted SSE of dctzhip_rd_probe / _rd_probe_nd is divided by value (value <= 1: off). */
