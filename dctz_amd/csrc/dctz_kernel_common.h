@@ -808,7 +808,7 @@ __device__ __forceinline__ void box_rem_block(const P& p, const BoxGeo& g, T* co
 }
 
 
-// FastDiv's windows on the host's terms (dctz_shim.hip: divisor_in_window / value_in_window): unbiased exponent of a
+// FastDiv's windows on the host's terms (dctz_quant_host.h: divisor_in_window / value_in_window): unbiased exponent of a
 // finite non-zero double in [lo, hi)
 __device__ __forceinline__ bool exp_in(double v, int lo, int hi) {
   const int e = (int)(((unsigned)__double2hiint(v) >> 20) & 0x7ffu) - 1023;     // subnormal / zero: -1023, inf / NaN: 1024

@@ -25,6 +25,7 @@
 #include "dctz_device.h"
 #include "dctz_tables.h"
 #include "dctz_spec_memory.h"
+#include "dctz_quant_host.h"
 
 // RCCL is loaded with dlopen (single-GPU users need none), so its header is not needed -- but where it is installed at build
 // time, the things this file restates from it are checked against it by the compiler (the header declares, it defines
@@ -853,21 +854,11 @@ extern "C" int dctzhip_sync(dctzhip_ctx* c) {
   return DCTZHIP_OK;
 }
 
-// FastDiv's divisor window (dctz_kernels.hip): |d| in [2^-250, 2^250] (f64) / [2^-30, 2^30] (f32)
-static unsigned divisor_in_window(int dtype, double d) {
-  if (!(d == d) || d == 0.0 || std::isinf(d)) return 0;      // (inf: sf of an array that holds an infinity; frexp says nothing about it)
-  int e = 0;
-  (void)frexp(fabs(d), &e);                      // |d| = m * 2^e, m in [0.5, 1)
-  return (dtype == DCTZHIP_F64) ? (e - 1 >= -250 && e - 1 < 250) : (e - 1 >= -30 && e - 1 < 30);
-}
-
-// FastDiv's numerator window: |x| in [2^-500, 2^500] (f64) / [2^-63, 2^63] (f32), zero excluded
-static bool value_in_window(int dtype, double v) {
-  if (!(v == v) || v == 0.0 || std::isinf(v)) return false;
-  int e = 0;
-  (void)frexp(fabs(v), &e);
-  return (dtype == DCTZHIP_F64) ? (e - 1 >= -500 && e - 1 < 500) : (e - 1 >= -63 && e - 1 < 63);
-}
+// The launch constants of dctz_quant_host.h into a parameter block, or into a batch record, which holds them widened to double
+template <typename P, typename T>
+static void set_quant(P& p, const InvQuant<T>& q) { p.bin_width = q.bin_width; p.range_min = q.range_min; p.range_max = q.range_max; }
+template <typename P, typename T>
+static void set_quant(P& p, const FwdQuant<T>& q) { p.bin_width = q.bin_width; p.range_min = q.range_min; p.range_max = q.range_max; p.fast_bw = q.fast_bw; }
 
 static size_t elem_size(int dtype) { return dtype == DCTZHIP_F64 ? 8 : 4; }
 
@@ -1253,18 +1244,8 @@ static int compress_one(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int 
   if (mode == DCTZHIP_QT) c->one_cslot ^= 1u;
   p.ctl = c->one_ctl;
   p.nfull = nfull; p.ntiles = ntiles; p.last_is_full = rem ? 0u : 1u;
-  // bin ranges, dctz-comp-lib.c:271-281 (computed in double, stored in T)
-  const int half = DCTZHIP_NBINS / 2;
   p.sf = (T)1;
-  p.bin_width = (T)(eb * 2.0 * 1.0);
-  p.range_min = (T)(-(half * 2 + 1) * (eb * 1.0));
-  p.range_max = (T)((half * 2 + 1) * (eb * 1.0));
-  p.fast_bw = c->fastdiv ? divisor_in_window(dtype, (double)p.bin_width) : 0u;
-  {
-    volatile T u = (T)(p.range_max - p.range_min);      // (bit 1: see compress_pass)
-    volatile T q = (T)(u / p.bin_width);
-    if (p.fast_bw && c->fastdiv >= 2 && q >= (T)255) p.fast_bw |= 2u;
-  }
+  set_quant(p, fwd_quant<T>(eb, c->fastdiv));
   c->pass_fast_bw = p.fast_bw;
   a.b.ga = c->one_ga; a.b.gb = c->one_gb; a.b.rec = c->one_rec; a.b.epoch = epoch; a.b.nwg = nwg; a.b.dbg = c->one_dbg;
   a.sft = {c->sf_thr[dtype], c->sf_pw[dtype], c->sf_nk[dtype], c->fastdiv, dtype};
@@ -1291,9 +1272,9 @@ static int compress_one(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int 
   if (c->profiling) { HIPCHK(c, hipEventSynchronize(c->ev[4])); rc = read_timings(c, 2); if (rc) return rc; }
   // the scaling factor the device chose from its decade tables against the host's own expression on the true statistics
   const HostStats st = {hb->fstats[0], hb->fstats[1], hb->fstats[2]};
-  const double sf = hb->sf_used, true_sf = scaling_factor(dtype, st.max_abs);
-  const bool window_ok = hb->fast_used != 2 || (value_in_window(dtype, st.min_abs) && value_in_window(dtype, st.max_abs));
-  if (!((T)true_sf == (T)sf && window_ok)) {
+  const double sf = hb->sf_used;
+  double true_sf;
+  if (!device_sf_stands(dtype, st.max_abs, st.min_abs, sf, hb->fast_used, &true_sf)) {
     c->one = 0;                                     // (a table bug: never seen; the chain has the host in its loop)
     if (d_scaled && (const void*)d_scaled == (const void*)d_in)
       return fail(c, DCTZHIP_E_INTERNAL, "scaling factor %g chosen on the device differs from the host's %g after an in-place pass", sf, true_sf);
@@ -1327,9 +1308,7 @@ static int decompress_one(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_d
   p.ctl = c->one_ctl + 2;
   p.nfull = nfull; p.ntiles = ntiles; p.ac_count = ac_count;
   p.sf = (T)sf;
-  p.bin_width = (T)((T)eb * 2 * 1.0);             // gen_bins / gen_bins_f (binning.c:17 / :37), as decompress_impl
-  p.range_max = (T)(eb * DCTZHIP_NBINS);          // dctz-decomp-lib.c:372-381
-  p.range_min = (T)(-eb * DCTZHIP_NBINS);
+  set_quant(p, inv_quant<T>(eb));
   p.eb = eb;
   if (mode == DCTZHIP_QT) memcpy(a.qtab, qtable_host, sizeof(T) * 64);      // (the table rides in the kernel's arguments: no copy in front of the launch)
   a.b.ga = c->one_ga; a.b.gb = c->one_gb; a.b.rec = c->one_rec; a.b.epoch = epoch; a.b.nwg = nwg; a.b.dbg = c->one_dbg;
@@ -1372,8 +1351,6 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   *sf_out = sf;
   c->memo.valid = false; c->memo_pass = false;       // (ttot / memo_start are about to be rewritten)
 
-  // ---- bin ranges, dctz-comp-lib.c:271-281 (computed in double, stored in T) --
-  const int half = DCTZHIP_NBINS / 2;
   FwdParams<T> p;
   memset(&p, 0, sizeof(p));
   p.x = d_in; p.bin = d_bin; p.dc = d_dc; p.ac = d_ac; p.coef = d_coef;
@@ -1389,21 +1366,8 @@ static int compress_pass(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
   p.stat_part = fused ? c->part : nullptr;
   p.nfull = nfull; p.ntiles = ntiles; p.last_is_full = rem ? 0u : 1u;
   p.sf = (T)sf;
-  p.bin_width = (T)(eb * 2.0 * 1.0);
-  p.range_min = (T)(-(half * 2 + 1) * (eb * 1.0));
-  p.range_max = (T)((half * 2 + 1) * (eb * 1.0));
-  // 2: every element is inside FastDiv's window (min|x| and max|x| are there) -> no per-element test
-  p.fast_sf = c->fastdiv ? divisor_in_window(dtype, (double)p.sf) : 0u;
-  if (!device_sf && p.fast_sf && c->fastdiv >= 2 && value_in_window(dtype, st.min_abs) && value_in_window(dtype, st.max_abs)) p.fast_sf = 2;
-  p.fast_bw = c->fastdiv ? divisor_in_window(dtype, (double)p.bin_width) : 0u;
-  {
-    // bit 1: "item > range_max  =>  (item - range_min) / bin_width >= 255" holds for these launch constants, in T
-    // arithmetic, so k_compress needs no separate range test (dctz_kernels.hip, bin_value): the smallest such
-    // numerator is fl(range_max - range_min) = 2 range_max, and rounding is monotonic.
-    volatile T u = (T)(p.range_max - p.range_min);
-    volatile T q = (T)(u / p.bin_width);
-    if (p.fast_bw && c->fastdiv >= 2 && q >= (T)255) p.fast_bw |= 2u;
-  }
+  set_quant(p, fwd_quant<T>(eb, c->fastdiv));
+  p.fast_sf = fast_sf_level(dtype, c->fastdiv, (double)p.sf, st.min_abs, st.max_abs, !device_sf);
   *sf_t_out = p.sf; *fast_sf_out = p.fast_sf;
   c->pass_fast_bw = p.fast_bw;
   if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
@@ -1670,10 +1634,9 @@ static int compress_impl(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int
     // what the kernels used against what the TRUE statistics ask for (the fused ones of a speculative call; else the
     // full pass's own, which the device has turned into sf by the host's tables: a mismatch there would be a table bug)
     const HostStats truth = spec ? HostStats{hs[4], hs[5], hs[6]} : HostStats{hb->stats[0], hb->stats[1], hb->stats[2]};
-    const double true_sf = scaling_factor(dtype, truth.max_abs);
-    const bool window_ok = fast_sf != 2 || (value_in_window(dtype, truth.min_abs) && value_in_window(dtype, truth.max_abs));
+    double true_sf;
     st = truth;
-    if ((T)true_sf == sf_t && window_ok) {
+    if (device_sf_stands(dtype, truth.max_abs, truth.min_abs, (double)sf_t, fast_sf, &true_sf)) {
       sf = true_sf;
       if (spec) {
         flags |= DCTZHIP_INFO_STATS_FUSED; c->spec_hits++;
@@ -1946,11 +1909,7 @@ static int decompress_impl(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_
   if (nd) p.nd = *nd; else memset(&p.nd, 0, sizeof(p.nd));
   p.nfull = nfull; p.ntiles = ntiles; p.ac_count = ac_count;
   p.sf = (T)sf;
-  // gen_bins / gen_bins_f (binning.c:17 / :37): bin_width = error_bound*2*BRSF in
-  // the data type (gen_bins_f receives error_bound already rounded to float)
-  p.bin_width = (T)((T)eb * 2 * 1.0);
-  p.range_max = (T)(eb * DCTZHIP_NBINS);          // dctz-decomp-lib.c:372-381
-  p.range_min = (T)(-eb * DCTZHIP_NBINS);
+  set_quant(p, inv_quant<T>(eb));
   p.eb = eb;
   const bool scale = (p.sf != (T)1.0);            // :496 / :505
 
@@ -2141,9 +2100,7 @@ static void ra_fill_streams(dctzhip_ctx* c, P& p, const StreamSet& st) {
   p.ctl = c->ctl;
   p.ac_count = st.ac_count;
   p.sf = (T)st.sf;
-  p.bin_width = (T)((T)st.eb * 2 * 1.0);            // as decompress_impl (binning.c:17 / :37)
-  p.range_max = (T)(st.eb * DCTZHIP_NBINS);
-  p.range_min = (T)(-st.eb * DCTZHIP_NBINS);
+  set_quant(p, inv_quant<T>(st.eb));
   p.eb = st.eb;
 }
 template <typename T, typename P>
@@ -3438,16 +3395,12 @@ static int rd_probe_impl(dctzhip_ctx* c, const T* d_in, size_t n, const NdShape*
   const double sf = scaling_factor(dtype, mx);
   p.sf = (T)sf;
   // the launch constants of k_compress (compress_pass): FastDiv where the host's windows allow it
-  p.fast_sf = c->fastdiv ? divisor_in_window(dtype, (double)p.sf) : 0u;
-  if (p.fast_sf && c->fastdiv >= 2 && value_in_window(dtype, mn) && value_in_window(dtype, mx)) p.fast_sf = 2;
+  p.fast_sf = fast_sf_level(dtype, c->fastdiv, (double)p.sf, mn, mx, true);
   T* hb = reinterpret_cast<T*>(c->h_pin + PIN_TAB);
-  const int half = DCTZHIP_NBINS / 2;
-  for (int i = 0; i < k; i++) {                                   // dctz-comp-lib.c:271-281 (computed in double, stored in T)
-    const double eb = ebs[i];
-    hb[3 * i] = (T)(-(half * 2 + 1) * (eb * 1.0));
-    hb[3 * i + 1] = (T)((half * 2 + 1) * (eb * 1.0));
-    hb[3 * i + 2] = (T)(eb * 2.0 * 1.0);
-    if (c->fastdiv && divisor_in_window(dtype, (double)hb[3 * i + 2])) p.fast_bw |= 1u << i;
+  for (int i = 0; i < k; i++) {                                   // (of fast_bw the window bit only: the probe keeps the range test)
+    const FwdQuant<T> fq = fwd_quant<T>(ebs[i], c->fastdiv);
+    hb[3 * i] = fq.range_min; hb[3 * i + 1] = fq.range_max; hb[3 * i + 2] = fq.bin_width;
+    p.fast_bw |= (fq.fast_bw & 1u) << i;
   }
   double* d_bounds = c->rd_slab + rows * RD_SLOT;
   p.bounds = reinterpret_cast<const T*>(d_bounds);
@@ -3881,7 +3834,6 @@ static int launch_compress_seq(dctzhip_ctx* c, const dctzhip_batch_citem* items,
   unsigned* f_stats = hfirst, *f_main = hfirst + (k + 1), *f_list = hfirst + 2 * (k + 1), *f_scale = hfirst + 3 * (k + 1);
   unsigned* rem_items = hfirst + 4 * (k + 1);
   const size_t first_off = align16(k * sizeof(BatchFwd<T>));
-  const int half = DCTZHIP_NBINS / 2;
   unsigned a_stats = 0, a_main = 0, a_list = 0, a_scale = 0, nrem = 0;
   for (size_t j = 0; j < k; j++) {
     const dctzhip_batch_citem& it = items[q.idx[j]];
@@ -3905,15 +3857,7 @@ static int launch_compress_seq(dctzhip_ctx* c, const dctzhip_batch_citem* items,
     p.nfull = q.nfull[j]; p.ntiles = q.ntiles[j]; p.last_is_full = q.rem[j] ? 0u : 1u;
     p.nlists_main = q.G[j];
     p.sf = (T)1; p.fast_sf = 0;                       // (placeholders: p.guess is set)
-    p.bin_width = (T)(eb * 2.0 * 1.0);                // dctz-comp-lib.c:271-281, as compress_pass
-    p.range_min = (T)(-(half * 2 + 1) * (eb * 1.0));
-    p.range_max = (T)((half * 2 + 1) * (eb * 1.0));
-    p.fast_bw = c->fastdiv ? divisor_in_window(dtype, (double)p.bin_width) : 0u;
-    {
-      volatile T u = (T)(p.range_max - p.range_min);
-      volatile T qq = (T)(u / p.bin_width);
-      if (p.fast_bw && c->fastdiv >= 2 && qq >= (T)255) p.fast_bw |= 2u;
-    }
+    set_quant(p, fwd_quant<T>(eb, c->fastdiv));
     b.eb = eb; b.scaled = (T*)it.d_scaled; b.n = (unsigned)it.n; b.rem = q.rem[j];
     b.nlists = q.G[j] + (q.rem[j] ? 1u : 0u);
     b.nparts = q.nparts[j]; b.part_base = q.part_base[j]; b.sample = q.sample[j];
@@ -4030,8 +3974,6 @@ static int ensure_one_bctl(dctzhip_ctx* c, size_t K) {
 
 template <typename T>
 static int fill_one_recs_c(dctzhip_ctx* c, const dctzhip_batch_citem* items, const OnePlan& pl, OneRecC* recs) {
-  const int dtype = sizeof(T) == 8 ? DCTZHIP_F64 : DCTZHIP_F32;
-  const int half = DCTZHIP_NBINS / 2;
   unsigned base = 0;
   size_t at = 0;
   for (size_t j = 0; j < pl.idx.size(); j++) {
@@ -4042,14 +3984,8 @@ static int fill_one_recs_c(dctzhip_ctx* c, const dctzhip_batch_citem* items, con
     r.x = it.d_in; r.bin = it.d_bin_index; r.dc = it.d_dc; r.ac = it.d_ac_exact; r.scaled = it.d_scaled;
     r.nfull = (unsigned)(it.n / 64); r.rem = (unsigned)(it.n % 64); r.ntiles = (r.nfull + TILE_BLKS - 1) / TILE_BLKS;
     if (r.rem) { const T* rt = nullptr; int rc = rtab_for<T>(c, (int)r.rem, &rt); if (rc) return rc; r.rtab = rt; }
-    const T bw = (T)(eb * 2.0 * 1.0), rmin = (T)(-(half * 2 + 1) * (eb * 1.0)), rmax = (T)((half * 2 + 1) * (eb * 1.0));   // dctz-comp-lib.c:271-281
-    r.bin_width = (double)bw; r.range_min = (double)rmin; r.range_max = (double)rmax; r.eb = eb;
-    r.fast_bw = c->fastdiv ? divisor_in_window(dtype, (double)bw) : 0u;
-    {
-      volatile T u = (T)(rmax - rmin);
-      volatile T q = (T)(u / bw);
-      if (r.fast_bw && c->fastdiv >= 2 && q >= (T)255) r.fast_bw |= 2u;
-    }
+    set_quant(r, fwd_quant<T>(eb, c->fastdiv));
+    r.eb = eb;
     r.nwg = pl.nwg[j]; r.board_base = base; r.item = (unsigned)(pl.item_off + j);
     for (unsigned w = 0; w < pl.nwg[j]; w++) { r.wg_local = w; recs[at++] = r; }
     base += pl.nwg[j];
@@ -4152,10 +4088,8 @@ static int batch_one_compress(dctzhip_ctx* c, int k, const dctzhip_batch_citem* 
       const bool in_place = false;                   // (such arrays are not in this launch)
       if (r.error == ONE_ERR_TIMEOUT) { gave_up = true; continue; }
       if (r.error) return fail(c, DCTZHIP_E_INTERNAL, "array %d: in-kernel error flag set (code %u)", i, r.error);
-      const double true_sf = scaling_factor(dt, r.stats[0]);
-      const bool same = dt == DCTZHIP_F64 ? true_sf == r.sf_used : (float)true_sf == (float)r.sf_used;
-      const bool window_ok = r.fast_used != 2 || (value_in_window(dt, r.stats[1]) && value_in_window(dt, r.stats[0]));
-      if (!same || !window_ok) {                     // (a table bug: never seen; the array is done again by the chain)
+      double true_sf;
+      if (!device_sf_stands(dt, r.stats[0], r.stats[1], r.sf_used, r.fast_used, &true_sf)) {   // (a table bug: never seen; the array is done again by the chain)
         if (in_place) return fail(c, DCTZHIP_E_INTERNAL, "array %d: scaling factor chosen on the device differs from the host's after an in-place pass", i);
         c->one = 0;
         continue;
@@ -4189,9 +4123,7 @@ static int fill_one_recs_d(dctzhip_ctx* c, const dctzhip_batch_ditem* items, con
       r.qtab = qt_dev + (pl.item_off + j) * 64 * sizeof(double);
     }
     r.sf = (double)(T)it.sf;
-    r.bin_width = (double)(T)((T)it.error_bound * 2 * 1.0);      // gen_bins / gen_bins_f (binning.c:17 / :37), as decompress_impl
-    r.range_max = (double)(T)(it.error_bound * DCTZHIP_NBINS);   // dctz-decomp-lib.c:372-381
-    r.range_min = (double)(T)(-it.error_bound * DCTZHIP_NBINS);
+    set_quant(r, inv_quant<T>(it.error_bound));
     r.eb = it.error_bound;
     r.nwg = pl.nwg[j]; r.board_base = base; r.item = (unsigned)(pl.item_off + j);
     for (unsigned w = 0; w < pl.nwg[j]; w++) { r.wg_local = w; recs[at++] = r; }
@@ -4407,11 +4339,10 @@ extern "C" int dctzhip_compress_batch(dctzhip_ctx* c, int k, const dctzhip_batch
         const int i = q.idx[j];
         const BatchResC& r = res[q.item_off + j];
         const int dtype = q.dtype;
-        const double true_sf = scaling_factor(dtype, r.stats[0]);
-        const bool same = dtype == DCTZHIP_F64 ? true_sf == r.sf_used : (float)true_sf == (float)r.sf_used;
-        const bool window_ok = r.fast_used != 2 || (value_in_window(dtype, r.stats[1]) && value_in_window(dtype, r.stats[0]));
+        double true_sf;
+        const bool stands = device_sf_stands(dtype, r.stats[0], r.stats[1], r.sf_used, r.fast_used, &true_sf);
         if (q.sample[j]) c->b_spec_items++;
-        if (!same || !window_ok) {                    // (a speculative item whose sample missed the decade; else a table bug: never seen): done again on its own
+        if (!stands) {                                // (a speculative item whose sample missed the decade; else a table bug: never seen): done again on its own
           if (q.sample[j]) { c->b_spec_misses++; c->spec_misses++; c->spec_cooldown = SPEC_COOLDOWN; }
           // ... unless k_scale_batch has already divided the input in place by the wrong factor: nothing to run it on again
           if (items[i].d_scaled && items[i].d_scaled == items[i].d_in)
@@ -4518,9 +4449,7 @@ static int launch_decompress_seq(dctzhip_ctx* c, const dctzhip_batch_ditem* item
     p.ctl = c->b_ctl + q.item_off + j;
     p.nfull = q.nfull[j]; p.ntiles = q.ntiles[j]; p.ac_count = it.ac_count; p.nwg = q.nwg[j];
     p.sf = (T)it.sf;
-    p.bin_width = (T)((T)it.error_bound * 2 * 1.0);   // gen_bins / gen_bins_f (binning.c:17 / :37), as decompress_impl
-    p.range_max = (T)(it.error_bound * DCTZHIP_NBINS); // dctz-decomp-lib.c:372-381
-    p.range_min = (T)(-it.error_bound * DCTZHIP_NBINS);
+    set_quant(p, inv_quant<T>(it.error_bound));
     p.eb = it.error_bound;
     b.n = (unsigned)it.n; b.rem = q.rem[j]; b.scale = (p.sf != (T)1.0) ? 1u : 0u; b.cnt_wgs = q.nwg[j] ? q.nwg[j] : 1u;
     b.rem_cnt = c->b_remcnt + q.item_off + j;

@@ -15,8 +15,8 @@ The same with the separable bases of the 8 x 8 and 4 x 4 x 4 tiles, and with the
 array really holds is COUNTED from the oracle's coefficient tap (census): a case claims classes, and each claimed class must
 hold at least NEED coefficients -- a condition on the data, checked on the CPU, that keeps the GPU tests from passing vacuously.
 
-classify / strip_width restate the host's predicates (dctz_shim.hip: divisor_in_window and the bit-1 test of compress_pass) in
-numpy; bin_ids restates bin_value in its two forms for the negative control."""
+classify / strip_width restate the host's predicates (dctz_quant_host.h: divisor_in_window and the bit-1 test of fwd_quant) in
+numpy, never calling them (tests/test_quant_host_cpu.py compares the two bit for bit); bin_ids restates bin_value in its two forms for the negative control."""
 import functools
 import math
 
