@@ -489,6 +489,7 @@ extern "C" int dctzhip_debug_knob(dctzhip_ctx* c, int key, int value) {
     case 1: c->eo_lb_fail = value != 0; break;       // one tile's look-back of k_compress_eo reports that it gave up
     case 2: c->one_cooldown = value; break;
     case 3: c->rd_sse_div = value > 1 ? value : 1; break;   // every predicted SSE of dctzhip_rd_probe divided by value (step-down path)
+    case 4: c->one_epoch = (unsigned)value; break;   // the tag of the last one-launch kernel (value's 32 bits: -3 is 2^32 - 3), to meet the wrap
     default: return fail(c, DCTZHIP_E_ARG, "dctzhip_debug_knob: no knob %d", key);
   }
   return DCTZHIP_OK;
@@ -1204,8 +1205,21 @@ static unsigned one_capacity(dctzhip_ctx* c, bool decode, int mode, bool scaled)
   }
   return slot > 0 ? (unsigned)(slot * c->num_cu) : 0u;
 }
+// The tag of the next one-launch kernel's granules.  The board is never cleared between launches -- a granule of another
+// launch carries another tag -- so when the 32-bit tag wraps, the granules of 2^32 launches ago would pass for this launch's
+// wherever a workgroup index has not been written since: the board is cleared on the wrap, in stream order in front of the
+// launch (as lb_desc is on the wrap of lb_epoch).  0 on failure (never a tag).
 static unsigned one_next_epoch(dctzhip_ctx* c) {
-  if (++c->one_epoch == 0u) c->one_epoch = 1u;
+  if (++c->one_epoch == 0u) {
+    if (hipMemsetAsync(c->one_ga, 0, sizeof(unsigned long long) * ONE_BOARD, c->stream) != hipSuccess ||
+        hipMemsetAsync(c->one_gb, 0, sizeof(unsigned long long) * ONE_BOARD, c->stream) != hipSuccess ||
+        hipMemsetAsync(c->one_rec, 0, sizeof(double) * 3 * ONE_BOARD, c->stream) != hipSuccess) {
+      c->one_epoch = 0xFFFFFFFFu;                      // (the next call wraps, and clears, again)
+      (void)fail(c, DCTZHIP_E_HIP, "one-launch board: clearing it on the wrap of the epoch failed");
+      return 0u;
+    }
+    c->one_epoch = 1u;
+  }
   return c->one_epoch;
 }
 // a launch gave up (or never reported): back to a known state, and the chain for a while
@@ -1235,6 +1249,7 @@ static int compress_one(dctzhip_ctx* c, const T* d_in, size_t n, double eb, int 
   hipStream_t s = c->stream;
   if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   const unsigned epoch = one_next_epoch(c);
+  if (!epoch) return DCTZHIP_E_HIP;
   OneFwd<T> a;
   memset(&a, 0, sizeof(a));
   FwdParams<T>& p = a.p;
@@ -1300,6 +1315,7 @@ static int decompress_one(dctzhip_ctx* c, const uint8_t* d_bin, const float* d_d
   hipStream_t s = c->stream;
   if (rem) { int rc = upload_rtab<T>(c, rem); if (rc) return rc; }
   const unsigned epoch = one_next_epoch(c);
+  if (!epoch) return DCTZHIP_E_HIP;
   OneInv<T> a;
   memset(&a, 0, sizeof(a));
   InvParams<T>& p = a.p;
@@ -4043,6 +4059,7 @@ static int batch_one_compress(dctzhip_ctx* c, int k, const dctzhip_batch_citem* 
     const OnePlan& q = pl[dt];
     if (q.idx.empty()) continue;
     const unsigned epoch = one_next_epoch(c);
+    if (!epoch) { (void)one_gave_up(c); c->one_bdirty[0] = c->one_bdirty[1] = (unsigned)c->one_bctl_cap; return DCTZHIP_E_HIP; }
     const bool prof = c->profiling != 0;
     hipEvent_t* ev = c->b_ev[dt];
     if (prof) { for (int i = 0; i < 5; i++) if (!ev[i]) HIPCHK(c, hipEventCreate(&ev[i])); HIPCHK(c, hipEventRecord(ev[0], s)); HIPCHK(c, hipEventRecord(ev[1], s)); }
@@ -4174,6 +4191,7 @@ static int batch_one_decompress(dctzhip_ctx* c, int k, const dctzhip_batch_ditem
     const OnePlan& q = pl[dt];
     if (q.idx.empty()) continue;
     const unsigned epoch = one_next_epoch(c);
+    if (!epoch) { (void)one_gave_up(c); return DCTZHIP_E_HIP; }
     const bool prof = c->profiling != 0;
     hipEvent_t* ev = c->b_ev[dt];
     if (prof) { for (int i = 0; i < 5; i++) if (!ev[i]) HIPCHK(c, hipEventCreate(&ev[i])); HIPCHK(c, hipEventRecord(ev[0], s)); HIPCHK(c, hipEventRecord(ev[1], s)); }

@@ -347,6 +347,11 @@ class Context:
         return buf.value.decode()
 
     def knob(self, key, value):
+        """dctzhip_debug_knob (include/dctz_hip.h): 0 withhold a granule, 1 a look-back gives up, 2 the one-launch cooldown,
+        3 the divisor of predicted SSEs, 4 the tag of the last one-launch kernel (its 32 bits: 2**32 - 3 and -3 are the same)."""
+        value = int(value)
+        if key == 4:
+            value = ((value & 0xFFFFFFFF) ^ 0x80000000) - 0x80000000      # the 32 bits as the C int that carries them
         self._check(self.lib.dctzhip_debug_knob(self.h, int(key), int(value)), "debug_knob")
 
     def set_blocking(self, on=True):

@@ -166,7 +166,9 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
  * fast_sf is what it reported) -- and knobs that
  * make a rare path run on purpose -- key 0: workgroup 0 of the one-launch kernels withholds its granule (the launch gives
  * up after 20 ms, the call is run through the chain), 1: one look-back of k_compress_eo gives up, 2: sets counter 2,
- * 3: every predicted SSE of dctzhip_rd_probe / _rd_probe_nd is divided by value (value <= 1: off). */
+ * 3: every predicted SSE of dctzhip_rd_probe / _rd_probe_nd is divided by value (value <= 1: off), 4: sets the tag of the
+ * last one-launch kernel to value's 32 bits (-3: 2^32 - 3), so that the next calls meet the wrap of the tag, on which the
+ * board of granules is cleared. */
 int dctzhip_debug_counter(dctzhip_ctx *ctx, int which, unsigned long long *value);
 int dctzhip_debug_knob(dctzhip_ctx *ctx, int key, int value);
 /* (tools) the name rocprofv3 lists the big kernel of the last call under, every template argument: which = 0 compress,
