@@ -51,6 +51,7 @@ struct dctzhip_ctx {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   hipStream_t side_stream = nullptr;   // serial-order mean, runs beside the host zlib tail
+  hipEvent_t serial_ev = nullptr;      // ... behind what is queued on `stream` when dctzhip_serial_mean_begin is called
   double* serial_out = nullptr;
   size_t serial_n = 0;
   int serial_dtype = -1;
@@ -379,6 +380,7 @@ extern "C" void dctzhip_ctx_destroy(dctzhip_ctx* c) {
   if (c->mb_pin) (void)hipHostFree(c->mb_pin);
   if (c->dfl_len) (void)hipHostFree(c->dfl_len);
   if (c->dfl_ev) (void)hipEventDestroy(c->dfl_ev);
+  if (c->serial_ev) (void)hipEventDestroy(c->serial_ev);
   for (int i = 0; i < dctzhip_ctx::STAGE_WORKERS; i++) {
     if (c->stage[i]) (void)hipHostFree(c->stage[i]);
     if (c->stage_stream[i]) (void)hipStreamDestroy(c->stage_stream[i]);
@@ -1745,6 +1747,10 @@ extern "C" int dctzhip_serial_mean_begin(dctzhip_ctx* c, const void* d_in, size_
   if (rc) return rc;
   if (!d_in) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   HIPCHK(c, hipSetDevice(c->device));
+  // the input may still be in the making on the context's stream: the side stream reads behind what is queued there now
+  if (!c->serial_ev) HIPCHK(c, hipEventCreateWithFlags(&c->serial_ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->serial_ev, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->serial_ev, 0));
   if (dtype == DCTZHIP_F64) launch_serial_sum<double>((const double*)d_in, n, c->serial_out, c->side_stream);
   else launch_serial_sum<float>((const float*)d_in, n, c->serial_out, c->side_stream);
   HIPCHK(c, hipGetLastError());

@@ -265,7 +265,9 @@ def _host_ptr(a):
 
 class Context:
     """One dctzhip context on a GPU; kernels run on torch's current stream (bound before every call: the raw
-    handle, where 0 = the legacy default stream, goes to dctzhip_set_stream as is)."""
+    handle, where 0 = the legacy default stream, goes to dctzhip_set_stream as is).  When the current stream is another
+    one than the last call ran on, the new stream first waits for the old one (include/dctz_hip.h, dctzhip_set_stream:
+    the context's scratch and control blocks are ordered by the stream it ran on)."""
 
     def __init__(self, device=0):
         import torch
@@ -281,6 +283,7 @@ class Context:
             raise DctzHipError(f"dctzhip_ctx_create: {self.lib.dctzhip_last_error(None).decode()}")
         self.h = h
         self._bound = object()            # nothing bound yet
+        self._stream = None               # the torch Stream that was bound (kept alive: the next hop waits for it)
         self._bind_stream()
 
     def _bind_stream(self):
@@ -291,8 +294,11 @@ class Context:
         except AttributeError:
             s = self.torch.cuda.current_stream(self.device).cuda_stream
         if s != self._bound:
+            cur = self.torch.cuda.current_stream(self.device)
+            if self._stream is not None:
+                cur.wait_stream(self._stream)             # the last call's tail kernels still use the context's scratch
             self.lib.dctzhip_set_stream(self.h, C.c_void_p(s))
-            self._bound = s
+            self._bound, self._stream = s, cur
 
     def close(self):
         if getattr(self, "h", None):

@@ -94,7 +94,15 @@ int dctzhip_reserve(dctzhip_ctx *ctx, size_t n, int dtype, int mode);
 /* Run on a caller-owned hipStream_t (e.g. torch's current stream) instead of the
  * context's own.  NULL is the legacy default stream, as everywhere in HIP (what a
  * caller that never created a stream runs on -- ordered against its other work);
- * dctzhip_use_own_stream goes back to the context's private non-blocking stream. */
+ * dctzhip_use_own_stream goes back to the context's private non-blocking stream.
+ * Moving a context between streams: its scratch arena, control blocks and tables are
+ * ordered by the stream it ran on, and a call's last kernels may still be running there
+ * when the call returns.  Before binding another stream the caller either completes the
+ * old one (hipStreamSynchronize) or orders the new one behind it (an event recorded on
+ * the old stream that the new one waits for).  The library itself records nothing on a
+ * stream it is told to leave -- the caller may have destroyed it already -- and queues no
+ * wait on the new one; both calls only drop the decode memo.  (dctz_amd.Context, which
+ * follows torch's current stream on the caller's behalf, does this ordering itself.) */
 int dctzhip_set_stream(dctzhip_ctx *ctx, void *hip_stream);
 int dctzhip_use_own_stream(dctzhip_ctx *ctx);
 void *dctzhip_get_stream(dctzhip_ctx *ctx);
@@ -269,7 +277,11 @@ int dctzhip_stats(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype, dctzh
  * sum of x[1..N-1] in the data type, then / N) -- bit-identical to the
  * reference, which a parallel reduction cannot be.  begin() enqueues a
  * single-wavefront kernel on a side stream and returns at once; end() waits
- * for it.  d_in must stay unmodified in between.  (~0.5 s per GiB of fp64: meant
+ * for it.  The kernel is ordered behind everything that is queued on the context's
+ * stream when begin() is called (an event there that the side stream waits for), so
+ * d_in may still be in the making on that stream; nothing later on the context's stream
+ * waits for the side stream, so d_in must stay unmodified until end() has returned.
+ * (~0.5 s per GiB of fp64: meant
  * to run underneath the host zlib tail, which is 20x longer.) */
 int dctzhip_serial_mean_begin(dctzhip_ctx *ctx, const void *d_in, size_t n, int dtype);
 int dctzhip_serial_mean_end(dctzhip_ctx *ctx, double *mean);

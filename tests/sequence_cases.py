@@ -589,3 +589,25 @@ def census(schedules):
             elif name is not None and not applies(kind, name):
                 inapplicable += 1
     return {"kinds": kinds, "pairs": pairs, "compressed": compressed, "decoded": decoded, "knobs": knobs, "inapplicable": inapplicable}
+
+
+# ---- stream order (tests/test_gpu_stream_order.py; DESIGN.md section 4, "Stream order") -------------------------------------
+STREAM_REPLAY = ("walk_30", "walk_31", "d_qt_maxima", "f_same_buffers", "e_after_refusals")
+STREAM_WALK = (38, 60)                  # (the first seed whose 60 ops bring set_speculation(off) a compress and a decode)
+HOP_WALK = "walk_32"
+# spec memory across a change of decade: `big` two decades up lives in the same device buffer as `big` (not in SUBJECTS: the
+# walks draw their subjects from there, and stay what they are)
+BIG_UP = Subject("big_up", (BIG_N,), F64, O.EC, gain=100.0, dims=(3, BIG_N // 3))
+
+
+def stream_schedules():
+    """name -> schedule: what is replayed with producers pending on the stream and the buffers recycled behind every call."""
+    a = all_schedules()
+    d = {n: a[n] for n in STREAM_REPLAY}
+    d["walk_%d_%d" % STREAM_WALK] = walk(*STREAM_WALK)
+    return d
+
+
+def hop_stream(i):
+    """h_stream_hops: the stream op i of HOP_WALK runs on -- 0 / 1 two streams of the caller's, 2 the legacy default stream."""
+    return 2 if i % 3 == 2 else (i - i // 3) % 2
