@@ -730,6 +730,24 @@ template <typename T> void launch_decompress_coarse(const CoarseParams<T>& p, in
 template <typename T> void launch_decompress_coarse_rem(const CoarseParams<T>& p, int mode, hipStream_t s);
 template <typename T> void launch_decompress_coarse_dc(const float* dc, T* out, unsigned nblk, T sf, hipStream_t s);
 
+// A box of a tiled array's coarse decode (dctz_kernels_ndcbox.hip: k_ndcoarse_box, k_ndcoarse_box_dc).  `c` is the whole-array
+// call's block (c.out: prod ext elements; c.ntiles unused); the box [lo, lo + ext) is in COARSE coordinates, inside c.od.
+// With K = edge / factor block coordinate b owns the coarse cells [b K, b K + K) per axis, so the blocks that hold box
+// cells are again a box of the block grid, and [t0, t1) are the candidate stream tiles as for NdBoxParams.
+template <typename T>
+struct CoarseBoxParams {
+  CoarseParams<T> c;
+  unsigned lo[3], ext[3];          // the box, in coarse cells (the array in the last axes)
+  unsigned t0, t1;
+  BoxGeo blocks;                   // the blocks that hold box cells, a box of the row-major block grid (dim = c.nb): rank() is the hit test
+};
+constexpr bool ndcbox_k_ok(int geom, int k) { return geom == GEOM_2D ? (k == 2 || k == 4) : geom == GEOM_3D && k == 2; }
+template <typename T> int ndcbox_occupancy(int mode, int geom, int k);
+template <typename T> void launch_ndcoarse_box(const CoarseBoxParams<T>& p, int mode, int geom, int k, int grid, hipStream_t s);
+// factor = block edge: out[o] = sf DC[B(o)] / 8 over the box [lo, lo + ext) of the block grid nb; returns the grid
+template <typename T> unsigned launch_ndcoarse_box_dc(const float* dc, T* out, const unsigned (&nb)[3], const unsigned (&lo)[3],
+                                                      const unsigned (&ext)[3], T sf, hipStream_t s);
+
 // Tile summaries (dctz_kernels_summary.hip: k_tile_summary, k_tile_summary_rem, k_tile_summary_final): one record per stream
 // tile of the reconstruction's extremes and sums, with `ref` also of its error against the original.  Flat blocks only; the
 // streams and the index describe the whole array as for RangeParams.

@@ -108,7 +108,8 @@ struct dctzhip_ctx {
   void* mask_filled = nullptr;      // dctzhip_compress_masked without d_filled: the filled copy
   size_t mask_filled_cap = 0;       // bytes
   int coarse_occ[2][2][3][5] = {};  // dctzhip_decompress_coarse / _coarse_nd: the same of k_decompress_coarse / _coarse_nd, [fp64][QT][geometry][log2 K - 1]
-  unsigned box_grid = 0, box_tiles = 0;  // ... its last call: workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
+  int ndcbox_occ[2][2][2][2] = {};  // dctzhip_decompress_coarse_box_nd: the same of k_ndcoarse_box, [fp64][QT][3-D][K == 4]
+  unsigned box_grid = 0, box_tiles = 0;  // the last box call (_box, _box_nd, _coarse_box_nd): workgroups launched, candidate tiles (dctzhip_debug_counter 11 / 12)
   // dctzhip_decompress_boxes: the box table (records, then the boxes of the short block) in pinned host memory and on the
   // device, the list of hit (box, tile) items, resident workgroups per CU of k_decompress_mbox [fp64][QT]
   unsigned char* mb_pin = nullptr;
@@ -470,7 +471,7 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 8: *value = c->b_spec_items; break;         // batch items that took their scaling factor from a sample
     case 9: *value = c->b_spec_misses; break;        // ... whose guess the true statistics refused (done again on their own)
     case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
-    case 11: *value = c->box_grid; break;            // dctzhip_decompress_box / _box_nd, last call: workgroups of its kernel
+    case 11: *value = c->box_grid; break;            // dctzhip_decompress_box / _box_nd / _coarse_box_nd, last call: workgroups of its kernel
     case 12: *value = c->box_tiles; break;           // ... candidate tiles (more than workgroups: the grid-stride loop ran)
     case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes / _boxes_nd, last call of either: (box, hit tile) items in its list
     case 14: *value = c->mbox_grid; break;           // ... workgroups of its decode launch (fewer than items: they took several each)
@@ -2325,11 +2326,12 @@ static int nd_front(dctzhip_ctx* c, int ndims, const size_t* dims, int dtype, in
   return check_common(c, sh->nblk * 64, dtype, mode);
 }
 // The box [lo, hi) of a tiled array: inside the array, cnt its elements, [t0, t1) the stream tiles from the one of its first
-// intersecting block to the one of its last (blocks in the row-major order of the block grid).
+// intersecting block to the one of its last (blocks in the row-major order of the block grid).  cell != 0: sh.d are coarse
+// extents and a block owns `cell` of their cells per axis (sh.nb is still the block grid).
 static int nd_box_front(dctzhip_ctx* c, const char* what, const NdShape& sh, const size_t* lo, const size_t* hi, size_t* cnt, unsigned* t0,
-                        unsigned* t1) {
+                        unsigned* t1, size_t cell = 0) {
   if (!lo || !hi) return fail(c, DCTZHIP_E_ARG, "%s: null lo or hi", what);
-  const size_t edge = sh.nd == 2 ? 8 : 4;
+  const size_t edge = cell ? cell : sh.nd == 2 ? 8 : 4;
   size_t first = 0, last = 0;
   *cnt = 1;
   for (int i = 0; i < sh.nd; i++) {
@@ -2465,10 +2467,11 @@ extern "C" int dctzhip_decompress_nd(dctzhip_ctx* c, const void* d_bin, const fl
 
 // ---- a box of an array compressed in tiles (include/dctz_hip.h; dctz_kernels_ndbox.hip) -------------------------
 // The checked box [lo, hi) as the kernels take it: the array in the last sh.nd of three axes (nb: blocks per axis; blo, ext:
-// the box in elements), and the intersecting blocks as a box of the block grid (dim = nb; rank() is the hit test).
+// the box in elements), and the intersecting blocks as a box of the block grid (dim = nb; rank() is the hit test).  cell: as
+// for nd_box_front.
 static void nd_box_geometry(const NdShape& sh, const size_t* lo, const size_t* hi, unsigned (&nb)[3], unsigned (&blo)[3], unsigned (&ext)[3],
-                            BoxGeo* blocks) {
-  const unsigned edge = sh.nd == 2 ? 8u : 4u;
+                            BoxGeo* blocks, unsigned cell = 0) {
+  const unsigned edge = cell ? cell : sh.nd == 2 ? 8u : 4u;
   memset(blocks, 0, sizeof(*blocks));
   for (int i = 0; i < BOX_ND; i++) { blocks->dim[i] = 1u; blocks->lo[i] = 0u; blocks->ext[i] = 1u; }
   for (int i = 0; i < 3; i++) { nb[i] = 1u; blo[i] = 0u; ext[i] = 1u; }
@@ -2788,6 +2791,81 @@ extern "C" int dctzhip_decompress_coarse_nd(dctzhip_ctx* c, const void* d_bin, c
   HIPCHK(c, hipSetDevice(c->device));
   return (dtype == DCTZHIP_F64) ? decompress_coarse_impl<double>(c, st, &sh, factor, (double*)d_out)
                                 : decompress_coarse_impl<float>(c, st, &sh, factor, (float*)d_out);
+}
+
+// ---- a box of a tiled array at reduced resolution (include/dctz_hip.h; dctz_kernels_ndcbox.hip) -----------------
+// cs: the coarse array as a shape -- extents ceil(dims / factor) over the block grid of the array itself; a block owns k cells
+// of it per axis.  The box is checked; [t0, t1) are its candidate stream tiles.
+template <typename T>
+static int decompress_coarse_box_nd_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape& cs, int factor, int k, const size_t* lo,
+                                         const size_t* hi, unsigned t0, unsigned t1, T* d_out) {
+  hipStream_t s = c->stream;
+  const int mode = st.mode, geom = cs.nd == 2 ? GEOM_2D : GEOM_3D;
+  { int rc = ra_begin<T>(c, mode, st.qtable); if (rc) return rc; }
+  CoarseBoxParams<T> p;
+  ra_fill<T>(c, p.c, st, d_out);
+  p.c.rtab = nullptr;
+  p.c.n = (unsigned)(cs.nblk * 64); p.c.nfull = (unsigned)cs.nblk; p.c.ntiles = (p.c.nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+  p.c.factor = (unsigned)factor;
+  last_axes(cs.nd, p.c.od, 1u, [&](int i) { return cs.d[i]; });
+  p.t0 = t0; p.t1 = t1;
+  nd_box_geometry(cs, lo, hi, p.c.nb, p.lo, p.ext, &p.blocks, (unsigned)k);
+  if (k == 1) {
+    // the block grid is the output grid: the DC stream alone
+    c->box_grid = launch_ndcoarse_box_dc<T>(st.dc, d_out, p.c.nb, p.lo, p.ext, (T)st.sf, s); c->box_tiles = 0;
+    SET_LAST(c, 1, "k_ndcoarse_box_dc<%s>", tname<T>());
+  } else {
+    // a workgroup per candidate tile
+    const unsigned tiles = t1 - t0;
+    // (the kernel is small: 32 of its workgroups fit a CU, so most boxes are resident at once.  DCTZHIP_WG_PER_CU, as for the
+    // big kernels, sets the number instead: the grid-stride loop on purpose, for A/B runs and tests)
+    int forced = c->wg_per_cu;
+    int& occ = forced ? forced : c->ndcbox_occ[sizeof(T) == 8][mode == DCTZHIP_QT][cs.nd == 3][k == 4];
+    const int grid = (int)resident_grid(c, occ, tiles, [&] { return ndcbox_occupancy<T>(mode, geom, k); });
+    c->box_grid = (unsigned)grid; c->box_tiles = tiles;
+    launch_ndcoarse_box<T>(p, mode, geom, k, grid, s);
+    SET_LAST(c, 1, "k_ndcoarse_box<%s, %d, %d, %d>", tname<T>(), mode, geom, k);
+  }
+  return ra_finish(c);
+}
+
+extern "C" int dctzhip_decompress_coarse_box_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                                const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims,
+                                                int dtype, double eb, double sf, int mode, int factor, const size_t* lo,
+                                                const size_t* hi, void* d_out) {
+  static const char* const what = "dctzhip_decompress_coarse_box_nd";
+  NdShape sh;
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
+  if (rc) return rc;
+  const int geom = ndims == 2 ? GEOM_2D : GEOM_3D;
+  const int k = coarse_k(geom, factor);
+  if (!k) return fail(c, DCTZHIP_E_ARG, "%s: factor %d is not one of %s", what, factor, geom == GEOM_2D ? "2, 4, 8" : "2, 4");
+  NdShape cs = sh;
+  for (int i = 0; i < ndims; i++) cs.d[i] = (sh.d[i] + (size_t)factor - 1) / (size_t)factor;
+  size_t cnt = 1;
+  unsigned t0 = 0, t1 = 0;
+  if ((rc = nd_box_front(c, what, cs, lo, hi, &cnt, &t0, &t1, (size_t)k))) return rc;
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
+  if (k > 1) {
+    if ((rc = streams_given(c, st, " and the output", true, d_out))) return rc;
+    // what the call may read: the candidate tiles and AC_exact
+    if ((rc = ra_check_spans(c, what, st, t0, t1, d_out, cnt * elem_size(dtype)))) return rc;
+  } else {
+    // the DC stream alone, from the first to the last block of the box
+    if (!st.dc || !d_out) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+    if (!aligned16(d_out) || ((uintptr_t)st.dc & 3u)) return fail(c, DCTZHIP_E_ARG, "the output must be 16-byte aligned, DC 4-byte aligned");
+    if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+    size_t first = 0, last = 0;
+    for (int i = 0; i < ndims; i++) { first = first * sh.nb[i] + lo[i]; last = last * sh.nb[i] + (hi[i] - 1); }
+    Span sp[2];
+    size_t m = 0;
+    add_span(sp, &m, st.dc + first, (last - first + 1) * sizeof(float), SPAN_READ, 0);
+    add_span(sp, &m, d_out, cnt * elem_size(dtype), SPAN_OUT, 0);
+    if ((rc = check_spans(c, sp, m, what, nullptr))) return rc;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  return (dtype == DCTZHIP_F64) ? decompress_coarse_box_nd_impl<double>(c, st, cs, factor, k, lo, hi, t0, t1, (double*)d_out)
+                                : decompress_coarse_box_nd_impl<float>(c, st, cs, factor, k, lo, hi, t0, t1, (float*)d_out);
 }
 
 // ---- what the summary and correction-list calls share: a whole stream set with its index, flat or tiled ----------

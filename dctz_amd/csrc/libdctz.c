@@ -2053,6 +2053,48 @@ int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r) {
   return 1;
 }
 
+/* ------------------------------------------------------ dctz_decompress_coarse_box_nd -- */
+/* A box, in coarse coordinates, of what dctz_decompress_coarse returns for a DZND container (include/dctz_hip.h:
+ * dctzhip_decompress_coarse_box_nd), the way of decompress_part: with K = edge / factor the blocks lo / K ... (hi - 1) / K hold
+ * the box; bin ids up to the end of the last of their stream tiles, DC up to the last of them -- with factor == edge that
+ * DC prefix alone -- the index built once over the prefix, one device call, only the box copied back. */
+int dctz_decompress_coarse_box_nd(t_var *var_z, int factor, const size_t *lo, const size_t *hi, t_var *var_r) {
+  const double t_begin = now_s();
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
+  if (v.nd == 0 || dzc_geometry(&v) != 0) return -1;               /* a flat container, or extents that are no shape */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
+  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const int edge = v.nd == 2 ? 8 : 4;
+  if (n == 0 || !var_r || !lo || !hi || factor < 2 || factor > edge || (factor & (factor - 1))) return -1;
+  const size_t K = (size_t)(edge / factor);
+  size_t first = 0, last = 0, out_elems = 1;                   /* blocks of the row-major block grid */
+  for (int i = 0; i < v.nd; i++) {
+    const size_t cd = (v.dims[i] + (size_t)factor - 1) / (size_t)factor, nb = (v.dims[i] + (size_t)edge - 1) / (size_t)edge;
+    if (lo[i] >= hi[i] || hi[i] > cd) return -1;
+    out_elems *= hi[i] - lo[i];
+    first = first * nb + lo[i] / K;
+    last = last * nb + (hi[i] - 1) / K;
+  }
+  if (last >= nblk) return -1;
+  const int dc_only = K == 1;
+  const size_t S = DCTZHIP_INDEX_STRIDE;
+  const size_t t1 = ((last + 1) * BLK_SZ + S - 1) / S;         /* the candidate tiles end here */
+  const size_t dc_bytes = (last + 1) * sizeof(float);
+  const size_t dc_dev = dc_only ? last + 1 : MIN(nblk, t1 * (S / BLK_SZ));   /* DC words the candidate tiles cover on the device */
+  dev_streams s;
+  if (sections_to_device(&v, dc_only ? 0 : MIN(n, S * t1), dc_bytes, dc_dev * sizeof(float), dc_only, &s) != 1) return -1;
+  const double t0 = now_s();
+  grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
+  const int rc = dctzhip_decompress_coarse_box_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, factor, lo, hi, g_dev.out);
+  if (rc == DCTZHIP_E_ARG) return -1;                          /* the streams disagree with each other */
+  if (rc != DCTZHIP_OK) die("dctzhip_decompress_coarse_box_nd");
+  const double t1s = now_s();
+  if (dctzhip_memcpy_d2h(s.c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
+  part_times(&s, t_begin, t0, t1s);
+  return 1;
+}
+
 /* ------------------------------------------------------------------ dctz_tile_summary -- */
 /* Per-tile records of the reconstruction, and with var_ref of its error (include/dctz_hip.h: dctzhip_tile_summary,
  * dctzhip_tile_summary_nd): the three sections inflated, the index built once, the original uploaded when given; records and

@@ -156,6 +156,9 @@ _PROTOS = {
     "dctzhip_decompress_coarse_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                                C.c_void_p]),
+    "dctzhip_decompress_coarse_box_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
     "dctzhip_summary_tiles": (C.c_size_t, [C.c_size_t]),
     "dctzhip_tile_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
@@ -704,6 +707,26 @@ class Context:
             self.h, b, d, a, int(cnt), ix, _host_ptr(q), len(shape), arr(*shape),
             _dt(dtype), float(eb), float(sf), mode, int(factor), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_coarse_nd")
+        return dst.view(ext)
+
+    def decompress_coarse_box_nd(self, out, cnt, shape, dtype, eb, sf, factor, lo, hi, index=None, mode=EC, qtable=None, dst=None):
+        """The box lo[i] <= c[i] < hi[i], in COARSE coordinates, of what decompress_coarse_nd() gives for the same arguments, bit
+        for bit; only the stream tiles that hold cells of the box are read.  With factor == tile edge only out["dc"] is
+        read.  Returns dst shaped hi - lo."""
+        t = self.torch
+        self._bind_stream()
+        shape, lo, hi = [int(v) for v in shape], [int(v) for v in lo], [int(v) for v in hi]
+        nd = len(shape)
+        assert len(lo) == nd and len(hi) == nd
+        ext = [max(h - l, 0) for l, h in zip(lo, hi)]
+        if dst is None:
+            dst = t.empty(ext, dtype=dtype, device=self.device)
+        (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_decompress_coarse_box_nd(
+            self.h, b, d, a, int(cnt), ix, _host_ptr(q), nd, arr(*shape),
+            _dt(dtype), float(eb), float(sf), mode, int(factor), arr(*lo), arr(*hi), dst.data_ptr())
+        self._check(rc, "dctzhip_decompress_coarse_box_nd")
         return dst.view(ext)
 
     # ---- flat and tiled streams through one body per operation ----

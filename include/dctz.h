@@ -215,6 +215,15 @@ int dctz_decompress_boxes_nd(t_var *var_z, int k,
  * Returns 1, or -1 for a bad factor, a null var_r and streams that disagree with each other -- dctz_decompress_box's
  * conventions. */
 int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r);
+/* A box of that, for DZND containers (ADDITION, EC and QT builds): a window at zoom level `factor` (include/dctz_hip.h:
+ * dctzhip_decompress_coarse_box_nd).  lo / hi are in COARSE coordinates, lo[i] < hi[i] <= ceil(dims[i] / factor), rows of
+ * the container's dimensions; var_r->buf, allocated by the caller, receives prod (hi[i] - lo[i]) elements, dense, in C order:
+ * byte for byte the slice of what dctz_decompress_coarse returns for the same container and factor.  Only the prefix of the
+ * sections the box needs is inflated and uploaded -- bin_index up to the end of the last stream tile that may hold a cell of
+ * the box, DC up to the last block of the box; with factor equal to the block edge that DC prefix alone -- the exception
+ * index is built once, and only the box is copied back.  Returns 1, or -1 for a flat container, a bad factor, a null lo, hi
+ * or var_r, a box that is not inside the coarse extents and streams that disagree with each other. */
+int dctz_decompress_coarse_box_nd(t_var *var_z, int factor, const size_t *lo, const size_t *hi, t_var *var_r);
 /* Verify and survey without a reconstruction (ADDITION, EC and QT builds; include/dctz_hip.h: dctzhip_tile_summary holds the
  * definition).  One record per 4096 elements of what dctz_decompress would rebuild from var_z -- its minimum, maximum, sum
  * and sum of squares -- and, with var_ref, the minimum and maximum of the original, max |x - r| and sum (x - r)^2 of the

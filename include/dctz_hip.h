@@ -163,7 +163,8 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
  * through the chain), 2 calls left on the chain after such a launch, 3 calls through k_compress_eo, 4 of them with
  * single-pass placement, 5 look-backs that gave up, 6 / 7 verified / wrong guesses of the scaling factor, 8 / 9 speculative
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr / _psnr_nd, 11 / 12 workgroups and
- * candidate tiles of the last dctzhip_decompress_box / _box_nd call (12 > 11: its grid-stride loop ran), 13 / 14 / 15 items
+ * candidate tiles of the last dctzhip_decompress_box / _box_nd / _coarse_box_nd call, whichever ran last (12 > 11: its
+ * grid-stride loop ran; a _coarse_box_nd call with factor == block edge reads no tiles: 12 is 0), 13 / 14 / 15 items
  * in the list of the last dctzhip_decompress_boxes or dctzhip_decompress_boxes_nd call (whichever of the two ran last),
  * workgroups of its decode launch and the list's bound, 16 / 17
  * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again, 18 / 19 guesses of the
@@ -540,7 +541,9 @@ int dctzhip_decompress_boxes_nd(dctzhip_ctx *ctx, const void *d_bin_index, const
  * the part of the reconstruction below frequency K at the centres of the K cells of `factor` elements (the K-point
  * orthonormal DCT-III of sqrt(K/N) c[0 .. K-1]).  The mean of y over a block is the block mean of the full reconstruction;
  * K = 1 gives sf c[0] / sqrt(N).  Tiles use the formula separably along every axis, on the low corner k_a < K of the
- * tile's row-major coefficients.  Whole arrays only: a part at full resolution is what the box calls are for.
+ * tile's row-major coefficients.  dctzhip_decompress_coarse and dctzhip_decompress_coarse_nd write the whole array; a window
+ * of a TILED array at the same reduced resolution is dctzhip_decompress_coarse_box_nd below, and a part at full resolution
+ * is what the box calls are for.  (In flat blocks "coarse" thins the flat index, not the axes of an N-D view: no box there.)
  *
  * dctzhip_decompress_coarse   flat 64-element blocks (dctzhip_compress); factor in {2, 4, 8, 16, 32, 64}.
  *   d_out       receives dctzhip_coarse_len(n, factor) = ceil(n / factor) elements of the data type; block b writes
@@ -573,6 +576,33 @@ int dctzhip_decompress_coarse_nd(dctzhip_ctx *ctx, const void *d_bin_index, cons
                                  uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
                                  const size_t *dims, int dtype, double error_bound, double sf, int mode, int factor,
                                  void *d_out);
+/* A box of what dctzhip_decompress_coarse_nd writes: a window at zoom level `factor`.  Everything up to `factor` is that
+ * call's (factor in {2, 4, 8} for 2-D, {2, 4} for 3-D); lo / hi are in COARSE coordinates, lo[i] < hi[i] <= ceil(dims[i] /
+ * factor).
+ *   d_out       receives prod (hi[i] - lo[i]) elements, dense, in C order; each is, bit for bit, the element that
+ *               dctzhip_decompress_coarse_nd writes at the same coarse coordinates with the same remaining arguments (EC and
+ *               QT, fp32 and fp64, aligned and ragged extents; a cell that straddles a ragged edge keeps that call's rule).
+ *   locality    with K = edge / factor, block coordinate b owns the coarse cells [b K, b K + K) per axis: the blocks that
+ *               hold box cells are lo[i] / K ... (hi[i] - 1) / K, a box of the row-major block grid.  A stream tile (64
+ *               consecutive blocks) is HIT if it holds one of them; candidate tiles run from the first to the last such
+ *               block.  Only hit tiles are read and decoded, once each -- their bin ids and DC values, idx[t] and idx[t + 1],
+ *               AC_exact[idx[t], idx[t + 1]) -- and nothing outside d_out[0, prod ext) is written.
+ *   factor == block edge   the block grid is the output grid: the box is gathered from the DC stream alone ((T)DC * 0.125,
+ *               then * sf if sf != 1, as the whole-array call), the DC words from the first to the last block of the box;
+ *               d_bin_index, d_ac_exact and d_index may be NULL.
+ *   refusals    before any launch, DCTZHIP_E_ARG: what dctzhip_decompress_coarse_nd refuses for ctx, shape, dtype, mode,
+ *               factor, the streams, alignment and the QT table; a null lo or hi; a box that is not inside the coarse
+ *               extents; a d_out that overlaps what the call may read (the candidate tiles' bin ids, DC values and index
+ *               entries and AC_exact[0, ac_count); for factor == block edge the DC words named above).  On the device, for
+ *               hit tiles only, the index check of the whole-array call: a failing tile reads no AC_exact, the call returns
+ *               DCTZHIP_E_ARG, the output is undefined and the context stays usable.
+ * Returns once that check is known, as the box calls do (the call has synchronised the stream).
+ * dctzhip_debug_last_kernel(ctx, 1, ...) names the kernel (k_ndcoarse_box<...> | k_ndcoarse_box_dc<...>); dctzhip_debug_counter
+ * 11 / 12 report this call too: the workgroups of its launch and its candidate tiles (0 for factor == block edge). */
+int dctzhip_decompress_coarse_box_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                                     uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                                     const size_t *dims, int dtype, double error_bound, double sf, int mode, int factor,
+                                     const size_t *lo, const size_t *hi, void *d_out);
 
 /* ---- tile summaries: verify and survey without writing the decode ----------- */
 /* Two questions about a compressed array that need no reconstruction in memory: how far is it from the original, and where
