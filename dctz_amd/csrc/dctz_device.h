@@ -748,6 +748,24 @@ template <typename T> void launch_ndcoarse_box(const CoarseBoxParams<T>& p, int 
 template <typename T> unsigned launch_ndcoarse_box_dc(const float* dc, T* out, const unsigned (&nb)[3], const unsigned (&lo)[3],
                                                       const unsigned (&ext)[3], T sf, hipStream_t s);
 
+// A list of such boxes in one call (dctz_kernels_mcboxnd.hip: k_ndcoarse_mbox, k_ndcoarse_mbox_dc; the list is
+// k_boxlist_build's).  `c` is the whole-array call's block (c.out, c.rtab and c.ntiles unused).  Per box one BoxRec -- g the
+// box of the block grid as CoarseBoxParams::blocks, [t0, t1) the candidate stream tiles, the builder's unit TILE_BLKS blocks
+// and its end nblk -- and, in a second table, the box in coarse cells.
+template <typename T>
+struct MCBoxNdParams {
+  CoarseParams<T> c;
+  const BoxRec* recs;              // `out` is read
+  const NdBoxElems* elems;         // the box in coarse cells, as CoarseBoxParams::lo / ext
+  const BoxItem* items;
+  unsigned cap;                    // capacity of items
+};
+template <typename T> int mcboxnd_occupancy(int mode, int geom, int k);
+template <typename T> void launch_ndcoarse_mbox(const MCBoxNdParams<T>& p, int mode, int geom, int k, int grid, hipStream_t s);
+// factor = block edge: box i of nbox from the DC stream alone, no list; max_cells: of the largest box; returns the workgroups
+template <typename T> unsigned launch_ndcoarse_mbox_dc(const float* dc, const BoxRec* recs, const NdBoxElems* elems, unsigned nbox,
+                                                       unsigned max_cells, const unsigned (&nb)[3], T sf, hipStream_t s);
+
 // Tile summaries (dctz_kernels_summary.hip: k_tile_summary, k_tile_summary_rem, k_tile_summary_final): one record per stream
 // tile of the reconstruction's extremes and sums, with `ref` also of its error against the original.  Flat blocks only; the
 // streams and the index describe the whole array as for RangeParams.

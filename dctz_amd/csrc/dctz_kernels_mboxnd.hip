@@ -14,22 +14,12 @@
 // k_decompress_box: that kernel's text stays as it was measured (EXPERIMENTS.md, "Many boxes of a tiled array").  A change
 // to either belongs in both.  There is no short block (n = 64 nblk), so no _rem kernel.
 #include "dctz_nd_image.h"
+#include "dctz_uniform_words.h"
 
 namespace dctz {
 // (a namespace of its own: the kernel's qualified name is dctz::tiled::k_decompress_mbox_nd, so that a listing of the flat
 // call's kernels by the prefix dctz::k_decompress_mbox keeps showing those alone)
 namespace tiled {
-
-// a record into scalar registers, word by word (every lane reads the same address)
-template <typename R>
-__device__ __forceinline__ R uniform_words(const R* r) {
-  static_assert(sizeof(R) % 4 == 0, "read word by word");
-  struct Words { unsigned w[sizeof(R) / 4]; } v;
-  const unsigned* s = reinterpret_cast<const unsigned*>(r);
-#pragma unroll
-  for (unsigned i = 0; i < sizeof(R) / 4; i++) v.w[i] = (unsigned)__builtin_amdgcn_readfirstlane((int)s[i]);
-  return __builtin_bit_cast(R, v);
-}
 
 template <typename T, int MODE, int GEOM>
 __global__ __launch_bounds__(64) void k_decompress_mbox_nd(MBoxNdParams<T> p) {

@@ -14,6 +14,9 @@
 // extents, so a cell that begins past the array is never inside it: the whole-array kernel's edge rule needs no test of
 // its own here.
 //
+// k_ndcoarse_mbox (dctz_kernels_mcboxnd.hip: a list of such boxes in one call) carries a COPY of the tile body, from the
+// coarse_tile_head call to the closing barrier.  A change to either belongs in both.
+//
 // k_ndcoarse_box_dc: factor = block edge.  The block grid IS the output grid; the box is gathered from the DC stream alone,
 // a thread per output element, consecutive lanes consecutive x, with k_decompress_coarse_dc's expressions in its order.
 #include "dctz_coarse_block.h"

@@ -118,6 +118,7 @@ struct dctzhip_ctx {
   size_t mb_items_cap = 0;          // items
   int mbox_occ[2][2] = {{0, 0}, {0, 0}};
   int mboxnd_occ[2][2][2] = {};     // dctzhip_decompress_boxes_nd: the same of k_decompress_mbox_nd, [fp64][QT][3-D]; table, list and counters are shared
+  int mcboxnd_occ[2][2][2][2] = {}; // dctzhip_decompress_coarse_boxes_nd: the same of k_ndcoarse_mbox, [fp64][QT][3-D][K == 4]; shared likewise
   unsigned mbox_items = 0, mbox_grid = 0, mbox_bound = 0;   // ... its last call: items listed, workgroups of the decode launch, the bound B (dctzhip_debug_counter 13 / 14 / 15)
   int dec_il = 1;                   // 0: k_decompress with a contiguous tile range per workgroup; 1: interleaved for fp64 EC; 2: for all (DCTZHIP_DEC_IL)
   size_t qcnt_cap = 0;              // tiles the two hold
@@ -473,7 +474,7 @@ extern "C" int dctzhip_debug_counter(dctzhip_ctx* c, int which, unsigned long lo
     case 10: *value = c->rd_stepdowns; break;        // dctzhip_compress_psnr: measured misses that stepped down a point of the grid
     case 11: *value = c->box_grid; break;            // dctzhip_decompress_box / _box_nd / _coarse_box_nd, last call: workgroups of its kernel
     case 12: *value = c->box_tiles; break;           // ... candidate tiles (more than workgroups: the grid-stride loop ran)
-    case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes / _boxes_nd, last call of either: (box, hit tile) items in its list
+    case 13: *value = c->mbox_items; break;          // dctzhip_decompress_boxes / _boxes_nd / _coarse_boxes_nd, last call of any: (box, hit tile) items in its list
     case 14: *value = c->mbox_grid; break;           // ... workgroups of its decode launch (fewer than items: they took several each)
     case 15: *value = c->mbox_bound; break;          // ... the host's bound B of the items, the list's capacity
     case 16: *value = c->memo_decodes; break;        // dctzhip_decompress calls launched on the last compress call's tile counts (the decode memo)
@@ -2543,15 +2544,20 @@ static int mbox_table(dctzhip_ctx* c) {
 // sh null: st.n elements in flat blocks; else the tiles of sh (st.n = 64 sh->nblk, no short block).  recs[0, k) are complete
 // but for the device side of the table; side[0, side_bytes) is the table's second half -- flat: the boxes that reach into
 // the short block, an unsigned each; tiled: the k boxes in elements, an NdBoxElems each; B bounds the hits.
+// cz (or null): the boxes are of the coarse decode -- sh is the coarse shape, the boxes are in its cells, cz->k per block and
+// axis; with cz->k == 1 there is no list (B = 0): one gather from the DC stream, cz->max_cells the cells of the largest box.
+namespace {
+struct CoarseZoom { int factor, k; unsigned max_cells; };
+}
 template <typename T>
 static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, const NdShape* sh, int k, const BoxRec* recs, const void* side,
-                                 size_t side_bytes, unsigned total, size_t B) {
+                                 size_t side_bytes, unsigned total, size_t B, const CoarseZoom* cz = nullptr) {
   hipStream_t s = c->stream;
   const int mode = st.mode;
   const int nrem = sh ? 0 : (int)(side_bytes / sizeof(unsigned));
   int rc;
   if ((rc = mbox_table(c))) return rc;
-  if ((rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
+  if (B && (rc = regrow(c, &c->mb_items, &c->mb_items_cap, B, sizeof(BoxItem)))) return rc;
   c->ctl_dirty = 1;                                  // the list's counter is the control block's: cleared in stream order, always
   if ((rc = ra_begin<T>(c, mode, st.qtable))) return rc;
   if (nrem) { if ((rc = upload_rtab<T>(c, (int)(st.n % 64)))) return rc; }      // (it can fail: in front of the table's copy)
@@ -2591,6 +2597,31 @@ static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, const NdSh
     launch_boxlist_build(lp, s);
     launch_decompress_mbox<T>(p, mode, grid, nrem, s);
     SET_LAST(c, 1, "k_decompress_mbox<%s, %d>", tname<T>(), mode);
+  } else if (cz) {
+    const int geom = sh->nd == 2 ? GEOM_2D : GEOM_3D;
+    MCBoxNdParams<T> p;
+    ra_fill<T>(c, p.c, st, (T*)nullptr);
+    p.c.rtab = nullptr;
+    p.c.n = (unsigned)st.n; p.c.nfull = (unsigned)sh->nblk; p.c.ntiles = (p.c.nfull + (unsigned)TILE_BLKS - 1u) / (unsigned)TILE_BLKS;
+    p.c.factor = (unsigned)cz->factor;
+    last_axes(sh->nd, p.c.nb, 1u, [&](int i) { return sh->nb[i]; });
+    last_axes(sh->nd, p.c.od, 1u, [&](int i) { return sh->d[i]; });
+    p.recs = lp.recs; p.items = c->mb_items; p.cap = (unsigned)B;
+    p.elems = reinterpret_cast<const NdBoxElems*>(c->mb_dev + rec_bytes);
+    if (cz->k == 1) {
+      // the block grid is the output grid: every box from the DC stream alone, in one launch
+      c->mbox_grid = launch_ndcoarse_mbox_dc<T>(st.dc, p.recs, p.elems, (unsigned)k, cz->max_cells, p.c.nb, (T)st.sf, s);
+      SET_LAST(c, 1, "k_ndcoarse_mbox_dc<%s>", tname<T>());
+    } else {
+      // (DCTZHIP_WG_PER_CU sets the resident workgroups instead, as for the single call)
+      int forced = c->wg_per_cu;
+      int& occ = forced ? forced : c->mcboxnd_occ[sizeof(T) == 8][mode == DCTZHIP_QT][sh->nd == 3][cz->k == 4];
+      const int grid = (int)resident_grid(c, occ, B, [&] { return mcboxnd_occupancy<T>(mode, geom, cz->k); });
+      c->mbox_grid = (unsigned)grid;
+      launch_boxlist_build(lp, s);
+      launch_ndcoarse_mbox<T>(p, mode, geom, cz->k, grid, s);
+      SET_LAST(c, 1, "k_ndcoarse_mbox<%s, %d, %d, %d>", tname<T>(), mode, geom, cz->k);
+    }
   } else {
     const int geom = sh->nd == 2 ? GEOM_2D : GEOM_3D;
     MBoxNdParams<T> p;
@@ -2608,10 +2639,12 @@ static int decompress_boxes_impl(dctzhip_ctx* c, const StreamSet& st, const NdSh
   return rc;
 }
 
-// What the two entry points share from the k check on.  sh null: the flat array of st.n elements seen with the shape dims[0, ndim),
-// which is checked here; else the tiles of sh.
+// What the entry points share from the k check on.  sh null: the flat array of st.n elements seen with the shape dims[0, ndim),
+// which is checked here; else the tiles of sh.  factor != 0: the boxes of the coarse decode at that (checked) factor -- sh is
+// the coarse shape over the array's own block grid, a block owns cell = edge / factor of its cells per axis; with cell == 1
+// the DC stream alone is read, per box from its first to its last block, and the other streams may be missing.
 static int decompress_boxes_call(dctzhip_ctx* c, const char* what, const StreamSet& st, const NdShape* sh, int ndim, const size_t* dims, int k,
-                                 const dctzhip_box_item* boxes) {
+                                 const dctzhip_box_item* boxes, int factor = 0, int cell = 0) {
   int rc;
   if (k < 1 || k > DCTZHIP_BOXES_MAX) return fail(c, DCTZHIP_E_ARG, "%s: k must be in [1, %d]", what, DCTZHIP_BOXES_MAX);
   if (!boxes) return fail(c, DCTZHIP_E_ARG, "%s: null boxes", what);
@@ -2619,7 +2652,12 @@ static int decompress_boxes_call(dctzhip_ctx* c, const char* what, const StreamS
     if (ndim < 1 || ndim > DCTZHIP_BOX_MAXDIM) return fail(c, DCTZHIP_E_ARG, "%s: ndim must be in [1, %d]", what, DCTZHIP_BOX_MAXDIM);
     if (!dims) return fail(c, DCTZHIP_E_ARG, "%s: null dims", what);
   }
-  if ((rc = streams_given(c, st, " and the outputs"))) return rc;           // (the outputs themselves: box by box, below)
+  const bool dc_only = cell == 1;
+  if (dc_only) {
+    if (!st.dc) return fail(c, DCTZHIP_E_ARG, "null device buffer");
+    if ((uintptr_t)st.dc & 3u) return fail(c, DCTZHIP_E_ARG, "DC must be 4-byte aligned");
+    if (st.mode == DCTZHIP_QT && !st.qtable) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
+  } else if ((rc = streams_given(c, st, " and the outputs"))) return rc;    // (the outputs themselves: box by box, below)
   const unsigned nfull = (unsigned)(st.n / 64);
   const bool rem = st.n % 64 != 0;
   const size_t unit = sh ? TILE_BLKS : TILE_ELEMS;  // what a candidate spans: the blocks, or of a flat array the elements, of a stream tile
@@ -2629,8 +2667,8 @@ static int decompress_boxes_call(dctzhip_ctx* c, const char* what, const StreamS
   std::vector<NdBoxElems> elems(sh ? (size_t)k : 0);
   // every buffer of the call against every other: the outputs may overlap nothing, neither each other nor what any box reads
   std::vector<Span> sp((size_t)k * 4 + 1);
-  size_t m = 0, B = 0, total = 0;
-  add_span(sp.data(), &m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, -1);
+  size_t m = 0, B = 0, total = 0, max_cells = 0;
+  if (!dc_only) add_span(sp.data(), &m, st.ac, (size_t)st.ac_count * sizeof(float), SPAN_READ, -1);
   for (int i = 0; i < k; i++) {
     char box[56];
     snprintf(box, sizeof(box), "%s: box %d", what, i);
@@ -2643,13 +2681,22 @@ static int decompress_boxes_call(dctzhip_ctx* c, const char* what, const StreamS
       r.g = canonical_box(ndim, dims, boxes[i].lo, boxes[i].hi);
       if (rem && r.g.rank((unsigned)st.n) != r.g.rank(nfull * 64u)) rem_boxes.push_back((unsigned)i);
     } else {
-      if ((rc = nd_box_front(c, box, *sh, boxes[i].lo, boxes[i].hi, &cnt, &r.t0, &r.t1))) return rc;
+      if ((rc = nd_box_front(c, box, *sh, boxes[i].lo, boxes[i].hi, &cnt, &r.t0, &r.t1, (size_t)cell))) return rc;
       unsigned nb[3];
-      nd_box_geometry(*sh, boxes[i].lo, boxes[i].hi, nb, elems[(size_t)i].lo, elems[(size_t)i].ext, &r.g);
+      nd_box_geometry(*sh, boxes[i].lo, boxes[i].hi, nb, elems[(size_t)i].lo, elems[(size_t)i].ext, &r.g, (unsigned)cell);
     }
     if (!boxes[i].d_out) return fail(c, DCTZHIP_E_ARG, "%s: null output", box);
     if (!aligned16(boxes[i].d_out)) return fail(c, DCTZHIP_E_ARG, "%s: the output must be 16-byte aligned", box);
-    tile_read_spans(sp.data(), &m, st, r.t0, r.t1, i);
+    if (dc_only) {
+      // no candidates, no list: the DC words from the first to the last block of the box
+      size_t first = 0, last = 0;
+      for (int d = 0; d < sh->nd; d++) { first = first * sh->nb[d] + boxes[i].lo[d]; last = last * sh->nb[d] + (boxes[i].hi[d] - 1); }
+      add_span(sp.data(), &m, st.dc + first, (last - first + 1) * sizeof(float), SPAN_READ, i);
+      r.t0 = r.t1 = 0;
+      max_cells = std::max(max_cells, cnt);
+    } else {
+      tile_read_spans(sp.data(), &m, st, r.t0, r.t1, i);
+    }
     add_span(sp.data(), &m, boxes[i].d_out, cnt * elem_size(st.dtype), SPAN_OUT, i);
     r.cand0 = (unsigned)total;                      // (k <= 2^12 boxes of <= 2^19 candidates each)
     r.out = boxes[i].d_out;
@@ -2666,8 +2713,10 @@ static int decompress_boxes_call(dctzhip_ctx* c, const char* what, const StreamS
   HIPCHK(c, hipSetDevice(c->device));
   const void* side = sh ? (const void*)elems.data() : (const void*)rem_boxes.data();
   const size_t side_bytes = sh ? elems.size() * sizeof(NdBoxElems) : rem_boxes.size() * sizeof(unsigned);
-  return (st.dtype == DCTZHIP_F64) ? decompress_boxes_impl<double>(c, st, sh, k, recs.data(), side, side_bytes, (unsigned)total, B)
-                                   : decompress_boxes_impl<float>(c, st, sh, k, recs.data(), side, side_bytes, (unsigned)total, B);
+  const CoarseZoom zoom = {factor, cell, (unsigned)max_cells};
+  const CoarseZoom* const cz = factor ? &zoom : nullptr;
+  return (st.dtype == DCTZHIP_F64) ? decompress_boxes_impl<double>(c, st, sh, k, recs.data(), side, side_bytes, (unsigned)total, B, cz)
+                                   : decompress_boxes_impl<float>(c, st, sh, k, recs.data(), side, side_bytes, (unsigned)total, B, cz);
 }
 
 extern "C" int dctzhip_decompress_boxes(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
@@ -2866,6 +2915,25 @@ extern "C" int dctzhip_decompress_coarse_box_nd(dctzhip_ctx* c, const void* d_bi
   HIPCHK(c, hipSetDevice(c->device));
   return (dtype == DCTZHIP_F64) ? decompress_coarse_box_nd_impl<double>(c, st, cs, factor, k, lo, hi, t0, t1, (double*)d_out)
                                 : decompress_coarse_box_nd_impl<float>(c, st, cs, factor, k, lo, hi, t0, t1, (float*)d_out);
+}
+
+// ---- a list of such boxes in one call (include/dctz_hip.h; dctz_kernels_mcboxnd.hip) -----------------------------
+// The list calls' host path (decompress_boxes_call) over the coarse shape, formed as the single call forms it.
+extern "C" int dctzhip_decompress_coarse_boxes_nd(dctzhip_ctx* c, const void* d_bin, const float* d_dc, const float* d_ac, uint32_t ac_count,
+                                                  const uint32_t* d_index, const void* qtable_host, int ndims, const size_t* dims,
+                                                  int dtype, double eb, double sf, int mode, int factor, int k,
+                                                  const dctzhip_box_item* boxes) {
+  static const char* const what = "dctzhip_decompress_coarse_boxes_nd";
+  NdShape sh;
+  int rc = nd_front(c, ndims, dims, dtype, mode, &sh);
+  if (rc) return rc;
+  const int geom = ndims == 2 ? GEOM_2D : GEOM_3D;
+  const int cell = coarse_k(geom, factor);
+  if (!cell) return fail(c, DCTZHIP_E_ARG, "%s: factor %d is not one of %s", what, factor, geom == GEOM_2D ? "2, 4, 8" : "2, 4");
+  NdShape cs = sh;
+  for (int i = 0; i < ndims; i++) cs.d[i] = (sh.d[i] + (size_t)factor - 1) / (size_t)factor;
+  const StreamSet st = {(const uint8_t*)d_bin, d_dc, d_ac, ac_count, d_index, qtable_host, sh.nblk * 64, dtype, eb, sf, mode};
+  return decompress_boxes_call(c, what, st, &cs, ndims, dims, k, boxes, factor, cell);
 }
 
 // ---- what the summary and correction-list calls share: a whole stream set with its index, flat or tiled ----------

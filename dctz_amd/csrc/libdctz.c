@@ -2058,6 +2058,21 @@ int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r) {
  * dctzhip_decompress_coarse_box_nd), the way of decompress_part: with K = edge / factor the blocks lo / K ... (hi - 1) / K hold
  * the box; bin ids up to the end of the last of their stream tiles, DC up to the last of them -- with factor == edge that
  * DC prefix alone -- the index built once over the prefix, one device call, only the box copied back. */
+/* A box in coarse coordinates against the extents of a DZND container (factor is one of the geometry's): 0 and its first and
+ * last block of the row-major block grid and its cell count, or -1. */
+static int coarse_span(const dzc_view *v, int factor, const size_t *lo, const size_t *hi, size_t *first, size_t *last, size_t *elems) {
+  if (!lo || !hi) return -1;
+  const size_t edge = v->nd == 2 ? 8 : 4, K = edge / (size_t)factor;
+  *first = 0; *last = 0; *elems = 1;
+  for (int i = 0; i < v->nd; i++) {
+    const size_t cd = (v->dims[i] + (size_t)factor - 1) / (size_t)factor, nb = (v->dims[i] + edge - 1) / edge;
+    if (lo[i] >= hi[i] || hi[i] > cd) return -1;
+    *elems *= hi[i] - lo[i];
+    *first = *first * nb + lo[i] / K;
+    *last = *last * nb + (hi[i] - 1) / K;
+  }
+  return *last >= v->nblk ? -1 : 0;
+}
 int dctz_decompress_coarse_box_nd(t_var *var_z, int factor, const size_t *lo, const size_t *hi, t_var *var_r) {
   const double t_begin = now_s();
   dzc_view v;
@@ -2069,14 +2084,7 @@ int dctz_decompress_coarse_box_nd(t_var *var_z, int factor, const size_t *lo, co
   if (n == 0 || !var_r || !lo || !hi || factor < 2 || factor > edge || (factor & (factor - 1))) return -1;
   const size_t K = (size_t)(edge / factor);
   size_t first = 0, last = 0, out_elems = 1;                   /* blocks of the row-major block grid */
-  for (int i = 0; i < v.nd; i++) {
-    const size_t cd = (v.dims[i] + (size_t)factor - 1) / (size_t)factor, nb = (v.dims[i] + (size_t)edge - 1) / (size_t)edge;
-    if (lo[i] >= hi[i] || hi[i] > cd) return -1;
-    out_elems *= hi[i] - lo[i];
-    first = first * nb + lo[i] / K;
-    last = last * nb + (hi[i] - 1) / K;
-  }
-  if (last >= nblk) return -1;
+  if (coarse_span(&v, factor, lo, hi, &first, &last, &out_elems) != 0) return -1;
   const int dc_only = K == 1;
   const size_t S = DCTZHIP_INDEX_STRIDE;
   const size_t t1 = ((last + 1) * BLK_SZ + S - 1) / S;         /* the candidate tiles end here */
@@ -2093,6 +2101,60 @@ int dctz_decompress_coarse_box_nd(t_var *var_z, int factor, const size_t *lo, co
   if (dctzhip_memcpy_d2h(s.c, var_bytes(var_r), g_dev.out, out_elems * ts) != DCTZHIP_OK) die("D2H output");
   part_times(&s, t_begin, t0, t1s);
   return 1;
+}
+
+/* ---------------------------------------------------- dctz_decompress_coarse_boxes_nd -- */
+/* k such boxes (rows of the container's own number of dimensions, coarse coordinates, one factor) through the same machinery
+ * ONCE (include/dctz_hip.h: dctzhip_decompress_coarse_boxes_nd): bin ids up to the end of the last candidate stream tile of
+ * any box and DC up to the last block of any box -- with factor == edge that DC prefix alone -- one index, one device call
+ * into one arena (every output at a multiple of 16 bytes), k copies back.  Returns as dctz_decompress_coarse_box_nd does; a bad
+ * box anywhere in the list is refused before anything is written. */
+int dctz_decompress_coarse_boxes_nd(t_var *var_z, int factor, int k, const size_t *lo, const size_t *hi, t_var *const *var_r) {
+  const double t_begin = now_s();
+  dzc_view v;
+  dzc_header(&v, var_bytes(var_z), DCTZ_QT, (int)var_z->datatype); /* dctz-decomp-lib.c:84-94 */
+  if (v.nd == 0 || dzc_geometry(&v) != 0) return -1;               /* a flat container, or extents that are no shape */
+  const size_t ts = v.ts, n = v.npos, nblk = v.nblk;
+  const int dtype = v.is_d ? DCTZHIP_F64 : DCTZHIP_F32;
+  const int edge = v.nd == 2 ? 8 : 4;
+  if (n == 0 || factor < 2 || factor > edge || (factor & (factor - 1))) return -1;
+  if (k < 1 || k > DCTZHIP_BOXES_MAX || !lo || !hi || !var_r) return -1;
+  dctzhip_box_item *items = (dctzhip_box_item *)calloc((size_t)k, sizeof(dctzhip_box_item));
+  if (!items) { fprintf(stderr, "Out of memory: box list\n"); exit(1); }
+  size_t last = 0, out_elems = 0;                              /* the last block of any box; the arena */
+  for (int j = 0; j < k; j++) {
+    size_t jfirst, jlast, elems;
+    const size_t *jlo = lo + (size_t)j * v.nd, *jhi = hi + (size_t)j * v.nd;
+    if (!var_r[j] || coarse_span(&v, factor, jlo, jhi, &jfirst, &jlast, &elems) != 0) { free(items); return -1; }
+    if (jlast > last) last = jlast;
+    for (int i = 0; i < v.nd; i++) { items[j].lo[i] = jlo[i]; items[j].hi[i] = jhi[i]; }
+    items[j].d_out = (void *)(uintptr_t)(out_elems * ts);      /* offset for now: the arena may still move */
+    out_elems += (elems * ts + 15) / 16 * 16 / ts;
+  }
+  const int dc_only = factor == edge;
+  const size_t S = DCTZHIP_INDEX_STRIDE;
+  const size_t t1 = ((last + 1) * BLK_SZ + S - 1) / S;         /* the candidate tiles end here */
+  const size_t dc_dev = dc_only ? last + 1 : MIN(nblk, t1 * (S / BLK_SZ));   /* DC words the candidate tiles cover on the device */
+  dev_streams s;
+  if (sections_to_device(&v, dc_only ? 0 : MIN(n, S * t1), (last + 1) * sizeof(float), dc_dev * sizeof(float), dc_only, &s) != 1) { free(items); return -1; }
+  int ret = -1;
+  const double t0 = now_s();
+  grow(&g_dev.out, &g_dev.out_cap, out_elems * ts);
+  for (int j = 0; j < k; j++) items[j].d_out = (unsigned char *)g_dev.out + (uintptr_t)items[j].d_out;
+  const int rc = dctzhip_decompress_coarse_boxes_nd(DEV_STREAMS(s), v.nd, v.dims, dtype, v.h.error_bound, v.sf, DCTZ_MODE, factor, k, items);
+  if (rc == DCTZHIP_E_ARG) goto out;                           /* the streams disagree with each other */
+  if (rc != DCTZHIP_OK) die("dctzhip_decompress_coarse_boxes_nd");
+  const double t1s = now_s();
+  for (int j = 0; j < k; j++) {
+    size_t elems = 1;
+    for (int i = 0; i < v.nd; i++) elems *= items[j].hi[i] - items[j].lo[i];
+    if (dctzhip_memcpy_d2h(s.c, var_bytes(var_r[j]), items[j].d_out, elems * ts) != DCTZHIP_OK) die("D2H output");
+  }
+  part_times(&s, t_begin, t0, t1s);
+  ret = 1;
+out:
+  free(items);
+  return ret;
 }
 
 /* ------------------------------------------------------------------ dctz_tile_summary -- */

@@ -159,6 +159,9 @@ _PROTOS = {
     "dctzhip_decompress_coarse_box_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                                    C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_void_p]),
+    "dctzhip_decompress_coarse_boxes_nd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                     C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                     C.c_int, C.c_void_p]),
     "dctzhip_summary_tiles": (C.c_size_t, [C.c_size_t]),
     "dctzhip_tile_summary": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
@@ -508,11 +511,9 @@ class Context:
         self._check(rc, name)
         return dst.view(ext)
 
-    def _decompress_boxes(self, flat, out, cnt, dims, dtype, eb, sf, boxes, index, mode, qtable, dsts):
+    def _box_items(self, nd, boxes, dtype, dsts):
+        """The host table of a list call: (items, dsts, extents) of the boxes (lo, hi); `dsts` None: allocated."""
         t = self.torch
-        self._bind_stream()
-        dims = [int(v) for v in dims]
-        nd = len(dims)
         boxes = [([int(v) for v in lo], [int(v) for v in hi]) for lo, hi in boxes]
         exts = []
         for lo, hi in boxes:
@@ -521,23 +522,30 @@ class Context:
         if dsts is None:
             dsts = [t.empty(e, dtype=dtype, device=self.device) for e in exts]
         assert len(dsts) == len(boxes)
-        q = self._qtable(mode, qtable, dtype)
         items = (BoxItem * max(len(boxes), 1))()
         for it, (lo, hi), d in zip(items, boxes, dsts):
             for i in range(min(nd, BOX_MAXDIM)):
                 it.lo[i], it.hi[i] = lo[i], hi[i]
             it.d_out = d.data_ptr()
+        return items, dsts, exts
+
+    def _decompress_boxes(self, flat, out, cnt, dims, dtype, eb, sf, boxes, index, mode, qtable, dsts):
+        self._bind_stream()
+        dims = [int(v) for v in dims]
+        nd = len(dims)
+        items, dsts, exts = self._box_items(nd, boxes, dtype, dsts)
+        q = self._qtable(mode, qtable, dtype)
         arr = C.c_size_t * max(nd, 1)
         b, d, a, ix, qp = out["bin_index"].data_ptr(), out["dc"].data_ptr(), out["ac_exact"].data_ptr(), index.data_ptr(), _host_ptr(q)
         if flat:
             name = "dctzhip_decompress_boxes"
             n = int(np.prod(dims, dtype=np.int64)) if nd else 0
             rc = self.lib.dctzhip_decompress_boxes(self.h, b, d, a, int(cnt), ix, qp, n, _dt(dtype), float(eb), float(sf),
-                                                   mode, nd, arr(*dims), len(boxes), C.cast(items, C.c_void_p))
+                                                   mode, nd, arr(*dims), len(dsts), C.cast(items, C.c_void_p))
         else:
             name = "dctzhip_decompress_boxes_nd"
             rc = self.lib.dctzhip_decompress_boxes_nd(self.h, b, d, a, int(cnt), ix, qp, nd, arr(*dims), _dt(dtype),
-                                                      float(eb), float(sf), mode, len(boxes), C.cast(items, C.c_void_p))
+                                                      float(eb), float(sf), mode, len(dsts), C.cast(items, C.c_void_p))
         self._check(rc, name)
         return [d.view(e) for d, e in zip(dsts, exts)]
 
@@ -728,6 +736,23 @@ class Context:
             _dt(dtype), float(eb), float(sf), mode, int(factor), arr(*lo), arr(*hi), dst.data_ptr())
         self._check(rc, "dctzhip_decompress_coarse_box_nd")
         return dst.view(ext)
+
+    def decompress_coarse_boxes_nd(self, out, cnt, shape, dtype, eb, sf, factor, boxes, index=None, mode=EC, qtable=None, dsts=None):
+        """The boxes (lo, hi) of `boxes`, in COARSE coordinates at ONE factor, each what decompress_coarse_box_nd() gives for
+        it, in ONE call (one work list of the hit stream tiles of all boxes, one decode launch, one synchronisation; with
+        factor == tile edge one gather from out["dc"] alone).  Boxes may overlap or repeat.  Returns the list of tensors
+        shaped hi - lo; `dsts` (or None: allocated) are the outputs, one per box."""
+        self._bind_stream()
+        shape = [int(v) for v in shape]
+        nd = len(shape)
+        items, dsts, exts = self._box_items(nd, boxes, dtype, dsts)
+        (b, d, a), ix, q = self._stream_args(out, index, mode, qtable, dtype)
+        arr = C.c_size_t * max(nd, 1)
+        rc = self.lib.dctzhip_decompress_coarse_boxes_nd(
+            self.h, b, d, a, int(cnt), ix, _host_ptr(q), nd, arr(*shape),
+            _dt(dtype), float(eb), float(sf), mode, int(factor), len(dsts), C.cast(items, C.c_void_p))
+        self._check(rc, "dctzhip_decompress_coarse_boxes_nd")
+        return [d.view(e) for d, e in zip(dsts, exts)]
 
     # ---- flat and tiled streams through one body per operation ----
     # What a public method makes of its geometry argument: the geometry arguments of the C call (in the flat call's place of n),

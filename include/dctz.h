@@ -224,6 +224,15 @@ int dctz_decompress_coarse(t_var *var_z, int factor, t_var *var_r);
  * index is built once, and only the box is copied back.  Returns 1, or -1 for a flat container, a bad factor, a null lo, hi
  * or var_r, a box that is not inside the coarse extents and streams that disagree with each other. */
 int dctz_decompress_coarse_box_nd(t_var *var_z, int factor, const size_t *lo, const size_t *hi, t_var *var_r);
+/* k such boxes of ONE DZND container at ONE factor in one call (ADDITION, EC and QT builds), 1 <= k <= 4096: lo and hi hold k
+ * rows of as many entries as the container has dimensions, in COARSE coordinates; var_r[j]->buf (allocated by the caller)
+ * receives box j, the bytes dctz_decompress_coarse_box_nd gives for it.  Boxes may overlap or repeat.  The container is gone
+ * through ONCE: bin_index is inflated up to the end of the last candidate stream tile of any box and DC up to the last block
+ * of any box (plain and DZIX) -- with factor equal to the block edge that DC prefix alone --, one exception index is built,
+ * one device call (include/dctz_hip.h: dctzhip_decompress_coarse_boxes_nd) decodes the hit stream tiles of every box into one
+ * device arena, and k copies bring the boxes back.  Return values are dctz_decompress_coarse_box_nd's, for any box of the list
+ * (nothing is written then); a k outside 1 .. 4096 and a null lo, hi, var_r or var_r[j] return -1 as well. */
+int dctz_decompress_coarse_boxes_nd(t_var *var_z, int factor, int k, const size_t *lo, const size_t *hi, t_var *const *var_r);
 /* Verify and survey without a reconstruction (ADDITION, EC and QT builds; include/dctz_hip.h: dctzhip_tile_summary holds the
  * definition).  One record per 4096 elements of what dctz_decompress would rebuild from var_z -- its minimum, maximum, sum
  * and sum of squares -- and, with var_ref, the minimum and maximum of the original, max |x - r| and sum (x - r)^2 of the

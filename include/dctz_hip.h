@@ -165,7 +165,7 @@ int dctzhip_set_decode_memo(dctzhip_ctx *ctx, int on);
  * items of batches / those whose guess was refused, 10 step-downs of dctzhip_compress_psnr / _psnr_nd, 11 / 12 workgroups and
  * candidate tiles of the last dctzhip_decompress_box / _box_nd / _coarse_box_nd call, whichever ran last (12 > 11: its
  * grid-stride loop ran; a _coarse_box_nd call with factor == block edge reads no tiles: 12 is 0), 13 / 14 / 15 items
- * in the list of the last dctzhip_decompress_boxes or dctzhip_decompress_boxes_nd call (whichever of the two ran last),
+ * in the list of the last dctzhip_decompress_boxes, _boxes_nd or _coarse_boxes_nd call (whichever of them ran last),
  * workgroups of its decode launch and the list's bound, 16 / 17
  * dctzhip_decompress calls launched on the decode memo / of them found stale and decoded again, 18 / 19 guesses of the
  * scaling factor taken from the remembered statistics of the same input that verified / that did not, 20 the division
@@ -603,6 +603,38 @@ int dctzhip_decompress_coarse_box_nd(dctzhip_ctx *ctx, const void *d_bin_index, 
                                      uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
                                      const size_t *dims, int dtype, double error_bound, double sf, int mode, int factor,
                                      const size_t *lo, const size_t *hi, void *d_out);
+/* k such boxes of the SAME tiled array at ONE zoom level in one call: what dctzhip_decompress_boxes_nd is to
+ * dctzhip_decompress_box_nd.  Everything up to `factor` is dctzhip_decompress_coarse_box_nd's (factor in {2, 4, 8} for 2-D,
+ * {2, 4} for 3-D; one factor serves the whole call -- a caller with three levels makes three calls); boxes is a HOST array
+ * of 1 <= k <= DCTZHIP_BOXES_MAX items, lo / hi in COARSE coordinates, the first ndims entries are used.  One box table
+ * handed over in one transfer, one work list of (box, hit stream tile) pairs built on the device from the boxes of the
+ * block grid, one persistent decode launch whose workgroups take list items, and one synchronisation.
+ *   boxes[i].d_out  receives exactly the bytes dctzhip_decompress_coarse_box_nd writes for box i with the same remaining
+ *               arguments -- the slice of dctzhip_decompress_coarse_nd, bit for bit (EC and QT, fp32 and fp64, aligned and
+ *               ragged extents; a cell that straddles a ragged edge keeps the whole-array call's rule).
+ *   overlap     boxes may overlap, nest or repeat.  A stream tile hit by m boxes is decoded m times.
+ *   locality    the call reads the bin ids, DC values, idx[t], idx[t + 1] and AC_exact[idx[t], idx[t + 1]) of stream tiles
+ *               hit by at least one box and nothing else of the streams; it writes nothing outside the k outputs.
+ *   factor == block edge   all boxes are gathered from the DC stream alone in one launch, without a list ((T)DC * 0.125,
+ *               then * sf if sf != 1); d_bin_index, d_ac_exact and d_index may be NULL.  Per box only the DC words from its
+ *               first to its last block count as read.
+ *   refusals    before anything is launched or written, all or nothing, DCTZHIP_E_ARG: k < 1, k > DCTZHIP_BOXES_MAX, a null
+ *               boxes; what dctzhip_decompress_coarse_box_nd refuses for ctx, shape, dtype, mode, factor, the streams,
+ *               alignment and the QT table; for any box what it refuses for lo, hi and d_out (the message names "box i");
+ *               an output that overlaps another output or what any box of the call may read (its candidate tiles' bin ids,
+ *               DC values and index entries, AC_exact[0, ac_count); for factor == block edge the DC words named above);
+ *               for other factors, boxes that may hit more than 2^24 stream tiles in all (the bound of the work list, as
+ *               for dctzhip_decompress_boxes_nd).  On the device, for listed tiles only, the index check of the
+ *               whole-array call: a failing tile reads no AC_exact, the call returns DCTZHIP_E_ARG, the outputs are
+ *               undefined and the context stays usable.
+ * Returns once that check is known, having synchronised the context's stream once.
+ * dctzhip_debug_counter 13 / 14 / 15 report this call like the other list calls: items of its list, workgroups of its
+ * decode launch, the list's bound (factor == block edge: no list, items and bound are 0).  dctzhip_debug_last_kernel(ctx, 1,
+ * ...) names the kernel (k_ndcoarse_mbox<T, mode, geometry, K> | k_ndcoarse_mbox_dc<T>). */
+int dctzhip_decompress_coarse_boxes_nd(dctzhip_ctx *ctx, const void *d_bin_index, const float *d_dc, const float *d_ac_exact,
+                                       uint32_t ac_count, const uint32_t *d_index, const void *qtable_host, int ndims,
+                                       const size_t *dims, int dtype, double error_bound, double sf, int mode, int factor,
+                                       int k, const dctzhip_box_item *boxes /* host */);
 
 /* ---- tile summaries: verify and survey without writing the decode ----------- */
 /* Two questions about a compressed array that need no reconstruction in memory: how far is it from the original, and where
