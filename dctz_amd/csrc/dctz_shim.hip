@@ -2007,6 +2007,7 @@ extern "C" int dctzhip_decompress(dctzhip_ctx* c, const void* d_bin, const float
   if (rc) return rc;
   if (!d_bin || !d_dc || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   if (!aligned16(d_bin) || !aligned16(d_out)) return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
+  if (((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u)) return fail(c, DCTZHIP_E_ARG, "DC and AC_exact must be 4-byte aligned");
   if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
   {
     Span sp[4];
@@ -2455,6 +2456,7 @@ extern "C" int dctzhip_decompress_nd(dctzhip_ctx* c, const void* d_bin, const fl
   if (rc) return rc;
   if (!d_bin || !d_dc || !d_out || (ac_count && !d_ac)) return fail(c, DCTZHIP_E_ARG, "null device buffer");
   if (!aligned16(d_bin) || !aligned16(d_out)) return fail(c, DCTZHIP_E_ARG, "device buffers must be 16-byte aligned");
+  if (((uintptr_t)d_dc & 3u) || ((uintptr_t)d_ac & 3u)) return fail(c, DCTZHIP_E_ARG, "DC and AC_exact must be 4-byte aligned");
   if (mode == DCTZHIP_QT && !qtable_host) return fail(c, DCTZHIP_E_ARG, "QT mode needs the 64-entry table");
   HIPCHK(c, hipSetDevice(c->device));
   rc = ensure_scratch(c, sh.nblk * 64, dtype, DCTZHIP_EC, false);
@@ -4660,6 +4662,7 @@ extern "C" int dctzhip_decompress_batch(dctzhip_ctx* c, int k, const dctzhip_bat
     if (rc) return rc;
     if (!it.d_bin_index || !it.d_dc || !it.d_out || (it.ac_count && !it.d_ac_exact)) return fail(c, DCTZHIP_E_ARG, "array %d: null device buffer", i);
     if (!aligned16(it.d_bin_index) || !aligned16(it.d_out)) return fail(c, DCTZHIP_E_ARG, "array %d: device buffers must be 16-byte aligned", i);
+    if (((uintptr_t)it.d_dc & 3u) || ((uintptr_t)it.d_ac_exact & 3u)) return fail(c, DCTZHIP_E_ARG, "array %d: DC and AC_exact must be 4-byte aligned", i);
     if (mode == DCTZHIP_QT && !it.qtable_host) return fail(c, DCTZHIP_E_ARG, "array %d: QT mode needs the 64-entry table", i);
     if (status) status[i] = DCTZHIP_OK;
   }

@@ -302,6 +302,9 @@ int dctzhip_scale_inplace(dctzhip_ctx *ctx, void *d_x, size_t n, int dtype, doub
  *   d_out        n elements out; must not overlap d_bin_index (n bytes), d_dc (nblk
  *                floats) or the ac_count floats of d_ac_exact (else DCTZHIP_E_ARG
  *                before a launch)
+ *   alignment    d_bin_index and d_out 16-byte aligned; DC, AC_exact: 4-byte aligned (else
+ *                DCTZHIP_E_ARG before a launch) -- dctzhip_decompress_nd and the items of
+ *                dctzhip_decompress_batch alike
  * Returns once the stream is known to be consistent with ac_count (the only thing the
  * host has to learn); the reconstruction itself is complete in STREAM order -- for
  * any later call or copy on the context's stream, or after dctzhip_sync(). */
@@ -432,8 +435,8 @@ typedef struct {
   void *d_scaled;            /* optional: x / sf (dctz-comp-lib.c:193-216); may be NULL, may be d_in exactly */
 } dctzhip_batch_citem;
 typedef struct {
-  const void *d_bin_index;
-  const float *d_dc;
+  const void *d_bin_index;   /* 16-byte aligned, like d_out */
+  const float *d_dc;         /* DC, AC_exact: 4-byte aligned */
   const float *d_ac_exact;
   uint32_t ac_count;         /* header.tot_AC_exact_count of this array */
   const void *qtable_host;   /* QT: 64 values in the data type, host memory; EC: NULL */

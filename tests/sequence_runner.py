@@ -17,6 +17,13 @@ ONE_CALLS, ONE_GAVE_UP, SPEC_HITS, MEMO, HIST_HITS, VARIANT = 0, 1, 6, 16, 18, 2
 E2 = object()                           # in a check: the expected value is the fresh context's
 
 
+class E2Of:
+    """In a check: the expected value is fn(the fresh context's result `label` of ANOTHER op) -- a slice taken on the host."""
+
+    def __init__(self, op, label, fn):
+        self.op, self.label, self.fn = op, label, fn
+
+
 def _tdt(dtype):
     import torch
     return torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
@@ -27,28 +34,32 @@ def _up(n):
 
 
 class Arena:
-    """A device buffer of 0xA5 bytes that outputs are cut from, each 256-byte aligned with 256 bytes of guard on either side."""
+    """A device buffer of 0xA5 bytes that outputs are cut from, each 256-byte aligned (or at `align` bytes past a multiple of
+    256: take(..., align=a), 0 <= a < 256) with at least 256 bytes of guard on either side."""
 
     def __init__(self, device, nbytes):
         import torch
         self.buf = torch.full((nbytes,), FILL, dtype=torch.uint8, device=device)
+        self.base = self.buf.data_ptr()
         self.top = 0
         self.live = []                  # (start, nbytes) of every output cut since the last reset
 
-    def take(self, shape, dtype):
+    def take(self, shape, dtype, align=256, role=None):         # role: what the buffer is for (tests/placement_cases.py)
         import torch
         shape = tuple(int(v) for v in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
-        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty(0, dtype=dtype).element_size()
-        start = self.top + GUARD
-        assert start + _up(nbytes) + GUARD <= self.buf.numel(), "arena too small"
-        self.top = start + _up(nbytes)
+        esize = torch.empty(0, dtype=dtype).element_size()
+        nbytes = int(np.prod(shape, dtype=np.int64)) * esize
+        assert self.base % GUARD == 0 and 0 <= align % GUARD < GUARD and (align % GUARD) % esize == 0
+        start = self.top + GUARD + align % GUARD         # (top is a multiple of 256, and so is the arena's own address)
+        assert _up(start + nbytes) + GUARD <= self.buf.numel(), "arena too small"
+        self.top = _up(start + nbytes)
         self.live.append((start, nbytes))
         return self.buf[start:start + nbytes].view(dtype).view(shape)
 
-    def put(self, a):
+    def put(self, a, align=256, role=None):
         import torch
         t = torch.from_numpy(np.array(a, copy=True, order="C"))
-        d = self.take(tuple(t.shape), t.dtype)
+        d = self.take(tuple(t.shape), t.dtype, align, role)
         d.copy_(t)
         return d
 
@@ -56,7 +67,7 @@ class Arena:
         """Bytes that are not 0xA5 in the guards of the live outputs and in the space no output was cut from (a tensor)."""
         parts = [self.buf[self.top:]]
         for start, nbytes in self.live:
-            parts += [self.buf[start - GUARD:start], self.buf[start + nbytes:start + _up(nbytes)]]
+            parts += [self.buf[start - GUARD - start % GUARD:start], self.buf[start + nbytes:_up(start + nbytes)]]
         import torch
         return (torch.cat(parts) != FILL).sum()
 
@@ -99,13 +110,20 @@ class Runner:
         self.stream = stream
         with self._on_stream():
             self.ctx = dctz_amd.Context(0)
-            self.keep = Arena(self.ctx.device, persistent)        # the slots: outputs that stay for later ops
-            self.tmp = Arena(self.ctx.device, transient)          # the outputs of one op
+            self.keep = self._arena(persistent)                   # the slots: outputs that stay for later ops
+            self.tmp = self._arena(transient)                     # the outputs of one op
         self.ctx.torch = _ArenaTorch(self.tmp)
         self.e2, self.record = e2, record
         self.slots, self.holder, self.inputs, self.indices = {}, {}, {}, {}
         self.pending = None
         self.trace = []
+
+    def _arena(self, nbytes):
+        return Arena(self.ctx.device, nbytes)
+
+    def _upload(self, a, role):
+        """A device copy of a subject's array or index (a torch allocation; the placement runner cuts it from an arena)."""
+        return self.torch.from_numpy(np.array(a, copy=True)).to(self.ctx.device)
 
     def _on_stream(self):
         import contextlib
@@ -119,12 +137,12 @@ class Runner:
         key = (name, raw)
         if key not in self.inputs:
             s = S.SUBJECTS[name]
-            self.inputs[key] = self.torch.from_numpy(np.array(s.raw if raw else s.x, copy=True)).to(self.ctx.device)
+            self.inputs[key] = self._upload(s.raw if raw else s.x, 16)
         return self.inputs[key]
 
     def index(self, name):
         if name not in self.indices:
-            self.indices[name] = self.torch.from_numpy(np.array(S.index(name), copy=True)).to(self.ctx.device)
+            self.indices[name] = self._upload(S.index(name), 4)
         return self.indices[name]
 
     def slot(self, slot, name, for_decode=False):
@@ -198,6 +216,11 @@ class Runner:
                 self.record[key] = got.copy()
                 return
             want = self.e2(op)[key]
+        elif isinstance(want, E2Of):
+            if self.record is not None:                  # (a fresh context's own result: two of them are compared once)
+                self.record[S.e2_key(op[0], op[1], op[2]) + (label,)] = got.copy()
+                return
+            want = want.fn(self.e2(want.op)[S.e2_key(*want.op) + (want.label,)])
         want = self._host(want)
         g, w = got.reshape(-1).view(np.uint8), want.reshape(-1).view(np.uint8)
         if got.size == want.size and got.dtype.itemsize == want.dtype.itemsize and np.array_equal(g, w):
@@ -302,6 +325,23 @@ def _coarse(R, kind, name, a):
     return [("coarse", r, E2)]
 
 
+def _coarse_box(R, kind, name, a):
+    """A box, or a list of boxes, of the coarse array: the slices of the whole-array op's fresh-context result."""
+    s, c, b, tdt = _decode_args(R, name, a)
+    f = a["factor"]
+    whole = (("coarse_nd", name, {"factor": f}), "coarse")
+    ext = S.coarse_shape(s.shape, f)
+
+    def cut(lo, hi):
+        return lambda v: np.ascontiguousarray(v.reshape(ext)[tuple(slice(l, h) for l, h in zip(lo, hi))])
+    if kind == "coarse_boxes_nd":
+        rs = R.ctx.decompress_coarse_boxes_nd(b, c.cnt, s.shape, tdt, S.EB, c.sf, f, [tuple(bx) for bx in a["boxes"]], index=R.index(name), mode=s.mode,
+                                              qtable=_q(c, s))
+        return [(f"coarse box {i}", r, E2Of(*whole, cut(lo, hi))) for i, (r, (lo, hi)) in enumerate(zip(rs, a["boxes"]))]
+    r = R.ctx.decompress_coarse_box_nd(b, c.cnt, s.shape, tdt, S.EB, c.sf, f, a["lo"], a["hi"], index=R.index(name), mode=s.mode, qtable=_q(c, s))
+    return [("coarse box", r, E2Of(*whole, cut(a["lo"], a["hi"])))]
+
+
 def _summary(R, kind, name, a):
     s, c, b, tdt = _decode_args(R, name, a)
     ref = R.x(name) if kind.endswith("_ref") else None
@@ -320,8 +360,8 @@ def _fixup(R, kind, name, a):
     start_w, off_w, val_w = S.fix_list(name, a["mult"])
     bound = S.fix_bound(name, a["mult"])
     if "apply" in kind:
-        fix = (R.tmp.put(start_w.view(np.int32)), R.tmp.put(off_w.view(np.int16)), R.tmp.put(val_w), int(off_w.size))
-        dst = R.tmp.put(S.decode(name))
+        fix = (R.tmp.put(start_w.view(np.int32), role=4), R.tmp.put(off_w.view(np.int16), role=2), R.tmp.put(val_w, role="es"), int(off_w.size))
+        dst = R.tmp.put(S.decode(name), role="es")
         r = R.ctx.fixup_apply(fix, s.n, tdt, dst) if s.flat else R.ctx.fixup_apply_nd(fix, s.shape, tdt, dst)
         return [("applied", r, S.fix_applied(name, a["mult"]))]
     f = R.ctx.fixup_build if s.flat else R.ctx.fixup_build_nd
@@ -343,8 +383,8 @@ def _mask(R, kind, name, a):
         m, k, fd = f(raw, H.MISS_ABS_GE, 0.0, S.LIMIT)
         return [("mask", m, words), ("count", k, count), ("filled", fd, filled), ("input", raw, s.raw)]
     if kind == "mask_apply":
-        dst = R.tmp.put(S.decode(name))
-        m = R.tmp.put(words.view(np.int64))
+        dst = R.tmp.put(S.decode(name), role="es")
+        m = R.tmp.put(words.view(np.int64), role=8)
         if s.flat:
             r = R.ctx.mask_apply(m, s.n, a["fill"], dst)
         else:
@@ -485,6 +525,7 @@ _IMPL = {"decompress": _decompress, "compress_nd": _compress_nd, "decompress_nd"
 _IMPL.update({k: _compress for k in ("compress", "compress_scaled", "compress_inplace", "compress_coef")})
 _IMPL.update({k: _box for k in ("box", "boxes", "box_nd", "boxes_nd")})
 _IMPL.update({k: _coarse for k in ("coarse", "coarse_nd")})
+_IMPL.update({k: _coarse_box for k in ("coarse_box_nd", "coarse_boxes_nd")})
 _IMPL.update({k: _summary for k in ("summary", "summary_ref", "summary_nd", "summary_nd_ref")})
 _IMPL.update({k: _fixup for k in S.OPS if k.startswith("fixup")})
 _IMPL.update({k: _mask for k in ("mask_build", "mask_build_nd", "compress_masked", "compress_masked_nd", "mask_apply")})

@@ -371,6 +371,16 @@ def test_single_compress_with_a_scaled_copy_partly_over_its_input_is_refused(ctx
     _refused(lambda: ctx.compress(x, 1e-3, O.EC, out=ar.outs(16 * 4, 3 * MB, 4 * MB, N_ARG)), ctx, [ar.a])
 
 
+class _Off:
+    """A stream buffer as the wrapper reads it (data_ptr), `nbytes` past the tensor's start."""
+
+    def __init__(self, t, nbytes):
+        self._p = t.data_ptr() + nbytes
+
+    def data_ptr(self):
+        return self._p
+
+
 def _streams_in_arena(ctx, dtype, mode):
     """A compressed array whose streams live in an arena at 0 / 1 MiB / 2 MiB, and its oracle record."""
     import torch
@@ -395,6 +405,13 @@ def test_decode_output_over_its_streams_is_refused(ctx, dtype, mode):
         good = ar.v(8 * MB, N_ARG, tdt)
         _refused(lambda: ctx.decompress_batch([out, out], [c.cnt] * 2, [N_ARG] * 2, [tdt] * 2, 1e-3, [c.sf] * 2, mode,
                                               qtables=[c.qtable] * 2, dsts=[good, dst]), ctx, [ar.a])
+    # DC or AC_exact 2 bytes off a 4-byte boundary (include/dctz_hip.h: DC, AC_exact: 4-byte aligned)
+    good = ar.v(8 * MB, N_ARG, tdt)
+    for key in ("dc", "ac_exact"):
+        off = dict(out, **{key: _Off(out[key], 2)})
+        _refused(lambda: ctx.decompress(off, c.cnt, N_ARG, tdt, 1e-3, c.sf, mode, qtable=c.qtable, dst=good), ctx, [ar.a])
+        _refused(lambda: ctx.decompress_batch([out, off], [c.cnt] * 2, [N_ARG] * 2, [tdt] * 2, 1e-3, [c.sf] * 2, mode,
+                                              qtables=[c.qtable] * 2, dsts=[good, ar.v(9 * MB, N_ARG, tdt)]), ctx, [ar.a])
     # two decode outputs over each other
     d0, d1 = ar.v(8 * MB, N_ARG, tdt), ar.v(8 * MB + 16 * 5, N_ARG, tdt)
     _refused(lambda: ctx.decompress_batch([out, out], [c.cnt] * 2, [N_ARG] * 2, [tdt] * 2, 1e-3, [c.sf] * 2, mode,

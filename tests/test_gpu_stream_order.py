@@ -169,8 +169,8 @@ class StreamRunner(Runner):
     def _track(self, arena):
         put = arena.put
 
-        def tracked(a):
-            d = put(a)
+        def tracked(a, *args, **kw):
+            d = put(a, *args, **kw)
             if self.gate.armed is not None:               # (behind the call's queue nothing would put the true bytes back)
                 self.transients.append((d, d.clone()))
                 _decoy(d)
@@ -352,7 +352,7 @@ def test_bind_orders_the_new_stream_behind_the_old(delay):
 
 
 def test_h_stream_hops(delay):
-    """walk_32 with the ops alternating between two streams and every third op on the legacy default stream; an op is
+    """walk_11 with the ops alternating between two streams and every third op on the legacy default stream; an op is
     launched before the results of the op in front of it are looked at, and nothing but finish() waits on the host."""
     import torch
     sched = S.all_schedules()[S.HOP_WALK]

@@ -206,6 +206,22 @@ def test_hip_nd_rejects_bad_shapes(ctx):
         ctx.nd_blocks((5,))
     with pytest.raises(dctz_amd.hip.DctzHipError):
         ctx.nd_blocks((4, 0, 4))
+    # DC or AC_exact 2 bytes off a 4-byte boundary: refused before a launch, the output untouched
+    class Off:
+        def __init__(self, t):
+            self.p = t.data_ptr() + 2
+
+        def data_ptr(self):
+            return self.p
+    x = torch.from_numpy(field((13, 22), np.float32)).to(ctx.device)
+    out, info = ctx.compress_nd(x, 1e-3)
+    dst = torch.full((13, 22), 7.0, dtype=torch.float32, device=ctx.device)
+    for key in ("dc", "ac_exact"):
+        with pytest.raises(dctz_amd.hip.DctzHipError) as e:
+            ctx.decompress_nd(dict(out, **{key: Off(out[key])}), info.cnt, (13, 22), torch.float32, 1e-3, info.sf, dst=dst)
+        assert f"({dctz_amd.hip.E_ARG})" in str(e.value) and "4-byte aligned" in str(e.value)
+        assert bool((dst == 7.0).all())
+    assert ctx.decompress_nd(out, info.cnt, (13, 22), torch.float32, 1e-3, info.sf, dst=dst) is dst
 
 
 # ------------------------------------------------------------------------- drop-in library, container, CLI --
